@@ -13,13 +13,18 @@ The other BASELINE configs keep the partitioning BASELINE.json states for them:
               after the timed region the root gathers the result and compares it with its own single-GPU separation.
   --config 5  repet.simonline on 64 30-s clips, 64/N per rank, batched through every stage: total work fixed, "strong".
 
-    python bench.py                       # 1 GPU, finishes in a few minutes (incl. the CPU baseline)
+    python bench.py --gpus 1 --steps K --warmup W     # the headline alone: set-up, W warm-up steps, K timed steps, the line
+    python bench.py --full                # 1 GPU, everything below as well; finishes in a few minutes (incl. the CPU baseline)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line. `roofline` describes the stage with the largest device time, measured
-with HIP events recorded on the engine's stream during the timed steps; `cpu_baseline` is the NumPy
-oracle (a port of the reference, validated against it) timed on this host on a bounded sample.
+with HIP events recorded on the engine's stream during the timed steps. A plain run times ONE region of
+exactly K steps and measures nothing else; `--full` adds what takes runs or checks of its own: five timed
+regions (median reported), `cpu_baseline` (the NumPy oracle, a port of the reference validated against
+it, timed on this host on a bounded sample), the drop-in call's wall time, the per-kernel and fp32-GEMM
+child runs, the scatter/gather leg and the multi-rank verifications. `--dump-outputs DIR` writes what the
+timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -71,6 +76,28 @@ def cpu_baseline(fs, channels, seconds, algo="sim", n_clips=1):
             "sample": f"oracle.{algo} (NumPy float64 port of repet.py) on {n_clips} x {seconds:g}-s {fs} Hz {channels}-ch synth clip "
                       f"(the bench workload itself when 180 s), {dt:.1f} s wall; single-threaded except the "
                       f"matrix products ({blas} BLAS threads); host has {os.cpu_count()} logical cores"}
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array a caller of the timed path receives, as out_dir/<name>.npy in float32 (the engine computes
+    in fp32 and widens to float64 on download: nothing is lost). At most DUMP_LIMIT_BYTES in all. An array too large for its
+    share is written as a fixed sample instead: the sample frames (rows of all channels) at positions drawn with seed 0,
+    sorted, in <name>.npy, and those positions (float64) in <name>_frames.npy. The headline's 180-s stereo clip fits whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 2 * 4096      # (room for the .npy headers)
+    for name, a in arrays.items():
+        if a.size * 4 <= share:
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+            continue
+        frames = a.reshape(-1, a.shape[-1])
+        k = share // (frames.shape[1] * 4 + 8)
+        rows = np.unique(np.random.default_rng(0).integers(0, frames.shape[0], size=k))
+        np.save(os.path.join(out_dir, name + ".npy"), frames[rows].astype(np.float32))
+        np.save(os.path.join(out_dir, name + "_frames.npy"), rows.astype(np.float64))
 
 
 def bind_to_gpu_node(local_rank):
@@ -148,9 +175,14 @@ def scatter_gather_leg(dist, rank, world, local_rank, algo, fs, channels, second
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=400, help="steps per timed region (default 400: with 5 regions about two seconds of GPU work at "
-                                                           "cfg 2, long enough for a coarse GPU-activity sampler to see it)")
-    ap.add_argument("--series", type=int, default=5, help="timed regions of exactly --steps steps each; value / ms_per_step are the MEDIAN series, all of them are listed")
+    ap.add_argument("--steps", type=int, default=400, help="steps per timed region (default 400: with --full's 5 regions about two seconds of GPU work "
+                                                           "at cfg 2, long enough for a coarse GPU-activity sampler to see it)")
+    ap.add_argument("--series", type=int, default=None, help="timed regions of exactly --steps steps each (default 1; 5 with --full); value / ms_per_step "
+                                                             "are the MEDIAN series, all of them are listed")
+    ap.add_argument("--full", action="store_true", help="besides the headline: 5 timed regions, the CPU baseline, the drop-in call, the child runs "
+                                                        "(per-kernel times, fp32 GEMM, three clips in flight), the scatter/gather leg, the verifications")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-variants", action="store_true", help="skip the fp32-GEMM variant (a child run of this script under REPET_GRAM=f32)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--duration", type=float, default=180.0, help="clip length in seconds (config 2: 180)")
@@ -165,7 +197,7 @@ def main():
                     help="BASELINE.json configs[i-1]: 1 original on the reference's 23-s example clip (--wav, only where the "
                          "reference tree is present), 2 sim 180 s (headline), 3 extended 600 s, 4 adaptive 300 s 48 kHz "
                          "mono, 5 simonline 30-s clips (64 over all ranks)")
-    ap.add_argument("--wav", default="/root/reference/audio_file.wav", help="config 1: the reference's example clip")
+    ap.add_argument("--wav", default=None, help="config 1: path of the reference's example clip (audio_file.wav; not part of this repository)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--scatter-lenient", action="store_true", help="exit 0 even when the scatter/gather leg fails (default: 1, after the headline line has been printed)")
     ap.add_argument("--no-scatter", action="store_true", help="skip the scatter -> separate -> gather leg (8 clips from the root's host RAM)")
@@ -173,6 +205,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=180.0,
                     help="length of the CPU-baseline clip (default: the whole config-2 clip, ~25 s of host time)")
     args = ap.parse_args()
+    if args.series is None:
+        args.series = 5 if args.full else 1
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # Started as plain `python bench.py --gpus N`: this process becomes the launcher. It starts the N ranks as a CHILD
@@ -196,8 +230,8 @@ def main():
     example_clip = None
     if args.config == 1:
         import scipy.io.wavfile            # the clip is not redistributed with this repository: build container only
-        if not os.path.exists(args.wav):
-            raise SystemExit(f"--config 1 needs the reference's example clip ({args.wav}); it is not part of this repository")
+        if not args.wav or not os.path.exists(args.wav):
+            raise SystemExit(f"--config 1 needs the reference's example clip (--wav PATH, given: {args.wav}); it is not part of this repository")
         args.fs, pcm = scipy.io.wavfile.read(args.wav)
         example_clip = pcm / pow(2, pcm.itemsize * 8 - 1)
         args.algo, args.duration, args.channels = "original", len(pcm) / args.fs, pcm.shape[1]
@@ -214,12 +248,13 @@ def main():
     # the CPU baseline FIRST, while this process may still use every CPU it was given (its BLAS threads are created here, unbound);
     # then the process binds itself to the GPU's NUMA node, before torch / the library create a thread or pin a page
     cpu_line = None
-    if world == 1 and not args.no_cpu_baseline and example_clip is None:
+    if args.full and world == 1 and not args.no_cpu_baseline and example_clip is None:
         # a bounded sample of the same workload: the whole clip for configs 2, 3 and 4 (10-30 s of host time each), 8 of the 64
         # clips of config 5
         sample_s = args.cpu_seconds if args.config == 2 else args.duration
         cpu_line = cpu_baseline(args.fs, args.channels, min(sample_s, args.duration), args.algo, 8 if args.config == 5 else 1)
-    numa = bind_to_gpu_node(local_rank)
+    # (the binding serves the drop-in call's host side, which only --full measures; the device times do not care)
+    numa = bind_to_gpu_node(local_rank) if args.full else None
     if world != args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus} inside a job of WORLD_SIZE {world}: the two must agree "
                          f"(python -m torch.distributed.run --nproc-per-node {args.gpus} ... bench.py --gpus {args.gpus}, or plain python bench.py --gpus {args.gpus})")
@@ -371,14 +406,26 @@ def main():
     all_elapsed = [r[0] for r in regions]
     median_at = sorted(range(len(regions)), key=lambda i: regions[i][0])[(len(regions) - 1) // 2]
     elapsed, stage_ms, stage_meta = regions[median_at]                                               # the median series
-    if len(ctxs) > 1:                           # per-stage device times of one clip, outside the timed region
+    # what the timed path returned in its last step, before anything else runs on the contexts
+    out = got = None
+    if sharded:
+        if args.dump_outputs:
+            got = shard.gather(0)                # a collective: every rank sends its owned samples, the root gets the clip
+    else:
+        out = ctxs[-1].download()
+        assert out.shape[-2:] == clip.shape and np.all(np.isfinite(out)), "separation produced non-finite samples"
+    if args.dump_outputs and rank == 0:
+        if not sharded and len(ctxs) > 1:
+            got = np.stack([c.download() for c in ctxs[:-1]] + [out])
+        dump_outputs(args.dump_outputs, {"background": got if got is not None else out})
+    if args.full and len(ctxs) > 1:             # per-stage device times of one clip, outside the timed region
         for _ in range(args.steps):
             tm = ctxs[0].execute(args.algo, params, timing=True)
             for s in tm["stages"]:
                 stage_ms[s["name"]] = stage_ms.get(s["name"], 0.0) + s["ms"]
                 stage_meta[s["name"]] = s
     verified = None
-    if sharded:
+    if sharded and args.full:
         # per-stage device times of rank 0's range (outside the timed region; what the steps add on top is the border exchange)
         if shard.ctx is not None and rank == 0:
             for _ in range(args.steps):
@@ -399,21 +446,19 @@ def main():
             verified = {"ok": bool(np.all(np.isfinite(got)) and worst <= 2e-6), "max_abs_difference": worst, "tolerance": 2e-6,
                         "how": "all ranks' owned samples gathered on the root vs the root's own single-GPU repet.extended of the whole clip "
                                "(a border sample is the fp32 sum of two ranks' rounded products where one GPU uses a fused multiply-add)"}
+    if sharded:
         ctx = shard.ctx
-    else:
-        out = ctxs[-1].download()
-        assert out.shape[-2:] == clip.shape and np.all(np.isfinite(out)), "separation produced non-finite samples"
-        if dist is not None:
-            # every rank checks one of its own clips against a fresh single call on its device: bit for bit
-            probe = ctxs[-1]
-            one = out if out.ndim == 2 else out[-1]
-            repet.set_device(local_rank)
-            same = bool(np.array_equal(one, getattr(repet, args.algo)(clips[-1], fs)))
-            flags = [None] * world
-            dist.all_gather_object(flags, same)
-            verified = {"ok": all(flags), "per_rank": flags,
-                        "how": "the last resident clip of every rank == repet.%s of the same array on that rank's GPU, bit for bit" % args.algo}
-    want_scatter = not args.no_scatter and args.config == 2 and example_clip is None
+    elif dist is not None and args.full:
+        # every rank checks one of its own clips against a fresh single call on its device: bit for bit
+        probe = ctxs[-1]
+        one = out if out.ndim == 2 else out[-1]
+        repet.set_device(local_rank)
+        same = bool(np.array_equal(one, getattr(repet, args.algo)(clips[-1], fs)))
+        flags = [None] * world
+        dist.all_gather_object(flags, same)
+        verified = {"ok": all(flags), "per_rank": flags,
+                    "how": "the last resident clip of every rank == repet.%s of the same array on that rank's GPU, bit for bit" % args.algo}
+    want_scatter = args.full and not args.no_scatter and args.config == 2 and example_clip is None
     line = None
 
     if rank == 0:
@@ -527,35 +572,37 @@ def main():
             stages.append(entry)
         # the dominant KERNEL: "peaks+rank_columns" is two chains of seven launches side by side on two streams, not a kernel --
         # the line names both: the longest stage by time (dominant_stage) and the longest single-kernel stage (kernel, priced)
-        single = [s for s in stages if s["name"] != "peaks+rank_columns"] or stages
-        dom = max(single, key=lambda s: s["ms"])
-        longest = max(stages, key=lambda s: s["ms"])
-        roof = {"kernel": dom["name"], "dominant_stage": {"name": longest["name"], "ms": longest["ms"],
-                                                           "is_a_single_kernel": longest["name"] != "peaks+rank_columns"}}
-        roof.update({k: dom[k] for k in ("bound", "achieved", "peak", "unit", "frac") if k in dom})
-        roof["traffic"] = None
-        # HBM-side bytes per launch of the dominant kernel: NOT measured by this run -- read from the committed PMC pass of
-        # this same workload and build (profiles/), if there is one for it
-        try:
-            if args.config == 2 and args.algo == "sim" and args.duration == 180.0:
-                with open(os.path.join(ROOT, "profiles", PMC_FILE)) as fh:
-                    doc = json.load(fh)
-                pmc = doc["stages"][dom["name"].replace("_f16x3", "")]
-                import hashlib
-                with open(_native.LIB_PATH, "rb") as fh:
-                    lib_sha = hashlib.sha256(fh.read()).hexdigest()
-                roof["traffic"] = pmc["hbm_bytes_per_launch"]
-                roof["traffic_source"] = f"profiles/{PMC_FILE} (committed rocprofv3 --pmc pass of this workload; static, not measured in this run); " \
-                                         "FETCH_SIZE*1024*k + WRITE_SIZE*1024 per launch, fetch correction " + pmc["fetch_correction"]
-                roof["traffic_library_sha256"] = doc.get("library_sha256")
-                roof["traffic_is_of_this_library"] = doc.get("library_sha256") == lib_sha
-        except (OSError, KeyError, ValueError):
-            pass
-        roof["ms_per_launch"] = dom["ms"]
-        roof["algorithmic_per_launch"] = dom.get("algorithmic")
-        for extra in ("network", "survey_8d_bytes", "fp32_equivalent", "frac_vs_full_rate_valu", "full_rate_valu_peak", "peak_note", "valu_view", "planes", "k_mean"):
-            if extra in dom:
-                roof[extra] = dom[extra]
+        roof = None                      # (no stage times: several clips per rank, or a sharded clip, without --full)
+        if stages:
+            single = [s for s in stages if s["name"] != "peaks+rank_columns"] or stages
+            dom = max(single, key=lambda s: s["ms"])
+            longest = max(stages, key=lambda s: s["ms"])
+            roof = {"kernel": dom["name"], "dominant_stage": {"name": longest["name"], "ms": longest["ms"],
+                                                               "is_a_single_kernel": longest["name"] != "peaks+rank_columns"}}
+            roof.update({k: dom[k] for k in ("bound", "achieved", "peak", "unit", "frac") if k in dom})
+            roof["traffic"] = None
+            # HBM-side bytes per launch of the dominant kernel: NOT measured by this run -- read from the committed PMC pass of
+            # this same workload and build (profiles/), if there is one for it
+            try:
+                if args.config == 2 and args.algo == "sim" and args.duration == 180.0:
+                    with open(os.path.join(ROOT, "profiles", PMC_FILE)) as fh:
+                        doc = json.load(fh)
+                    pmc = doc["stages"][dom["name"].replace("_f16x3", "")]
+                    import hashlib
+                    with open(_native.LIB_PATH, "rb") as fh:
+                        lib_sha = hashlib.sha256(fh.read()).hexdigest()
+                    roof["traffic"] = pmc["hbm_bytes_per_launch"]
+                    roof["traffic_source"] = f"profiles/{PMC_FILE} (committed rocprofv3 --pmc pass of this workload; static, not measured in this run); " \
+                                             "FETCH_SIZE*1024*k + WRITE_SIZE*1024 per launch, fetch correction " + pmc["fetch_correction"]
+                    roof["traffic_library_sha256"] = doc.get("library_sha256")
+                    roof["traffic_is_of_this_library"] = doc.get("library_sha256") == lib_sha
+            except (OSError, KeyError, ValueError):
+                pass
+            roof["ms_per_launch"] = dom["ms"]
+            roof["algorithmic_per_launch"] = dom.get("algorithmic")
+            for extra in ("network", "survey_8d_bytes", "fp32_equivalent", "frac_vs_full_rate_valu", "full_rate_valu_peak", "peak_note", "valu_view", "planes", "k_mean"):
+                if extra in dom:
+                    roof[extra] = dom[extra]
         line = {
             "metric": f"audio-seconds/sec (x real-time) for repet.{args.algo}, {fs / 1000:g} kHz {'stereo' if channels == 2 else str(channels) + '-ch'}",
             "value": round(args.duration * args.clips * args.steps * (1 if sharded else world) / elapsed, 2),
@@ -593,7 +640,7 @@ def main():
                 "largest_level1_minus_level2": ex["level2_max_diff"], "input_has_remainders": ex["input_has_remainders"],
                 "note": "rows whose float64 verdicts on the fp32 spectra are closer than 2.5e-7 are decided again from float64 spectra "
                         "(inside the peak-picking stage's time); REPET_PEAK_EXACT=0 turns it off"}
-        if world == 1:
+        if args.full and world == 1:
             # PCIe-inclusive drop-in call (float64 NumPy in host RAM -> float64 NumPy out): reported beside `value`,
             # never as `value`. Includes upload, f64->f32, the run, f32->f64 and download. Twice: the synthetic
             # clip as it is (float64 noise: the fp32 remainders of the samples travel too, for the float64 spectra of the
@@ -629,7 +676,7 @@ def main():
                 pcm_clip = np.round(clip * 32768.0).clip(-32768, 32767) / 32768.0
                 line["array_in_array_out_pcm16"] = with_floor(drop_in(pcm_clip))
                 line["array_in_array_out_pcm16"]["note"] = "the same call on the clip rounded to 16-bit PCM values (float64 array, exact in fp32: no remainders travel)"
-        if world == 1 and args.config == 2 and not args.no_variants and example_clip is None and "peaks+rank_columns" in stage_ms:
+        if args.full and world == 1 and args.config == 2 and not args.no_variants and example_clip is None and "peaks+rank_columns" in stage_ms:
             # "peaks+rank_columns" is two chains of kernels side by side on two streams. A child run with REPET_RANK_OVERLAP=0 puts
             # the sort BEHIND the peak picking on the main stream with a timing mark behind every kernel: live per-kernel times,
             # each priced on what binds THAT kernel (SURVEY 8d's 4 T^2 bytes for this stage are not read any more: the peak
@@ -714,7 +761,7 @@ def main():
             for st in stages:
                 if st["name"] == roof["dominant_stage"]["name"] and "frac" in st and not roof["dominant_stage"]["is_a_single_kernel"]:
                     roof["dominant_stage"].update({k: st[k] for k in ("bound", "achieved", "peak", "unit", "frac", "chains_alone_ms") if k in st})
-        if world == 1 and args.config == 2 and not args.no_variants and example_clip is None and args.clips == 1:
+        if args.full and world == 1 and args.config == 2 and not args.no_variants and example_clip is None and args.clips == 1:
             # A GPU that serves INDEPENDENT clips can keep several in flight: three contexts (three streams, three resident clips)
             # fill the latency-bound stages of one another. Beside the headline, never instead of it (the metric is quoted on one clip).
             import subprocess
@@ -727,7 +774,7 @@ def main():
                                                  "note": "three contexts, one clip and stream each, a step = the three separations enqueued together and awaited"}
             except Exception as exc:  # noqa: BLE001
                 line["three_clips_in_flight"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and args.config == 2 and not args.no_variants and example_clip is None:
+        if args.full and world == 1 and args.config == 2 and not args.no_variants and example_clip is None:
             # north_star names an fp32 MFMA GEMM for the similarity matrix; the default is the f16x3 split of the fp32 operands.
             # The exact-fp32 kernel (REPET_GRAM=f32, read once per process) is timed by a child run of this script.
             import subprocess

@@ -185,7 +185,7 @@ def _bench(args, env_extra, timeout=900):
 def test_bench_config3_sharded_over_ranks_dry_run():
     """`bench.py --gpus 3 --config 3` with the ranks sharing this box's GPU: ONE 600-s clip, 119 segments in three contiguous
     ranges, border exchange inside the step, result gathered and compared with the root's single-GPU separation."""
-    line = _bench(["--gpus", "3", "--config", "3", "--steps", "2", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
+    line = _bench(["--full", "--gpus", "3", "--config", "3", "--steps", "2", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
                   {"REPET_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == 3 and line["scaling"] == "strong" and line["ranks_share_gpus"] is True and line["backend"] == "gloo"
     assert line["verified"]["ok"] is True and line["verified"]["max_abs_difference"] <= 2e-6
@@ -196,10 +196,10 @@ def test_bench_config3_sharded_over_ranks_dry_run():
 def test_bench_config5_and_config2_over_ranks_dry_run():
     """config 5: 64 clips in total, 32 per rank at N = 2 (strong scaling), every rank verifies a clip of its batch against the
     single call; config 2: one clip per rank (weak) and the scatter / gather leg, verified bit for bit against the root."""
-    line = _bench(["--gpus", "2", "--config", "5", "--steps", "1", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
+    line = _bench(["--full", "--gpus", "2", "--config", "5", "--steps", "1", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
                   {"REPET_BENCH_BACKEND": "gloo"})
     assert line["scaling"] == "strong" and line["config"]["clips_per_step"] == 64 and line["verified"]["ok"] is True
-    line = _bench(["--gpus", "2", "--duration", "40", "--steps", "2", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
+    line = _bench(["--full", "--gpus", "2", "--duration", "40", "--steps", "2", "--warmup", "1", "--series", "1", "--prewarm-ms", "5"],
                   {"REPET_BENCH_BACKEND": "gloo"})
     assert line["scaling"] == "weak" and line["verified"]["ok"] is True and line["verified"]["per_rank"] == [True, True]
     sg = line["scatter_gather"]
@@ -246,7 +246,7 @@ def test_bench_over_rccl_verifies_itself():
     """The driver's command on every device this node has: config 3 (segment ranges + border exchange over xGMI) and config 2
     with the scatter / gather leg; both lines must carry a passed verification and rccl_ranks == N."""
     n = _device_count()
-    line = _bench(["--gpus", str(n), "--config", "3", "--steps", "5", "--warmup", "2", "--series", "2"], {})
+    line = _bench(["--full", "--gpus", str(n), "--config", "3", "--steps", "5", "--warmup", "2", "--series", "2"], {})
     assert line["rccl_ranks"] == n and line["backend"] == "nccl" and line["verified"]["ok"] is True and line["scaling"] == "strong"
-    line = _bench(["--gpus", str(n), "--steps", "5", "--warmup", "2", "--series", "2"], {})
+    line = _bench(["--full", "--gpus", str(n), "--steps", "5", "--warmup", "2", "--series", "2"], {})
     assert line["rccl_ranks"] == n and line["verified"]["ok"] is True and line["scatter_gather"]["verified"] is True
