@@ -46,7 +46,9 @@ typedef enum repet_algo {
     REPET_SIMONLINE = 4  /* repet.py:712-911 */
 } repet_algo;
 
-typedef enum repet_dtype { REPET_F32 = 0, REPET_F64 = 1, REPET_I16 = 2 } repet_dtype;
+/* REPET_F16 / REPET_BF16: the device-side entries only (repet_ctx_upload_device_strided, repet_run_device); the host entries
+ * refuse them. */
+typedef enum repet_dtype { REPET_F32 = 0, REPET_F64 = 1, REPET_I16 = 2, REPET_F16 = 3, REPET_BF16 = 4 } repet_dtype;
 
 /* The reference's nine module globals (repet.py:42-63), already converted to frames/bins/samples. */
 typedef struct repet_params {
@@ -158,6 +160,23 @@ int repet_ctx_upload_device(repet_ctx* ctx, const float* dev_audio, int64_t n_sa
 int repet_ctx_upload_device_split(repet_ctx* ctx, const float* dev_audio, const float* dev_audio_lo, int64_t n_samples,
                                   int32_t n_channels, int32_t n_clips);
 int repet_ctx_download_device(repet_ctx* ctx, float* dev_out);
+/* Device-resident caller buffers of any layout (torch tensors on a ROCm device, a C++ host's own buffers), ordered by events
+ * on the caller's stream; neither call waits on the host. Element i of the source is src[b * strides[0] + n * strides[1] +
+ * c * strides[2]] for clip b, sample n, channel c (ELEMENT strides, non-negative: channels-first views, step slices and batch
+ * slices are read as they lie).
+ * repet_ctx_upload_device_strided : the context's stream waits for what `wait_stream` (a hipStream_t; NULL: the null stream)
+ *     has enqueued so far, then narrows the source (REPET_F64 / F32 / I16 / F16 / BF16) into the resident fp32 samples --
+ *     and, for REPET_F64, their fp32 remainders (see repet_ctx_upload_device_split): the planes a host upload of the same
+ *     values leaves, bit for bit. The context is left as repet_ctx_upload_device_split leaves it (the planes are not scanned).
+ *     REPET_FLAG_REFUSE_NONFINITE (repet_ctx_set_strict_reference(ctx, 0)) is the one case that waits: the ingest notes a
+ *     sample that is not finite and the call reads that note back (one host wait) to refuse such a clip as the host path does.
+ * repet_ctx_download_device_strided : the result widened into `dst` (REPET_F64: (double)v; or REPET_F32) of shape
+ *     [n_clips][n_samples][n_channels] with the given strides (elements must not overlap), enqueued on the context's stream
+ *     behind what `signal_stream` has enqueued so far; `signal_stream` then waits for it, so the caller's next work on that
+ *     stream sees the result. */
+int repet_ctx_upload_device_strided(repet_ctx* ctx, const void* src, int dtype, int32_t n_clips, int64_t n_samples,
+                                    int32_t n_channels, const int64_t strides[3], void* wait_stream);
+int repet_ctx_download_device_strided(repet_ctx* ctx, void* dst, int dtype, const int64_t strides[3], void* signal_stream);
 /* (ABI 3) Borrowed views for a host that keeps the exchange on the device (one process per GPU, torch.distributed over
  * RCCL: repet/parallel.py). The pointers stay valid until the next upload of this context (a larger clip may move the
  * buffers); what a run writes into the result is ordered on the context's stream, which repet_ctx_stream hands out so that
@@ -253,6 +272,13 @@ int repet_median_network_info(int32_t list_bound, int32_t* network_size, int32_t
 int repet_release_thread_ctx(void);
 int repet_run(int algo, const void* audio, int dtype, int64_t n_samples, int32_t n_channels,
               const repet_params* p, double* out, int device, repet_timing* timing /* nullable */);
+/* The device-side twin of repet_run, for a host that keeps its audio on the GPU and has a HIP stream of its own: the same
+ * per-thread, per-device context; ingest (repet_ctx_upload_device_strided, waiting for `stream`), repet_ctx_execute_async and
+ * egress into `dst` (out_dtype REPET_F64 or REPET_F32, signalling `stream`), all ordered on `stream` without a host wait
+ * (except for REPET_FLAG_REFUSE_NONFINITE, see above, and the one-time growth of workspaces on a new shape). */
+int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n_samples, int32_t n_channels,
+                     const int64_t in_strides[3], void* dst, int out_dtype, const int64_t out_strides[3],
+                     const repet_params* p, int device, void* stream);
 
 /* Batch of independent clips dealt round-robin (longest first) over n_devices GPUs of this process: one host thread,
  * context and stream per device; every device uploads its own clips from the caller's arrays and downloads its own

@@ -1,0 +1,345 @@
+// Device-side ingest and egress of caller tensors (torch tensors on a ROCm device, a C++ host's own buffers): the engine's
+// fp32 interleaved planes are filled from, and its result is widened into, device memory of any layout the caller holds --
+// (n_clips, n_samples, n_channels) with arbitrary non-negative element strides -- ordered on the caller's stream by events,
+// with no host wait and no host bounce.
+//   ingest  source (F64 / F32 / I16 / F16 / BF16, strided) -> audio [clip][n][c] fp32, and for F64 also audio_lo, the fp32
+//           remainders: hi = (float)x, lo = (float)(x - (double)hi) -- exactly what narrow_f64 / split_part of hostio.hip
+//           produce, so the planes equal a host upload's bit for bit. I16 is the raw (float) cast of narrow_i16; F16 / BF16
+//           widen exactly. With a flag word it also notes a sample that is not finite (the refusal mode reads it).
+//   egress  out [clip][n][c] fp32 -> destination (F64: (double)v as widen_f32 does, or F32), strided.
+// Both are bandwidth kernels: every thread owns a few consecutive elements of the interleaved side, which it reads or writes
+// with one vector access, so that each 128-byte line of that side is moved whole by one instruction of one wave; the strided
+// side takes element accesses, vector ones when it is the same dense layout and aligned.
+#include "engine.h"
+
+namespace repet {
+namespace {
+
+constexpr int kIoThreads = 256;
+
+struct IoGeo {
+    int64_t count;                 // n_clips * n_samples * n_channels
+    int64_t n_samples;
+    int32_t n_channels;
+    int64_t s_clip, s_sample, s_channel;   // element strides of the strided side
+};
+
+// element i of the interleaved side -> offset on the strided side (i is the first of a thread's run; the rest step along)
+struct Walker {
+    int64_t b, n, c, off;
+    __device__ Walker(const IoGeo& g, int64_t i) {
+        c = i % g.n_channels;
+        const int64_t t = i / g.n_channels;
+        n = t % g.n_samples;
+        b = t / g.n_samples;
+        off = b * g.s_clip + n * g.s_sample + c * g.s_channel;
+    }
+    __device__ void next(const IoGeo& g) {
+        if (++c < g.n_channels) { off += g.s_channel; return; }
+        c = 0;
+        if (++n < g.n_samples) { off += g.s_sample - (int64_t)(g.n_channels - 1) * g.s_channel; return; }
+        n = 0; ++b;
+        off = b * g.s_clip;
+    }
+};
+
+template <typename T> struct Src;
+template <> struct Src<double> { static __device__ double load(const double* p) { return *p; } };
+template <> struct Src<float> { static __device__ float load(const float* p) { return *p; } };
+template <> struct Src<int16_t> { static __device__ float load(const int16_t* p) { return (float)*p; } };
+struct Half { uint16_t bits; };
+__device__ inline float h2f(uint16_t bits) { return (float)__builtin_bit_cast(_Float16, bits); }
+struct BHalf { uint16_t bits; };
+template <> struct Src<Half> { static __device__ float load(const Half* p) { return h2f(p->bits); } };
+template <> struct Src<BHalf> { static __device__ float load(const BHalf* p) { return __uint_as_float((uint32_t)p->bits << 16); } };
+
+template <typename T> __device__ inline bool not_finite(T v);
+template <> __device__ inline bool not_finite<double>(double v) { return !(fabs(v) <= 1.7976931348623157e308); }
+template <> __device__ inline bool not_finite<float>(float v) { return !(fabsf(v) <= 3.402823466e38f); }
+
+// one sample -> (hi, lo); lo only for float64 sources
+template <typename T> __device__ inline void split1(const T* src, float& hi, float& lo, bool& bad, bool check) {
+    auto x = Src<T>::load(src);
+    if constexpr (std::is_same<T, double>::value) {
+        hi = (float)x;
+        lo = (float)(x - (double)hi);
+        if (check) bad |= not_finite(x);
+    } else {
+        hi = x; lo = 0.f;
+        if (check && !std::is_same<T, int16_t>::value) bad |= not_finite(hi);
+    }
+}
+
+// dense source (its layout IS the interleaved one) aligned for a 4-element vector load
+template <typename T> __device__ inline void load4_dense(const T* src, float (&hi)[4], float (&lo)[4]);
+template <> __device__ inline void load4_dense<double>(const double* src, float (&hi)[4], float (&lo)[4]) {
+    const double2 a = reinterpret_cast<const double2*>(src)[0], b = reinterpret_cast<const double2*>(src)[1];
+    const double x[4] = {a.x, a.y, b.x, b.y};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { hi[k] = (float)x[k]; lo[k] = (float)(x[k] - (double)hi[k]); }
+}
+// (the float64 check is on the double itself: a finite sample above FLT_MAX narrows to inf but is not refused, as on the host)
+__device__ inline bool dense_not_finite(const double* src) {
+    const double2 a = reinterpret_cast<const double2*>(src)[0], b = reinterpret_cast<const double2*>(src)[1];
+    return not_finite(a.x) || not_finite(a.y) || not_finite(b.x) || not_finite(b.y);
+}
+template <> __device__ inline void load4_dense<float>(const float* src, float (&hi)[4], float (&lo)[4]) {
+    const float4 a = *reinterpret_cast<const float4*>(src);
+    hi[0] = a.x; hi[1] = a.y; hi[2] = a.z; hi[3] = a.w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lo[k] = 0.f;
+}
+template <> __device__ inline void load4_dense<int16_t>(const int16_t* src, float (&hi)[4], float (&lo)[4]) {
+    const short4 a = *reinterpret_cast<const short4*>(src);
+    hi[0] = (float)a.x; hi[1] = (float)a.y; hi[2] = (float)a.z; hi[3] = (float)a.w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lo[k] = 0.f;
+}
+template <> __device__ inline void load4_dense<Half>(const Half* src, float (&hi)[4], float (&lo)[4]) {
+    const ushort4 a = *reinterpret_cast<const ushort4*>(src);
+    hi[0] = h2f(a.x); hi[1] = h2f(a.y);
+    hi[2] = h2f(a.z); hi[3] = h2f(a.w);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lo[k] = 0.f;
+}
+template <> __device__ inline void load4_dense<BHalf>(const BHalf* src, float (&hi)[4], float (&lo)[4]) {
+    const ushort4 a = *reinterpret_cast<const ushort4*>(src);
+    hi[0] = __uint_as_float((uint32_t)a.x << 16); hi[1] = __uint_as_float((uint32_t)a.y << 16);
+    hi[2] = __uint_as_float((uint32_t)a.z << 16); hi[3] = __uint_as_float((uint32_t)a.w << 16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lo[k] = 0.f;
+}
+
+// Four consecutive interleaved elements per thread: one dwordx4 store per plane, 1 KiB per wave instruction.
+template <typename T>
+__device__ inline void ingest_body(const T* __restrict__ src, IoGeo g, int dense, float* __restrict__ hi_out,
+                                   float* __restrict__ lo_out, unsigned int* nonfinite) {
+    constexpr bool kSplit = std::is_same<T, double>::value;
+    const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * 4;
+    if (i0 >= g.count) return;
+    const bool check = nonfinite != nullptr;
+    bool bad = false;
+    float hi[4], lo[4];
+    if (i0 + 4 <= g.count) {
+        if (dense) {
+            load4_dense<T>(src + i0, hi, lo);
+            if (check) {
+                if constexpr (kSplit) bad |= dense_not_finite(src + i0);
+                else if constexpr (!std::is_same<T, int16_t>::value) {
+                    for (int k = 0; k < 4; ++k) bad |= not_finite(hi[k]);
+                }
+            }
+        } else {
+            Walker w(g, i0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                split1<T>(src + w.off, hi[k], lo[k], bad, check);
+                if (k < 3) w.next(g);
+            }
+        }
+        *reinterpret_cast<float4*>(hi_out + i0) = make_float4(hi[0], hi[1], hi[2], hi[3]);
+        if constexpr (kSplit) *reinterpret_cast<float4*>(lo_out + i0) = make_float4(lo[0], lo[1], lo[2], lo[3]);
+    } else {                                                      // the tail of the plane: one thread, element by element
+        Walker w(g, i0);
+        for (int64_t i = i0; i < g.count; ++i) {
+            float h, l;
+            split1<T>(src + w.off, h, l, bad, check);
+            hi_out[i] = h;
+            if constexpr (kSplit) lo_out[i] = l;
+            w.next(g);
+        }
+    }
+    if (bad) *nonfinite = 1u;                                     // (every writer stores the same value)
+}
+
+// Egress: EPT consecutive interleaved elements per thread, read with one vector load (F64: 2 -> float2 in, double2 out;
+// F32: 4 -> float4 in and out), so that the interleaved side and a dense destination move whole lines per instruction.
+template <typename T, int EPT>
+__device__ inline void egress_body(const float* __restrict__ in, IoGeo g, int dense, T* __restrict__ dst) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * EPT;
+    if (i0 >= g.count) return;
+    if (i0 + EPT <= g.count) {
+        float v[EPT];
+        if constexpr (EPT == 2) { const float2 a = *reinterpret_cast<const float2*>(in + i0); v[0] = a.x; v[1] = a.y; }
+        else { const float4 a = *reinterpret_cast<const float4*>(in + i0); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
+        if (dense) {
+            if constexpr (EPT == 2) *reinterpret_cast<double2*>(dst + i0) = make_double2((double)v[0], (double)v[1]);
+            else *reinterpret_cast<float4*>(dst + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            Walker w(g, i0);
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) {
+                dst[w.off] = (T)v[k];
+                if (k < EPT - 1) w.next(g);
+            }
+        }
+    } else {
+        Walker w(g, i0);
+        for (int64_t i = i0; i < g.count; ++i) { dst[w.off] = (T)in[i]; w.next(g); }
+    }
+}
+
+// stable names, one per source / destination type (rocprofv3 rows)
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_f64(const double* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<double>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_f32(const float* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<float>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_i16(const int16_t* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<int16_t>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_f16(const Half* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<Half>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_bf16(const BHalf* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<BHalf>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_egress_f64(const float* in, IoGeo g, int dense, double* dst) { egress_body<double, 2>(in, g, dense, dst); }
+__global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, IoGeo g, int dense, float* dst) { egress_body<float, 4>(in, g, dense, dst); }
+
+int element_size(int dtype) {
+    switch (dtype) {
+        case REPET_F64: return 8;
+        case REPET_F32: return 4;
+        default: return 2;
+    }
+}
+
+// the strided side is the interleaved layout itself (strides of a C-contiguous [clip][n][c]; a size-1 dimension's stride
+// does not matter) and its base allows a vector access of `vec_bytes`
+bool is_dense(const void* p, const IoGeo& g, int32_t n_clips, int vec_bytes) {
+    if (reinterpret_cast<uintptr_t>(p) % vec_bytes) return false;
+    if (g.n_channels > 1 && g.s_channel != 1) return false;
+    if (g.n_samples > 1 && g.s_sample != g.n_channels) return false;
+    if (n_clips > 1 && g.s_clip != g.n_samples * g.n_channels) return false;
+    return true;
+}
+
+}  // namespace
+}  // namespace repet
+
+using namespace repet_eng;
+using namespace repet;
+
+namespace repet_eng {
+
+static int check_strides(const int64_t* strides) {
+    if (!strides) return fail(REPET_ERR_BAD_ARG, "strides is null");
+    for (int k = 0; k < 3; ++k)
+        if (strides[k] < 0) return fail(REPET_ERR_BAD_ARG, "negative stride (make the tensor contiguous first)");
+    return REPET_OK;
+}
+
+// a destination whose elements do not overlap: with its dimensions of more than one element ordered by stride, each stride
+// must step past everything the smaller ones span (a stride-0 `expand` view, or any other aliasing, would have several egress
+// threads write different values to one address)
+static int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch) {
+    const int64_t size[3] = {n_clips, n, ch};
+    int order[3] = {0, 1, 2};
+    std::sort(order, order + 3, [&](int a, int b) { return strides[a] < strides[b]; });
+    int64_t span = 0;                                 // largest offset reachable through the dimensions taken so far
+    for (int k : order) {
+        if (size[k] <= 1) continue;
+        if (strides[k] <= span) return fail(REPET_ERR_BAD_ARG, "the destination's elements overlap (an expanded or aliasing view)");
+        span += strides[k] * (size[k] - 1);
+    }
+    return REPET_OK;
+}
+
+static int ensure_io_events(repet_ctx* c) {
+    if (!c->io_wait) HIP_TRY(hipEventCreateWithFlags(&c->io_wait, hipEventDisableTiming));
+    if (!c->io_done) HIP_TRY(hipEventCreateWithFlags(&c->io_done, hipEventDisableTiming));
+    return REPET_OK;
+}
+
+}  // namespace repet_eng
+
+extern "C" {
+
+int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch,
+                                    const int64_t strides[3], void* wait_stream) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (n < 0 || ch < 1 || n_clips < 1) return fail(REPET_ERR_BAD_ARG, "audio_signal must be (number_samples, number_channels)");
+    if (dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "unsupported dtype");
+    RP_TRY(check_strides(strides));
+    const int64_t count = n * ch * n_clips;
+    if (count > 0 && !src) return fail(REPET_ERR_BAD_ARG, "null argument");
+    DeviceGuard guard(c->device);
+    HIP_TRY(c->audio.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
+    HIP_TRY(c->out.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
+    if (dtype == REPET_F64) HIP_TRY(c->audio_lo.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
+    RP_TRY(ensure_io_events(c));
+    // the producer of `src` is the caller's stream: the context's stream starts the ingest behind what it has enqueued so far
+    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(wait_stream)));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    // a float64 host upload of this context may still have its remainder plane on the way into audio_lo (copy stream): the
+    // ingest must land after it, not under it. (lo_in_flight stays set: the host has not seen the copy finish, and the ring's
+    // remainder buffer must not be refilled before it has -- StagingRing waits for lo_done then.)
+    if (c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
+    const bool refuse = !c->strict;
+    unsigned int* flag = nullptr;
+    if (refuse) {
+        HIP_TRY(c->nonfinite_word.ensure(sizeof(unsigned int)));
+        flag = c->nonfinite_word.as<unsigned int>();
+        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
+    }
+    if (count > 0) {
+        IoGeo g{count, n, ch, strides[0], strides[1], strides[2]};
+        const int vec_bytes = dtype == REPET_F64 ? 16 : 4 * element_size(dtype);
+        const int dense = is_dense(src, g, n_clips, vec_bytes) ? 1 : 0;
+        const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
+        float* hi = c->audio.as<float>();
+        float* lo = c->audio_lo.as<float>();
+        switch (dtype) {
+            case REPET_F64: devio_ingest_f64<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const double*>(src), g, dense, hi, lo, flag); break;
+            case REPET_F32: devio_ingest_f32<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag); break;
+            case REPET_I16: devio_ingest_i16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag); break;
+            case REPET_F16: devio_ingest_f16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag); break;
+            default: devio_ingest_bf16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (refuse) {
+        // the refusal mode's one host wait: the flag word decides whether the clip is accepted
+        unsigned int seen = 0;
+        HIP_TRY(hipMemcpyAsync(&seen, flag, sizeof(seen), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (seen) {
+            c->n_channels = 0;
+            return fail(REPET_ERR_BAD_ARG, "audio_signal contains NaN or infinite samples");
+        }
+    }
+    // as repet_ctx_upload_device_split leaves it: device planes are not scanned (strict mode never reads the flag word),
+    // what they hold is computed on; a float64 source always brings its remainder plane
+    c->has_lo = dtype == REPET_F64 && count > 0;
+    c->input_not_finite = false;
+    c->input_unscanned = true;
+    c->n_samples = n; c->n_channels = ch; c->n_clips = n_clips; c->clip_base = 0;
+    c->win_total = 0; c->win_offset = 0;
+    return REPET_OK;
+}
+
+int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const int64_t strides[3], void* signal_stream) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
+    if (dtype != REPET_F32 && dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_strides(strides));
+    RP_TRY(check_no_overlap(strides, c->n_clips, c->n_samples, c->n_channels));
+    const int64_t count = c->n_samples * c->n_channels * c->n_clips;
+    if (count > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null argument");
+    DeviceGuard guard(c->device);
+    RP_TRY(ensure_io_events(c));
+    // the destination belongs to the caller's stream: what that stream has enqueued up to now (a pending reader of a block the
+    // caching allocator has just handed out again, the caller's own writes to `dst`) comes before the egress writes it
+    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(signal_stream)));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    if (count > 0) {
+        IoGeo g{count, c->n_samples, c->n_channels, strides[0], strides[1], strides[2]};
+        const float* in = c->out.as<float>();
+        if (dtype == REPET_F64) {
+            const dim3 grid((unsigned)ceil_div(ceil_div(count, 2), kIoThreads));
+            devio_egress_f64<<<grid, kIoThreads, 0, c->stream>>>(in, g, is_dense(dst, g, c->n_clips, 16) ? 1 : 0, static_cast<double*>(dst));
+        } else {
+            const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
+            devio_egress_f32<<<grid, kIoThreads, 0, c->stream>>>(in, g, is_dense(dst, g, c->n_clips, 16) ? 1 : 0, static_cast<float*>(dst));
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    // the caller's stream continues behind the egress
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+}  // extern "C"

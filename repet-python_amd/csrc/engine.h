@@ -113,6 +113,10 @@ struct repet_ctx {
     // the resident clip was never scanned (device planes -- the RCCL transport, torch tensors --, float WAVE payloads): under
     // `strict` the passes that reproduce the reference on such samples then run unconditionally (they cost microseconds)
     bool input_unscanned = false;
+    // device-side ingest / egress of caller buffers (devio.hip): the context's stream waits on io_wait recorded on the
+    // caller's stream, the caller's stream on io_done recorded behind the egress; the refusal mode's non-finite flag word
+    hipEvent_t io_wait = nullptr, io_done = nullptr;
+    DevBuf nonfinite_word;
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
     DevBuf X, V, Vn, P, S, band, beat, idx, cnt, periods, win_periods, frames, tmp_a, tmp_b, tmp_c;
@@ -136,8 +140,10 @@ struct repet_ctx {
     // geometry for which the constant median-pad rows of R are in place (they survive every run of that geometry)
     const void* r_pads_ptr = nullptr; int64_t r_pads_stride = 0, r_pads_row = 0; int r_pads_channels = 0, r_pads_fs = 0;
     std::map<int, std::unique_ptr<Tables>> tables;
-    DevBuf tiles;                 // Gram tile list of the last (nb, ndiag)
-    int tiles_nb = -1, tiles_ndiag = -1, tiles_count = 0;
+    // Gram tile lists by (nb, ndiag), kept side by side: variants that alternate on one context (each with its own list) do
+    // not rebuild one -- and wait for the stream to drain before overwriting it -- on every call
+    struct TileList { DevBuf buf; int count = 0; };
+    std::map<std::pair<int, int>, TileList> tile_lists;
     DevBuf tiles_big;             // upper-triangle list of 256 x 256 tiles (gram_f16_big.hip)
     int tiles_big_nb = -1, tiles_big_count = 0;
     // last run

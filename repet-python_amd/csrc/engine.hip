@@ -93,17 +93,30 @@ int upload_twiddle_only(repet_ctx* c, int W, const float2** tw) {
 int get_tiles(repet_ctx* c, int64_t T, int ndiag, const int2** tiles, int* count) {
     const int nb = (int)ceil_div(T, kTile);
     if (ndiag > nb) ndiag = nb;
-    if (c->tiles_nb != nb || c->tiles_ndiag != ndiag) {
+    const std::pair<int, int> key(nb, ndiag);
+    auto it = c->tile_lists.find(key);
+    if (it == c->tile_lists.end()) {
+        constexpr size_t kMaxLists = 8;                     // (a few KB each; a context that has seen many clip lengths starts over)
+        if (c->tile_lists.size() >= kMaxLists) {
+            HIP_TRY(hipStreamSynchronize(c->stream));      // the lists may still be in use
+            for (auto& kv : c->tile_lists) kv.second.buf.release();
+            c->tile_lists.clear();
+        }
         std::vector<int2> host;
         const int n = gram_tile_list(nb, ndiag, &host);
-        HIP_TRY(hipStreamSynchronize(c->stream));          // the previous list may still be in use
-        HIP_TRY(c->tiles.ensure(std::max<size_t>(host.size() * sizeof(int2), 256)));
-        HIP_TRY(hipMemcpyAsync(c->tiles.p, host.data(), host.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->tiles_nb = nb; c->tiles_ndiag = ndiag; c->tiles_count = n;
+        repet_ctx::TileList list;
+        list.count = n;
+        hipError_t e = list.buf.ensure(std::max<size_t>(host.size() * sizeof(int2), 256));
+        if (e == hipSuccess) e = hipMemcpyAsync(list.buf.p, host.data(), host.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);          // (`host` goes out of scope)
+        if (e != hipSuccess) {                                             // (only a complete list is cached)
+            list.buf.release();
+            return fail(e == hipErrorOutOfMemory ? REPET_ERR_OOM : REPET_ERR_HIP, std::string("tile list: ") + hipGetErrorString(e));
+        }
+        it = c->tile_lists.emplace(key, list).first;
     }
-    *tiles = c->tiles.as<int2>();
-    *count = c->tiles_count;
+    *tiles = it->second.buf.as<int2>();
+    *count = it->second.count;
     return REPET_OK;
 }
 
@@ -570,9 +583,10 @@ int repet_ctx_destroy(repet_ctx* c) {
                       &c->refine_stats, &c->R, &c->Vs, &c->rank_codes, &c->code_planes, &c->median_codes, &c->tiles_big,
                       &c->audio_lo, &c->redo_list, &c->redo_flag, &c->u64, &c->u64_gen, &c->exact_scratch,
                       &c->lite_list, &c->lite_flag, &c->lite_records, &c->frame_list, &c->frame_flag,
-                      &c->seg,
-                      &c->idx, &c->cnt, &c->periods, &c->win_periods, &c->frames, &c->tmp_a, &c->tmp_b, &c->tmp_c, &c->tiles})
+                      &c->seg, &c->nonfinite_word,
+                      &c->idx, &c->cnt, &c->periods, &c->win_periods, &c->frames, &c->tmp_a, &c->tmp_b, &c->tmp_c})
         b->release();
+    for (auto& kv : c->tile_lists) kv.second.buf.release();
     for (auto& kv : c->tables) { kv.second->window.release(); kv.second->twiddle.release(); kv.second->window64.release(); kv.second->twiddle64.release(); }
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
@@ -582,6 +596,8 @@ int repet_ctx_destroy(repet_ctx* c) {
     if (c->join_event) (void)hipEventDestroy(c->join_event);
     if (c->norms_fork) (void)hipEventDestroy(c->norms_fork);
     if (c->norms_done) (void)hipEventDestroy(c->norms_done);
+    if (c->io_wait) (void)hipEventDestroy(c->io_wait);
+    if (c->io_done) (void)hipEventDestroy(c->io_done);
     (void)hipStreamDestroy(c->stream);
     delete c;
     return REPET_OK;
@@ -1139,6 +1155,18 @@ int repet_run(int algo, const void* audio, int dtype, int64_t n, int32_t ch, con
     if (timing) RP_TRY(repet_ctx_execute(c, algo, p, timing));
     else RP_TRY(repet_ctx_execute_async(c, algo, p));
     return repet_ctx_download(c, out);
+}
+
+int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t in_strides[3],
+                     void* dst, int out_dtype, const int64_t out_strides[3], const repet_params* p, int device, void* stream) {
+    repet_ctx* c = nullptr;
+    RP_TRY(thread_ctx(device, &c));
+    RP_TRY(check_params(p));
+    if (out_dtype != REPET_F32 && out_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    c->strict = !(p->flags & REPET_FLAG_REFUSE_NONFINITE);
+    RP_TRY(repet_ctx_upload_device_strided(c, src, dtype, n_clips, n, ch, in_strides, stream));
+    RP_TRY(repet_ctx_execute_async(c, algo, p));
+    return repet_ctx_download_device_strided(c, dst, out_dtype, out_strides, stream);
 }
 
 }  // extern "C"

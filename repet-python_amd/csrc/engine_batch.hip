@@ -105,6 +105,8 @@ int run_batch_impl(int algo, int32_t n_clips, const void* const* audio, int dtyp
                    int one_device) {
     if (n_clips < 0 || (n_clips > 0 && (!audio || !n_samples || !n_channels || !out)))
         return fail(REPET_ERR_BAD_ARG, "null argument");
+    // (host arrays only: REPET_F16 / REPET_BF16 are for the device-side entries)
+    if (dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "unsupported dtype");
     const int physical = repet_device_count();
     if (physical < 1) return fail(REPET_ERR_HIP, "no HIP device");
     const int avail = transport == 1 ? physical : transport == 2 ? 8 : logical_device_count(physical);     // (RCCL needs distinct physical devices)

@@ -9,7 +9,8 @@ Same call surface as the reference module ``repet.py``::
     background_signal = repet.simonline(audio_signal, sampling_frequency)   # repet.py:712
 
 ``audio_signal`` is ``(number_samples, number_channels)``; the result is a fresh float64 array of the
-same shape. The nine module-level parameters below have the reference's names and defaults
+same shape. A torch tensor on a ROCm device is separated where it lies: the result is a float64 tensor on the same
+device, ordered on that device's current stream without a host wait (``separate`` also takes batches and ``out=``). The nine module-level parameters below have the reference's names and defaults
 (repet.py:42-63) and are read at call time, so ``repet.period_range = [1, 5]`` before a call behaves as
 it does there. All arithmetic runs in hand-written HIP kernels for gfx950 behind ``librepet_hip.so``
 (``include/repet_hip.h``); this module only validates, derives the integer sizes with the reference's
@@ -113,9 +114,34 @@ def release_workspaces():
     notion: its arrays die with the call). Worth calling after a one-off long ``sim``: the similarity matrix of a
     10-minute clip is several GB of HBM."""
     _native.check(_native.lib().repet_release_thread_ctx())
+    _native.release_tensor_contexts()
+
+
+def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False):
+    """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
+    events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check)."""
+    import torch
+    params = derive_params(sampling_frequency)
+    layout = _native.tensor_layout(audio_signal, batched)
+    x, shape = layout[0], layout[2]
+    result_shape = shape if x.dim() == 3 else shape[1:]
+    if out is not None:
+        if not _native.is_device_tensor(out) or out.device != x.device:
+            raise ValueError(f"out must be a tensor on {x.device}")
+        if tuple(out.shape) != result_shape:
+            raise ValueError(f"out has shape {tuple(out.shape)}, the result {result_shape}")
+        _native.result_tensor_code(out)
+    ctx = _native.tensor_context(x.device.index)
+    ctx.set_strict_reference(strict_reference)
+    stream = torch.cuda.current_stream(x.device)
+    ctx.upload_layout(*layout, stream=stream)
+    ctx.execute_async(algo, params)
+    return ctx.download_tensor(out, stream)
 
 
 def _separate(algo, audio_signal, sampling_frequency):
+    if _native.is_device_tensor(audio_signal):
+        return _separate_tensor(algo, audio_signal, sampling_frequency)
     number_samples, number_channels = np.shape(audio_signal)   # 1-D input: ValueError, like repet.py:125
     params = derive_params(sampling_frequency)
     signal, code = _native.as_input(audio_signal)
@@ -151,6 +177,19 @@ def sim(audio_signal, sampling_frequency):
 def simonline(audio_signal, sampling_frequency):
     """Online REPET-SIM over a circular buffer of past frames (repet.py:712-911)."""
     return _separate("simonline", audio_signal, sampling_frequency)
+
+
+def separate(algo, audio_signal, sampling_frequency, out=None):
+    """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
+    batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
+    clips one after another). Returns a float64 tensor on the tensor's device -- or fills ``out``, a float32 / float64 tensor
+    of the same shape with any strides, and returns it. Every clip's result is what the one-clip call returns, bit for bit;
+    the work is ordered on the device's current stream with no host wait (see ``_separate_tensor``)."""
+    if algo not in _native.ALGO_IDS:
+        raise ValueError(f"unknown algorithm {algo!r}")
+    if not _native.is_device_tensor(audio_signal):
+        raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
+    return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True)
 
 
 def online(sampling_frequency, number_channels):

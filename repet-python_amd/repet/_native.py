@@ -2,6 +2,8 @@
 is missing the calls raise, loudly."""
 import ctypes as C
 import os
+import sys
+import threading
 import weakref
 
 import numpy as np
@@ -12,7 +14,7 @@ LIB_PATH = os.environ.get("REPET_HIP_LIB", os.path.join(os.path.dirname(_HERE), 
 ABI_VERSION = 4
 ORIGINAL, EXTENDED, ADAPTIVE, SIM, SIMONLINE = range(5)
 ALGO_IDS = {"original": ORIGINAL, "extended": EXTENDED, "adaptive": ADAPTIVE, "sim": SIM, "simonline": SIMONLINE}
-F32, F64, I16 = 0, 1, 2
+F32, F64, I16, F16, BF16 = 0, 1, 2, 3, 4      # (F16 / BF16: the device-side entries only)
 MAX_STAGES = 16
 
 ERR_BAD_ARG, ERR_TOO_SHORT, ERR_HIP, ERR_OOM, ERR_LIMIT = -1, -2, -3, -4, -5
@@ -73,6 +75,8 @@ _SIGNATURES = {
     "repet_ctx_upload_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "repet_ctx_upload_device_split": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "repet_ctx_download_device": (C.c_int, [_P, _P]),
+    "repet_ctx_upload_device_strided": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _P]),
+    "repet_ctx_download_device_strided": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int64), _P]),
     "repet_last_batch_info": (C.c_int, [C.POINTER(C.c_int64)]),
     "repet_ctx_download_input": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "repet_ctx_set_window": (C.c_int, [_P, C.c_int64, C.c_int64]),
@@ -106,6 +110,8 @@ _SIGNATURES = {
                                   C.POINTER(C.c_int32), C.POINTER(Params), C.POINTER(_P), C.c_int32]),
     "repet_run_stream": (C.c_int, [C.c_int, C.c_int32, C.POINTER(_P), C.c_int, C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int32), C.POINTER(Params), C.POINTER(_P), C.c_int, C.c_int32]),
+    "repet_run_device": (C.c_int, [C.c_int, _P, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _P, C.c_int,
+                                   C.POINTER(C.c_int64), C.POINTER(Params), C.c_int, _P]),
     "repet_host_conversion_selftest": (C.c_int64, [C.c_int64, C.c_uint32]),
     "repet_frame_count": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "repet_stft": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64]),
@@ -213,6 +219,80 @@ def as_input(audio_signal):
     return np.ascontiguousarray(a), code
 
 
+# ---- torch tensors on a ROCm device (devio.hip) ----------------------------------------------------------------------
+# torch is never imported here: a tensor is recognised by its type once the caller has imported torch, so a host without
+# torch still imports repet.
+_TENSOR_CODES = {"torch.float64": F64, "torch.float32": F32, "torch.int16": I16, "torch.float16": F16, "torch.bfloat16": BF16}
+
+
+def is_tensor(x):
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def is_device_tensor(x):
+    """A torch tensor in GPU memory (ROCm devices are torch's "cuda" devices); CPU tensors take the NumPy path."""
+    return is_tensor(x) and x.device.type == "cuda"
+
+
+def tensor_layout(x, batched=False):
+    """(tensor, dtype code, (n_clips, n_samples, n_channels), element strides) of a tensor as the strided ingest reads it.
+    ``batched``: ``(N, C)`` or ``(B, N, C)``; otherwise ``(N, C)`` only (ValueError like the NumPy path's ``np.shape``
+    unpacking). Real dtypes the ingest does not take are converted with ``x.to(torch.float64)`` (what ``as_input``'s
+    ``astype(float64)`` does); negative strides fall back to a contiguous copy."""
+    import torch
+    if x.dim() != 2 and not (batched and x.dim() == 3):
+        raise ValueError("audio_signal must be (number_samples, number_channels)" +
+                         (" or (number_clips, number_samples, number_channels)" if batched else ""))
+    code = _TENSOR_CODES.get(str(x.dtype))
+    if code is None:
+        x = x.to(torch.float64)
+        code = F64
+    if any(st < 0 for st in x.stride()):
+        x = x.contiguous()
+    shape = tuple(int(d) for d in x.shape)
+    strides = tuple(int(st) for st in x.stride())
+    if x.dim() == 2:
+        shape = (1,) + shape
+        strides = (shape[1] * shape[2],) + strides
+    return x, code, shape, strides
+
+
+def result_tensor_code(out):
+    code = {"torch.float64": F64, "torch.float32": F32}.get(str(out.dtype))
+    if code is None:
+        raise ValueError("out must be a float32 or float64 tensor")
+    return code
+
+
+def _strides(strides):
+    return (C.c_int64 * 3)(*strides)
+
+
+def _stream_handle(stream):
+    return C.c_void_p(int(stream.cuda_stream) or None)
+
+
+_tensor_ctx = threading.local()
+
+
+def tensor_context(device):
+    """This thread's context for tensors on ``device`` (one per thread and device, like repet_run's)."""
+    ctxs = getattr(_tensor_ctx, "by_device", None)
+    if ctxs is None:
+        ctxs = _tensor_ctx.by_device = {}
+    ctx = ctxs.get(device)
+    if ctx is None:
+        ctx = ctxs[device] = Context(device)
+    return ctx
+
+
+def release_tensor_contexts():
+    for ctx in getattr(_tensor_ctx, "by_device", {}).values():
+        ctx.close()
+    _tensor_ctx.by_device = {}
+
+
 def result_array(shape):
     """A fresh C-contiguous float64 array for a result, backed by a pinned host buffer of the library's recycling pool
     (repet_host_alloc): when the caller drops the array its buffer goes back to the pool, so the next result lands in
@@ -239,6 +319,9 @@ class Context:
         if lib().repet_device_count() < 1:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_ctx_create(int(device), C.byref(self._h)))
+        self._device = int(device)
+        self._torch_stream = None
+        self._ingested = None
         self.shape = None
 
     def close(self):
@@ -282,6 +365,69 @@ class Context:
         check(lib().repet_ctx_upload_device_split(self._h, C.c_void_p(int(data_ptr)), C.c_void_p(int(remainder_ptr)) if remainder_ptr else None,
                                                   int(number_samples), int(number_channels), int(number_clips)))
         self.shape = (number_samples, number_channels) if number_clips == 1 else (number_clips, number_samples, number_channels)
+
+    def upload_tensor(self, x, stream=None):
+        """A ``(N, C)`` or ``(B, N, C)`` torch tensor on this context's device (float64 / float32 / int16 / float16 / bfloat16,
+        any non-negative strides; other real dtypes are converted to float64) becomes the resident clip(s), narrowed on the
+        device. Ordered behind ``stream`` (default: the tensor device's current stream) by an event, and ``stream`` behind
+        the ingest: no host wait, except in the refusal mode (``set_strict_reference(False)``), which reads back whether a
+        sample was not finite."""
+        if not is_device_tensor(x):
+            raise TypeError("upload_tensor takes a torch tensor on a ROCm device")
+        return self.upload_layout(*tensor_layout(x, batched=True), stream=stream)
+
+    def upload_layout(self, x, code, shape, strides, stream=None):
+        """``upload_tensor`` of a tensor whose layout ``tensor_layout`` has already resolved."""
+        import torch
+        if x.device.index != self._device:
+            raise ValueError(f"tensor is on {x.device}, the context on device {self._device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        check(lib().repet_ctx_upload_device_strided(self._h, C.c_void_p(x.data_ptr() or None), code, shape[0], shape[1], shape[2],
+                                                    _strides(strides), _stream_handle(stream)))
+        # The tensor's memory must not be reused under the ingest. `stream` waits for the ingest (an event on the engine's
+        # stream) and the tensor is recorded on `stream`: the caching allocator then hands the block out again only behind
+        # it. (Recording it on the engine's stream itself would leave torch holding that stream's handle for as long as the
+        # block lives -- past release_workspaces(), which destroys the stream.) One event, re-recorded: a wait already
+        # enqueued keeps the point it was given.
+        if self._ingested is None:
+            self._ingested = torch.cuda.Event()
+        self._ingested.record(self.torch_stream())
+        stream.wait_event(self._ingested)
+        x.record_stream(stream)
+        self.shape = shape[1:] if x.dim() == 2 else shape
+        return x
+
+    def download_tensor(self, out=None, stream=None):
+        """The result of the last run into ``out`` (a float32 or float64 tensor of the resident shape, any non-negative
+        strides whose elements do not overlap) or a fresh float64 tensor, written on the engine's stream behind what
+        ``stream`` (default: the current stream of this context's device) has enqueued so far; ``stream`` then waits for it.
+        No host wait."""
+        import torch
+        device = torch.device("cuda", self._device)
+        if out is None:
+            out = torch.empty(self.shape, dtype=torch.float64, device=device)
+        elif not is_device_tensor(out) or out.device != device:
+            raise ValueError(f"out must be a tensor on {device}")
+        if tuple(out.shape) != tuple(self.shape):
+            raise ValueError(f"out has shape {tuple(out.shape)}, the result {tuple(self.shape)}")
+        if any(st < 0 for st in out.stride()):
+            raise ValueError("out has negative strides")
+        strides = tuple(int(st) for st in out.stride())
+        if out.dim() == 2:
+            strides = (out.shape[0] * out.shape[1],) + strides
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        check(lib().repet_ctx_download_device_strided(self._h, C.c_void_p(out.data_ptr() or None), result_tensor_code(out),
+                                                      _strides(strides), _stream_handle(stream)))
+        return out
+
+    def torch_stream(self):
+        """The context's stream as a ``torch.cuda.ExternalStream`` (cached)."""
+        if self._torch_stream is None:
+            import torch
+            self._torch_stream = torch.cuda.ExternalStream(self.stream(), device=torch.device("cuda", self._device))
+        return self._torch_stream
 
     def resident_input(self):
         """(fp32 samples, fp32 remainders, has_remainders) of the resident clip as the engine holds it."""
