@@ -431,6 +431,37 @@ int repet_online_push(repet_online* h, const void* audio, int dtype, int64_t n_s
 int repet_online_finish(repet_online* h, double* out, int64_t capacity, int64_t* n_written);
 int repet_online_close(repet_online* h);
 
+/* (ABI 4 additions) S live streams of one sampling frequency and channel count in ONE handle, in lockstep: every push brings
+ * the same number of samples n for every stream, so all the counters are shared and only the data is per stream. A push
+ * enqueues one fixed sequence of launches for all S streams (its length depends on neither S nor C). Each stream's
+ * concatenated output equals repet.simonline of that stream's concatenated input, bit for bit; repet_online_open / push /
+ * finish above are the S = 1 case of the same engine. Samples that are not finite are let through (REPET_FLAG_REFUSE_NONFINITE
+ * is not honoured here). Host and device pushes may be mixed on one handle.
+ * open_streams : max_push_samples sizes the sliding windows and the pending buffers at open (0: they grow on demand). A
+ *                device push of at most that many samples never waits on the host once the per-push workspaces have seen
+ *                a push of its size; a larger one may grow the buffers and wait for the device once.
+ * emit_count   : samples per stream that the next push of n samples (finishing = 0) or the finish (finishing = 1) will write:
+ *                full = (total - W) / H + 1 frames are complete once total >= W samples were pushed, a push writes
+ *                (full - frames done) * H, the finish the rest (REPET_ERR_TOO_SHORT, as repet_online_finish, before the
+ *                buffer has filled).
+ * push_streams : host chunk audio[S][n][C] (F32 / F64 / I16, C order) -> out[S][n_emit][C] float64 (capacity: samples per
+ *                stream); returns once out is written. For S = 1 this is exactly repet_online_push.
+ * push_device  : device chunk with element strides [stream, sample, channel] (F64 / F32 / I16 / F16 / BF16, as
+ *                repet_ctx_upload_device_strided), read behind what wait_stream has enqueued; the result is widened into dst
+ *                (F32 / F64, element strides, elements must not overlap) and signal_stream is made to wait for it. No host wait.
+ * finish_*     : the end of every stream, to the host or into a device destination like push_device's. */
+int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p,
+                              int64_t max_push_samples, repet_online** out);
+int repet_online_emit_count(repet_online* h, int64_t n, int finishing, int64_t* n_emit);
+int repet_online_push_streams(repet_online* h, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
+                              int64_t* n_written);
+int repet_online_push_device(repet_online* h, const void* src, int dtype, int64_t n, const int64_t src_strides[3],
+                             void* wait_stream, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                             int64_t* n_written);
+int repet_online_finish_streams(repet_online* h, double* out, int64_t capacity, int64_t* n_written);
+int repet_online_finish_device(repet_online* h, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                               int64_t* n_written);
+
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,
  * fp32 -> float64; non-temporal AVX-512 / AVX2 lines where the CPU has them) against scalar loops on n values with NaN,
  * infinities, denormals, PCM-exact runs and every misalignment. No GPU needed. Returns the number of values that differ

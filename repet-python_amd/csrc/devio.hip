@@ -188,6 +188,87 @@ __global__ __launch_bounds__(kIoThreads) void devio_ingest_bf16(const BHalf* src
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f64(const float* in, IoGeo g, int dense, double* dst) { egress_body<double, 2>(in, g, dense, dst); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, IoGeo g, int dense, float* dst) { egress_body<float, 4>(in, g, dense, dst); }
 
+// ---- the streaming handle's per-push data movement (engine_online.hip): S streams at a per-stream stride -------------------
+// Grids are streams (y) x four-element slots (x), both capped and walked grid-stride; every store of a whole slot is one
+// dwordx4. kRowCopyParts parts (z) per launch.
+constexpr int kMaxIoGroups = 4096;        // workgroups of one launch (16 per CU and more: several rounds of the grid)
+
+// Append: stream b's chunk [n][C] (strided source of any dtype; IoGeo's clip = stream) goes to hi / lo at b * d_stream + d_off,
+// as fp32 + fp32 remainder (0 for sources that are not float64). The slots are aligned on the DESTINATION (d_stream % 4 == 0,
+// hi / lo 16-byte aligned): the first one of a stream starts d_off % 4 elements before its first sample.
+template <typename T>
+__device__ inline void append_body(const T* __restrict__ src, IoGeo g, int32_t n_streams, float* __restrict__ hi_out,
+                                   float* __restrict__ lo_out, int64_t d_stream, int64_t d_off) {
+    const int64_t per = g.n_samples * g.n_channels;
+    const int64_t head = d_off & 3;
+    const int64_t slots = (head + per + 3) >> 2;
+    bool unused = false;
+    for (int64_t b = blockIdx.y; b < n_streams; b += gridDim.y) {
+        float* hi_b = hi_out + b * d_stream + d_off - head;
+        float* lo_b = lo_out + b * d_stream + d_off - head;
+        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+            const int64_t j0 = q * 4 - head;                      // chunk element of the slot's first position
+            if (j0 >= 0 && j0 + 4 <= per) {
+                float h[4], l[4];
+                Walker w(g, b * per + j0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    split1<T>(src + w.off, h[k], l[k], unused, false);
+                    if (k < 3) w.next(g);
+                }
+                *reinterpret_cast<float4*>(hi_b + q * 4) = make_float4(h[0], h[1], h[2], h[3]);
+                *reinterpret_cast<float4*>(lo_b + q * 4) = make_float4(l[0], l[1], l[2], l[3]);
+            } else {                                              // first / last slot of a stream: element by element
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t j = j0 + k;
+                    if (j < 0 || j >= per) continue;
+                    Walker w(g, b * per + j);
+                    float h, l;
+                    split1<T>(src + w.off, h, l, unused, false);
+                    hi_b[q * 4 + k] = h;
+                    lo_b[q * 4 + k] = l;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void online_append_f64(const double* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<double>(src, g, s, hi, lo, ds, off); }
+__global__ __launch_bounds__(kIoThreads) void online_append_f32(const float* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<float>(src, g, s, hi, lo, ds, off); }
+__global__ __launch_bounds__(kIoThreads) void online_append_i16(const int16_t* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<int16_t>(src, g, s, hi, lo, ds, off); }
+__global__ __launch_bounds__(kIoThreads) void online_append_f16(const Half* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<Half>(src, g, s, hi, lo, ds, off); }
+__global__ __launch_bounds__(kIoThreads) void online_append_bf16(const BHalf* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<BHalf>(src, g, s, hi, lo, ds, off); }
+
+// Row copies: part z moves `blocks` runs of `len` floats of every stream (or writes zeros where src is null). Slots of four
+// consecutive floats of a run; a whole slot is one dwordx4 store where the destination side is aligned (RowCopy::dst_vec)
+// and one dwordx4 load where the source side is (src_vec), element accesses otherwise.
+struct RowCopyDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream; int32_t src_vec, dst_vec; };
+struct RowCopyArgs { RowCopyDev part[repet_eng::kRowCopyParts]; int32_t n_streams; };
+
+__global__ __launch_bounds__(kIoThreads) void online_row_copies(RowCopyArgs a) {
+    const RowCopyDev p = a.part[blockIdx.z];
+    const int64_t slots = p.slots_per_block * p.blocks;
+    for (int64_t b = blockIdx.y; b < a.n_streams; b += gridDim.y) {
+        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+            const int64_t blk = q / p.slots_per_block;
+            const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+            float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
+            const float* s = p.src ? p.src + b * p.src_stream + blk * p.src_block + i0 : nullptr;
+            if (i0 + 4 <= p.len && p.dst_vec) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (s) {
+                    if (p.src_vec) v = *reinterpret_cast<const float4*>(s);
+                    else v = make_float4(s[0], s[1], s[2], s[3]);
+                }
+                *reinterpret_cast<float4*>(d) = v;
+            } else {
+                const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
+                for (int64_t k = 0; k < m; ++k) d[k] = s ? s[k] : 0.f;
+            }
+        }
+    }
+}
+
 int element_size(int dtype) {
     switch (dtype) {
         case REPET_F64: return 8;
@@ -214,7 +295,69 @@ using namespace repet;
 
 namespace repet_eng {
 
-static int check_strides(const int64_t* strides) {
+static dim3 stream_grid(int64_t slots, int32_t n_streams, int parts) {
+    const int64_t y = std::min<int64_t>(n_streams, 65535);
+    const int64_t x_cap = std::max<int64_t>(1, kMaxIoGroups / (y * parts));
+    return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(slots, kIoThreads), x_cap)), (unsigned)y, (unsigned)parts);
+}
+
+hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
+                                float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s) {
+    if (n <= 0 || n_streams <= 0) return hipSuccess;
+    if ((dst_stream & 3) || (reinterpret_cast<uintptr_t>(hi) & 15) || (reinterpret_cast<uintptr_t>(lo) & 15)) return hipErrorInvalidValue;
+    IoGeo g{n * ch * n_streams, n, ch, src_strides[0], src_strides[1], src_strides[2]};
+    const dim3 grid = stream_grid(ceil_div((dst_off & 3) + n * ch, 4), n_streams, 1);
+    switch (dtype) {
+        case REPET_F64: online_append_f64<<<grid, kIoThreads, 0, s>>>(static_cast<const double*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_F32: online_append_f32<<<grid, kIoThreads, 0, s>>>(static_cast<const float*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_I16: online_append_i16<<<grid, kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_F16: online_append_f16<<<grid, kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        default: online_append_bf16<<<grid, kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s) {
+    if (n_parts <= 0 || n_parts > kRowCopyParts || n_streams <= 0) return n_parts == 0 ? hipSuccess : hipErrorInvalidValue;
+    RowCopyArgs a{};
+    a.n_streams = n_streams;
+    int64_t most = 1;
+    auto aligned = [](const float* p, int64_t b1, int64_t b2) {
+        return !(reinterpret_cast<uintptr_t>(p) & 15) && !(b1 & 3) && !(b2 & 3);
+    };
+    for (int k = 0; k < kRowCopyParts; ++k) {
+        RowCopyDev& d = a.part[k];
+        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) {      // an empty part: no slots
+            d = RowCopyDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0};
+            continue;
+        }
+        const RowCopy& p = parts[k];
+        d.src = p.src; d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
+        d.src_block = p.src_block; d.dst_block = p.dst_block; d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
+        d.dst_vec = aligned(p.dst, p.dst_block, p.dst_stream) ? 1 : 0;
+        d.src_vec = p.src && aligned(p.src, p.src_block, p.src_stream) ? 1 : 0;
+        most = std::max(most, d.slots_per_block * d.blocks);
+    }
+    online_row_copies<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,
+                                const int64_t strides[3], hipStream_t s) {
+    const int64_t count = (int64_t)n_streams * n * ch;
+    if (count <= 0) return hipSuccess;
+    IoGeo g{count, n, ch, strides[0], strides[1], strides[2]};
+    if (dtype == REPET_F64) {
+        const dim3 grid((unsigned)ceil_div(ceil_div(count, 2), kIoThreads));
+        devio_egress_f64<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<double*>(dst));
+    } else {
+        const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
+        devio_egress_f32<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<float*>(dst));
+    }
+    return hipGetLastError();
+}
+
+int check_strides(const int64_t* strides) {
     if (!strides) return fail(REPET_ERR_BAD_ARG, "strides is null");
     for (int k = 0; k < 3; ++k)
         if (strides[k] < 0) return fail(REPET_ERR_BAD_ARG, "negative stride (make the tensor contiguous first)");
@@ -224,7 +367,7 @@ static int check_strides(const int64_t* strides) {
 // a destination whose elements do not overlap: with its dimensions of more than one element ordered by stride, each stride
 // must step past everything the smaller ones span (a stride-0 `expand` view, or any other aliasing, would have several egress
 // threads write different values to one address)
-static int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch) {
+int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch) {
     const int64_t size[3] = {n_clips, n, ch};
     int order[3] = {0, 1, 2};
     std::sort(order, order + 3, [&](int a, int b) { return strides[a] < strides[b]; });
@@ -237,7 +380,7 @@ static int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, 
     return REPET_OK;
 }
 
-static int ensure_io_events(repet_ctx* c) {
+int ensure_io_events(repet_ctx* c) {
     if (!c->io_wait) HIP_TRY(hipEventCreateWithFlags(&c->io_wait, hipEventDisableTiming));
     if (!c->io_done) HIP_TRY(hipEventCreateWithFlags(&c->io_done, hipEventDisableTiming));
     return REPET_OK;

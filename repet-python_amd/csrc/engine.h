@@ -257,6 +257,21 @@ void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr);
 int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
               bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr = nullptr);
 bool split_in_stft(int B);
+// device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events
+int check_strides(const int64_t* strides);
+int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch);
+int ensure_io_events(repet_ctx* c);
+// the streaming handle's per-push data movement (devio.hip), n_streams streams at per-stream element strides:
+//   append   chunk [S][n][C] (strided, any device dtype) -> hi / lo at s * dst_stream + dst_off (fp32 + fp32 remainder)
+//   copies   up to kRowCopyParts parts of `blocks` runs of `len` floats per stream (src null: zeros), one launch
+//   egress   fp32 [S][n][C] -> strided F32 / F64 destination
+struct RowCopy { const float* src; float* dst; int64_t len, blocks, src_block, dst_block, src_stream, dst_stream; };
+constexpr int kRowCopyParts = 5;
+hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
+                                float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s);
+hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s);
+hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,
+                                const int64_t strides[3], hipStream_t s);
 constexpr int kRankMinList = 24;     // shortest list bound for which the column sort is worth its time
 
 }  // namespace repet_eng

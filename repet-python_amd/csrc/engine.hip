@@ -228,14 +228,18 @@ int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, 
     if (unit_rows && gram_f16_enabled()) {
         c->band_on_f16 = true;
         const int64_t per_clip = round_up(T, kTile) * FS;
-        if (B > 1 && a_stride != per_clip) return fail(REPET_ERR_BAD_ARG, "internal: batch stride of the unit rows");
-        const int64_t count = per_clip * B;
+        // clips further apart than their padded rows (the streaming handle's windows): the split runs over the gaps too,
+        // and the halves keep the clips' stride
+        const int64_t clip_stride = B > 1 ? a_stride : per_clip;
+        if (clip_stride < per_clip || (planes_ready && clip_stride != per_clip))
+            return fail(REPET_ERR_BAD_ARG, "internal: batch stride of the unit rows");
+        const int64_t count = clip_stride * (B - 1) + per_clip;
         if (!planes_ready) {
             HIP_TRY(c->Vh.ensure((size_t)count * 4));
             HIP_TRY(launch_split_f16(A, c->Vh.p, count, c->stream));
         }
         c->band_lookback = lookback;
-        HIP_TRY(launch_gram_band_f16(c->Vh.p, T, FS, band, n_lags, LP, tiles, n, B, 2 * per_clip, band_stride, c->stream, nullptr, 0,
+        HIP_TRY(launch_gram_band_f16(c->Vh.p, T, FS, band, n_lags, LP, tiles, n, B, 2 * clip_stride, band_stride, c->stream, nullptr, 0,
                                      c->band_lookback));
         return REPET_OK;
     }

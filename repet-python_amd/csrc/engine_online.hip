@@ -16,8 +16,13 @@ using namespace repet_eng;
 struct repet_online {
     repet_ctx* ctx = nullptr;       // stream, tables, tile cache, scratch buffers
     repet_params p{};
+    int S = 1;                      // live streams in lockstep: every counter below is shared, only the data is per stream
     int C = 0, W = 0, H = 0, F = 0, FS = 0, B = 0, Hh = 0, LP = 0;
+    // per stream s, at the strides below: X / V [C planes of rows_cap + kPadRows rows][FS], Vn [rows_cap rows][FS], the
+    // pending samples [pend_cap][C] (pend_lo: their fp32 remainders), and in the per-push workspaces band / idx / cnt / outf
     DevBuf X[2], V[2], Vn[2], pend[2], pend_lo[2], band, outf, out64, staging;
+    void* host_in = nullptr; size_t host_in_cap = 0;      // pinned: a host chunk on its way in, the result on its way out
+    void* host_out = nullptr; size_t host_out_cap = 0;
     int cur = 0, pcur = 0;
     // the pending buffers start with `pend_hist` samples of HISTORY (already transformed: the frames of the sliding window,
     // whose float64 spectra the second level of the peak picking may ask for) followed by the pend_count unconsumed ones;
@@ -27,10 +32,30 @@ struct repet_online {
     int64_t pend_cap = 0, pend_count = 0;   // samples per channel
     int64_t hist_valid = 0;         // valid history rows, right-aligned at row Hh
     int64_t frames_done = 0, total_in = 0, emitted = 0;
+    int64_t max_push = 0;           // repet_online_open_streams: windows and pending buffers sized for pushes of this many samples
     bool finished = false;
+
+    int64_t plane() const { return (rows_cap + kPadRows) * FS; }        // elements between channel planes of X and V
+    int64_t spec_stride() const { return (int64_t)C * plane(); }      // ... between streams in X and V
+    int64_t vn_stride() const { return rows_cap * FS; }               // ... between streams in Vn
+    int64_t pend_stride() const { return pend_cap * C; }              // ... between streams in pend / pend_lo
 };
 
 namespace repet_eng {
+
+static void free_pinned(void*& p, size_t& cap) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+}
+
+static int ensure_pinned(void*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return REPET_OK;
+    free_pinned(p, cap);
+    const size_t want = std::max<size_t>((bytes + 4095) & ~size_t(4095), 4096);
+    HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+    cap = want;
+    return REPET_OK;
+}
 
 int online_ensure_windows(repet_online* o, int64_t n_new) {
     repet_ctx* c = o->ctx;
@@ -40,54 +65,79 @@ int online_ensure_windows(repet_online* o, int64_t n_new) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     DevBuf nx, nv, nvn;
     const size_t plane = (size_t)(new_cap + kPadRows) * o->FS;
-    HIP_TRY(nx.ensure(plane * o->C * sizeof(float2)));
-    HIP_TRY(nv.ensure(plane * o->C * sizeof(float)));
-    HIP_TRY(nvn.ensure((size_t)new_cap * o->FS * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(nx.p, 0, plane * o->C * sizeof(float2), c->stream));
-    HIP_TRY(hipMemsetAsync(nv.p, 0, plane * o->C * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(nvn.p, 0, (size_t)new_cap * o->FS * sizeof(float), c->stream));
-    if (o->hist_valid > 0) {        // carry the history (rows [Hh - hist_valid, Hh)) into the bigger window
-        const int64_t r0 = o->Hh - o->hist_valid;
-        const size_t old_plane = (size_t)(o->rows_cap + kPadRows) * o->FS;
-        HIP_TRY(hipMemcpyAsync(nvn.as<float>() + r0 * o->FS, o->Vn[o->cur].as<float>() + r0 * o->FS,
-                               (size_t)o->hist_valid * o->FS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        for (int ch = 0; ch < o->C; ++ch) {
-            HIP_TRY(hipMemcpyAsync(nv.as<float>() + ch * plane + r0 * o->FS, o->V[o->cur].as<float>() + ch * old_plane + r0 * o->FS,
-                                   (size_t)o->hist_valid * o->FS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(nx.as<float2>() + ch * plane + r0 * o->FS, o->X[o->cur].as<float2>() + ch * old_plane + r0 * o->FS,
-                                   (size_t)o->hist_valid * o->FS * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
-        }
+    const size_t planes = plane * o->C * o->S;
+    const size_t vn = (size_t)new_cap * o->FS * o->S;
+    HIP_TRY(nx.ensure(planes * sizeof(float2)));
+    HIP_TRY(nv.ensure(planes * sizeof(float)));
+    HIP_TRY(nvn.ensure(vn * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(nx.p, 0, planes * sizeof(float2), c->stream));
+    HIP_TRY(hipMemsetAsync(nv.p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(nvn.p, 0, vn * sizeof(float), c->stream));
+    if (o->hist_valid > 0) {        // carry the history (rows [Hh - hist_valid, Hh)) of every stream into the bigger window
+        const int64_t r0 = o->Hh - o->hist_valid, len = o->hist_valid * o->FS;
+        const int64_t op = o->plane(), np = (int64_t)plane;
+        const RowCopy parts[3] = {
+            {o->Vn[o->cur].as<float>() + r0 * o->FS, nvn.as<float>() + r0 * o->FS, len, 1, 0, 0, o->vn_stride(), new_cap * o->FS},
+            {o->V[o->cur].as<float>() + r0 * o->FS, nv.as<float>() + r0 * o->FS, len, o->C, op, np, o->C * op, o->C * np},
+            {o->X[o->cur].as<float>() + 2 * r0 * o->FS, nx.as<float>() + 2 * r0 * o->FS, 2 * len, o->C, 2 * op, 2 * np, 2 * o->C * op, 2 * o->C * np}};
+        HIP_TRY(launch_row_copies(parts, 3, o->S, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     o->X[o->cur].release(); o->V[o->cur].release(); o->Vn[o->cur].release();
     o->X[o->cur] = nx; o->V[o->cur] = nv; o->Vn[o->cur] = nvn;
     // the other window is only ever written after being (re)initialised below
     o->X[o->cur ^ 1].release(); o->V[o->cur ^ 1].release(); o->Vn[o->cur ^ 1].release();
-    HIP_TRY(o->X[o->cur ^ 1].ensure(plane * o->C * sizeof(float2)));
-    HIP_TRY(o->V[o->cur ^ 1].ensure(plane * o->C * sizeof(float)));
-    HIP_TRY(o->Vn[o->cur ^ 1].ensure((size_t)new_cap * o->FS * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(o->X[o->cur ^ 1].p, 0, plane * o->C * sizeof(float2), c->stream));
-    HIP_TRY(hipMemsetAsync(o->V[o->cur ^ 1].p, 0, plane * o->C * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(o->Vn[o->cur ^ 1].p, 0, (size_t)new_cap * o->FS * sizeof(float), c->stream));
+    HIP_TRY(o->X[o->cur ^ 1].ensure(planes * sizeof(float2)));
+    HIP_TRY(o->V[o->cur ^ 1].ensure(planes * sizeof(float)));
+    HIP_TRY(o->Vn[o->cur ^ 1].ensure(vn * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(o->X[o->cur ^ 1].p, 0, planes * sizeof(float2), c->stream));
+    HIP_TRY(hipMemsetAsync(o->V[o->cur ^ 1].p, 0, planes * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(o->Vn[o->cur ^ 1].p, 0, vn * sizeof(float), c->stream));
     o->rows_cap = new_cap;
+    // the streams' channel planes follow each other at the same stride: S x C planes for the pad rows
     for (int k = 0; k < 2; ++k)
-        HIP_TRY(launch_fill_pad_rows(o->V[k].as<float>(), (new_cap + kPadRows) * o->FS, o->C, new_cap, o->FS, c->stream));
+        HIP_TRY(launch_fill_pad_rows(o->V[k].as<float>(), (new_cap + kPadRows) * o->FS, o->C * o->S, new_cap, o->FS, c->stream));
     return REPET_OK;
 }
 
-// Process n_new frames starting at global frame o->frames_done (the samples are at the front of the pending
-// buffer; samples past pend_count read as zero) and write `n_emit` output samples per channel, starting at
-// the first sample of hop frames_done, to out (float64, interleaved).
-int online_process(repet_online* o, int64_t n_new, int64_t n_emit, double* out) {
+// room for `n` more samples per stream in the pending buffers (a multiple of 4 samples: 16-byte aligned streams)
+int online_ensure_pending(repet_online* o, int64_t n) {
     repet_ctx* c = o->ctx;
-    if (n_new <= 0 && n_emit <= 0) {
-        HIP_TRY(hipStreamSynchronize(c->stream));      // the caller's chunk has been copied
-        return REPET_OK;
+    const int64_t need = o->pend_hist + o->pend_count + n;
+    if (need <= o->pend_cap) return REPET_OK;
+    const int64_t cap = round_up(std::max<int64_t>(need + o->W + (int64_t)o->Hh * o->H, 2 * o->pend_cap), 4);
+    const size_t bytes = (size_t)cap * o->C * o->S * sizeof(float);
+    DevBuf a, b, al, bl;
+    HIP_TRY(a.ensure(bytes));
+    HIP_TRY(b.ensure(bytes));
+    HIP_TRY(al.ensure(bytes));
+    HIP_TRY(bl.ensure(bytes));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t live = (o->pend_hist + o->pend_count) * o->C;
+    if (live > 0) {
+        const RowCopy parts[2] = {{o->pend[o->pcur].as<float>(), a.as<float>(), live, 1, 0, 0, o->pend_stride(), cap * o->C},
+                                  {o->pend_lo[o->pcur].as<float>(), al.as<float>(), live, 1, 0, 0, o->pend_stride(), cap * o->C}};
+        HIP_TRY(launch_row_copies(parts, 2, o->S, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    o->pend[0].release(); o->pend[1].release(); o->pend_lo[0].release(); o->pend_lo[1].release();
+    o->pend[0] = a; o->pend[1] = b; o->pend_lo[0] = al; o->pend_lo[1] = bl; o->pcur = 0; o->pend_cap = cap;
+    return REPET_OK;
+}
+
+// Process n_new frames of every stream starting at global frame o->frames_done (the samples are at the front of the pending
+// buffers; samples past pend_count read as zero) and leave `n_emit` output samples per stream and channel, starting at the
+// first sample of hop frames_done, in outf [S][n_emit][C] (fp32). Enqueues only: no host wait unless a buffer grows. One
+// fixed sequence of launches, whatever S and C.
+int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
+    repet_ctx* c = o->ctx;
+    if (n_new <= 0 && n_emit <= 0) return REPET_OK;
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, o->W, &tb));
     RP_TRY(online_ensure_windows(o, n_new));
-    const int64_t plane = (o->rows_cap + kPadRows) * o->FS;      // chan_stride of X and V
+    const int S = o->S;
+    const int64_t plane = o->plane();                            // chan_stride of X and V
+    const int64_t spec = o->spec_stride(), vns = o->vn_stride(), pst = o->pend_stride();
     const int64_t r0 = o->Hh - o->hist_valid;                    // first valid window row
     const int64_t Tw = o->hist_valid + n_new;                    // valid rows (history + new), relative to r0
     float2* Xb = o->X[o->cur].as<float2>() + r0 * o->FS;
@@ -102,91 +152,167 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, double* out) 
         a.W = o->W; a.H = o->H; a.T = n_new; a.FS = o->FS; a.centred = 0;
         a.X = Xb + o->hist_valid * o->FS; a.V = Vb + o->hist_valid * o->FS; a.chan_stride = plane;
         a.Vn = Vnb + o->hist_valid * o->FS;
+        a.n_batch = S; a.batch_sample_stride = o->pend_cap; a.batch_spec_stride = spec; a.batch_mean_stride = vns;
         HIP_TRY(launch_stft(a, c->stream));
         // rows behind the new frames up to the next tile boundary must read as zero for the Gram tiles
         const int64_t Tpad = round_up(Tw, kTile);
-        HIP_TRY(hipMemsetAsync(Vnb + Tw * o->FS, 0, (size_t)(Tpad - Tw) * o->FS * sizeof(float), c->stream));
+        const RowCopy zero{nullptr, Vnb + Tw * o->FS, (Tpad - Tw) * o->FS, 1, 0, 0, 0, vns};
+        HIP_TRY(launch_row_copies(&zero, 1, S, c->stream));
 
         const int64_t first_active = std::max<int64_t>(o->frames_done, o->B - 1);     // global frame number
         const int64_t n_active = o->frames_done + n_new - first_active;
         const int K = o->p.sim_number, KP = std::max(K, kMinIdxPitch);
         if (n_active > 0) {
-            HIP_TRY(o->band.ensure((size_t)Tpad * o->LP * sizeof(float)));
-            RP_TRY(run_gram_band(c, Vnb, Tw, o->FS, o->band.as<float>(), o->B, o->LP, true, 1, 0, 0, false, true));
+            const int64_t band_stride = Tpad * o->LP;
+            HIP_TRY(o->band.ensure((size_t)S * band_stride * sizeof(float)));
+            RP_TRY(run_gram_band(c, Vnb, Tw, o->FS, o->band.as<float>(), o->B, o->LP, true, S, vns, band_stride, false, true));
             const int peak_mode = c->band_lookback ? 2 : 1;
-            HIP_TRY(c->idx.ensure((size_t)n_active * KP * sizeof(int32_t)));
-            HIP_TRY(c->cnt.ensure((size_t)n_active * sizeof(int32_t)));
+            HIP_TRY(c->idx.ensure((size_t)S * n_active * KP * sizeof(int32_t)));
+            HIP_TRY(c->cnt.ensure((size_t)S * n_active * sizeof(int32_t)));
             PeakRefine rf{};
-            RP_TRY(make_refine(c, Vnb, o->FS, o->p.sim_threshold, &rf, n_active, 1, o->B, o->p.sim_distance_frames, Tpad));
+            RP_TRY(make_refine(c, Vnb, o->FS, o->p.sim_threshold, &rf, n_active, S, o->B, o->p.sim_distance_frames, Tpad));
+            const PeakBatch pb{S, band_stride, n_active * KP, n_active, vns};
             hipError_t e = launch_local_maxima(o->band.as<float>(), n_active, first_active, o->B, o->LP, peak_mode, (float)o->p.sim_threshold,
                                                o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), c->stream,
-                                               first_global, &rf);
+                                               first_global, &rf, S > 1 ? &pb : nullptr);
             if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "online: buffer too long for the peak-picking kernel");
             HIP_TRY(e);
             // second level: window row fr is global frame first_global + fr, whose first sample sits hist_valid - fr hops
-            // before the pending ones in the buffer (zero beyond what has been pushed, as in the offline run's last frame)
+            // before the pending ones in ITS stream's buffer (zero beyond what has been pushed, as in the offline run's last frame)
             const Geo go = make_geo(o->W, o->H, Tw, o->C);
             RP_TRY(run_exact_rows(c, tb, go, o->band.as<float>(), first_active, o->B, o->LP, peak_mode, (float)o->p.sim_threshold,
-                                  o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_global, rf, nullptr,
-                                  o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(), o->pend_hist + o->pend_count, 0,
-                                  o->pend_hist - o->hist_valid * (int64_t)o->H, Tpad, 1));
+                                  o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_global, rf,
+                                  S > 1 ? &pb : nullptr, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
+                                  o->pend_hist + o->pend_count, pst, o->pend_hist - o->hist_valid * (int64_t)o->H, Tpad, S));
         }
         MaskArgs m{};
         m.V = Vb; m.chan_stride = plane; m.n_channels = o->C; m.T = Tw; m.F = o->F; m.FS = o->FS; m.X = Xb; m.mask = nullptr;
-        m.cutoff = o->p.cutoff_bins; m.pad_row = o->rows_cap - r0; m.n_batch = 1; m.batch_stride = 0; m.frame0 = o->hist_valid;
+        m.cutoff = o->p.cutoff_bins; m.pad_row = o->rows_cap - r0; m.frame0 = o->hist_valid;
+        m.n_batch = S; m.batch_stride = spec;
+        m.idx_batch_stride = std::max<int64_t>(n_active, 0) * KP; m.cnt_batch_stride = std::max<int64_t>(n_active, 0);
         const int64_t first_frame = Tw - std::max<int64_t>(n_active, 0);          // warm-up rows before it are zeroed
         const int max_peaks = (int)std::min<int64_t>(K, ceil_div(o->B, o->p.sim_distance_frames + 1));
         HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_frame, max_peaks, c->stream,
                                 c->side_stream, c->fork_event, c->join_event));
     }
     if (n_emit > 0) {
-        HIP_TRY(o->outf.ensure((size_t)n_emit * o->C * sizeof(float)));
-        HIP_TRY(o->out64.ensure((size_t)n_emit * o->C * sizeof(double)));
+        HIP_TRY(o->outf.ensure((size_t)S * n_emit * o->C * sizeof(float)));
         IstftOlaArgs a{};
         a.Y = Xb; a.chan_stride = plane; a.n_channels = o->C; a.T = Tw; a.FS = o->FS; a.W = o->W;
         a.twiddle = tb->twiddle.as<float2>(); a.trim = o->hist_valid * (int64_t)o->H; a.out = o->outf.as<float>();
         a.n_out = n_emit; a.out_offset = 0; a.scale = (float)(1.0 / tb->cola);
+        a.n_batch = S; a.batch_first = 0; a.batch_step = 1; a.batch_total = S; a.batch_local0 = 0;
+        a.batch_spec_stride = spec; a.batch_out_stride = n_emit; a.overlap = 0;
         hipError_t e = launch_istft_ola(a, c->stream);
         if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
         HIP_TRY(e);
-        HIP_TRY(launch_convert_out(o->outf.as<float>(), o->out64.as<double>(), n_emit * o->C, c->stream));
-        HIP_TRY(hipMemcpyAsync(out, o->out64.p, (size_t)n_emit * o->C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     if (n_new > 0) {
-        // slide: the last min(Hh, Tw) rows become the history of the other window; drop the consumed samples
+        // slide, one launch for every stream and channel: the last min(Hh, Tw) rows of V and Vn and the last masked spectrum
+        // (overlap-add tail of the next hop) become the history of the other window; the samples of the window's frames
+        // (h2 hops of history) and the unconsumed ones move to the front of the other pending buffer
         const int64_t h2 = std::min<int64_t>(o->Hh, Tw);
         const int nxt = o->cur ^ 1;
         const int64_t src = r0 + Tw - h2, dst = o->Hh - h2;
-        HIP_TRY(hipMemcpyAsync(o->Vn[nxt].as<float>() + dst * o->FS, o->Vn[o->cur].as<float>() + src * o->FS,
-                               (size_t)h2 * o->FS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        for (int ch = 0; ch < o->C; ++ch) {
-            HIP_TRY(hipMemcpyAsync(o->V[nxt].as<float>() + ch * plane + dst * o->FS, o->V[o->cur].as<float>() + ch * plane + src * o->FS,
-                                   (size_t)h2 * o->FS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            // only the last masked spectrum is needed again (overlap-add tail of the next hop)
-            HIP_TRY(hipMemcpyAsync(o->X[nxt].as<float2>() + ch * plane + (o->Hh - 1) * o->FS,
-                                   o->X[o->cur].as<float2>() + ch * plane + (r0 + Tw - 1) * o->FS,
-                                   (size_t)o->FS * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
-        }
-        o->cur = nxt;
-        o->hist_valid = h2;
         const int64_t consumed = std::min<int64_t>(n_new * (int64_t)o->H, o->pend_count);
         const int64_t left = o->pend_count - consumed;
-        // the samples of the window's frames stay in front of the unconsumed ones (h2 hops of history)
         const int64_t keep = std::min<int64_t>(h2 * (int64_t)o->H, o->pend_hist + consumed);
         const int64_t from = o->pend_hist + consumed - keep;
-        if (keep + left > 0) {
-            HIP_TRY(hipMemcpyAsync(o->pend[o->pcur ^ 1].p, o->pend[o->pcur].as<float>() + from * o->C,
-                                   (size_t)(keep + left) * o->C * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(o->pend_lo[o->pcur ^ 1].p, o->pend_lo[o->pcur].as<float>() + from * o->C,
-                                   (size_t)(keep + left) * o->C * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        }
+        const int64_t FS = o->FS;
+        const RowCopy parts[kRowCopyParts] = {
+            {o->Vn[o->cur].as<float>() + src * FS, o->Vn[nxt].as<float>() + dst * FS, h2 * FS, 1, 0, 0, vns, vns},
+            {o->V[o->cur].as<float>() + src * FS, o->V[nxt].as<float>() + dst * FS, h2 * FS, o->C, plane, plane, spec, spec},
+            {o->X[o->cur].as<float>() + 2 * (r0 + Tw - 1) * FS, o->X[nxt].as<float>() + 2 * (o->Hh - 1) * FS, 2 * FS, o->C,
+             2 * plane, 2 * plane, 2 * spec, 2 * spec},
+            {o->pend[o->pcur].as<float>() + from * o->C, o->pend[o->pcur ^ 1].as<float>(), (keep + left) * o->C, 1, 0, 0, pst, pst},
+            {o->pend_lo[o->pcur].as<float>() + from * o->C, o->pend_lo[o->pcur ^ 1].as<float>(), (keep + left) * o->C, 1, 0, 0, pst, pst}};
+        HIP_TRY(launch_row_copies(parts, kRowCopyParts, S, c->stream));
+        o->cur = nxt;
+        o->hist_valid = h2;
         o->pcur ^= 1;
         o->pend_hist = keep;
         o->pend_count = left;
         o->frames_done += n_new;
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
     o->emitted += n_emit;
+    return REPET_OK;
+}
+
+// what a push of n samples per stream (finishing = false) or the finish (true) writes per stream: (n_new, n_emit)
+int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new, int64_t* n_emit) {
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    if (finishing) {
+        const int64_t N = o->total_in;
+        if (N < (int64_t)(o->B - 2) * o->H + o->W)      // the reference's warm-up needs B-1 whole frames (repet.py:795-810)
+            return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
+        const int64_t T = repet_frame_count(N, o->W, o->H, 0);                   // repet.py:781, last frame zero-padded
+        *n_new = std::max<int64_t>(T - o->frames_done, 0);
+        *n_emit = N - o->emitted;                                                 // truncate to the samples pushed
+        return REPET_OK;
+    }
+    if (n < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
+    const int64_t total = o->total_in + n;
+    const int64_t full = total >= o->W ? (total - o->W) / o->H + 1 : 0;          // frames completely covered
+    *n_new = std::max<int64_t>(full - o->frames_done, 0);
+    *n_emit = *n_new * (int64_t)o->H;
+    return REPET_OK;
+}
+
+// the chunk's samples (already where `src` says, device memory) appended to every stream's pending buffer
+int online_append(repet_online* o, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
+    if (n <= 0) return REPET_OK;
+    RP_TRY(online_ensure_pending(o, n));
+    hipError_t e = launch_stream_append(src, dtype, o->S, n, o->C, strides, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
+                                        o->pend_stride(), (o->pend_hist + o->pend_count) * o->C, o->ctx->stream);
+    HIP_TRY(e);
+    o->pend_count += n;
+    o->total_in += n;
+    return REPET_OK;
+}
+
+// host side of a push or finish: the result [S][n_emit][C] widened on the device, one copy into the pinned buffer, then `out`
+int online_host_result(repet_online* o, int64_t n_emit, double* out) {
+    repet_ctx* c = o->ctx;
+    const int64_t count = (int64_t)o->S * n_emit * o->C;
+    if (count > 0) {
+        HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
+        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
+        const int64_t dense[3] = {n_emit * o->C, o->C, 1};
+        HIP_TRY(launch_stream_egress(o->outf.as<float>(), o->S, n_emit, o->C, o->out64.p, REPET_F64, dense, c->stream));
+        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (count > 0) std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    return REPET_OK;
+}
+
+// device side: the result into the caller's strided destination, then the caller's stream behind it
+int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], hipStream_t signal) {
+    repet_ctx* c = o->ctx;
+    HIP_TRY(launch_stream_egress(o->outf.as<float>(), o->S, n_emit, o->C, dst, dst_dtype, dst_strides, c->stream));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(signal, c->io_done, 0));
+    return REPET_OK;
+}
+
+int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int dst_dtype, const int64_t dst_strides[3]) {
+    if (dst_dtype != REPET_F32 && dst_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_strides(dst_strides));
+    RP_TRY(check_no_overlap(dst_strides, o->S, n_emit, o->C));
+    if (n_emit > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    return REPET_OK;
+}
+
+// the engine's stream behind what the caller's stream(s) have enqueued so far (the producer of the chunk, earlier users of dst)
+int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
+    repet_ctx* c = o->ctx;
+    RP_TRY(ensure_io_events(c));
+    HIP_TRY(hipEventRecord(c->io_wait, wait));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    if (signal != wait) {
+        HIP_TRY(hipEventRecord(c->io_wait, signal));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    }
     return REPET_OK;
 }
 
@@ -194,18 +320,35 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, double* out) 
 
 extern "C" {
 
-int repet_online_open(int device, int32_t n_channels, const repet_params* p, repet_online** out) {
+int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p, int64_t max_push_samples,
+                              repet_online** out) {
     if (!out) return fail(REPET_ERR_BAD_ARG, "out is null");
-    RP_TRY(check_params(p));
+    if (n_streams < 1 || n_streams > 65535) return fail(REPET_ERR_BAD_ARG, "online: between 1 and 65535 streams");
     if (n_channels < 1) return fail(REPET_ERR_BAD_ARG, "online: at least one channel");
+    if (max_push_samples < 0) return fail(REPET_ERR_BAD_ARG, "online: negative max_push_samples");
+    RP_TRY(check_params(p));
     if (p->buffer_frames < 2 || p->sim_number < 1) return fail(REPET_ERR_BAD_ARG, "online: bad buffer length or similarity number");
     auto* o = new repet_online();
     int rc = repet_ctx_create(device, &o->ctx);
     if (rc != REPET_OK) { delete o; return rc; }
-    o->p = *p; o->C = n_channels; o->W = p->window_length; o->H = p->step_length; o->F = o->W / 2 + 1;
+    o->p = *p; o->S = n_streams; o->C = n_channels; o->W = p->window_length; o->H = p->step_length; o->F = o->W / 2 + 1;
     o->FS = (int)round_up(o->F, kFreqAlign); o->B = p->buffer_frames; o->Hh = o->B - 1; o->LP = (int)round_up(o->B, 64);
+    o->max_push = max_push_samples;
+    if (max_push_samples > 0) {
+        // a push of up to max_push_samples completes at most max_push / H + 1 frames, the finish at most W / H + 1
+        DeviceGuard guard(o->ctx->device);
+        const int64_t frames = std::max<int64_t>(max_push_samples / o->H + 1, o->W / o->H + 1);
+        rc = online_ensure_windows(o, frames);
+        if (rc == REPET_OK) rc = online_ensure_pending(o, max_push_samples + o->W);
+        if (rc == REPET_OK) rc = ensure_io_events(o->ctx);
+        if (rc != REPET_OK) { repet_online_close(o); return rc; }
+    }
     *out = o;
     return REPET_OK;
+}
+
+int repet_online_open(int device, int32_t n_channels, const repet_params* p, repet_online** out) {
+    return repet_online_open_streams(device, 1, n_channels, p, 0, out);
 }
 
 int repet_online_close(repet_online* o) {
@@ -215,82 +358,109 @@ int repet_online_close(repet_online* o) {
         (void)hipStreamSynchronize(o->ctx->stream);
         for (int k = 0; k < 2; ++k) { o->X[k].release(); o->V[k].release(); o->Vn[k].release(); o->pend[k].release(); o->pend_lo[k].release(); }
         o->band.release(); o->outf.release(); o->out64.release(); o->staging.release();
+        free_pinned(o->host_in, o->host_in_cap);
+        free_pinned(o->host_out, o->host_out_cap);
     }
     repet_ctx_destroy(o->ctx);
     delete o;
     return REPET_OK;
 }
 
-int repet_online_push(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
-                      int64_t* n_written) {
+int repet_online_emit_count(repet_online* o, int64_t n, int finishing, int64_t* n_emit) {
+    if (!o || !n_emit) return fail(REPET_ERR_BAD_ARG, "null argument");
+    int64_t n_new = 0;
+    return online_plan(o, n, finishing != 0, &n_new, n_emit);
+}
+
+int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
+                              int64_t* n_written) {
     if (!o || !n_written || (n > 0 && !audio)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     *n_written = 0;
-    const int64_t total = o->total_in + n;
-    const int64_t full = total >= o->W ? (total - o->W) / o->H + 1 : 0;          // frames completely covered
-    const int64_t n_new = std::max<int64_t>(full - o->frames_done, 0);
-    const int64_t n_emit = n_new * (int64_t)o->H;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs n_samples + window_length)");
-    // append the new samples to the pending buffer (fp32, interleaved)
-    const int64_t need = o->pend_hist + o->pend_count + n;
-    if (need > o->pend_cap) {
-        const int64_t cap = std::max<int64_t>(need + o->W + (int64_t)o->Hh * o->H, 2 * o->pend_cap);
-        DevBuf a, b, al, bl;
-        HIP_TRY(a.ensure((size_t)cap * o->C * sizeof(float)));
-        HIP_TRY(b.ensure((size_t)cap * o->C * sizeof(float)));
-        HIP_TRY(al.ensure((size_t)cap * o->C * sizeof(float)));
-        HIP_TRY(bl.ensure((size_t)cap * o->C * sizeof(float)));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const size_t live = (size_t)(o->pend_hist + o->pend_count) * o->C * sizeof(float);
-        if (live > 0) {
-            HIP_TRY(hipMemcpy(a.p, o->pend[o->pcur].p, live, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(al.p, o->pend_lo[o->pcur].p, live, hipMemcpyDeviceToDevice));
-        }
-        o->pend[0].release(); o->pend[1].release(); o->pend_lo[0].release(); o->pend_lo[1].release();
-        o->pend[0] = a; o->pend[1] = b; o->pend_lo[0] = al; o->pend_lo[1] = bl; o->pcur = 0; o->pend_cap = cap;
-    }
     if (n > 0) {
-        const int64_t at = (o->pend_hist + o->pend_count) * o->C;
-        float* dst = o->pend[o->pcur].as<float>() + at;
-        float* dst_lo = o->pend_lo[o->pcur].as<float>() + at;
+        // the chunk [S][n][C] through the pinned buffer into the staging buffer, then appended to every stream on the device
         const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
-        if (dtype == REPET_F32) {
-            HIP_TRY(hipMemcpyAsync(dst, audio, (size_t)n * o->C * esz, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemsetAsync(dst_lo, 0, (size_t)n * o->C * sizeof(float), c->stream));
-        } else {
-            HIP_TRY(o->staging.ensure((size_t)n * o->C * esz));
-            HIP_TRY(hipMemcpyAsync(o->staging.p, audio, (size_t)n * o->C * esz, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(launch_convert_in(o->staging.p, dtype, dst, n * o->C, c->stream, dst_lo));
-        }
-        o->pend_count += n;
-        o->total_in = total;
+        const size_t bytes = (size_t)o->S * n * o->C * esz;
+        HIP_TRY(hipStreamSynchronize(c->stream));          // a device push may still be running; the pinned buffer is free
+        RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
+        HIP_TRY(o->staging.ensure(bytes));
+        std::memcpy(o->host_in, audio, bytes);
+        HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+        const int64_t dense[3] = {n * o->C, o->C, 1};
+        RP_TRY(online_append(o, o->staging.p, dtype, n, dense));
     }
-    RP_TRY(online_process(o, n_new, n_emit, out));
+    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_host_result(o, n_emit, out));
     *n_written = n_emit;
     return REPET_OK;
 }
 
-int repet_online_finish(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+int repet_online_push(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
+                      int64_t* n_written) {
+    return repet_online_push_streams(o, audio, dtype, n, out, capacity, n_written);
+}
+
+int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_t n, const int64_t src_strides[3],
+                             void* wait_stream, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                             int64_t* n_written) {
+    if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    if (n < 0 || dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    RP_TRY(check_strides(src_strides));
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
+    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_append(o, src, dtype, n, src_strides));
+    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
+    *n_written = n_emit;
+    return REPET_OK;
+}
+
+int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     *n_written = 0;
-    const int64_t N = o->total_in;
-    if (N < (int64_t)(o->B - 2) * o->H + o->W)      // the reference's warm-up needs B-1 whole frames (repet.py:795-810)
-        return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
-    const int64_t T = repet_frame_count(N, o->W, o->H, 0);                       // repet.py:781, last frame zero-padded
-    const int64_t n_new = std::max<int64_t>(T - o->frames_done, 0);
-    const int64_t n_emit = N - o->emitted;                                       // truncate to the samples pushed
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    RP_TRY(online_process(o, n_new, n_emit, out));
+    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_host_result(o, n_emit, out));
+    *n_written = n_emit;
+    o->finished = true;
+    return REPET_OK;
+}
+
+int repet_online_finish(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
+    return repet_online_finish_streams(o, out, capacity, n_written);
+}
+
+int repet_online_finish_device(repet_online* o, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                               int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
+    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
     *n_written = n_emit;
     o->finished = true;
     return REPET_OK;
 }
 
 }  // extern "C"
-

@@ -199,6 +199,19 @@ def online(sampling_frequency, number_channels):
     return _OnlineSeparator(derive_params(sampling_frequency), number_channels, _device)
 
 
+def online_streams(sampling_frequency, number_channels, number_streams, max_push_samples=None):
+    """Many live streams at once: ``number_streams`` streams of ``number_channels`` channels at one sampling frequency in ONE
+    streaming handle on the device of :func:`set_device`, pushed in lockstep. ``push(chunk, out=None)`` takes a chunk
+    ``(number_streams, n, number_channels)`` -- a host array, or a ROCm tensor (the dtypes :func:`separate` takes, any strides)
+    -- and returns the ``(number_streams, n_emit, number_channels)`` background samples that became final: a float64 array
+    for a host chunk; for a tensor a float64 tensor on its device, or ``out`` (float32 / float64, any strides) filled, ordered
+    on the current stream with no host wait. ``finish(out=None)`` returns the rest, ``close()`` frees the device state. Each
+    stream's concatenated output equals ``simonline`` of its concatenated input, bit for bit. ``max_push_samples`` sizes the
+    device buffers at open (pushes up to that size then never grow them); the module parameters are snapshotted now."""
+    return _native.OnlineStreams(derive_params(sampling_frequency), number_channels, number_streams, _device,
+                                 max_push_samples or 0)
+
+
 def run_batch(algo, audio_signals, sampling_frequency, n_devices=1, transport="host", device=None, depth=None):
     """Separate a list of independent clips, dealt longest-first over ``n_devices`` GPUs of this process. ``transport``:
     "host" -- every device moves its own clips over its own PCIe link; "rccl" -- the clips enter through device 0 and

@@ -140,6 +140,12 @@ _SIGNATURES = {
     "repet_online_push": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_finish": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_close": (C.c_int, [_P]),
+    "repet_online_open_streams": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(Params), C.c_int64, C.POINTER(_P)]),
+    "repet_online_emit_count": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "repet_online_push_streams": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_push_device": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_online_finish_streams": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_finish_device": (C.c_int, [_P, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -639,6 +645,132 @@ class OnlineSeparator:
                 continue
             check(rc)
             return out[:written.value].copy()
+
+    def close(self):
+        if self._h:
+            lib().repet_online_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class OnlineStreams:
+    """S live streams of one sampling frequency and channel count in one streaming handle (``repet.online_streams``), pushed
+    in lockstep: every ``push`` brings ``(S, n, C)`` samples, and each stream's concatenated output equals ``repet.simonline``
+    of its concatenated input. Host chunks (NumPy arrays, lists, CPU tensors) return float64 ``(S, n_emit, C)`` arrays; ROCm
+    tensors return a float64 tensor on their device (or fill ``out``), ordered on its current stream with no host wait."""
+
+    def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0):
+        self._h = C.c_void_p()
+        self._channels = int(n_channels)
+        self._streams = int(n_streams)
+        self._device = int(device)
+        self._last_on_device = False
+        if self._streams < 1 or self._channels < 1:
+            raise ValueError("at least one stream and one channel")
+        if lib().repet_device_count() < 1:
+            raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
+        check(lib().repet_online_open_streams(self._device, self._streams, self._channels, C.byref(params),
+                                              int(max_push_samples or 0), C.byref(self._h)))
+
+    @property
+    def shape(self):
+        """(number_streams, number_channels)"""
+        return self._streams, self._channels
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the stream handle is closed")
+        return self._h
+
+    def emit_count(self, number_samples, finishing=False):
+        """Samples per stream the next push of ``number_samples`` (or the finish) will return."""
+        n = C.c_int64()
+        check(lib().repet_online_emit_count(self._handle(), int(number_samples), int(bool(finishing)), C.byref(n)))
+        return n.value
+
+    def _check_shape(self, shape):
+        if len(shape) != 3:
+            raise ValueError("a chunk is (number_streams, number_samples, number_channels)")
+        if shape[0] != self._streams:
+            raise ValueError(f"chunk has {shape[0]} streams, the handle {self._streams}")
+        if shape[2] != self._channels:
+            raise ValueError(f"chunk has {shape[2]} channels, the streams {self._channels}")
+
+    def _device_out(self, out, n_emit):
+        import torch
+        device = torch.device("cuda", self._device)
+        shape = (self._streams, n_emit, self._channels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=device)
+        else:
+            if not is_device_tensor(out) or out.device != device:
+                raise ValueError(f"out must be a tensor on {device}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
+            if any(st < 0 for st in out.stride()):
+                raise ValueError("out has negative strides")
+        return out, result_tensor_code(out), tuple(int(st) for st in out.stride())
+
+    def push(self, chunk, out=None):
+        """Feed ``(S, n, C)`` more samples; returns the ``(S, n_emit, C)`` background samples that became final."""
+        if is_device_tensor(chunk):
+            return self._push_device(chunk, out)
+        if out is not None:
+            raise ValueError("out is for device chunks (a host chunk returns a new array)")
+        if is_tensor(chunk):
+            chunk = chunk.numpy()
+        a, code = as_input(chunk)
+        self._check_shape(a.shape)
+        n = a.shape[1]
+        n_emit = self.emit_count(n)
+        result = np.empty((self._streams, n_emit, self._channels), dtype=np.float64)
+        written = C.c_int64()
+        check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(result), n_emit, C.byref(written)))
+        self._last_on_device = False
+        return result
+
+    def _push_device(self, x, out):
+        import torch
+        if x.device.index != self._device:
+            raise ValueError(f"tensor is on {x.device}, the streams on device {self._device}")
+        if x.dim() != 3:
+            raise ValueError("a chunk is (number_streams, number_samples, number_channels)")
+        self._check_shape(tuple(x.shape))
+        x, code, shape, strides = tensor_layout(x, batched=True)
+        n = shape[1]
+        out, out_code, out_strides = self._device_out(out, self.emit_count(n))
+        stream = torch.cuda.current_stream(x.device)
+        written = C.c_int64()
+        check(lib().repet_online_push_device(self._handle(), C.c_void_p(x.data_ptr() or None), code, n, _strides(strides),
+                                             _stream_handle(stream), C.c_void_p(out.data_ptr() or None), out_code,
+                                             _strides(out_strides), _stream_handle(stream), C.byref(written)))
+        # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
+        # recorded on it, the caching allocator hands its block out again only once the ingest has read it
+        x.record_stream(stream)
+        self._last_on_device = True
+        return out
+
+    def finish(self, out=None):
+        """End every stream: the remaining samples, ``(S, n_rest, C)`` -- a float64 tensor on the device when ``out`` is given
+        or the last push was a device chunk, a NumPy array otherwise. ValueError if the streams are shorter than the buffer."""
+        n_emit = self.emit_count(0, finishing=True)
+        if out is not None or self._last_on_device:
+            import torch
+            out, out_code, out_strides = self._device_out(out, n_emit)
+            stream = torch.cuda.current_stream(out.device)
+            written = C.c_int64()
+            check(lib().repet_online_finish_device(self._handle(), C.c_void_p(out.data_ptr() or None), out_code,
+                                                   _strides(out_strides), _stream_handle(stream), C.byref(written)))
+            return out
+        result = np.empty((self._streams, n_emit, self._channels), dtype=np.float64)
+        written = C.c_int64()
+        check(lib().repet_online_finish_streams(self._handle(), ptr(result), n_emit, C.byref(written)))
+        return result
 
     def close(self):
         if self._h:

@@ -1,0 +1,119 @@
+"""Latency per push of S live 44.1-kHz stereo streams: one ``repet.online_streams`` handle (host chunks and ROCm-tensor
+chunks) against S separate ``repet.online`` handles pushed one after another, at 1 and 4 hops per push. Each latency is one
+call plus, for device chunks, a synchronize; the streams are first pushed past the 10-s warm-up buffer so that every frame
+is active. Prints one JSON document (median and p95 in ms per push, and the audio it carries)."""
+import argparse
+import json
+import sys
+import time
+
+import numpy as np
+
+sys.path[:0] = ["repet-python_amd", "."]
+import repet  # noqa: E402
+from repet_synth import synth  # noqa: E402
+
+
+def stream_signals(S, seconds, fs, ch):
+    """S distinct streams from a few synthesised clips (rolled and scaled: synthesis of 256 clips would dominate the run)."""
+    base = [synth(seconds, fs, ch, seed) for seed in range(4)]
+    return np.stack([np.roll(base[s % 4], 997 * s, axis=0) * (1.0 - 0.001 * s) for s in range(S)])
+
+
+def stats(lat_s, n, fs):
+    lat = np.array(lat_s) * 1e3
+    return {"latency_ms_median": round(float(np.median(lat)), 3), "latency_ms_p95": round(float(np.percentile(lat, 95)), 3),
+            "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
+
+
+def one_handle(xs, fs, hops, device, timed, warm_s):
+    import torch
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    n = hops * hop
+    src = torch.tensor(xs, device="cuda:0") if device else xs
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    h = repet.online_streams(fs, ch, S, max_push_samples=n)
+    pos = 0
+    while pos < warm_s * fs:                                   # fill the buffer in half-second pushes
+        h.push(src[:, pos:pos + fs // 2])
+        pos += fs // 2
+    for _ in range(3):                                         # the per-push workspaces take their size
+        h.push(src[:, pos:pos + n])
+        pos += n
+    torch.cuda.synchronize()
+    held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
+    lat = []
+    for _ in range(timed):
+        if pos + n > N:
+            break
+        t0 = time.perf_counter()
+        h.push(src[:, pos:pos + n])
+        if device:
+            torch.cuda.synchronize()
+        lat.append(time.perf_counter() - t0)
+        pos += n
+    h.close()
+    out = stats(lat, n, fs)
+    out["device_mb_per_stream"] = round(held / S / 2**20, 1)
+    return out
+
+
+def separate_handles(xs, fs, hops, timed, warm_s):
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    n = hops * hop
+    hs = [repet.online(fs, ch) for _ in range(S)]
+    pos = 0
+    while pos < warm_s * fs:
+        for s, h in enumerate(hs):
+            h.push(xs[s, pos:pos + fs // 2])
+        pos += fs // 2
+    lat = []
+    for _ in range(timed + 3):
+        if pos + n > N:
+            break
+        t0 = time.perf_counter()
+        for s, h in enumerate(hs):
+            h.push(xs[s, pos:pos + n])
+        lat.append(time.perf_counter() - t0)
+        pos += n
+    for h in hs:
+        h.close()
+    return stats(lat[3:], n, fs)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--streams", default="1,8,64,256")
+    ap.add_argument("--hops", default="1,4")
+    ap.add_argument("--timed", type=int, default=60, help="pushes timed per case")
+    ap.add_argument("--separate-max", type=int, default=64, help="largest S run as S separate repet.online handles")
+    ap.add_argument("--only", choices=["all", "device"], default="all", help="device: the one-handle device-chunk cases only")
+    args = ap.parse_args()
+    fs, ch, warm_s = 44100, 2, 11
+    streams = [int(s) for s in args.streams.split(",")]
+    hops_list = [int(h) for h in args.hops.split(",")]
+    hop = repet.derive_params(fs).step_length
+    seconds = warm_s + 1 + (args.timed + 4) * max(hops_list) * hop / fs
+    result = {"fs": fs, "channels": ch, "cases": []}
+    for S in streams:
+        xs = stream_signals(S, seconds, fs, ch)
+        for hops in hops_list:
+            case = {"streams": S, "hops_per_push": hops}
+            case["one_handle_device_chunks"] = one_handle(xs, fs, hops, True, args.timed, warm_s)
+            if args.only == "all":
+                case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s)
+                if S <= args.separate_max:
+                    case["separate_handles_host"] = separate_handles(xs, fs, hops, args.timed, warm_s)
+            result["cases"].append(case)
+            print(json.dumps(case), file=sys.stderr, flush=True)
+    one = {(c["streams"], c["hops_per_push"]): c["one_handle_device_chunks"]["latency_ms_median"] for c in result["cases"]}
+    result["device_push_ratio_to_S1"] = {f"S{S}_{h}hop": round(one[(S, h)] / one[(1, h)], 2)
+                                         for (S, h) in one if (1, h) in one}
+    print(json.dumps(result, indent=1))
+
+
+if __name__ == "__main__":
+    main()
