@@ -462,6 +462,33 @@ int repet_online_finish_streams(repet_online* h, double* out, int64_t capacity, 
 int repet_online_finish_device(repet_online* h, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                                int64_t* n_written);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) Streams that join and leave ONE BY ONE. The S streams of
+ * a handle are S slots. Pushes stay in lockstep ((S, n, C) in, (S, n_emit, C) out, n_emit as above); what is per slot is which
+ * stream lives in it and since when. With P = samples per slot pushed so far, W the window, H = W / 2, B buffer_frames:
+ * restart_streams : each named slot begins a new stream whose sample 0 is the handle's sample P. Only where P % H == 0
+ *                   (REPET_ERR_BAD_ARG otherwise, nothing changes). What lived in the slot is discarded; the frame that
+ *                   straddles P and everything older reach neither the new stream's similarity buffer nor its overlap-add
+ *                   (NaN in them included). The slot's lockstep output from sample P on, followed by its finish_stream (or
+ *                   finish) tail, equals repet.simonline of the new stream's samples, bit for bit: zeros while it is younger
+ *                   than B - 1 frames, then its own B-frame buffer at circular positions (its own frame number) % B.
+ * release_streams : the named slots become idle without output. An idle slot ignores what the lockstep chunk carries for it
+ *                   (NaN included) and emits zeros.
+ * stream_emit_count / finish_stream(_device): end the stream of ONE slot where the handle stands (any P, on the hop grid or not):
+ *                   its zero-padded last frame and its tail of P - (samples emitted) samples, out[n][C] float64 on the host or
+ *                   a device destination with element strides [sample, channel] as finish_device's. REPET_ERR_BAD_ARG for an
+ *                   idle slot, REPET_ERR_TOO_SHORT for a stream shorter than (B - 2) H + W (the slot then stays as it was).
+ *                   Touches no other slot and no counter of the handle; the slot is idle afterwards.
+ * repet_online_finish_* keeps its meaning: it ends every live slot, each with its own length (a stream still younger than the
+ * buffer has only zeros to give); idle slots return zeros. Every call enqueues on the handle's stream with no host wait (the
+ * host forms of finish_stream wait for their result); restart / release are one launch per 256 slots named. A handle on which
+ * none of these calls was made behaves exactly as before. */
+int repet_online_restart_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
+int repet_online_release_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
+int repet_online_stream_emit_count(repet_online* h, int32_t slot, int64_t* n_emit);
+int repet_online_finish_stream(repet_online* h, int32_t slot, double* out, int64_t capacity, int64_t* n_written);
+int repet_online_finish_stream_device(repet_online* h, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
+                                      void* signal_stream, int64_t* n_written);
+
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,
  * fp32 -> float64; non-temporal AVX-512 / AVX2 lines where the CPU has them) against scalar loops on n values with NaN,
  * infinities, denormals, PCM-exact runs and every misalignment. No GPU needed. Returns the number of values that differ

@@ -290,7 +290,10 @@ struct PeakRefine {
 // float64 L2 norm of every fp32 row: norms[r] = sqrt(sum_k rows[r * pitch + k]^2), n_rows rows of `pitch` floats (pitch % 4 == 0)
 hipError_t launch_unit_row_norms(const float* rows, int64_t n_rows, int32_t pitch, double* norms, hipStream_t s);
 // batch (nullable): blockIdx.y = clip of a batch of equal-shape matrices; element strides between the clips
-struct PeakBatch { int32_t n_batch; int64_t m_stride, idx_stride, cnt_stride, unit_stride; };
+// origin (nullable; modes 1 and 2, the streaming handle's slots): frame number at which clip b's own stream began. The clip's rows
+// are numbered from there (row0 and shift both count from origin[b]: circular positions are those of the clip's own frames,
+// the band rows stay where they are), and a row younger than n_cols - 1 frames is not active: count 0, no list.
+struct PeakBatch { int32_t n_batch; int64_t m_stride, idx_stride, cnt_stride, unit_stride; const int64_t* origin; };
 hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int32_t n_cols, int64_t pitch,
                                int32_t mode, float min_value, int32_t d, int32_t number, int32_t* idx,
                                int32_t idx_pitch, int32_t* count, hipStream_t s, int64_t shift = 0,
@@ -370,6 +373,10 @@ struct MaskArgs {
     // P == nullptr: the packed network on R.
     const unsigned* P; int32_t n_planes;
     unsigned* median_codes;       // bit-sliced selection: one word per cell, V's geometry (upper code << 16 | lower code | flag)
+    // mask_sim only (nullable; the streaming handle's slots): clip b's own stream began at frame slot_start[b], and frame row t
+    // is frame slot_bias + t + (warm-up length) of the handle: rows with t + slot_bias < slot_start[b] are warm-up rows of that
+    // clip whatever first_frame says (the list rows stay numbered from first_frame)
+    const int64_t* slot_start; int64_t slot_bias;
 };
 constexpr int kPadRows = 8;       // rows kept behind the Tpad frame rows of V (2 used)
 constexpr int kMinIdxPitch = 128; // index lists are readable up to the largest network size

@@ -242,19 +242,25 @@ __global__ __launch_bounds__(kIoThreads) void online_append_bf16(const BHalf* sr
 // Row copies: part z moves `blocks` runs of `len` floats of every stream (or writes zeros where src is null). Slots of four
 // consecutive floats of a run; a whole slot is one dwordx4 store where the destination side is aligned (RowCopy::dst_vec)
 // and one dwordx4 load where the source side is (src_vec), element accesses otherwise.
-struct RowCopyDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream; int32_t src_vec, dst_vec; };
-struct RowCopyArgs { RowCopyDev part[repet_eng::kRowCopyParts]; int32_t n_streams; };
+struct RowCopyDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream; int32_t src_vec, dst_vec; int64_t row_len, frame0; };
+struct RowCopyArgs { RowCopyDev part[repet_eng::kRowCopyParts]; int32_t n_streams; const int64_t* slot_start; };
 
 __global__ __launch_bounds__(kIoThreads) void online_row_copies(RowCopyArgs a) {
     const RowCopyDev p = a.part[blockIdx.z];
     const int64_t slots = p.slots_per_block * p.blocks;
     for (int64_t b = blockIdx.y; b < a.n_streams; b += gridDim.y) {
+        int64_t len = p.len;
+        if (p.row_len > 0) {                                      // only the frame rows before the slot's own first frame
+            const int64_t rows = a.slot_start ? a.slot_start[b] - p.frame0 : 0;
+            len = rows <= 0 ? 0 : (rows < p.len / p.row_len ? rows * p.row_len : p.len);
+        }
         for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
             const int64_t blk = q / p.slots_per_block;
             const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+            if (i0 >= len) continue;
             float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
             const float* s = p.src ? p.src + b * p.src_stream + blk * p.src_block + i0 : nullptr;
-            if (i0 + 4 <= p.len && p.dst_vec) {
+            if (i0 + 4 <= len && p.dst_vec) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (s) {
                     if (p.src_vec) v = *reinterpret_cast<const float4*>(s);
@@ -262,9 +268,35 @@ __global__ __launch_bounds__(kIoThreads) void online_row_copies(RowCopyArgs a) {
                 }
                 *reinterpret_cast<float4*>(d) = v;
             } else {
-                const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
+                const int64_t m = len - i0 < 4 ? len - i0 : 4;
                 for (int64_t k = 0; k < m; ++k) d[k] = s ? s[k] : 0.f;
             }
+        }
+    }
+}
+
+// Slot reset (restart / release of slots of the streaming handle): workgroups (x, slot of the list, part) write the part's
+// runs of zeros into that slot's share of the buffers, and one thread per slot its new first frame.
+struct ZeroPartDev { float* dst; int64_t len, slots_per_block, blocks, dst_block, dst_stream; int32_t vec; };
+struct SlotResetArgs {
+    ZeroPartDev part[repet_eng::kRowCopyParts]; int64_t* slot_start; int64_t value; int32_t n_slots;
+    unsigned short slot[repet_eng::kSlotResetIds];
+};
+
+__global__ __launch_bounds__(kIoThreads) void online_slot_reset(SlotResetArgs a) {
+    const int64_t b = a.slot[blockIdx.y];
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) a.slot_start[b] = a.value;
+    const ZeroPartDev p = a.part[blockIdx.z];
+    const int64_t slots = p.slots_per_block * p.blocks;
+    for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+        const int64_t blk = q / p.slots_per_block;
+        const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+        float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
+        if (i0 + 4 <= p.len && p.vec) {
+            *reinterpret_cast<float4*>(d) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
+            for (int64_t k = 0; k < m; ++k) d[k] = 0.f;
         }
     }
 }
@@ -317,10 +349,11 @@ hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, i
     return hipGetLastError();
 }
 
-hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s) {
+hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s, const int64_t* slot_start) {
     if (n_parts <= 0 || n_parts > kRowCopyParts || n_streams <= 0) return n_parts == 0 ? hipSuccess : hipErrorInvalidValue;
     RowCopyArgs a{};
     a.n_streams = n_streams;
+    a.slot_start = slot_start;
     int64_t most = 1;
     auto aligned = [](const float* p, int64_t b1, int64_t b2) {
         return !(reinterpret_cast<uintptr_t>(p) & 15) && !(b1 & 3) && !(b2 & 3);
@@ -328,7 +361,7 @@ hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_stream
     for (int k = 0; k < kRowCopyParts; ++k) {
         RowCopyDev& d = a.part[k];
         if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) {      // an empty part: no slots
-            d = RowCopyDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0};
+            d = RowCopyDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             continue;
         }
         const RowCopy& p = parts[k];
@@ -336,10 +369,38 @@ hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_stream
         d.src_block = p.src_block; d.dst_block = p.dst_block; d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
         d.dst_vec = aligned(p.dst, p.dst_block, p.dst_stream) ? 1 : 0;
         d.src_vec = p.src && aligned(p.src, p.src_block, p.src_stream) ? 1 : 0;
+        d.row_len = p.row_len; d.frame0 = p.frame0;
         most = std::max(most, d.slots_per_block * d.blocks);
     }
     online_row_copies<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
+}
+
+hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* slots, int32_t n_slots, const ZeroPart* parts,
+                             int n_parts, hipStream_t s) {
+    if (n_slots <= 0) return hipSuccess;
+    if (!slot_start || !slots || n_parts < 0 || n_parts > kRowCopyParts) return hipErrorInvalidValue;
+    SlotResetArgs a{};
+    a.slot_start = slot_start; a.value = value;
+    int64_t most = 1;
+    for (int k = 0; k < kRowCopyParts; ++k) {
+        ZeroPartDev& d = a.part[k];
+        d = ZeroPartDev{nullptr, 0, 1, 0, 0, 0, 0};
+        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;
+        const ZeroPart& p = parts[k];
+        d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
+        d.dst_block = p.dst_block; d.dst_stream = p.dst_stream;
+        d.vec = !(reinterpret_cast<uintptr_t>(p.dst) & 15) && !(p.dst_block & 3) && !(p.dst_stream & 3) ? 1 : 0;
+        most = std::max(most, d.slots_per_block * d.blocks);
+    }
+    for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
+        a.n_slots = std::min<int32_t>(kSlotResetIds, n_slots - first);
+        for (int32_t k = 0; k < a.n_slots; ++k) a.slot[k] = (unsigned short)slots[first + k];
+        online_slot_reset<<<stream_grid(most, a.n_slots, kRowCopyParts), kIoThreads, 0, s>>>(a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,

@@ -265,11 +265,20 @@ int ensure_io_events(repet_ctx* c);
 //   append   chunk [S][n][C] (strided, any device dtype) -> hi / lo at s * dst_stream + dst_off (fp32 + fp32 remainder)
 //   copies   up to kRowCopyParts parts of `blocks` runs of `len` floats per stream (src null: zeros), one launch
 //   egress   fp32 [S][n][C] -> strided F32 / F64 destination
-struct RowCopy { const float* src; float* dst; int64_t len, blocks, src_block, dst_block, src_stream, dst_stream; };
+//            a part with row_len > 0 covers frame rows of row_len floats, the first of them frame `frame0`: of stream b only
+//            the rows of frames before slot_start[b] are written (the rows of a slot whose own stream has not begun)
+//   reset    the named slots' own stream begins at frame `value` (kSlotIdle: never): slot_start[slot] = value and up to
+//            kRowCopyParts runs of zeros per slot (ZeroPart, strides as RowCopy's), one launch per kSlotResetIds slots
+struct RowCopy { const float* src; float* dst; int64_t len, blocks, src_block, dst_block, src_stream, dst_stream; int64_t row_len = 0, frame0 = 0; };
 constexpr int kRowCopyParts = 5;
+struct ZeroPart { float* dst; int64_t len, blocks, dst_block, dst_stream; };
+constexpr int kSlotResetIds = 256;
+constexpr int64_t kSlotIdle = (int64_t)1 << 60;
+hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* slots, int32_t n_slots, const ZeroPart* parts,
+                             int n_parts, hipStream_t s);
 hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
                                 float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s);
-hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s);
+hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s, const int64_t* slot_start = nullptr);
 hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,
                                 const int64_t strides[3], hipStream_t s);
 constexpr int kRankMinList = 24;     // shortest list bound for which the column sort is worth its time

@@ -12,11 +12,23 @@ using namespace repet_eng;
 // bit-identical to repet.simonline of the whole signal. Device state: a sliding window of the last B-1
 // frames (magnitudes, unit rows, the last masked spectrum for the overlap-add tail) plus the unconsumed
 // samples; every push processes all newly complete frames in one batch of launches.
+// A handle of S streams is a handle of S slots: the pushes and the counters are shared, but a slot's own stream may begin
+// later than the handle's (repet_online_restart_streams), end earlier (repet_online_finish_stream) or be absent
+// (repet_online_release_streams). All of that is one number per slot, the frame at which its stream began, which the peak
+// picking, the mask and the row zeroing behind the STFT read on the device; the launch shapes are the handle's.
 // =====================================================================================================
 struct repet_online {
     repet_ctx* ctx = nullptr;       // stream, tables, tile cache, scratch buffers
     repet_params p{};
-    int S = 1;                      // live streams in lockstep: every counter below is shared, only the data is per stream
+    int S = 1;                      // slots pushed in lockstep: the counters below are the handle's, the data is per slot
+    // Which stream lives in a slot, and since when: slot s's own stream began at handle frame start[s] (sample start[s] * H;
+    // kSlotIdle: no stream). slot_start is the same on the device, read by the peak picking, the mask and the row zeroing
+    // once slots_on (a restart, release or finish_stream was made; until then every slot's stream is the handle's and no
+    // kernel is given the table). latest_start: the largest frame a restart named; n_idle: idle slots.
+    std::vector<int64_t> start;
+    DevBuf slot_start;
+    bool slots_on = false;
+    int64_t latest_start = 0, n_idle = 0;
     int C = 0, W = 0, H = 0, F = 0, FS = 0, B = 0, Hh = 0, LP = 0;
     // per stream s, at the strides below: X / V [C planes of rows_cap + kPadRows rows][FS], Vn [rows_cap rows][FS], the
     // pending samples [pend_cap][C] (pend_lo: their fp32 remainders), and in the per-push workspaces band / idx / cnt / outf
@@ -129,25 +141,32 @@ int online_ensure_pending(repet_online* o, int64_t n) {
 // buffers; samples past pend_count read as zero) and leave `n_emit` output samples per stream and channel, starting at the
 // first sample of hop frames_done, in outf [S][n_emit][C] (fp32). Enqueues only: no host wait unless a buffer grows. One
 // fixed sequence of launches, whatever S and C.
-int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
+// slot >= 0 (finish_stream): the same sequence on that slot alone (a batch of one at the slot's offsets), with no slide and
+// no counter touched: the handle goes on as if the call had not been made.
+int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1) {
     repet_ctx* c = o->ctx;
     if (n_new <= 0 && n_emit <= 0) return REPET_OK;
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, o->W, &tb));
     RP_TRY(online_ensure_windows(o, n_new));
-    const int S = o->S;
+    const bool all = slot < 0;
+    const int S = all ? o->S : 1;
+    const int64_t sb = all ? 0 : slot;
     const int64_t plane = o->plane();                            // chan_stride of X and V
     const int64_t spec = o->spec_stride(), vns = o->vn_stride(), pst = o->pend_stride();
     const int64_t r0 = o->Hh - o->hist_valid;                    // first valid window row
     const int64_t Tw = o->hist_valid + n_new;                    // valid rows (history + new), relative to r0
-    float2* Xb = o->X[o->cur].as<float2>() + r0 * o->FS;
-    float* Vb = o->V[o->cur].as<float>() + r0 * o->FS;
-    float* Vnb = o->Vn[o->cur].as<float>() + r0 * o->FS;
+    float2* Xb = o->X[o->cur].as<float2>() + sb * spec + r0 * o->FS;
+    float* Vb = o->V[o->cur].as<float>() + sb * spec + r0 * o->FS;
+    float* Vnb = o->Vn[o->cur].as<float>() + sb * vns + r0 * o->FS;
+    const float* pend = o->pend[o->pcur].as<float>() + sb * pst;
+    const float* pend_lo = o->pend_lo[o->pcur].as<float>() + sb * pst;
     const int64_t first_global = o->frames_done - o->hist_valid; // global frame number of window row r0
+    const int64_t* starts = o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr;      // the slots' own first frames
 
     if (n_new > 0) {
         StftArgs a{};
-        a.audio = o->pend[o->pcur].as<float>(); a.n_samples = o->pend_count; a.n_channels = o->C; a.sample_offset = o->pend_hist;
+        a.audio = pend; a.n_samples = o->pend_count; a.n_channels = o->C; a.sample_offset = o->pend_hist;
         a.window = tb->window.as<float>(); a.twiddle = tb->twiddle.as<float2>();
         a.W = o->W; a.H = o->H; a.T = n_new; a.FS = o->FS; a.centred = 0;
         a.X = Xb + o->hist_valid * o->FS; a.V = Vb + o->hist_valid * o->FS; a.chan_stride = plane;
@@ -156,8 +175,16 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
         HIP_TRY(launch_stft(a, c->stream));
         // rows behind the new frames up to the next tile boundary must read as zero for the Gram tiles
         const int64_t Tpad = round_up(Tw, kTile);
-        const RowCopy zero{nullptr, Vnb + Tw * o->FS, (Tpad - Tw) * o->FS, 1, 0, 0, 0, vns};
-        HIP_TRY(launch_row_copies(&zero, 1, S, c->stream));
+        // (same launch) the new rows of frames before a slot's own first frame -- the frame that straddles a restart, every
+        // frame of an idle slot -- hold nothing of that slot's stream: zero in Vn, V and X, whatever the chunk carried
+        const bool early = starts && (o->n_idle > 0 || o->latest_start > o->frames_done);
+        const int64_t hv = o->hist_valid * o->FS, nn = n_new * o->FS;
+        const RowCopy zero[4] = {
+            {nullptr, Vnb + Tw * o->FS, (Tpad - Tw) * o->FS, 1, 0, 0, 0, vns},
+            {nullptr, Vnb + hv, nn, 1, 0, 0, 0, vns, o->FS, o->frames_done},
+            {nullptr, Vb + hv, nn, o->C, 0, plane, 0, spec, o->FS, o->frames_done},
+            {nullptr, reinterpret_cast<float*>(Xb) + 2 * hv, 2 * nn, o->C, 0, 2 * plane, 0, 2 * spec, 2 * (int64_t)o->FS, o->frames_done}};
+        HIP_TRY(launch_row_copies(zero, early ? 4 : 1, S, c->stream, starts));
 
         const int64_t first_active = std::max<int64_t>(o->frames_done, o->B - 1);     // global frame number
         const int64_t n_active = o->frames_done + n_new - first_active;
@@ -171,10 +198,11 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
             HIP_TRY(c->cnt.ensure((size_t)S * n_active * sizeof(int32_t)));
             PeakRefine rf{};
             RP_TRY(make_refine(c, Vnb, o->FS, o->p.sim_threshold, &rf, n_active, S, o->B, o->p.sim_distance_frames, Tpad));
-            const PeakBatch pb{S, band_stride, n_active * KP, n_active, vns};
+            const PeakBatch pb{S, band_stride, n_active * KP, n_active, vns, starts};
+            const PeakBatch* batch = (S > 1 || starts) ? &pb : nullptr;
             hipError_t e = launch_local_maxima(o->band.as<float>(), n_active, first_active, o->B, o->LP, peak_mode, (float)o->p.sim_threshold,
                                                o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), c->stream,
-                                               first_global, &rf, S > 1 ? &pb : nullptr);
+                                               first_global, &rf, batch);
             if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "online: buffer too long for the peak-picking kernel");
             HIP_TRY(e);
             // second level: window row fr is global frame first_global + fr, whose first sample sits hist_valid - fr hops
@@ -182,13 +210,14 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
             const Geo go = make_geo(o->W, o->H, Tw, o->C);
             RP_TRY(run_exact_rows(c, tb, go, o->band.as<float>(), first_active, o->B, o->LP, peak_mode, (float)o->p.sim_threshold,
                                   o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_global, rf,
-                                  S > 1 ? &pb : nullptr, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
+                                  batch, pend, pend_lo,
                                   o->pend_hist + o->pend_count, pst, o->pend_hist - o->hist_valid * (int64_t)o->H, Tpad, S));
         }
         MaskArgs m{};
         m.V = Vb; m.chan_stride = plane; m.n_channels = o->C; m.T = Tw; m.F = o->F; m.FS = o->FS; m.X = Xb; m.mask = nullptr;
         m.cutoff = o->p.cutoff_bins; m.pad_row = o->rows_cap - r0; m.frame0 = o->hist_valid;
         m.n_batch = S; m.batch_stride = spec;
+        m.slot_start = starts; m.slot_bias = first_global - (o->B - 1);     // row t is the slot's frame first_global + t - start
         m.idx_batch_stride = std::max<int64_t>(n_active, 0) * KP; m.cnt_batch_stride = std::max<int64_t>(n_active, 0);
         const int64_t first_frame = Tw - std::max<int64_t>(n_active, 0);          // warm-up rows before it are zeroed
         const int max_peaks = (int)std::min<int64_t>(K, ceil_div(o->B, o->p.sim_distance_frames + 1));
@@ -207,7 +236,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
         if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
         HIP_TRY(e);
     }
-    if (n_new > 0) {
+    if (n_new > 0 && all) {
         // slide, one launch for every stream and channel: the last min(Hh, Tw) rows of V and Vn and the last masked spectrum
         // (overlap-add tail of the next hop) become the history of the other window; the samples of the window's frames
         // (h2 hops of history) and the unconsumed ones move to the front of the other pending buffer
@@ -234,7 +263,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit) {
         o->pend_count = left;
         o->frames_done += n_new;
     }
-    o->emitted += n_emit;
+    if (all) o->emitted += n_emit;
     return REPET_OK;
 }
 
@@ -271,14 +300,15 @@ int online_append(repet_online* o, const void* src, int dtype, int64_t n, const 
 }
 
 // host side of a push or finish: the result [S][n_emit][C] widened on the device, one copy into the pinned buffer, then `out`
-int online_host_result(repet_online* o, int64_t n_emit, double* out) {
+int online_host_result(repet_online* o, int64_t n_emit, double* out, int streams = 0) {
     repet_ctx* c = o->ctx;
-    const int64_t count = (int64_t)o->S * n_emit * o->C;
+    const int S = streams > 0 ? streams : o->S;
+    const int64_t count = (int64_t)S * n_emit * o->C;
     if (count > 0) {
         HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
         RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
         const int64_t dense[3] = {n_emit * o->C, o->C, 1};
-        HIP_TRY(launch_stream_egress(o->outf.as<float>(), o->S, n_emit, o->C, o->out64.p, REPET_F64, dense, c->stream));
+        HIP_TRY(launch_stream_egress(o->outf.as<float>(), S, n_emit, o->C, o->out64.p, REPET_F64, dense, c->stream));
         HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -287,18 +317,19 @@ int online_host_result(repet_online* o, int64_t n_emit, double* out) {
 }
 
 // device side: the result into the caller's strided destination, then the caller's stream behind it
-int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], hipStream_t signal) {
+int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], hipStream_t signal,
+                         int streams = 0) {
     repet_ctx* c = o->ctx;
-    HIP_TRY(launch_stream_egress(o->outf.as<float>(), o->S, n_emit, o->C, dst, dst_dtype, dst_strides, c->stream));
+    HIP_TRY(launch_stream_egress(o->outf.as<float>(), streams > 0 ? streams : o->S, n_emit, o->C, dst, dst_dtype, dst_strides, c->stream));
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(signal, c->io_done, 0));
     return REPET_OK;
 }
 
-int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int dst_dtype, const int64_t dst_strides[3]) {
+int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int dst_dtype, const int64_t dst_strides[3], int streams = 0) {
     if (dst_dtype != REPET_F32 && dst_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
     RP_TRY(check_strides(dst_strides));
-    RP_TRY(check_no_overlap(dst_strides, o->S, n_emit, o->C));
+    RP_TRY(check_no_overlap(dst_strides, streams > 0 ? streams : o->S, n_emit, o->C));
     if (n_emit > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
     return REPET_OK;
 }
@@ -316,9 +347,112 @@ int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
     return REPET_OK;
 }
 
+// restart (first_frame = the handle's next frame) or release (kSlotIdle) of the named slots: one launch writes their first
+// frame on the device and clears what the slots hold of an earlier stream -- the history rows of Vn and V, the last masked
+// spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
+int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t first_frame) {
+    repet_ctx* c = o->ctx;
+    if (n <= 0) return REPET_OK;
+    const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), held = (o->pend_hist + o->pend_count) * o->C;
+    ZeroPart parts[kRowCopyParts] = {};
+    int n_parts = 0;
+    if (o->rows_cap > 0) {
+        parts[n_parts++] = ZeroPart{o->Vn[o->cur].as<float>(), o->Hh * FS, 1, 0, o->vn_stride()};
+        parts[n_parts++] = ZeroPart{o->V[o->cur].as<float>(), o->Hh * FS, o->C, plane, spec};
+        parts[n_parts++] = ZeroPart{o->X[o->cur].as<float>() + 2 * (o->Hh - 1) * FS, 2 * FS, o->C, 2 * plane, 2 * spec};
+    }
+    if (o->pend_cap > 0 && held > 0) {
+        parts[n_parts++] = ZeroPart{o->pend[o->pcur].as<float>(), held, 1, 0, o->pend_stride()};
+        parts[n_parts++] = ZeroPart{o->pend_lo[o->pcur].as<float>(), held, 1, 0, o->pend_stride()};
+    }
+    HIP_TRY(launch_slot_reset(o->slot_start.as<int64_t>(), first_frame, slots, n, parts, n_parts, c->stream));
+    for (int32_t k = 0; k < n; ++k) {
+        int64_t& st = o->start[(size_t)slots[k]];
+        o->n_idle += (first_frame == kSlotIdle ? 1 : 0) - (st == kSlotIdle ? 1 : 0);
+        st = first_frame;
+    }
+    if (first_frame != kSlotIdle) o->latest_start = std::max(o->latest_start, first_frame);
+    o->slots_on = true;
+    return REPET_OK;
+}
+
+int online_check_slots(const repet_online* o, const int32_t* slots, int32_t n) {
+    if (!o || n < 0 || (n > 0 && !slots)) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    for (int32_t k = 0; k < n; ++k)
+        if (slots[k] < 0 || slots[k] >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    return REPET_OK;
+}
+
+// what finish_stream of `slot` writes: the frames still to process and the samples of the tail. The slot's stream is the
+// handle's samples [start * H, total_in): it ends where the handle stands, so both numbers are those of the handle's own
+// finish; only the length that must cover the buffer is the slot's
+int online_plan_slot(const repet_online* o, int32_t slot, int64_t* n_new, int64_t* n_emit) {
+    if (!o || !n_new || !n_emit) return fail(REPET_ERR_BAD_ARG, "null argument");
+    RP_TRY(online_check_slots(o, &slot, 1));
+    const int64_t st = o->start[(size_t)slot];
+    if (st == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
+    const int64_t N = o->total_in - st * (int64_t)o->H;
+    if (N < (int64_t)(o->B - 2) * o->H + o->W)
+        return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
+    return online_plan(o, 0, true, n_new, n_emit);
+}
+
 }  // namespace repet_eng
 
 extern "C" {
+
+int repet_online_restart_streams(repet_online* o, const int32_t* slots, int32_t n) {
+    RP_TRY(online_check_slots(o, slots, n));
+    if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, "online: a stream can only begin on a hop boundary (samples pushed % step_length == 0)");
+    DeviceGuard guard(o->ctx->device);
+    return online_reset_slots(o, slots, n, o->total_in / o->H);
+}
+
+int repet_online_release_streams(repet_online* o, const int32_t* slots, int32_t n) {
+    RP_TRY(online_check_slots(o, slots, n));
+    DeviceGuard guard(o->ctx->device);
+    return online_reset_slots(o, slots, n, kSlotIdle);
+}
+
+int repet_online_stream_emit_count(repet_online* o, int32_t slot, int64_t* n_emit) {
+    int64_t n_new = 0;
+    return online_plan_slot(o, slot, &n_new, n_emit);
+}
+
+int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64_t capacity, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
+    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    DeviceGuard guard(o->ctx->device);
+    o->slots_on = true;
+    RP_TRY(online_process(o, n_new, n_emit, slot));
+    RP_TRY(online_host_result(o, n_emit, out, 1));
+    RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
+    *n_written = n_emit;
+    return REPET_OK;
+}
+
+int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
+                                      void* signal_stream, int64_t* n_written) {
+    if (!o || !n_written || !dst_strides) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
+    const int64_t strides[3] = {0, dst_strides[0], dst_strides[1]};
+    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, strides, 1));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    o->slots_on = true;
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_process(o, n_new, n_emit, slot));
+    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
+    RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
+    *n_written = n_emit;
+    return REPET_OK;
+}
 
 int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p, int64_t max_push_samples,
                               repet_online** out) {
@@ -334,6 +468,13 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
     o->p = *p; o->S = n_streams; o->C = n_channels; o->W = p->window_length; o->H = p->step_length; o->F = o->W / 2 + 1;
     o->FS = (int)round_up(o->F, kFreqAlign); o->B = p->buffer_frames; o->Hh = o->B - 1; o->LP = (int)round_up(o->B, 64);
     o->max_push = max_push_samples;
+    o->start.assign((size_t)n_streams, 0);
+    {   // every slot's stream begins with the handle's until a restart or release says otherwise
+        DeviceGuard guard(o->ctx->device);
+        hipError_t e = o->slot_start.ensure((size_t)n_streams * sizeof(int64_t));
+        if (e == hipSuccess) e = hipMemsetAsync(o->slot_start.p, 0, (size_t)n_streams * sizeof(int64_t), o->ctx->stream);
+        if (e != hipSuccess) { repet_online_close(o); return fail(e == hipErrorOutOfMemory ? REPET_ERR_OOM : REPET_ERR_HIP, hipGetErrorString(e)); }
+    }
     if (max_push_samples > 0) {
         // a push of up to max_push_samples completes at most max_push / H + 1 frames, the finish at most W / H + 1
         DeviceGuard guard(o->ctx->device);
@@ -357,7 +498,7 @@ int repet_online_close(repet_online* o) {
         DeviceGuard guard(o->ctx->device);
         (void)hipStreamSynchronize(o->ctx->stream);
         for (int k = 0; k < 2; ++k) { o->X[k].release(); o->V[k].release(); o->Vn[k].release(); o->pend[k].release(); o->pend_lo[k].release(); }
-        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release();
+        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release();
         free_pinned(o->host_in, o->host_in_cap);
         free_pinned(o->host_out, o->host_out_cap);
     }

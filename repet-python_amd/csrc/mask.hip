@@ -136,6 +136,13 @@ __device__ __forceinline__ int pad_offset(int k, int n, int pad_row_bytes, int r
 }
 
 
+// first frame row of clip `clip` that is not a warm-up row: first_frame, or later where the clip is a slot of the streaming
+// handle whose own stream began after the handle's (MaskArgs::slot_start; one uniform load per workgroup)
+__device__ __forceinline__ int64_t warm_up_end(const MaskArgs& a, int64_t first_frame, int clip) {
+    if (!a.slot_start) return first_frame;
+    const int64_t own = a.slot_start[clip] - a.slot_bias;
+    return own > first_frame ? own : first_frame;
+}
 __device__ __forceinline__ void emit(const MaskArgs& a, int c, int64_t t, int f, float m) {
     const int64_t o = c * a.chan_stride + t * a.FS + f;
     if (a.mask) a.mask[o] = m;
@@ -237,7 +244,7 @@ __global__ __launch_bounds__(256) void mask_sim_kernel(MaskArgs a, const int* __
     const int nbins = SPLIT ? a.F - 1 : a.F;
     const int nfb = (nbins + 63) >> 6;
     const float* Vc = a.V + c * a.chan_stride;
-    if (t < first_frame) {           // online warm-up frames contribute nothing (repet.py:834)
+    if (t < warm_up_end(a, first_frame, blockIdx.z)) {           // online warm-up frames contribute nothing (repet.py:834)
         for (int f = threadIdx.x; f < a.F; f += 256) emit(a, c, t, f, 0.f);
         return;
     }
@@ -312,9 +319,10 @@ __global__ __launch_bounds__(256) void mask_sim_wide_kernel(MaskArgs a, const in
     const int row_bytes = a.FS * 4, pad_bytes = (int)a.pad_row * row_bytes;
     const __amdgpu_buffer_rsrc_t rsrc = channel_rsrc(Vc, a.chan_stride);
     const unsigned f_begin = blockIdx.x * kWideRun, f_end = min(f_begin + kWideRun, n_frames);
+    const int64_t warm_end = warm_up_end(a, first_frame, blockIdx.z);
     // the list of a frame, as the gathers need it: its length (wave-uniform) and entry `lane` (rows of idx hold >= 128 entries)
     auto fetch_list = [&](int64_t t, int& n, int& e) {
-        if (t < first_frame) { n = -1; e = 0; return; }                         // warm-up frame: nothing to gather
+        if (t < warm_end) { n = -1; e = 0; return; }                            // warm-up frame: nothing to gather
         const int64_t r = t - first_frame;
         n = count[r];
         e = idx[r * (int64_t)idx_pitch + lane];
@@ -368,10 +376,10 @@ __global__ __launch_bounds__(256) void mask_sim_wide_kernel(MaskArgs a, const in
             }
         }
     }
-    // (the Nyquist bin of a warm-up frame: mask_sim_kernel's emit(0) wrote all F bins; here bin F - 1 of frames < first_frame)
-    if (first_frame > a.frame0 + f_begin && threadIdx.x < kWideRun) {
+    // (the Nyquist bin of a warm-up frame: mask_sim_kernel's emit(0) wrote all F bins; here bin F - 1 of the warm-up frames)
+    if (warm_end > a.frame0 + f_begin && threadIdx.x < kWideRun) {
         const int64_t t = a.frame0 + f_begin + threadIdx.x;
-        if (t < first_frame && f_begin + threadIdx.x < f_end) emit(a, c, t, a.F - 1, 0.f);
+        if (t < warm_end && f_begin + threadIdx.x < f_end) emit(a, c, t, a.F - 1, 0.f);
     }
 }
 // REPET_MASK_WIDE=0: the one-bin-per-lane kernel for every list length (agreement test / A-B)
@@ -502,9 +510,9 @@ __global__ __launch_bounds__(64) void mask_sim_nyquist_kernel(MaskArgs a, const 
     count += blockIdx.z * a.cnt_batch_stride;
     const int64_t r0 = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t n_rows = a.T - first_frame;       // first_frame >= frame0: rows before it are warm-up frames
-    const bool active = r0 < n_rows;
-    const int64_t r = active ? r0 : n_rows - 1;
+    const int64_t r = r0 < n_rows ? r0 : n_rows - 1;
     const int64_t t = first_frame + r;
+    const bool active = r0 < n_rows && t >= warm_up_end(a, first_frame, blockIdx.z);   // (a slot's warm-up rows: the main kernel's)
     const float* Vc = a.V + c * a.chan_stride;
     const int n = count[r];
     const int* list = idx + r * (int64_t)idx_pitch;
@@ -546,6 +554,7 @@ __global__ __launch_bounds__(64) void mask_sim_nyquist_wave_kernel(MaskArgs a, c
     idx += blockIdx.z * a.idx_batch_stride;
     count += blockIdx.z * a.cnt_batch_stride;
     const int64_t r = blockIdx.x, t = first_frame + r;
+    if (t < warm_up_end(a, first_frame, blockIdx.z)) return;               // (a slot's warm-up rows: the main kernel's)
     const int lane = threadIdx.x;
     const float* Vc = a.V + c * a.chan_stride;
     const int f = a.F - 1;

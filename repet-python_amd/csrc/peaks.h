@@ -31,6 +31,7 @@ struct PeakArgs {
     // elements, the offset of the largest (NaN counted as +inf). With them the first pass looks at raw elements of the row
     // only where a window's edge cuts a segment whose maximum lies outside it, and around near-ties.
     const float* seg; int seg_pitch;
+    const int64_t* origin;         // (nullable) PeakBatch::origin
 };
 
 // diagnostics counters (common.h: kStatShards): the copy of this workgroup
@@ -39,6 +40,13 @@ __device__ __forceinline__ void stat_add(unsigned int* stats, int k, unsigned in
 }
 __device__ __forceinline__ void stat_max(unsigned int* stats, int k, unsigned int v) {
     atomicMax(&stats[kRefineStats * (1 + (int)(blockIdx.x & (kStatShards - 1))) + k], v);
+}
+// PeakBatch::origin: the clip's rows and band rows counted from its own first frame (one uniform load per wavefront)
+__device__ __forceinline__ void apply_origin(PeakArgs& a, int clip) {
+    if (!a.origin) return;
+    const int64_t o = a.origin[clip];
+    a.row0 -= o;
+    a.shift -= o;
 }
 __device__ __forceinline__ void flag_row_for_exact(const PeakArgs& a, int64_t r, int clip) {
     if (!a.redo_list) return;

@@ -74,6 +74,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
     a.count += blockIdx.y * a.cnt_stride;
     if (a.unit) a.unit += blockIdx.y * a.unit_stride;
     const int64_t r = blockIdx.x;           // row within this launch
+    apply_origin(a, blockIdx.y);
+    if (a.origin && a.row0 + r < n - 1) {   // a slot of the streaming handle still warming up (or idle): no list
+        for (int k = tid; k < a.number; k += 256) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
+        if (tid == 0) a.count[r] = 0;
+        return;
+    }
     const int64_t j = a.row0 + r;           // absolute row (mode 1: current frame)
     if (tid == 0) { n_peak = 0; n_amb = 0; n_riv = 0; n_unl = 0; n_close = 0; }
     float dlt = a.delta;                    // 0: no refinement
@@ -545,6 +551,7 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
     int n_batch = 1;
     if (batch && batch->n_batch > 0) {
         n_batch = batch->n_batch;
+        if (mode != 0) a.origin = batch->origin;
         a.m_stride = batch->m_stride; a.idx_stride = batch->idx_stride; a.cnt_stride = batch->cnt_stride;
         a.unit_stride = batch->unit_stride;
     }

@@ -686,6 +686,7 @@ __global__ __launch_bounds__(kExactThreads) void local_maxima_exact_kernel(Exact
         a.idx += clip * a.idx_stride;
         a.count += clip * a.cnt_stride;
         a.unit += clip * a.unit_stride;
+        apply_origin(a, clip);
         const int n = a.n, d = a.d;
         const int64_t j = a.row0 + r;
         const float dlt = a.delta;
@@ -1042,6 +1043,7 @@ hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_col
     if (batch && batch->n_batch > 0) {
         a.m_stride = batch->m_stride; a.idx_stride = batch->idx_stride; a.cnt_stride = batch->cnt_stride;
         a.unit_stride = batch->unit_stride;
+        if (mode != 0) a.origin = batch->origin;
     }
     x.delta2 = refine->delta2; x.redo_list = refine->redo_list; x.src = src; x.gen = refine->gen;
     int logM = 0;

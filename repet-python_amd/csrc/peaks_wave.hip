@@ -549,6 +549,12 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
     a.count += blockIdx.y * a.cnt_stride;
     if (a.unit) a.unit += blockIdx.y * a.unit_stride;
     if (a.unit_norm) a.unit_norm += blockIdx.y * (a.unit_stride / a.unit_pitch);
+    apply_origin(a, blockIdx.y);
+    if (a.origin && a.row0 + r < n - 1) {                    // a slot of the streaming handle still warming up (or idle): no list
+        for (int k = lane; k < a.number; k += 64) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
+        if (lane == 0) a.count[r] = 0;
+        return;
+    }
     const int64_t j = a.row0 + r;                            // absolute row (mode 1: current frame)
     float dlt = a.delta;                                     // 0: no refinement
 
@@ -1128,6 +1134,7 @@ __global__ __launch_bounds__(64) void local_maxima_lite_kernel(PeakArgs a0, Lite
         a.idx += clip * a.idx_stride;
         a.count += clip * a.cnt_stride;
         a.unit += clip * a.unit_stride;
+        apply_origin(a, clip);
         const int64_t j = a.row0 + r;
         const LiteRecord q = carve_record(a.records + (size_t)slot * a.record_bytes, a.peak_cap);
         const LiteHeader h = *q.h;

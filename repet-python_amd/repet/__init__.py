@@ -207,7 +207,19 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     for a host chunk; for a tensor a float64 tensor on its device, or ``out`` (float32 / float64, any strides) filled, ordered
     on the current stream with no host wait. ``finish(out=None)`` returns the rest, ``close()`` frees the device state. Each
     stream's concatenated output equals ``simonline`` of its concatenated input, bit for bit. ``max_push_samples`` sizes the
-    device buffers at open (pushes up to that size then never grow them); the module parameters are snapshotted now."""
+    device buffers at open (pushes up to that size then never grow them); the module parameters are snapshotted now.
+
+    Streams need not start and end together: the handle's streams are *slots*. ``restart(slots)`` begins a new stream in each
+    named slot at the handle's current sample (``samples_pushed``, which must be a multiple of the hop); ``finish_stream(slot,
+    out=None)`` ends one stream wherever the handle stands and returns its ``(n_rest, number_channels)`` tail
+    (``stream_emit_count(slot)`` tells its size; ValueError for an idle slot or a stream shorter than the buffer);
+    ``release(slots)`` drops streams without output. An idle slot ignores its share of every chunk, NaN included, and emits
+    zeros. Pushes stay in lockstep and none of these calls waits for the device (``finish_stream`` to the host waits for its
+    result). A slot's output from its ``restart`` on, followed by its ``finish_stream`` (or ``finish``) tail, equals
+    ``simonline`` of the samples pushed into it in between, bit for bit: zeros while it warms up, then its own buffer only.
+    ``stream_samples(slot)`` is the length of a slot's stream so far (None when idle). A server loop: open with
+    ``max_push_samples``, ``release`` every slot, ``restart`` a free slot when a call arrives, ``finish_stream`` it when the
+    call ends."""
     return _native.OnlineStreams(derive_params(sampling_frequency), number_channels, number_streams, _device,
                                  max_push_samples or 0)
 

@@ -146,6 +146,11 @@ _SIGNATURES = {
     "repet_online_push_device": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
     "repet_online_finish_streams": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_finish_device": (C.c_int, [_P, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_online_restart_streams": (C.c_int, [_P, _P, C.c_int32]),
+    "repet_online_release_streams": (C.c_int, [_P, _P, C.c_int32]),
+    "repet_online_stream_emit_count": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    "repet_online_finish_stream": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_finish_stream_device": (C.c_int, [_P, C.c_int32, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -662,7 +667,12 @@ class OnlineStreams:
     """S live streams of one sampling frequency and channel count in one streaming handle (``repet.online_streams``), pushed
     in lockstep: every ``push`` brings ``(S, n, C)`` samples, and each stream's concatenated output equals ``repet.simonline``
     of its concatenated input. Host chunks (NumPy arrays, lists, CPU tensors) return float64 ``(S, n_emit, C)`` arrays; ROCm
-    tensors return a float64 tensor on their device (or fill ``out``), ordered on its current stream with no host wait."""
+    tensors return a float64 tensor on their device (or fill ``out``), ordered on its current stream with no host wait.
+
+    The S streams are S *slots*: ``restart(slots)`` begins a new stream in each named slot at the handle's current sample (a
+    multiple of the hop), ``finish_stream(slot)`` ends one and returns its tail, ``release(slots)`` drops them without output.
+    An idle slot ignores what the lockstep chunks carry for it and emits zeros. A slot's output from its restart on, followed
+    by its ``finish_stream`` (or ``finish``) tail, equals ``repet.simonline`` of the samples pushed into it in between."""
 
     def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0):
         self._h = C.c_void_p()
@@ -676,6 +686,8 @@ class OnlineStreams:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open_streams(self._device, self._streams, self._channels, C.byref(params),
                                               int(max_push_samples or 0), C.byref(self._h)))
+        self._pushed = 0                              # samples per slot pushed so far
+        self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
 
     @property
     def shape(self):
@@ -731,6 +743,7 @@ class OnlineStreams:
         result = np.empty((self._streams, n_emit, self._channels), dtype=np.float64)
         written = C.c_int64()
         check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(result), n_emit, C.byref(written)))
+        self._pushed += n
         self._last_on_device = False
         return result
 
@@ -752,12 +765,87 @@ class OnlineStreams:
         # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
         # recorded on it, the caching allocator hands its block out again only once the ingest has read it
         x.record_stream(stream)
+        self._pushed += n
         self._last_on_device = True
         return out
 
+    @property
+    def samples_pushed(self):
+        """Samples per slot pushed into the handle so far."""
+        return self._pushed
+
+    def stream_samples(self, slot):
+        """Samples of the stream that lives in ``slot`` so far (None: the slot is idle)."""
+        begun = self._begun[self._slot(slot)]
+        return None if begun is None else self._pushed - begun
+
+    def _slot(self, slot):
+        slot = int(slot)
+        if not 0 <= slot < self._streams:
+            raise ValueError(f"slot {slot} of a handle of {self._streams}")
+        return slot
+
+    def _slot_list(self, slots):
+        slots = [self._slot(s) for s in ([slots] if np.isscalar(slots) else slots)]
+        return slots, (C.c_int32 * max(len(slots), 1))(*slots)
+
+    def restart(self, slots):
+        """Begin a new stream in every named slot: its sample 0 is the handle's sample ``samples_pushed``, which must be a
+        multiple of the hop (ValueError otherwise, nothing changes). What lived in the slots is discarded. No host wait."""
+        slots, arr = self._slot_list(slots)
+        check(lib().repet_online_restart_streams(self._handle(), arr, len(slots)))
+        for s in slots:
+            self._begun[s] = self._pushed
+
+    def release(self, slots):
+        """The named slots become idle without output: they ignore their share of the chunks and emit zeros."""
+        slots, arr = self._slot_list(slots)
+        check(lib().repet_online_release_streams(self._handle(), arr, len(slots)))
+        for s in slots:
+            self._begun[s] = None
+
+    def stream_emit_count(self, slot):
+        """Samples ``finish_stream(slot)`` will return. ValueError for an idle slot or a stream shorter than the buffer."""
+        n = C.c_int64()
+        check(lib().repet_online_stream_emit_count(self._handle(), self._slot(slot), C.byref(n)))
+        return n.value
+
+    def finish_stream(self, slot, out=None):
+        """End the stream of one slot where the handle stands: its ``(n_rest, C)`` tail, as ``finish`` returns for all (a
+        tensor on the device when ``out`` is given or the last push was a device chunk). The other slots and the handle's
+        counters are untouched and the slot is idle afterwards. ValueError for an idle slot, or for a stream shorter than the
+        buffer (the slot then stays as it was)."""
+        slot = self._slot(slot)
+        n_emit = self.stream_emit_count(slot)
+        written = C.c_int64()
+        if out is not None or self._last_on_device:
+            import torch
+            device = torch.device("cuda", self._device)
+            shape = (n_emit, self._channels)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=device)
+            elif not is_device_tensor(out) or out.device != device:
+                raise ValueError(f"out must be a tensor on {device}")
+            elif tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
+            elif any(st < 0 for st in out.stride()):
+                raise ValueError("out has negative strides")
+            stream = torch.cuda.current_stream(device)
+            strides = (C.c_int64 * 2)(*(int(st) for st in out.stride()))
+            check(lib().repet_online_finish_stream_device(self._handle(), slot, C.c_void_p(out.data_ptr() or None),
+                                                          result_tensor_code(out), strides, _stream_handle(stream),
+                                                          C.byref(written)))
+            self._begun[slot] = None
+            return out
+        result = np.empty((n_emit, self._channels), dtype=np.float64)
+        check(lib().repet_online_finish_stream(self._handle(), slot, ptr(result), n_emit, C.byref(written)))
+        self._begun[slot] = None
+        return result
+
     def finish(self, out=None):
         """End every stream: the remaining samples, ``(S, n_rest, C)`` -- a float64 tensor on the device when ``out`` is given
-        or the last push was a device chunk, a NumPy array otherwise. ValueError if the streams are shorter than the buffer."""
+        or the last push was a device chunk, a NumPy array otherwise. ValueError if the handle has seen fewer samples than the
+        buffer holds. Every live slot ends with its own length; idle slots return zeros."""
         n_emit = self.emit_count(0, finishing=True)
         if out is not None or self._last_on_device:
             import torch

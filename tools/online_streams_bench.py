@@ -1,7 +1,13 @@
 """Latency per push of S live 44.1-kHz stereo streams: one ``repet.online_streams`` handle (host chunks and ROCm-tensor
 chunks) against S separate ``repet.online`` handles pushed one after another, at 1 and 4 hops per push. Each latency is one
 call plus, for device chunks, a synchronize; the streams are first pushed past the 10-s warm-up buffer so that every frame
-is active. Prints one JSON document (median and p95 in ms per push, and the audio it carries)."""
+is active. Prints one JSON document (median and p95 in ms per push, and the audio it carries).
+
+``--churn K``: instead, streams that leave and join one by one. One handle of S slots, device chunks of one hop; on every
+K-th push one slot's stream is ended with ``finish_stream`` and a new one begun in it with ``restart`` (round robin over
+the slots). Reported: the latency of the pushes without a lifecycle call, of ``restart`` and of ``finish_stream`` (each
+call plus a synchronize), beside the same schedule on S separate ``repet.online`` handles, the only other way to end one
+stream and keep the rest: every hop is S pushes, a departure is one handle's ``finish`` and a new ``repet.online``."""
 import argparse
 import json
 import sys
@@ -84,6 +90,90 @@ def separate_handles(xs, fs, hops, timed, warm_s):
     return stats(lat[3:], n, fs)
 
 
+def churn_one_handle(xs, fs, every, timed, warm_s):
+    import torch
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    src = torch.tensor(xs, device="cuda:0")
+    h = repet.online_streams(fs, ch, S, max_push_samples=hop)
+    pos = 0
+    while pos < warm_s * fs // hop * hop:
+        n = min(fs // 2 // hop * hop, warm_s * fs // hop * hop - pos)
+        h.push(src[:, pos:pos + n])
+        pos += n
+    out = torch.empty((S, hop, ch), dtype=torch.float64, device="cuda:0")
+    tail = torch.empty((hop, ch), dtype=torch.float64, device="cuda:0")
+    for _ in range(3):
+        h.push(src[:, pos:pos + hop], out=out)
+        pos += hop
+    # one departure and arrival before the clock starts (the single-slot sequence and the reset kernel have run once); the
+    # slots that leave during the run are the oldest ones, so every stream that is finished is longer than the buffer
+    h.finish_stream(S - 1, out=tail)
+    h.restart(S - 1)
+    torch.cuda.synchronize()
+    plain, restart, finish, k, slot = [], [], [], 0, 0
+    while k < timed and pos + hop <= N:
+        t0 = time.perf_counter()
+        h.push(src[:, pos:pos + hop], out=out)
+        torch.cuda.synchronize()
+        plain.append(time.perf_counter() - t0)
+        pos += hop
+        k += 1
+        if k % every == 0 and slot < S - 1:
+            t0 = time.perf_counter()
+            h.finish_stream(slot, out=tail)
+            torch.cuda.synchronize()
+            finish.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            h.restart(slot)
+            torch.cuda.synchronize()
+            restart.append(time.perf_counter() - t0)
+            slot += 1
+    h.close()
+    ms = lambda v: round(float(np.median(np.array(v) * 1e3)), 3) if v else None
+    return {"push_ms_median": ms(plain), "push_ms_p95": round(float(np.percentile(np.array(plain) * 1e3, 95)), 3),
+            "finish_stream_ms_median": ms(finish), "restart_ms_median": ms(restart), "pushes_timed": len(plain),
+            "lifecycle_pairs": len(finish)}
+
+
+def churn_separate_handles(xs, fs, every, timed, warm_s):
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    hs = [repet.online(fs, ch) for _ in range(S)]
+    pos = 0
+    while pos < warm_s * fs // hop * hop:
+        n = min(fs // 2 // hop * hop, warm_s * fs // hop * hop - pos)
+        for s, h in enumerate(hs):
+            h.push(xs[s, pos:pos + n])
+        pos += n
+    for _ in range(3):
+        for s, h in enumerate(hs):
+            h.push(xs[s, pos:pos + hop])
+        pos += hop
+    plain, finish, reopen, k, slot = [], [], [], 0, 0
+    while k < timed and pos + hop <= N:
+        t0 = time.perf_counter()
+        for s, h in enumerate(hs):
+            h.push(xs[s, pos:pos + hop])
+        plain.append(time.perf_counter() - t0)
+        pos += hop
+        k += 1
+        if k % every == 0 and slot < S - 1:
+            t0 = time.perf_counter()
+            hs[slot].finish()
+            finish.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            hs[slot].close()
+            hs[slot] = repet.online(fs, ch)
+            reopen.append(time.perf_counter() - t0)
+            slot += 1
+    for h in hs:
+        h.close()
+    ms = lambda v: round(float(np.median(np.array(v) * 1e3)), 3) if v else None
+    return {"hop_ms_median": ms(plain), "finish_ms_median": ms(finish), "close_and_open_ms_median": ms(reopen),
+            "hops_timed": len(plain), "lifecycle_pairs": len(finish)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--streams", default="1,8,64,256")
@@ -91,9 +181,23 @@ def main():
     ap.add_argument("--timed", type=int, default=60, help="pushes timed per case")
     ap.add_argument("--separate-max", type=int, default=64, help="largest S run as S separate repet.online handles")
     ap.add_argument("--only", choices=["all", "device"], default="all", help="device: the one-handle device-chunk cases only")
+    ap.add_argument("--churn", type=int, default=0, metavar="K",
+                    help="the churn leg: one finish_stream and one restart on every K-th push of one hop")
+    ap.add_argument("--churn-separate", type=int, default=1, help="0: skip the separate-handles side of the churn leg")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
+    if args.churn > 0:
+        hop = repet.derive_params(fs).step_length
+        result = {"fs": fs, "channels": ch, "churn_every_pushes": args.churn, "cases": []}
+        for S in streams:
+            xs = stream_signals(S, warm_s + 1 + (args.timed + 8) * hop / fs, fs, ch)
+            case = {"streams": S, "one_handle_slots": churn_one_handle(xs, fs, args.churn, args.timed, warm_s)}
+            if args.churn_separate and S <= args.separate_max:
+                case["separate_handles_host"] = churn_separate_handles(xs, fs, args.churn, args.timed, warm_s)
+            result["cases"].append(case)
+        print(json.dumps(result, indent=1))
+        return
     hops_list = [int(h) for h in args.hops.split(",")]
     hop = repet.derive_params(fs).step_length
     seconds = warm_s + 1 + (args.timed + 4) * max(hops_list) * hop / fs
