@@ -176,10 +176,9 @@ struct IstftOlaArgs {
     int32_t out_channels, out_chan0;
 };
 hipError_t launch_istft_ola(const IstftOlaArgs& a, hipStream_t s);
-// register-resident variants for W = 2048 (stft_reg.hip); launch_stft / launch_istft_ola pick them themselves
+// register-resident variants for W = 2048 (stft_reg.hip); launch_stft / launch_istft_ola pick them themselves (their
+// launchers are declared in fft_path.h, which only those two and the stage exports include)
 bool reg_fft_supported(int W, int n_channels, bool inverse);
-hipError_t launch_stft_reg(const StftArgs& a, hipStream_t s);
-hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t s);
 // true when launch_istft_ola will take the register kernel for these arguments (the only one that applies a model itself)
 bool istft_reg_takes(const IstftOlaArgs& a);
 

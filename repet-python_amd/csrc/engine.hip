@@ -65,6 +65,10 @@ int get_tables(repet_ctx* c, int W, Tables** out) {
         win[n] = (float)wd[n];
         tw[n] = make_float2((float)std::cos(two_pi * n / W), (float)(-std::sin(two_pi * n / W)));
     }
+    // the quarter turns are exact: cos(pi / 2) and sin(pi) in floating point are 6e-17 and 1e-16, and the forward kernels form the
+    // Nyquist bin as e + twiddle[W / 2] * o -- with sin(pi) left in, the bin of a real signal came out with an imaginary part
+    // of 1e-16 of its size instead of none (found by tests/test_gpu_stft_stages.py, block kernel, W = 64)
+    tw[W / 4] = make_float2(0.f, -1.f); tw[W / 2] = make_float2(-1.f, 0.f); tw[3 * W / 4] = make_float2(0.f, 1.f);
     t->cola = wd[0] + wd[W / 2];
     std::vector<double2> tw64(W + 1);
     for (int n = 0; n <= W; ++n) tw64[n] = make_double2(std::cos(two_pi * n / W), -std::sin(two_pi * n / W));

@@ -1,5 +1,6 @@
 // stage-level exports and the accessors of the last run's integer intermediates (see engine.h for the map of the engine's files)
 #include "engine.h"
+#include "fft_path.h"
 
 using namespace repet;
 using namespace repet_eng;
@@ -65,6 +66,186 @@ int repet_istft(repet_ctx* c, const float* spec, int64_t T, const float* window,
     HIP_TRY(hipMemcpyAsync(y_out, c->tmp_a.p, (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return REPET_OK;
+}
+
+// ---- stage entries of the PRODUCTION launchers (tests/test_gpu_stft_stages.py) -----------------------------------------
+// repet_stft above is launch_stft for one mono clip and repet_istft runs two kernels nothing else launches. These two run
+// launch_stft / launch_istft_ola with everything the pipelines pass them -- channels, batches, offsets, the side products,
+// mask plane or model, the cross-fade of `extended` -- on buffers laid out by make_geo, with the kernel family as an
+// argument (fft_path.h), and say which kernel ran. Diagnostic exports like the ones below: not part of repet_hip.h.
+namespace {
+struct Scratch { DevBuf b; ~Scratch() { b.release(); } };
+
+int report_launch(const FftLaunch& info, char* kernel_out, int32_t kernel_cap, int64_t* launch_out) {
+    if (kernel_out && kernel_cap > 0) { std::strncpy(kernel_out, info.kernel, (size_t)kernel_cap - 1); kernel_out[kernel_cap - 1] = 0; }
+    if (launch_out) {
+        const int64_t v[8] = {info.family, info.run, info.rounds, info.slots, info.workgroups, info.units, info.launches, 0};
+        std::memcpy(launch_out, v, sizeof(v));
+    }
+    return REPET_OK;
+}
+bool window_length_ok(int W) { return W >= 64 && W <= 8192 && !(W & (W - 1)); }
+}  // namespace
+
+// audio (n_total, C) fp32 interleaved; n_batch clips of n_samples samples, the first at sample_offset, batch_sample_stride
+// apart. want: 1 Vm, 2 Vn, 4 P, 8 Vh (with Vn), 16 Ph + Ph_inv (register kernel only). Every device buffer is filled with
+// the byte `prefill` first. geo_out[6] = T, Tpad, rows = Tpad + pad rows, F, FS, chan_stride; with X_out null only geo_out
+// is filled (the caller sizes its arrays from it): X (B, C, rows, FS, 2), V (B, C, rows, FS), Vm / Vn / P (B, Tpad, FS),
+// Vh / Ph (B, Tpad, 2 FS) halves, Ph_inv (B, Tpad). launch_out[8] = family, run, rounds, slots, workgroups, units, launches, 0.
+int repet_debug_stft_stage(repet_ctx* c, const float* audio, int64_t n_total, int32_t C, const float* window, int32_t W, int32_t H,
+                           int32_t centred, int64_t sample_offset, int64_t n_samples, int32_t n_batch, int64_t batch_sample_stride,
+                           int32_t path, int32_t want, int32_t fix_infinite, int32_t prefill, int64_t* geo_out,
+                           float* X_out, float* V_out, float* Vm_out, float* Vn_out, float* P_out, uint16_t* Vh_out, uint16_t* Ph_out,
+                           float* Ph_inv_out, char* kernel_out, int32_t kernel_cap, int64_t* launch_out) {
+    if (!c || !audio || !window || !geo_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (!window_length_ok(W)) return fail(REPET_ERR_LIMIT, "window length must be a power of two in [64, 8192]");
+    if (H < 1 || H > W || C < 1 || C > 64 || n_batch < 1 || n_samples < 1 || sample_offset < 0 || batch_sample_stride < 0)
+        return fail(REPET_ERR_BAD_ARG, "bad size");
+    if (path < kFftPathAuto || path > kFftPathReg) return fail(REPET_ERR_BAD_ARG, "path: 0 as production picks, 1 block, 2 wave, 3 reg");
+    if (sample_offset + (int64_t)(n_batch - 1) * batch_sample_stride + n_samples > n_total)
+        return fail(REPET_ERR_BAD_ARG, "the clips do not fit into the audio buffer");
+    if ((want & 8) && !(want & 2)) return fail(REPET_ERR_BAD_ARG, "the f16 planes of the unit rows come with the unit rows");
+    if ((want & 16) && !reg_fft_supported(W, C, false, path)) return fail(REPET_ERR_BAD_ARG, "only the register kernel writes the row-scaled planes");
+    const int64_t T = repet_frame_count(n_samples, W, H, centred);
+    const Geo g = make_geo(W, H, T, C);
+    const int64_t rows = g.chan_stride / g.FS, geo[6] = {T, g.Tpad, rows, g.F, g.FS, g.chan_stride};
+    std::memcpy(geo_out, geo, sizeof(geo));
+    if (!X_out) return REPET_OK;
+    if (!V_out || ((want & 1) && !Vm_out) || ((want & 2) && !Vn_out) || ((want & 4) && !P_out) || ((want & 8) && !Vh_out) ||
+        ((want & 16) && (!Ph_out || !Ph_inv_out)))
+        return fail(REPET_ERR_BAD_ARG, "null output");
+    DeviceGuard guard(c->device);
+    const float2* tw = nullptr;
+    RP_TRY(upload_twiddle_only(c, W, &tw));
+    const size_t spec = (size_t)n_batch * C * g.chan_stride, mean = (size_t)n_batch * g.Tpad * g.FS;
+    Scratch in, win, X, V, Vm, Vn, P, Vh, Ph, Pi;
+    HIP_TRY(in.b.ensure((size_t)n_total * C * sizeof(float)));
+    HIP_TRY(win.b.ensure((size_t)W * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(in.b.p, audio, (size_t)n_total * C * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(win.b.p, window, (size_t)W * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    auto filled = [&](Scratch& s, bool on, size_t bytes) -> int {
+        if (!on) return REPET_OK;
+        HIP_TRY(s.b.ensure(bytes));
+        HIP_TRY(hipMemsetAsync(s.b.p, prefill & 255, bytes, c->stream));
+        return REPET_OK;
+    };
+    RP_TRY(filled(X, true, spec * sizeof(float2)));
+    RP_TRY(filled(V, true, spec * sizeof(float)));
+    RP_TRY(filled(Vm, want & 1, mean * sizeof(float)));
+    RP_TRY(filled(Vn, want & 2, mean * sizeof(float)));
+    RP_TRY(filled(P, want & 4, mean * sizeof(float)));
+    RP_TRY(filled(Vh, want & 8, mean * 2 * sizeof(uint16_t)));
+    RP_TRY(filled(Ph, want & 16, mean * 2 * sizeof(uint16_t)));
+    RP_TRY(filled(Pi, want & 16, (size_t)n_batch * g.Tpad * sizeof(float)));
+    StftArgs a{};
+    a.audio = in.b.as<float>(); a.n_samples = n_samples; a.n_channels = C; a.sample_offset = sample_offset;
+    a.window = win.b.as<float>(); a.twiddle = tw; a.W = W; a.H = H; a.T = T; a.FS = g.FS; a.centred = centred;
+    a.X = X.b.as<float2>(); a.V = V.b.as<float>(); a.chan_stride = g.chan_stride;
+    a.Vm = Vm.b.as<float>(); a.Vn = Vn.b.as<float>(); a.P = P.b.as<float>(); a.Vh = Vh.b.p;
+    a.Ph = Ph.b.p; a.Ph_inv = Pi.b.as<float>(); a.batch_inv_stride = g.Tpad;
+    a.n_batch = n_batch; a.batch_sample_stride = batch_sample_stride; a.batch_spec_stride = (int64_t)C * g.chan_stride;
+    a.batch_mean_stride = g.Tpad * g.FS;
+    FftLaunch info;
+    hipError_t e = launch_stft(a, c->stream, path, &info);
+    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "the kernel family asked for does not take this shape");
+    HIP_TRY(e);
+    if (fix_infinite) HIP_TRY(launch_infinite_frames_fix(a, c->stream));
+    auto back = [&](void* dst, const Scratch& s, bool on, size_t bytes) -> int {
+        if (on) HIP_TRY(hipMemcpyAsync(dst, s.b.p, bytes, hipMemcpyDeviceToHost, c->stream));
+        return REPET_OK;
+    };
+    RP_TRY(back(X_out, X, true, spec * sizeof(float2)));
+    RP_TRY(back(V_out, V, true, spec * sizeof(float)));
+    RP_TRY(back(Vm_out, Vm, want & 1, mean * sizeof(float)));
+    RP_TRY(back(Vn_out, Vn, want & 2, mean * sizeof(float)));
+    RP_TRY(back(P_out, P, want & 4, mean * sizeof(float)));
+    RP_TRY(back(Vh_out, Vh, want & 8, mean * 2 * sizeof(uint16_t)));
+    RP_TRY(back(Ph_out, Ph, want & 16, mean * 2 * sizeof(uint16_t)));
+    RP_TRY(back(Ph_inv_out, Pi, want & 16, (size_t)n_batch * g.Tpad * sizeof(float)));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return report_launch(info, kernel_out, kernel_cap, launch_out);
+}
+
+// Y (n_spec, C, T, F, 2) half spectra, hop W / 2. One of: nothing; M (n_spec, C, T, F), a mask plane; model (n_spec, C,
+// model_rows, F) with periods[n_spec] and cutoff (register kernel only). n_batch = 0: one clip at out_offset; n_batch > 0:
+// the segment-batch fields as run_original fills them (slot s: spectra batch_local0 + s batch_step, segment j = batch_first
+// + s batch_step written at out_offset + j batch_out_stride). `out` (out_len, C) is the caller's pre-filled buffer: it goes
+// to the device as it is and comes back whole.
+int repet_debug_istft_stage(repet_ctx* c, const float* Y, int32_t n_spec, int32_t C, int64_t T, int32_t W, int64_t trim, int64_t n_out,
+                            int64_t out_offset, float scale, const float* M, const float* model, const int32_t* periods,
+                            int32_t model_rows, int32_t cutoff, int32_t accumulate_weighted, int64_t fade_in, int64_t fade_out,
+                            int32_t n_batch, int32_t batch_first, int32_t batch_step, int32_t batch_total, int32_t batch_local0,
+                            int64_t batch_out_stride, int64_t overlap, int32_t path, float* out, int64_t out_len,
+                            char* kernel_out, int32_t kernel_cap, int64_t* launch_out) {
+    if (!c || !Y || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (!window_length_ok(W)) return fail(REPET_ERR_LIMIT, "window length must be a power of two in [64, 8192]");
+    if (n_spec < 1 || C < 1 || C > 64 || T < 1 || trim < 0 || n_out < 0 || out_offset < 0 || out_len < 1 || fade_in < 0 || fade_out < 0 ||
+        overlap < 0 || batch_out_stride < 0 || accumulate_weighted < 0 || accumulate_weighted > 2 || cutoff < 0)
+        return fail(REPET_ERR_BAD_ARG, "bad size");
+    if (path < kFftPathAuto || path > kFftPathReg) return fail(REPET_ERR_BAD_ARG, "path: 0 as production picks, 1 block, 2 wave, 3 reg");
+    if (M && model) return fail(REPET_ERR_BAD_ARG, "a mask plane or a model, not both");
+    if (model) {
+        if (!periods || model_rows < 1) return fail(REPET_ERR_BAD_ARG, "a model needs its periods");
+        for (int i = 0; i < n_spec; ++i)
+            if (periods[i] < 1 || periods[i] > model_rows) return fail(REPET_ERR_BAD_ARG, "a period outside the model's rows");
+    }
+    // every sample the launch may touch lies inside `out`, every spectrum it may read inside Y
+    if (n_batch < 0) return fail(REPET_ERR_BAD_ARG, "bad batch");
+    if (n_batch == 0) {
+        if (out_offset + n_out > out_len) return fail(REPET_ERR_BAD_ARG, "the span does not fit into the output buffer");
+    } else {
+        if (batch_step < 1 || batch_first < 0 || batch_local0 < 0) return fail(REPET_ERR_BAD_ARG, "bad batch");
+        const int64_t last_local = batch_local0 + (int64_t)(n_batch - 1) * batch_step, last_j = batch_first + (int64_t)(n_batch - 1) * batch_step;
+        if (last_local >= n_spec || last_j >= batch_total) return fail(REPET_ERR_BAD_ARG, "the batch reaches past its spectra or its segment count");
+        if (out_offset + last_j * batch_out_stride + n_out > out_len) return fail(REPET_ERR_BAD_ARG, "the span does not fit into the output buffer");
+    }
+    DeviceGuard guard(c->device);
+    const float2* tw = nullptr;
+    RP_TRY(upload_twiddle_only(c, W, &tw));
+    const Geo g = make_geo(W, W / 2, T, C);
+    const size_t planes = (size_t)n_spec * C, spec = planes * g.chan_stride;
+    Scratch Yd, Md, Wd, Pd, Od;
+    HIP_TRY(Yd.b.ensure(spec * sizeof(float2)));
+    HIP_TRY(hipMemsetAsync(Yd.b.p, 0, spec * sizeof(float2), c->stream));
+    for (size_t p = 0; p < planes; ++p)
+        HIP_TRY(hipMemcpy2DAsync(Yd.b.as<float2>() + p * g.chan_stride, (size_t)g.FS * sizeof(float2), Y + p * (size_t)T * g.F * 2,
+                                 (size_t)g.F * sizeof(float2), (size_t)g.F * sizeof(float2), T, hipMemcpyHostToDevice, c->stream));
+    if (M) {
+        HIP_TRY(Md.b.ensure(spec * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Md.b.p, 0, spec * sizeof(float), c->stream));
+        for (size_t p = 0; p < planes; ++p)
+            HIP_TRY(hipMemcpy2DAsync(Md.b.as<float>() + p * g.chan_stride, (size_t)g.FS * sizeof(float), M + p * (size_t)T * g.F,
+                                     (size_t)g.F * sizeof(float), (size_t)g.F * sizeof(float), T, hipMemcpyHostToDevice, c->stream));
+    }
+    if (model) {
+        const size_t cells = planes * model_rows * g.FS;
+        HIP_TRY(Wd.b.ensure(cells * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Wd.b.p, 0, cells * sizeof(float), c->stream));
+        HIP_TRY(hipMemcpy2DAsync(Wd.b.p, (size_t)g.FS * sizeof(float), model, (size_t)g.F * sizeof(float), (size_t)g.F * sizeof(float),
+                                 planes * model_rows, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(Pd.b.ensure((size_t)n_spec * sizeof(int32_t)));
+        HIP_TRY(hipMemcpyAsync(Pd.b.p, periods, (size_t)n_spec * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const size_t out_bytes = (size_t)out_len * C * sizeof(float);
+    HIP_TRY(Od.b.ensure(out_bytes));
+    HIP_TRY(hipMemcpyAsync(Od.b.p, out, out_bytes, hipMemcpyHostToDevice, c->stream));
+    IstftOlaArgs a{};
+    a.Y = Yd.b.as<float2>(); a.M = M ? Md.b.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = C; a.T = T; a.FS = g.FS; a.W = W;
+    a.twiddle = tw; a.trim = trim; a.out = Od.b.as<float>(); a.n_out = n_out; a.out_offset = out_offset; a.scale = scale;
+    a.accumulate_weighted = accumulate_weighted; a.fade_in = fade_in; a.fade_out = fade_out;
+    a.n_batch = n_batch; a.batch_first = batch_first; a.batch_step = batch_step; a.batch_total = batch_total; a.batch_local0 = batch_local0;
+    a.batch_spec_stride = (int64_t)C * g.chan_stride; a.batch_out_stride = batch_out_stride; a.overlap = overlap;
+    if (model) {
+        const ModelRef mr{Wd.b.as<float>(), Pd.b.as<int32_t>(), (int64_t)C * model_rows * g.FS, (int64_t)model_rows * g.FS, cutoff};
+        apply_model(a, c, &mr);
+    }
+    FftLaunch info;
+    hipError_t e = launch_istft_ola(a, c->stream, path, &info);
+    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "the kernel family asked for does not take this shape or mask form");
+    HIP_TRY(e);
+    HIP_TRY(hipMemcpyAsync(out, Od.b.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return report_launch(info, kernel_out, kernel_cap, launch_out);
 }
 
 static int stage_matrix_in(repet_ctx* c, DevBuf& buf, const float* host, int64_t T, int F, int FS, int64_t Tpad) {

@@ -6,6 +6,7 @@
 // Replaces repet.py:1001-1060 (_stft), :1063-1105 (_istft), the magnitude + channel mean of
 // :158,:162,:667 and the column normalisation of :1220.
 #include "common.h"
+#include "fft_path.h"
 
 #include <cstdlib>
 #include <map>
@@ -1164,7 +1165,10 @@ __global__ __launch_bounds__(256) void istft_ola_wave_kernel(IstftOlaArgs a, int
                 float* dst = a.out + (a.out_offset + n) * C + c;
                 if (a.accumulate_weighted) {
                     const float w = segment_weight(n, a.fade_in, a.fade_out, a.seg_step, a.later);
-                    *dst += w * v;
+                    // (2 = the first class of segments to write its span stores: it used to ADD here like 1, right only on a
+                    // cleared buffer -- found by tests/test_gpu_stft_stages.py)
+                    if (a.accumulate_weighted == 2) *dst = w * v;
+                    else *dst += w * v;
                 } else {
                     *dst = v;
                 }
@@ -1195,7 +1199,7 @@ static hipError_t dispatch_window(int W, Fn&& fn) {
 // is its run plus a fixed part (tables, the frame before an overlap-add run), so the run is chosen to minimise
 // rounds x (run + fixed): cfg 2's forward STFT was 1 939 workgroups of 4 frames on 768 slots -- three rounds, the last
 // half empty; 705 workgroups of 11 frames are one.
-static int frames_per_workgroup(const void* kernel, size_t dynamic_lds, int64_t units, int64_t batches, int least, double fixed) {
+static int frames_per_workgroup(const void* kernel, size_t dynamic_lds, int64_t units, int64_t batches, int least, double fixed, int* slots_out = nullptr) {
     static std::mutex mu;
     static std::map<std::pair<const void*, size_t>, int> slots_of;
     int slots;
@@ -1218,6 +1222,7 @@ static int frames_per_workgroup(const void* kernel, size_t dynamic_lds, int64_t 
         }
         slots = it->second;
     }
+    if (slots_out) *slots_out = slots;
     int best = least;
     double best_cost = 0;
     for (int run = least; run <= 8 * least; ++run) {
@@ -1276,14 +1281,29 @@ hipError_t launch_infinite_frames_fix(const StftArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_stft(const StftArgs& a, hipStream_t s) {
+static void report(FftLaunch* info, const char* kernel, int family, int run, int slots, int64_t workgroups, int64_t units) {
+    if (!info) return;
+    info->kernel = kernel; info->family = family; info->run = run; info->rounds = 0; info->slots = slots;
+    info->workgroups = workgroups; info->units = units; info->launches += 1;
+}
+
+hipError_t launch_stft(const StftArgs& a, hipStream_t s) { return launch_stft(a, s, kFftPathAuto, nullptr); }
+
+hipError_t launch_stft(const StftArgs& a, hipStream_t s, int path, FftLaunch* info) {
     if (a.T <= 0) return hipSuccess;
     // (also for the handful of frames of a streaming push: the stream's output must equal the offline result bit for bit)
-    if (reg_fft_supported(a.W, a.n_channels, false)) return launch_stft_reg(a, s);
-    if (use_wave_kernels() && a.W <= 4096 && a.n_channels <= 8) {
-        const int C = a.n_channels, N = a.W / 2;
+    if (reg_fft_supported(a.W, a.n_channels, false, path)) return launch_stft_reg(a, s, info);
+    if (path == kFftPathReg) return hipErrorInvalidValue;
+    // (the wave kernel's workspace must fit a CU's 160 KB of LDS: W = 4096 with eight channels asks for 177 KB, and the launch
+    // failed with hipErrorInvalidValue instead of going to the block kernel -- found by tests/test_gpu_stft_stages.py)
+    const size_t wave_lds = (size_t)(a.W + a.W / 2 + 2 * a.W) * sizeof(float2) +
+                            (size_t)(a.n_channels >= 4 ? 1 : 4 / std::max(a.n_channels, 1)) * a.n_channels * a.FS * sizeof(float);
+    const bool wave_takes = a.W <= 4096 && a.n_channels <= 8 && wave_lds <= 160 * 1024;
+    if (path == kFftPathWave && !wave_takes) return hipErrorInvalidValue;
+    if ((path == kFftPathWave || (path == kFftPathAuto && use_wave_kernels())) && wave_takes) {
+        const int C = a.n_channels;
         const int FI = C >= 4 ? 1 : 4 / C;
-        const size_t dyn = (size_t)(a.W + N + 4 * N) * sizeof(float2) + (size_t)FI * C * a.FS * sizeof(float);
+        const size_t dyn = wave_lds;
         const int fpw = (int)round_up(kStftFramesPerWg, FI);
         return dispatch_window(a.W, [&](auto w) {
             constexpr int Wc = decltype(w)::value;
@@ -1291,6 +1311,7 @@ hipError_t launch_stft(const StftArgs& a, hipStream_t s) {
                 (void)ensure_dynamic_lds(reinterpret_cast<const void*>(&stft_wave_kernel<Wc>), (int)dyn);
                 hipLaunchKernelGGL(stft_wave_kernel<Wc>, dim3((unsigned)ceil_div(a.T, fpw), (unsigned)(a.n_batch > 0 ? a.n_batch : 1)),
                                    dim3(256), dyn, s, a, fpw);
+                report(info, "stft_wave_kernel", kFftPathWave, fpw, 0, ceil_div(a.T, fpw) * (a.n_batch > 0 ? a.n_batch : 1), a.T);
             }
         });
     }
@@ -1299,15 +1320,19 @@ hipError_t launch_stft(const StftArgs& a, hipStream_t s) {
         return dispatch_window(a.W, [&](auto w) {
             constexpr int Wc = decltype(w)::value;
             if constexpr (Wc <= 2048) {
-                const int run = frames_per_workgroup(reinterpret_cast<const void*>(&stft_pair_kernel<Wc>), 0, a.T, batches, kStftFrameRun, 0.35);
+                int slots = 0;
+                const int run = frames_per_workgroup(reinterpret_cast<const void*>(&stft_pair_kernel<Wc>), 0, a.T, batches, kStftFrameRun, 0.35, &slots);
                 hipLaunchKernelGGL(stft_pair_kernel<Wc>, dim3((unsigned)ceil_div(a.T, run), (unsigned)batches), dim3(kFftThreads), 0, s, a, run);
+                report(info, "stft_pair_kernel", kFftPathBlock, run, slots, ceil_div(a.T, run) * batches, a.T);
             }
         });
     }
     return dispatch_window(a.W, [&](auto w) {
         constexpr int Wc = decltype(w)::value;
-        const int run = frames_per_workgroup(reinterpret_cast<const void*>(&stft_kernel<Wc>), 0, a.T, batches, kStftFrameRun, 0.35);
+        int slots = 0;
+        const int run = frames_per_workgroup(reinterpret_cast<const void*>(&stft_kernel<Wc>), 0, a.T, batches, kStftFrameRun, 0.35, &slots);
         hipLaunchKernelGGL(stft_kernel<Wc>, dim3((unsigned)ceil_div(a.T, run), (unsigned)batches), dim3(kFftThreads), 0, s, a, run);
+        report(info, "stft_kernel", kFftPathBlock, run, slots, ceil_div(a.T, run) * batches, a.T);
     });
 }
 
@@ -1319,7 +1344,9 @@ hipError_t launch_istft_frames(const IstftArgs& a, hipStream_t s) {
     });
 }
 
-hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s) {
+hipError_t launch_istft_ola(const IstftOlaArgs& a, hipStream_t s) { return launch_istft_ola(a, s, kFftPathAuto, nullptr); }
+
+hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s, int path, FftLaunch* info) {
     IstftOlaArgs a = a0;
     if (a.T <= 0 || a.n_out <= 0) return hipSuccess;
     // hops that intersect [trim, trim + n_out): first = floor(trim / N), last = floor((trim + n_out - 1) / N)
@@ -1329,15 +1356,21 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s) {
     if (a.last_hop > a.T) a.last_hop = a.T;                  // hop T holds the last frame's tail, later hops are empty
     const int64_t hops = a.last_hop - a.first_hop + 1;
     if (hops <= 0) return hipSuccess;
-    if (a.out_channels == 0 && reg_fft_supported(a.W, a.n_channels, true)) {
-        const hipError_t e = launch_istft_ola_reg(a, hops, s);
+    if (a.out_channels == 0 && reg_fft_supported(a.W, a.n_channels, true, path)) {
+        const hipError_t e = launch_istft_ola_reg(a, hops, s, info);
         if (e != hipErrorNotSupported) return e;
     }
+    if (path == kFftPathReg) return hipErrorInvalidValue;
     // Only the register kernel applies a repeating-segment MODEL itself (IstftOlaArgs::model with M == nullptr); the kernels
     // below would emit the unmasked mixture without a word. The engine asks istft_reg_takes() before it chooses the model
     // form; should the two ever disagree, this is an error, not a silent wrong answer.
     if (a.model) return hipErrorInvalidValue;
-    if (a.out_channels == 0 && use_wave_kernels() && a.W <= 4096 && a.n_channels <= 4 && a.n_channels != 3) {
+    // the same for a mask PLANE at the longest window: istft_ola_kernel<8192, masked> does not exist (no registers to spare,
+    // ensure_spectra keeps the mask in X there), and the plain kernel would ignore the plane
+    if (a.M && a.W > 4096) return hipErrorInvalidValue;
+    const bool wave_takes = a.out_channels == 0 && a.W <= 4096 && a.n_channels <= 4 && a.n_channels != 3;
+    if (path == kFftPathWave && !wave_takes) return hipErrorInvalidValue;
+    if ((path == kFftPathWave || (path == kFftPathAuto && use_wave_kernels())) && wave_takes) {
         const int C = a.n_channels;
         const int FI = 4 / C;
         const int run = (int)round_up(kOlaWaveRun + 1, FI) - 1;
@@ -1348,6 +1381,7 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s) {
                 (void)ensure_dynamic_lds(reinterpret_cast<const void*>(&istft_ola_wave_kernel<Wc>), (int)dynw);
                 hipLaunchKernelGGL(istft_ola_wave_kernel<Wc>, dim3((unsigned)ceil_div(hops, run), (unsigned)(a.n_batch > 0 ? a.n_batch : 1)),
                                    dim3(256), dynw, s, a, run);
+                report(info, "istft_ola_wave_kernel", kFftPathWave, run, 0, ceil_div(hops, run) * (a.n_batch > 0 ? a.n_batch : 1), hops);
             }
         });
     }
@@ -1364,7 +1398,7 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s) {
             g.Y = a0.Y + (int64_t)c0 * a0.chan_stride;
             if (a0.M) g.M = a0.M + (int64_t)c0 * a0.chan_stride;
             g.out_channels = a0.n_channels; g.out_chan0 = c0;
-            const hipError_t e = launch_istft_ola(g, s);
+            const hipError_t e = launch_istft_ola(g, s, path, info);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -1372,16 +1406,18 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s) {
     return dispatch_window(a.W, [&](auto w) {
         constexpr int Wc = decltype(w)::value;
         const int64_t batches = a.n_batch > 0 ? a.n_batch : 1;
-        auto go = [&](auto kernel) {
+        auto go = [&](auto kernel, const char* name) {
             (void)ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)dyn);
             // a run of r hops costs r + 1 inversions (the frame before it) and the twiddle prologue
-            const int run = frames_per_workgroup(reinterpret_cast<const void*>(kernel), dyn, hops, batches, kOlaRun - 2, 1.5);
+            int slots = 0;
+            const int run = frames_per_workgroup(reinterpret_cast<const void*>(kernel), dyn, hops, batches, kOlaRun - 2, 1.5, &slots);
             hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(hops, run), (unsigned)batches), dim3(kFftThreads), dyn, s, a, run);
+            report(info, name, kFftPathBlock, run, slots, ceil_div(hops, run) * batches, hops);
         };
         if constexpr (Wc <= 4096) {
-            if (a.M) go(&istft_ola_kernel<Wc, true>); else go(&istft_ola_kernel<Wc, false>);
+            if (a.M) go(&istft_ola_kernel<Wc, true>, "istft_ola_kernel<masked>"); else go(&istft_ola_kernel<Wc, false>, "istft_ola_kernel<plain>");
         } else {
-            go(&istft_ola_kernel<Wc, false>);       // the engine keeps the mask in X for the longest window (registers)
+            go(&istft_ola_kernel<Wc, false>, "istft_ola_kernel<plain>");       // the engine keeps the mask in X for the longest window (registers)
         }
     });
 }

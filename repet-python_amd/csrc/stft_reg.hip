@@ -13,6 +13,7 @@
 // spends 7 barriers per transform. The Hermitian split needs Z[N-k], which sits in lane 64-l, slot 15-s:
 // one ds_bpermute per component. Same arithmetic contract as stft.hip (repet.py:1001-1105, :158, :1220).
 #include "common.h"
+#include "fft_path.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -700,25 +701,30 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
 
 }  // namespace
 
-bool reg_fft_supported(int W, int n_channels, bool inverse) {
+bool reg_fft_supported(int W, int n_channels, bool inverse) { return reg_fft_supported(W, n_channels, inverse, kFftPathAuto); }
+
+// path (fft_path.h): kFftPathAuto reads REPET_FFT_PATH as below; a family named by the caller stands for the value of the
+// variable that selects it (block / wave: 0, reg: 3)
+bool reg_fft_supported(int W, int n_channels, bool inverse, int path) {
     // Both wave kernels are the default for mono and stereo clips at W = 2048 (cfg 2 / 3 / 4 / 5, block kernels -> these:
     // forward 0.095 / 0.62 / 0.099 / 0.795 ms -> 0.084 / 0.54 / 0.074 / 0.755; inverse 0.071 / 0.603 / 0.059 / 0.604 ->
     // 0.058 / 0.481 / 0.054 / 0.537 -- the inverse only once ALL loads of a transform were issued before the first is
     // consumed: in batches of four it was no faster than the block kernel).
     // REPET_FFT_PATH=block | wave: the LDS Stockham kernels of stft.hip for everything; =reg: both kernels of this file for
     // any channel count they take; =fwd: the forward one only.
-    static const int mode = [] {
+    static const int env_mode = [] {
         const char* e = getenv("REPET_FFT_PATH");
         if (!e || !e[0]) return 4;
         return e[0] == 'r' ? 3 : e[0] == 'f' ? 1 : 0;
     }();
+    const int mode = path == kFftPathAuto ? env_mode : path == kFftPathReg ? 3 : 0;
     if (W != 2 * kRegN) return false;
     if (inverse) return (mode & 6) && (n_channels == 1 || n_channels == 2);
     if (mode & 4) return n_channels == 1 || n_channels == 2;
     return (mode & 1) && n_channels >= 1;
 }
 
-hipError_t launch_stft_reg(const StftArgs& a, hipStream_t s) {
+hipError_t launch_stft_reg(const StftArgs& a, hipStream_t s, FftLaunch* info) {
     const int64_t batches = a.n_batch > 0 ? a.n_batch : 1;
     const int64_t units = a.T * batches;
     if (units >= (int64_t)1 << 31) return hipErrorInvalidValue;
@@ -737,10 +743,15 @@ hipError_t launch_stft_reg(const StftArgs& a, hipStream_t s) {
     if (a.n_channels == 2) go(&stft_reg_kernel<2>);
     else if (a.n_channels == 1) go(&stft_reg_kernel<1>);
     else go(&stft_reg_kernel<0>);
+    if (info) {
+        info->kernel = a.n_channels == 2 ? "stft_reg_kernel<2>" : a.n_channels == 1 ? "stft_reg_kernel<1>" : "stft_reg_kernel<0>";
+        info->family = kFftPathReg; info->run = kFwdWaves; info->rounds = (int)ceil_div(units, (int64_t)blocks * kFwdWaves);
+        info->slots = cus; info->workgroups = blocks; info->units = units; info->launches += 1;
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t s) {
+hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t s, FftLaunch* info) {
     const int64_t batches = a.n_batch > 0 ? a.n_batch : 1;
     const int64_t lim = (int64_t)1 << 30;
     if (a.accumulate_weighted && (a.n_out >= lim || a.batch_out_stride >= lim || a.overlap >= lim || a.fade_in >= lim || a.fade_out >= lim))
@@ -768,6 +779,13 @@ hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t
     const int mode = a.model ? 2 : a.M ? 1 : 0;
     if (a.n_channels == 2) { if (mode == 2) go(&istft_ola_reg_kernel<2, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<2, 1>); else go(&istft_ola_reg_kernel<2, 0>); }
     else { if (mode == 2) go(&istft_ola_reg_kernel<1, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<1, 1>); else go(&istft_ola_reg_kernel<1, 0>); }
+    if (info) {
+        static const char* const names[2][3] = {{"istft_ola_reg_kernel<1, 0>", "istft_ola_reg_kernel<1, 1>", "istft_ola_reg_kernel<1, 2>"},
+                                                {"istft_ola_reg_kernel<2, 0>", "istft_ola_reg_kernel<2, 1>", "istft_ola_reg_kernel<2, 2>"}};
+        info->kernel = names[a.n_channels == 2][mode];
+        info->family = kFftPathReg; info->run = kInvWaves * rounds - 1; info->rounds = rounds; info->slots = cus;
+        info->workgroups = (int64_t)blocks * batches; info->units = hops; info->launches += 1;
+    }
     return hipGetLastError();
 }
 

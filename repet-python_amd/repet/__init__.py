@@ -308,6 +308,111 @@ def _istft(audio_stft, window_function, step_length):
     return y.astype(np.float64)
 
 
+# ---- stage entries of the production FFT launchers (diagnostic exports, not part of the C ABI) ------------------------
+FFT_PATHS = {"auto": 0, "block": 1, "wave": 2, "reg": 3}
+_FFT_FAMILIES = {0: None, 1: "block", 2: "wave", 3: "reg"}
+_stage_entries = {}
+
+
+def _stage_entry(name):
+    import ctypes as C
+    if name not in _stage_entries:
+        fn = getattr(_native.lib(), name)
+        p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        fn.restype = C.c_int
+        fn.argtypes = {
+            "repet_debug_stft_stage": [p, p, i64, i32, p, i32, i32, i32, i64, i64, i32, i64, i32, i32, i32, i32, p] + [p] * 8 + [p, i32, p],
+            "repet_debug_istft_stage": [p, p, i32, i32, i64, i32, i64, i64, i64, C.c_float, p, p, p, i32, i32, i32, i64, i64,
+                                        i32, i32, i32, i32, i32, i64, i64, i32, p, i64, p, i32, p],
+        }[name]
+        _stage_entries[name] = fn
+    return _stage_entries[name]
+
+
+def _launch_report(name_buf, words):
+    return {"kernel": name_buf.value.decode(), "family": _FFT_FAMILIES[int(words[0])], "run": int(words[1]), "rounds": int(words[2]),
+            "slots": int(words[3]), "workgroups": int(words[4]), "units": int(words[5]), "launches": int(words[6])}
+
+
+def _stft_stage(audio, window_function, step_length, centred=True, sample_offset=0, n_samples=None, n_batch=1,
+                batch_sample_stride=0, path="auto", want=(), fix_infinite=False, prefill=0):
+    """``launch_stft`` as the pipelines call it. ``audio`` (n_total, C) fp32 interleaved; ``n_batch`` clips of ``n_samples``
+    samples, the first at ``sample_offset``, ``batch_sample_stride`` apart. ``want``: any of "Vm", "Vn", "P", "Vh", "Ph"
+    ("Ph" brings "Ph_inv"). Returns a dict of the buffers exactly as the kernel left them -- X (B, C, rows, FS) complex64 and
+    V with the pad bins and pad rows, the means (B, Tpad, FS), the f16 planes (B, Tpad, 2 FS) as float16 -- every one filled
+    with the byte ``prefill`` before the launch, plus "T", "F", "FS", "Tpad" and "launch": the kernel that ran, its family,
+    the frames per workgroup and the resident slots they were fitted to. A family that does not take the shape raises
+    RuntimeError (REPET_ERR_LIMIT)."""
+    import ctypes as C
+    x = _f32(audio)
+    if x.ndim == 1:
+        x = x[:, None]
+    window = _f32(window_function)
+    n_total, ch = x.shape
+    n = n_total - sample_offset if n_samples is None else n_samples
+    bits = sum({"Vm": 1, "Vn": 2, "P": 4, "Vh": 8, "Ph": 16}[k] for k in want)
+    geo = (C.c_int64 * 6)()
+    words = (C.c_int64 * 8)()
+    name = C.create_string_buffer(64)
+    fn = _stage_entry("repet_debug_stft_stage")
+    ctx = _native.default_context(_device).handle
+
+    def call(outs):
+        _native.check(fn(ctx, _native.ptr(x), n_total, ch, _native.ptr(window), len(window), int(step_length), int(bool(centred)),
+                         int(sample_offset), int(n), int(n_batch), int(batch_sample_stride), FFT_PATHS[path], bits,
+                         int(bool(fix_infinite)), int(prefill), geo, *outs, name, len(name), words))
+
+    call([None] * 8)
+    t, tpad, rows, f, fs, _ = (int(v) for v in geo)
+    b = int(n_batch)
+    X = np.empty((b, ch, rows, fs), dtype=np.complex64)
+    V = np.empty((b, ch, rows, fs), dtype=np.float32)
+    means = {k: np.empty((b, tpad, fs), dtype=np.float32) for k in ("Vm", "Vn", "P") if k in want}
+    planes = {k: np.empty((b, tpad, 2 * fs), dtype=np.float16) for k in ("Vh", "Ph") if k in want}
+    ph_inv = np.empty((b, tpad), dtype=np.float32) if "Ph" in want else None
+    opt = lambda a: None if a is None else _native.ptr(a)
+    call([_native.ptr(X), _native.ptr(V), opt(means.get("Vm")), opt(means.get("Vn")), opt(means.get("P")), opt(planes.get("Vh")),
+          opt(planes.get("Ph")), opt(ph_inv)])
+    out = {"X": X, "V": V, "T": t, "F": f, "FS": fs, "Tpad": tpad, "launch": _launch_report(name, words)}
+    out.update(means)
+    out.update(planes)
+    if ph_inv is not None:
+        out["Ph_inv"] = ph_inv
+    return out
+
+
+def _istft_stage(spectra, window_length, out, trim, n_out, out_offset=0, scale=1.0, mask=None, model=None, periods=None, cutoff=0,
+                 accumulate_weighted=0, fade_in=0, fade_out=0, batch=None, path="auto"):
+    """``launch_istft_ola`` as the pipelines call it. ``spectra`` (n_spec, C, T, F) complex half spectra; ``out`` (out_len, C)
+    the pre-filled output buffer, returned whole as the kernel left it (the argument is not changed). ``mask`` (n_spec, C, T, F)
+    or ``model`` (n_spec, C, rows, F) + ``periods`` (n_spec,) + ``cutoff``. ``batch``: dict of n_batch, batch_first, batch_step,
+    batch_total, batch_local0, batch_out_stride, overlap. Returns (out, launch report)."""
+    import ctypes as C
+    y = np.ascontiguousarray(spectra, dtype=np.complex64)
+    n_spec, ch, t, f = y.shape
+    assert f == window_length // 2 + 1
+    buf = np.array(out, dtype=np.float32, order="C", copy=True)
+    if buf.ndim == 1:
+        buf = buf[:, None]
+    assert buf.shape[1] == ch
+    m = None if mask is None else _f32(mask)
+    w = None if model is None else _f32(model)
+    per = None if periods is None else np.ascontiguousarray(periods, dtype=np.int32)
+    assert m is None or m.shape == y.shape
+    assert w is None or (w.shape[:2] == (n_spec, ch) and w.shape[3] == f and per is not None and per.shape == (n_spec,))
+    bt = dict(n_batch=0, batch_first=0, batch_step=0, batch_total=0, batch_local0=0, batch_out_stride=0, overlap=0)
+    bt.update(batch or {})
+    words = (C.c_int64 * 8)()
+    name = C.create_string_buffer(64)
+    opt = lambda a: None if a is None else _native.ptr(a)
+    _native.check(_stage_entry("repet_debug_istft_stage")(
+        _native.default_context(_device).handle, _native.ptr(y), n_spec, ch, t, int(window_length), int(trim), int(n_out), int(out_offset),
+        float(scale), opt(m), opt(w), opt(per), 0 if w is None else w.shape[2], int(cutoff), int(accumulate_weighted), int(fade_in),
+        int(fade_out), int(bt["n_batch"]), int(bt["batch_first"]), int(bt["batch_step"]), int(bt["batch_total"]), int(bt["batch_local0"]),
+        int(bt["batch_out_stride"]), int(bt["overlap"]), FFT_PATHS[path], _native.ptr(buf), buf.shape[0], name, len(name), words))
+    return buf, _launch_report(name, words)
+
+
 def _selfsimilaritymatrix(data_matrix):
     """Cosine self-similarity between the columns (repet.py:1209-1225)."""
     rows = _f32(np.asarray(data_matrix).T)

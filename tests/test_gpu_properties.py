@@ -91,6 +91,13 @@ def test_stft_istft_random_lengths(n, logw, seed):
     assert np.max(np.abs(spec - want)) < 3e-6 * max(1.0, np.max(np.abs(want)))
     y = repet._istft(spec, window, w // 2)
     assert np.max(np.abs(y[:n] - x)) < 5e-6 * max(1.0, np.max(np.abs(x)))      # COLA reconstruction
+    # the same through the fused inverse STFT + overlap-add kernel the pipelines run (launch_istft_ola), as production picks it
+    half = np.ascontiguousarray(spec[:w // 2 + 1].T)[None, None]
+    n_out = half.shape[2] * (w // 2) - w // 2
+    scale = 1.0 / float(np.sum(window.astype(np.float32).astype(np.float64)[0:w:w // 2]))
+    fused, launch = repet._istft_stage(half, w, np.zeros((n_out, 1), np.float32), w // 2, n_out, scale=scale)
+    assert launch["kernel"].startswith("istft_ola_") and fused.shape == (len(y), 1)
+    assert np.max(np.abs(fused[:n, 0] - x)) < 5e-6 * max(1.0, np.max(np.abs(x)))
 
 
 @settings(max_examples=15, deadline=None, suppress_health_check=list(HealthCheck))

@@ -44,6 +44,18 @@ def test_stft_is_hermitian_and_handles_odd_lengths():
         assert np.allclose(got[1:w // 2], np.conj(got[:w // 2:-1]))
 
 
+def _fused_istft(spec, window, h):
+    """repet._istft's contract (a (W, T) spectrum -> T h - (W - h) samples, scaled by the window's COLA sum) through the fused
+    inverse STFT + overlap-add kernel, as production picks it."""
+    w, t = spec.shape
+    half = np.ascontiguousarray(np.asarray(spec)[:w // 2 + 1].T)[None, None]
+    n_out = t * h - (w - h)
+    scale = 1.0 / float(sum(np.asarray(window, dtype=np.float32).astype(np.float64)[0:w:h]))
+    out, launch = repet._istft_stage(half, w, np.zeros((n_out, 1), np.float32), w - h, n_out, scale=scale)
+    assert launch["family"] in ("block", "wave", "reg") and launch["kernel"].startswith("istft_ola_")
+    return out[:, 0].astype(np.float64)
+
+
 @pytest.mark.parametrize("fs", [8000, 44100])
 def test_istft_roundtrip_and_oracle(fs):
     from repet_synth import synth
@@ -55,6 +67,10 @@ def test_istft_roundtrip_and_oracle(fs):
     assert got.shape == want.shape
     assert np.max(np.abs(got - want)) < 2e-6
     assert np.max(np.abs(got[:len(x)] - x)) < 2e-6          # COLA: exact reconstruction
+    fused = _fused_istft(spec, window, h)                    # the kernel the pipelines run (launch_istft_ola)
+    assert fused.shape == want.shape
+    assert np.max(np.abs(fused - want)) < 2e-6
+    assert np.max(np.abs(fused[:len(x)] - x)) < 2e-6
 
 
 def test_selfsimilarity(clip):
