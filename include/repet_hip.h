@@ -489,6 +489,40 @@ int repet_online_finish_stream(repet_online* h, int32_t slot, double* out, int64
 int repet_online_finish_stream_device(repet_online* h, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
                                       void* signal_stream, int64_t* n_written);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) The FOREGROUND, aligned. The repeating background is the
+ * means; audio - background is what most callers want, and a live handle returns its background behind the input (n_emit != n),
+ * so only the handle knows which input samples an emission belongs to. One selector with one meaning everywhere: */
+#define REPET_OUT_BACKGROUND 0   /* what every call returned so far, bit for bit (the default) */
+#define REPET_OUT_FOREGROUND 1   /* input - background of the same samples */
+#define REPET_OUT_MIXTURE 2      /* the input samples themselves, aligned with what was emitted (the delay-compensated input) */
+/* With x the sample as the engine holds it (fp32 sample + fp32 remainder: exact for F32 / F16 / BF16 / I16 input and for
+ * float64 input that came from PCM or fp32, 48 bits of any other float64 sample) and bg the fp32 background: mixture =
+ * (double)x, foreground = (double)x - (double)bg, rounded once; an F32 destination takes that value rounded once more. A sample
+ * before its slot's own stream began (the hop emitted behind a restart, every sample of an idle slot) is zero in all three
+ * signals, whatever the chunk carried there; from the slot's first own sample on, foreground and mixture are its input, the
+ * warm-up included (the background is zero there: nothing is removed before there is evidence).
+ * set_output       : what `out` / `dst` of every emitting call of the handle (push*, finish*, finish_stream*) carries from now on.
+ * also_emit        : ONE-SHOT: the next emitting call also writes `which` of the same samples, in the same launch, into `dst`:
+ *                    device memory of `dtype` (that call's dst_dtype) with element strides [stream, sample, channel] for the
+ *                    *_device calls (finish_stream_device ignores the stream stride), a dense float64 host array [S][n_emit][C]
+ *                    (dtype REPET_F64, strides ignored) for the host calls. The address ranges of the two destinations must
+ *                    not intersect. Consumed by that call whether it succeeds or not; checked by it before any launch.
+ * last_emission(_device): another signal of exactly the samples the last push or finish wrote -- out[S][n][C] float64 on the
+ *                    host, or a device destination as push_device's behind `signal_stream`, with no host wait. Valid until the
+ *                    next push, finish, restart or release on the handle (REPET_ERR_BAD_ARG afterwards: the handle no longer
+ *                    holds those samples). A finish_stream releases its slot, so its tail is had through also_emit only.
+ * No stage of the pipeline runs twice: the selected signal costs the launch the background's egress costs, a second one rides
+ * in the same launch. Offline contexts: repet_ctx_select_result chooses what repet_ctx_download_device_strided writes from now
+ * on (the resident samples and, after a float64 upload, their remainders against the result); repet_select_run_result does the
+ * same for the calling thread's repet_run_device context of `device`. */
+int repet_online_set_output(repet_online* h, int which);
+int repet_online_also_emit(repet_online* h, int which, void* dst, int dtype, const int64_t strides[3]);
+int repet_online_last_emission(repet_online* h, int which, double* out, int64_t capacity, int64_t* n_written);
+int repet_online_last_emission_device(repet_online* h, int which, void* dst, int dst_dtype, const int64_t dst_strides[3],
+                                      void* signal_stream, int64_t* n_written);
+int repet_ctx_select_result(repet_ctx* ctx, int which);
+int repet_select_run_result(int device, int which);
+
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,
  * fp32 -> float64; non-temporal AVX-512 / AVX2 lines where the CPU has them) against scalar loops on n values with NaN,
  * infinities, denormals, PCM-exact runs and every misalignment. No GPU needed. Returns the number of values that differ

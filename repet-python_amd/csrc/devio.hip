@@ -188,6 +188,111 @@ __global__ __launch_bounds__(kIoThreads) void devio_ingest_bf16(const BHalf* src
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f64(const float* in, IoGeo g, int dense, double* dst) { egress_body<double, 2>(in, g, dense, dst); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, IoGeo g, int dense, float* dst) { egress_body<float, 4>(in, g, dense, dst); }
 
+// Emission of the streaming handle, and the selected result of an offline context: what was emitted as background (`bg`, fp32
+// [S][n][C] dense), as foreground (input - background) or as mixture (the input itself, aligned with what was emitted), into
+// one or two strided destinations in ONE pass. The input is read where the engine holds it: fp32 samples `hi` and, where
+// present, their fp32 remainders `lo`, stream s at s * in_stream floats. In float64: mixture = hi + lo (exact),
+// foreground = mixture - bg (rounded once); an F32 destination takes that value rounded once more. A sample of stream s is
+// LIVE from handle sample slot_start[s] * hop on (pos0: handle sample of the emission's first one; no table: always); every
+// other sample is zero in all three signals by a select, so NaN in an idle slot's share of a chunk never shows.
+// EPT consecutive interleaved elements per thread as in egress_body: vector accesses on bg, on hi / lo where the run lies in
+// one stream and is aligned, on a dense destination.
+struct EmitOut { void* p; int64_t s_clip, s_sample, s_channel; int32_t which, dense; };
+struct EmitArgs {
+    const float* bg; const float* hi; const float* lo;
+    int64_t in_stream, count, per, n_samples;
+    const int64_t* slot_start; int64_t pos0, hop;
+    int32_t n_channels, n_out;
+    EmitOut out[2];
+};
+
+template <typename T, int EPT>
+__device__ inline void emit_body(const EmitArgs& a) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * EPT;
+    if (i0 >= a.count) return;
+    const int m = a.count - i0 < EPT ? (int)(a.count - i0) : EPT;
+    const int64_t s0 = i0 / a.per, r0 = i0 - s0 * a.per;
+    float b[EPT], h[EPT], l[EPT];
+    bool live[EPT];
+    if (m == EPT) {
+        if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(a.bg + i0); b[0] = v.x; b[1] = v.y; }
+        else { const float4 v = *reinterpret_cast<const float4*>(a.bg + i0); b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) b[k] = k < m ? a.bg[i0 + k] : 0.f;
+    }
+    const float* ph = a.hi + s0 * a.in_stream + r0;
+    const bool one_stream = m == EPT && r0 + EPT <= a.per;
+    if (one_stream && !(reinterpret_cast<uintptr_t>(ph) & (EPT * 4 - 1))) {
+        if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(ph); h[0] = v.x; h[1] = v.y; }
+        else { const float4 v = *reinterpret_cast<const float4*>(ph); h[0] = v.x; h[1] = v.y; h[2] = v.z; h[3] = v.w; }
+        if (a.lo) {
+            const float* pl = a.lo + s0 * a.in_stream + r0;         // (hi and lo are laid out alike: aligned together)
+            if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(pl); l[0] = v.x; l[1] = v.y; }
+            else { const float4 v = *reinterpret_cast<const float4*>(pl); l[0] = v.x; l[1] = v.y; l[2] = v.z; l[3] = v.w; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) l[k] = 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+            h[k] = 0.f; l[k] = 0.f;
+            if (k < m) {
+                int64_t s = s0, r = r0 + k;
+                if (r >= a.per) { s += r / a.per; r %= a.per; }
+                h[k] = a.hi[s * a.in_stream + r];
+                if (a.lo) l[k] = a.lo[s * a.in_stream + r];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        live[k] = true;
+        if (a.slot_start && k < m) {
+            int64_t s = s0, r = r0 + k;
+            if (r >= a.per) { s += r / a.per; r %= a.per; }
+            const int64_t start = a.slot_start[s];
+            live[k] = start < repet_eng::kSlotIdle && a.pos0 + r / a.n_channels >= start * a.hop;
+        }
+    }
+    double bgv[EPT], fgv[EPT], mix[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi)
+        const double x = fabsf(h[k]) <= 3.402823466e38f || h[k] != h[k] ? (double)h[k] + (double)l[k] : (double)h[k];
+        mix[k] = live[k] ? x : 0.0;
+        fgv[k] = live[k] ? x - (double)b[k] : 0.0;
+        bgv[k] = live[k] ? (double)b[k] : 0.0;
+    }
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        if (d >= a.n_out) break;
+        const EmitOut o = a.out[d];
+        T* dst = static_cast<T*>(o.p);
+        T v[EPT];
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) v[k] = (T)(o.which == REPET_OUT_BACKGROUND ? bgv[k] : (o.which == REPET_OUT_FOREGROUND ? fgv[k] : mix[k]));
+        if (m == EPT && o.dense) {
+            if constexpr (EPT == 2) *reinterpret_cast<double2*>(dst + i0) = make_double2(v[0], v[1]);
+            else *reinterpret_cast<float4*>(dst + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            const IoGeo g{a.count, a.n_samples, a.n_channels, o.s_clip, o.s_sample, o.s_channel};
+            Walker w(g, i0);
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) {
+                if (k < m) {
+                    dst[w.off] = v[k];
+                    if (k < m - 1) w.next(g);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void devio_emit_f64(EmitArgs a) { emit_body<double, 2>(a); }
+__global__ __launch_bounds__(kIoThreads) void devio_emit_f32(EmitArgs a) { emit_body<float, 4>(a); }
+
 // ---- the streaming handle's per-push data movement (engine_online.hip): S streams at a per-stream stride -------------------
 // Grids are streams (y) x four-element slots (x), both capped and walked grid-stride; every store of a whole slot is one
 // dwordx4. kRowCopyParts parts (z) per launch.
@@ -418,6 +523,35 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
     return hipGetLastError();
 }
 
+hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
+                              int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
+                              int n_dsts, hipStream_t s) {
+    const int64_t count = (int64_t)n_streams * n * ch;
+    if (count <= 0 || n_dsts <= 0) return hipSuccess;
+    if (n_dsts > 2 || !bg || !hi) return hipErrorInvalidValue;
+    EmitArgs a{};
+    a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
+    a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts;
+    for (int k = 0; k < n_dsts; ++k) {
+        const IoGeo g{count, n, ch, dsts[k].strides[0], dsts[k].strides[1], dsts[k].strides[2]};
+        a.out[k] = EmitOut{dsts[k].p, g.s_clip, g.s_sample, g.s_channel, dsts[k].which, is_dense(dsts[k].p, g, n_streams, 16) ? 1 : 0};
+    }
+    if (dtype == REPET_F64) devio_emit_f64<<<dim3((unsigned)ceil_div(ceil_div(count, 2), kIoThreads)), kIoThreads, 0, s>>>(a);
+    else devio_emit_f32<<<dim3((unsigned)ceil_div(ceil_div(count, 4), kIoThreads)), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// two destinations of one emission must not share memory: their address ranges (first to last element) must not intersect
+int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int64_t* st1, int elem_bytes, int32_t n_clips, int64_t n,
+                   int32_t ch) {
+    if ((int64_t)n_clips * n * ch <= 0) return REPET_OK;
+    auto last = [&](const int64_t* st) { return (st[0] * (n_clips - 1) + st[1] * (n - 1) + st[2] * (ch - 1) + 1) * elem_bytes; };
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p0), b0 = reinterpret_cast<uintptr_t>(p1);
+    if (a0 < b0 + (uintptr_t)last(st1) && b0 < a0 + (uintptr_t)last(st0))
+        return fail(REPET_ERR_BAD_ARG, "the two destinations overlap (their address ranges must not intersect)");
+    return REPET_OK;
+}
+
 int check_strides(const int64_t* strides) {
     if (!strides) return fail(REPET_ERR_BAD_ARG, "strides is null");
     for (int k = 0; k < 3; ++k)
@@ -514,6 +648,14 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     return REPET_OK;
 }
 
+int repet_ctx_select_result(repet_ctx* c, int which) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (which < REPET_OUT_BACKGROUND || which > REPET_OUT_MIXTURE)
+        return fail(REPET_ERR_BAD_ARG, "which must be REPET_OUT_BACKGROUND, REPET_OUT_FOREGROUND or REPET_OUT_MIXTURE");
+    c->result_which = which;
+    return REPET_OK;
+}
+
 int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const int64_t strides[3], void* signal_stream) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
@@ -528,7 +670,14 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
     // caching allocator has just handed out again, the caller's own writes to `dst`) comes before the egress writes it
     HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(signal_stream)));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
-    if (count > 0) {
+    if (count > 0 && c->result_which != REPET_OUT_BACKGROUND) {
+        // foreground / mixture: the resident samples and, where a float64 upload left them, their remainders beside the result
+        if (c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
+        EmitDst d{dst, c->result_which, {strides[0], strides[1], strides[2]}};
+        HIP_TRY(launch_stream_emit(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
+                                   c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels, dtype, &d, 1,
+                                   c->stream));
+    } else if (count > 0) {
         IoGeo g{count, c->n_samples, c->n_channels, strides[0], strides[1], strides[2]};
         const float* in = c->out.as<float>();
         if (dtype == REPET_F64) {

@@ -117,6 +117,7 @@ struct repet_ctx {
     // caller's stream, the caller's stream on io_done recorded behind the egress; the refusal mode's non-finite flag word
     hipEvent_t io_wait = nullptr, io_done = nullptr;
     DevBuf nonfinite_word;
+    int result_which = REPET_OUT_BACKGROUND;   // what repet_ctx_download_device_strided writes (repet_ctx_select_result)
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
     DevBuf X, V, Vn, P, S, band, beat, idx, cnt, periods, win_periods, frames, tmp_a, tmp_b, tmp_c;
@@ -281,6 +282,14 @@ hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, i
 hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s, const int64_t* slot_start = nullptr);
 hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,
                                 const int64_t strides[3], hipStream_t s);
+//   emit     background / foreground / mixture of an emission (or of an offline result) into one or two strided destinations
+//            of one dtype, one launch: bg fp32 [S][n][C]; the input hi (+ lo, nullable) with stream s at s * in_stream floats
+struct EmitDst { void* p = nullptr; int which = -1; int64_t strides[3] = {0, 0, 0}; };
+hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
+                              int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
+                              int n_dsts, hipStream_t s);
+int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int64_t* st1, int elem_bytes, int32_t n_clips, int64_t n,
+                   int32_t ch);
 constexpr int kRankMinList = 24;     // shortest list bound for which the column sort is worth its time
 
 }  // namespace repet_eng

@@ -1165,6 +1165,14 @@ int repet_run(int algo, const void* audio, int dtype, int64_t n, int32_t ch, con
     return repet_ctx_download(c, out);
 }
 
+int repet_select_run_result(int device, int which) {
+    if (which < REPET_OUT_BACKGROUND || which > REPET_OUT_MIXTURE)
+        return fail(REPET_ERR_BAD_ARG, "which must be REPET_OUT_BACKGROUND, REPET_OUT_FOREGROUND or REPET_OUT_MIXTURE");
+    repet_ctx* c = nullptr;
+    RP_TRY(thread_ctx(device, &c));
+    return repet_ctx_select_result(c, which);
+}
+
 int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t in_strides[3],
                      void* dst, int out_dtype, const int64_t out_strides[3], const repet_params* p, int device, void* stream) {
     repet_ctx* c = nullptr;

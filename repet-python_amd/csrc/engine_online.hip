@@ -46,6 +46,13 @@ struct repet_online {
     int64_t frames_done = 0, total_in = 0, emitted = 0;
     int64_t max_push = 0;           // repet_online_open_streams: windows and pending buffers sized for pushes of this many samples
     bool finished = false;
+    // What the emitting calls deliver (repet_online_set_output), the one-shot second destination of the next one
+    // (repet_online_also_emit), and where the samples of the last emission lie: the emitted range [pos0, pos0 + n) is the front
+    // of the unconsumed samples of the pending buffer `buf` AS IT WAS BEFORE THE SLIDE (`off` samples into every stream's
+    // share). Nothing writes that buffer before the next push's slide; restart / release and the next append end its validity.
+    int out_which = REPET_OUT_BACKGROUND;
+    struct Also { int which = -1; void* dst = nullptr; int dtype = REPET_F64; int64_t strides[3] = {0, 0, 0}; } also;
+    struct Emission { bool valid = false; int buf = 0, S = 0, slot = -1; int64_t off = 0, n = 0, pos0 = 0; } em;
 
     int64_t plane() const { return (rows_cap + kPadRows) * FS; }        // elements between channel planes of X and V
     int64_t spec_stride() const { return (int64_t)C * plane(); }      // ... between streams in X and V
@@ -145,6 +152,7 @@ int online_ensure_pending(repet_online* o, int64_t n) {
 // no counter touched: the handle goes on as if the call had not been made.
 int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1) {
     repet_ctx* c = o->ctx;
+    o->em = repet_online::Emission{true, o->pcur, slot < 0 ? o->S : 1, slot, o->pend_hist, std::max<int64_t>(n_emit, 0), o->emitted};
     if (n_new <= 0 && n_emit <= 0) return REPET_OK;
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, o->W, &tb));
@@ -290,6 +298,7 @@ int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new
 // the chunk's samples (already where `src` says, device memory) appended to every stream's pending buffer
 int online_append(repet_online* o, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
     if (n <= 0) return REPET_OK;
+    o->em.valid = false;
     RP_TRY(online_ensure_pending(o, n));
     hipError_t e = launch_stream_append(src, dtype, o->S, n, o->C, strides, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
                                         o->pend_stride(), (o->pend_hist + o->pend_count) * o->C, o->ctx->stream);
@@ -299,31 +308,86 @@ int online_append(repet_online* o, const void* src, int dtype, int64_t n, const 
     return REPET_OK;
 }
 
-// host side of a push or finish: the result [S][n_emit][C] widened on the device, one copy into the pinned buffer, then `out`
+// The last emission (o->em) into up to two strided device destinations of one dtype: one launch. The background alone takes the
+// plain egress it always took; everything else reads the emitted range of the pending samples beside the result.
+int online_emit(repet_online* o, const EmitDst* dsts, int n_dsts, int dtype) {
+    repet_ctx* c = o->ctx;
+    const repet_online::Emission& em = o->em;
+    if (!em.valid) return fail(REPET_ERR_BAD_ARG, "online: no emission to return");
+    if ((int64_t)em.S * em.n * o->C <= 0 || n_dsts <= 0) return REPET_OK;
+    if (n_dsts == 1 && dsts[0].which == REPET_OUT_BACKGROUND) {
+        HIP_TRY(launch_stream_egress(o->outf.as<float>(), em.S, em.n, o->C, dsts[0].p, dtype, dsts[0].strides, c->stream));
+        return REPET_OK;
+    }
+    if (em.off + em.n > o->pend_cap) return fail(REPET_ERR_LIMIT, "online: the emitted range is not in the pending buffer");
+    const int64_t sb = em.slot < 0 ? 0 : em.slot, at = sb * o->pend_stride() + em.off * o->C;
+    HIP_TRY(launch_stream_emit(o->outf.as<float>(), o->pend[em.buf].as<float>() + at, o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
+                               o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dtype, dsts,
+                               n_dsts, c->stream));
+    return REPET_OK;
+}
+
+// the handle's selected output, and the second one where repet_online_also_emit armed it
+static int online_outputs(const repet_online* o, void* dst, const int64_t* strides, void* also_dst, const int64_t* also_strides, EmitDst d[2]) {
+    d[0].p = dst; d[0].which = o->out_which;
+    for (int k = 0; k < 3; ++k) d[0].strides[k] = strides[k];
+    if (o->also.which < 0) return 1;
+    d[1].p = also_dst; d[1].which = o->also.which;
+    for (int k = 0; k < 3; ++k) d[1].strides[k] = also_strides[k];
+    return 2;
+}
+
+// host side of a push or finish: the result [S][n_emit][C] widened on the device (two blocks with a second output), one copy
+// into the pinned buffer, then `out` (and the second host array)
 int online_host_result(repet_online* o, int64_t n_emit, double* out, int streams = 0) {
     repet_ctx* c = o->ctx;
     const int S = streams > 0 ? streams : o->S;
     const int64_t count = (int64_t)S * n_emit * o->C;
+    const int blocks = o->also.which < 0 ? 1 : 2;
     if (count > 0) {
-        HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
-        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
+        HIP_TRY(o->out64.ensure((size_t)count * blocks * sizeof(double)));
+        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * blocks * sizeof(double)));
         const int64_t dense[3] = {n_emit * o->C, o->C, 1};
-        HIP_TRY(launch_stream_egress(o->outf.as<float>(), S, n_emit, o->C, o->out64.p, REPET_F64, dense, c->stream));
-        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        EmitDst d[2];
+        const int nd = online_outputs(o, o->out64.p, dense, o->out64.as<double>() + count, dense, d);
+        RP_TRY(online_emit(o, d, nd, REPET_F64));
+        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * blocks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (count > 0) std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    if (count > 0) {
+        std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+        if (blocks == 2) std::memcpy(o->also.dst, static_cast<double*>(o->host_out) + count, (size_t)count * sizeof(double));
+    }
     return REPET_OK;
 }
 
-// device side: the result into the caller's strided destination, then the caller's stream behind it
+// device side: the result into the caller's strided destination(s), then the caller's stream behind it
 int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], hipStream_t signal,
                          int streams = 0) {
     repet_ctx* c = o->ctx;
-    HIP_TRY(launch_stream_egress(o->outf.as<float>(), streams > 0 ? streams : o->S, n_emit, o->C, dst, dst_dtype, dst_strides, c->stream));
+    EmitDst d[2];
+    const int64_t also_strides[3] = {streams > 0 ? 0 : o->also.strides[0], o->also.strides[1], o->also.strides[2]};
+    const int nd = online_outputs(o, dst, dst_strides, o->also.dst, also_strides, d);
+    RP_TRY(online_emit(o, d, nd, dst_dtype));
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(signal, c->io_done, 0));
     return REPET_OK;
+}
+
+// the armed second output is consumed by the emitting call that follows it, whether that call succeeds or not
+struct AlsoScope {
+    repet_online* o;
+    explicit AlsoScope(repet_online* h) : o(h) {}
+    ~AlsoScope() { if (o) o->also.which = -1; }
+};
+
+// the second destination against the call that is about to emit (before any launch): host calls take a dense float64 array
+int online_check_also_host(const repet_online* o, int64_t n_emit, const double* out, int streams = 0) {
+    if (o->also.which < 0) return REPET_OK;
+    if (o->also.dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "online: the second output of a host call is float64");
+    const int S = streams > 0 ? streams : o->S;
+    const int64_t dense[3] = {n_emit * o->C, o->C, 1};
+    return check_disjoint(out, dense, o->also.dst, dense, 8, S, n_emit, o->C);
 }
 
 int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int dst_dtype, const int64_t dst_strides[3], int streams = 0) {
@@ -331,6 +395,15 @@ int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int
     RP_TRY(check_strides(dst_strides));
     RP_TRY(check_no_overlap(dst_strides, streams > 0 ? streams : o->S, n_emit, o->C));
     if (n_emit > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    if (o->also.which >= 0) {
+        if (n_emit > 0 && !o->also.dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+        const int S = streams > 0 ? streams : o->S;
+        const int64_t st[3] = {streams > 0 ? 0 : o->also.strides[0], o->also.strides[1], o->also.strides[2]};
+        if (o->also.dtype != dst_dtype) return fail(REPET_ERR_BAD_ARG, "online: the two outputs of one call have one dtype");
+        RP_TRY(check_strides(st));
+        RP_TRY(check_no_overlap(st, S, n_emit, o->C));
+        RP_TRY(check_disjoint(dst, dst_strides, o->also.dst, st, dst_dtype == REPET_F64 ? 8 : 4, S, n_emit, o->C));
+    }
     return REPET_OK;
 }
 
@@ -352,6 +425,7 @@ int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
 // spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
 int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t first_frame) {
     repet_ctx* c = o->ctx;
+    o->em.valid = false;
     if (n <= 0) return REPET_OK;
     const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), held = (o->pend_hist + o->pend_count) * o->C;
     ZeroPart parts[kRowCopyParts] = {};
@@ -402,6 +476,78 @@ int online_plan_slot(const repet_online* o, int32_t slot, int64_t* n_new, int64_
 
 extern "C" {
 
+static int check_which(int which) {
+    if (which < REPET_OUT_BACKGROUND || which > REPET_OUT_MIXTURE)
+        return fail(REPET_ERR_BAD_ARG, "which must be REPET_OUT_BACKGROUND, REPET_OUT_FOREGROUND or REPET_OUT_MIXTURE");
+    return REPET_OK;
+}
+
+int repet_online_set_output(repet_online* o, int which) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    RP_TRY(check_which(which));
+    o->out_which = which;
+    return REPET_OK;
+}
+
+int repet_online_also_emit(repet_online* o, int which, void* dst, int dtype, const int64_t strides[3]) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    o->also.which = -1;
+    RP_TRY(check_which(which));
+    if (dtype != REPET_F32 && dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    o->also.dst = dst; o->also.dtype = dtype;
+    for (int k = 0; k < 3; ++k) o->also.strides[k] = strides ? strides[k] : 0;
+    o->also.which = which;
+    return REPET_OK;
+}
+
+int repet_online_last_emission(repet_online* o, int which, double* out, int64_t capacity, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    RP_TRY(check_which(which));
+    if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, "online: the last emission is stale (a push, finish, restart or release came after it)");
+    const int64_t n = o->em.n, count = (int64_t)o->em.S * n * o->C;
+    if (n > capacity || (count > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    if (count > 0) {
+        HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
+        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
+        EmitDst d;
+        d.p = o->out64.p; d.which = which; d.strides[0] = n * o->C; d.strides[1] = o->C; d.strides[2] = 1;
+        RP_TRY(online_emit(o, &d, 1, REPET_F64));
+        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    }
+    *n_written = n;
+    return REPET_OK;
+}
+
+int repet_online_last_emission_device(repet_online* o, int which, void* dst, int dst_dtype, const int64_t dst_strides[3],
+                                      void* signal_stream, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    RP_TRY(check_which(which));
+    if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, "online: the last emission is stale (a push, finish, restart or release came after it)");
+    if (dst_dtype != REPET_F32 && dst_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_strides(dst_strides));
+    const int64_t strides[3] = {o->em.slot < 0 ? dst_strides[0] : 0, dst_strides[1], dst_strides[2]};
+    RP_TRY(check_no_overlap(strides, o->em.S, o->em.n, o->C));
+    if ((int64_t)o->em.S * o->em.n * o->C > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    EmitDst d;
+    d.p = dst; d.which = which;
+    for (int k = 0; k < 3; ++k) d.strides[k] = strides[k];
+    RP_TRY(online_emit(o, &d, 1, dst_dtype));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    *n_written = o->em.n;
+    return REPET_OK;
+}
+
 int repet_online_restart_streams(repet_online* o, const int32_t* slots, int32_t n) {
     RP_TRY(online_check_slots(o, slots, n));
     if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, "online: a stream can only begin on a hop boundary (samples pushed % step_length == 0)");
@@ -421,11 +567,13 @@ int repet_online_stream_emit_count(repet_online* o, int32_t slot, int64_t* n_emi
 }
 
 int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64_t capacity, int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
     RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    RP_TRY(online_check_also_host(o, n_emit, out, 1));
     DeviceGuard guard(o->ctx->device);
     o->slots_on = true;
     RP_TRY(online_process(o, n_new, n_emit, slot));
@@ -437,6 +585,7 @@ int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64
 
 int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
                                       void* signal_stream, int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written || !dst_strides) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
@@ -515,6 +664,7 @@ int repet_online_emit_count(repet_online* o, int64_t n, int finishing, int64_t* 
 
 int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
                               int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written || (n > 0 && !audio)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
@@ -524,6 +674,7 @@ int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int
     int64_t n_new = 0, n_emit = 0;
     RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs n_samples + window_length)");
+    RP_TRY(online_check_also_host(o, n_emit, out));
     if (n > 0) {
         // the chunk [S][n][C] through the pinned buffer into the staging buffer, then appended to every stream on the device
         const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
@@ -550,6 +701,7 @@ int repet_online_push(repet_online* o, const void* audio, int dtype, int64_t n, 
 int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_t n, const int64_t src_strides[3],
                              void* wait_stream, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                              int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
@@ -569,6 +721,7 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
 }
 
 int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
@@ -576,6 +729,7 @@ int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, 
     int64_t n_new = 0, n_emit = 0;
     RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    RP_TRY(online_check_also_host(o, n_emit, out));
     RP_TRY(online_process(o, n_new, n_emit));
     RP_TRY(online_host_result(o, n_emit, out));
     *n_written = n_emit;
@@ -589,6 +743,7 @@ int repet_online_finish(repet_online* o, double* out, int64_t capacity, int64_t*
 
 int repet_online_finish_device(repet_online* o, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                                int64_t* n_written) {
+    AlsoScope also(o);
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;

@@ -117,26 +117,33 @@ def release_workspaces():
     _native.release_tensor_contexts()
 
 
-def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False):
+def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background"):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
-    events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check)."""
+    events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
+    selects what the egress writes; "both" is two egress launches behind one run."""
     import torch
+    names = ("background", "foreground") if which == "both" else (which,)
+    _native.which_codes(which)
     params = derive_params(sampling_frequency)
     layout = _native.tensor_layout(audio_signal, batched)
     x, shape = layout[0], layout[2]
     result_shape = shape if x.dim() == 3 else shape[1:]
-    if out is not None:
-        if not _native.is_device_tensor(out) or out.device != x.device:
+    outs = _native.out_pair(out) if which == "both" else (out,)
+    for o in outs:
+        if o is None:
+            continue
+        if not _native.is_device_tensor(o) or o.device != x.device:
             raise ValueError(f"out must be a tensor on {x.device}")
-        if tuple(out.shape) != result_shape:
-            raise ValueError(f"out has shape {tuple(out.shape)}, the result {result_shape}")
-        _native.result_tensor_code(out)
+        if tuple(o.shape) != result_shape:
+            raise ValueError(f"out has shape {tuple(o.shape)}, the result {result_shape}")
+        _native.result_tensor_code(o)
     ctx = _native.tensor_context(x.device.index)
     ctx.set_strict_reference(strict_reference)
     stream = torch.cuda.current_stream(x.device)
     ctx.upload_layout(*layout, stream=stream)
     ctx.execute_async(algo, params)
-    return ctx.download_tensor(out, stream)
+    results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+    return results if which == "both" else results[0]
 
 
 def _separate(algo, audio_signal, sampling_frequency):
@@ -179,23 +186,35 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None):
+def separate(algo, audio_signal, sampling_frequency, out=None, which="background"):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
     clips one after another). Returns a float64 tensor on the tensor's device -- or fills ``out``, a float32 / float64 tensor
     of the same shape with any strides, and returns it. Every clip's result is what the one-clip call returns, bit for bit;
-    the work is ordered on the device's current stream with no host wait (see ``_separate_tensor``)."""
+    the work is ordered on the device's current stream with no host wait (see ``_separate_tensor``).
+
+    ``which``: "background" (default), "foreground" -- ``audio_signal - background`` written by the egress itself, in float64
+    from the samples as the engine holds them (exact for float32 / float16 / bfloat16 / int16 tensors; 48 bits of a float64
+    sample, so within ``2**-47 * max(|x|, |background|)`` of the float64 subtraction), rounded once more for a float32
+    ``out`` --, "mixture" (the input as the engine holds it) or "both": the pair ``(background, foreground)``, with ``out`` a
+    pair of tensors that share no memory."""
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
+    _native.which_codes(which)
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
-    return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True)
+    return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which)
 
 
 def online(sampling_frequency, number_channels):
     """Streaming form of :func:`simonline` (the reference needs the whole signal up front): returns an object with
     ``push(chunk) -> newly final background samples`` and ``finish() -> the remaining ones``. The module parameters are
-    snapshotted now; the concatenated output equals ``simonline`` of the concatenated input."""
+    snapshotted now; the concatenated output equals ``simonline`` of the concatenated input.
+
+    ``push(chunk, which=...)`` / ``finish(which=...)``: "background" (default), "foreground" -- the input minus the background
+    of exactly the emitted samples (the output runs behind the input; the handle keeps the delay line) --, "mixture" (those
+    input samples themselves) or "both", the pair ``(background, foreground)``. The concatenated foreground equals
+    ``x - simonline(x)``; during the 10-s warm-up, where ``simonline`` is silent, it is the input itself."""
     return _OnlineSeparator(derive_params(sampling_frequency), number_channels, _device)
 
 
@@ -219,7 +238,17 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     ``simonline`` of the samples pushed into it in between, bit for bit: zeros while it warms up, then its own buffer only.
     ``stream_samples(slot)`` is the length of a slot's stream so far (None when idle). A server loop: open with
     ``max_push_samples``, ``release`` every slot, ``restart`` a free slot when a call arrives, ``finish_stream`` it when the
-    call ends."""
+    call ends.
+
+    ``push``, ``finish`` and ``finish_stream`` take ``which="background"`` (default) / ``"foreground"`` / ``"mixture"`` /
+    ``"both"``: the foreground is the input minus the background OF THE EMITTED SAMPLES -- the output runs behind the input
+    (``n_emit != n``), and the handle subtracts from its own copy of them, per slot, at no extra launch. ``"mixture"`` is
+    that delay-compensated input; ``"both"`` returns ``(background, foreground)`` from one pass (``out=`` then takes a pair
+    of tensors of one dtype that share no memory). Per life the foreground equals ``x - simonline(x)`` bit for bit (float64
+    input that is not float32 + float32 exact: within ``2**-47 * max(|x|, |background|)``); while a stream warms up its
+    foreground is its input (nothing is removed before there is evidence); idle slots and the hop before a ``restart`` are
+    zero in every signal, whatever the chunk held there. ``last_emission(which, out=None)`` returns another signal of the
+    samples the last ``push`` / ``finish`` emitted, until the next push, finish, restart or release."""
     return _native.OnlineStreams(derive_params(sampling_frequency), number_channels, number_streams, _device,
                                  max_push_samples or 0)
 

@@ -20,6 +20,20 @@ MAX_STAGES = 16
 ERR_BAD_ARG, ERR_TOO_SHORT, ERR_HIP, ERR_OOM, ERR_LIMIT = -1, -2, -3, -4, -5
 FLAG_STRICT_REFERENCE = 1      # (ABI 3 opt-in; the default since ABI 4)
 FLAG_REFUSE_NONFINITE = 2
+# what an emitting call of a live handle, or the egress of a tensor call, delivers (REPET_OUT_* of include/repet_hip.h);
+# "both" is the Python layer's pair (background, foreground) from one pass
+OUT_BACKGROUND, OUT_FOREGROUND, OUT_MIXTURE = 0, 1, 2
+WHICH_CODES = {"background": OUT_BACKGROUND, "foreground": OUT_FOREGROUND, "mixture": OUT_MIXTURE}
+
+
+def which_codes(which):
+    """The REPET_OUT_* code(s) of ``which``: one for "background" / "foreground" / "mixture", the pair for "both".
+    ValueError for anything else -- raised before any device is touched."""
+    if which == "both":
+        return (OUT_BACKGROUND, OUT_FOREGROUND)
+    if not isinstance(which, str) or which not in WHICH_CODES:
+        raise ValueError(f"which must be 'background', 'foreground', 'mixture' or 'both', not {which!r}")
+    return (WHICH_CODES[which],)
 
 
 class Params(C.Structure):
@@ -151,6 +165,12 @@ _SIGNATURES = {
     "repet_online_stream_emit_count": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "repet_online_finish_stream": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_finish_stream_device": (C.c_int, [_P, C.c_int32, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_online_set_output": (C.c_int, [_P, C.c_int]),
+    "repet_online_also_emit": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "repet_online_last_emission": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_last_emission_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_ctx_select_result": (C.c_int, [_P, C.c_int]),
+    "repet_select_run_result": (C.c_int, [C.c_int, C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -278,6 +298,23 @@ def result_tensor_code(out):
 
 def _strides(strides):
     return (C.c_int64 * 3)(*strides)
+
+
+def out_pair(out):
+    """``out=`` of a ``which="both"`` call: None, or a pair of tensors (background, foreground) that share no memory."""
+    if out is None:
+        return None, None
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError('which="both" takes out=(background, foreground), a pair of tensors')
+    a, b = out
+    if is_tensor(a) and is_tensor(b) and a.dtype != b.dtype:
+        raise ValueError("the two tensors of out have one dtype")
+    if is_device_tensor(a) and is_device_tensor(b) and a.numel() and b.numel():
+        span = lambda t: (t.data_ptr(), t.data_ptr() + (sum(st * (d - 1) for st, d in zip(t.stride(), t.shape)) + 1) * t.element_size())
+        (a0, a1), (b0, b1) = span(a), span(b)
+        if a0 < b1 and b0 < a1:
+            raise ValueError("the two tensors of out overlap (their address ranges must not intersect)")
+    return a, b
 
 
 def _stream_handle(stream):
@@ -409,12 +446,17 @@ class Context:
         self.shape = shape[1:] if x.dim() == 2 else shape
         return x
 
-    def download_tensor(self, out=None, stream=None):
+    def download_tensor(self, out=None, stream=None, which="background"):
         """The result of the last run into ``out`` (a float32 or float64 tensor of the resident shape, any non-negative
         strides whose elements do not overlap) or a fresh float64 tensor, written on the engine's stream behind what
         ``stream`` (default: the current stream of this context's device) has enqueued so far; ``stream`` then waits for it.
-        No host wait."""
+        No host wait. ``which``: "background", "foreground" (resident input - background, from the samples and, after a
+        float64 upload, their remainders) or "mixture"."""
         import torch
+        codes = which_codes(which)
+        if len(codes) != 1:
+            raise ValueError("download_tensor writes one signal (repet.separate pairs two calls for \"both\")")
+        code = codes[0]
         device = torch.device("cuda", self._device)
         if out is None:
             out = torch.empty(self.shape, dtype=torch.float64, device=device)
@@ -429,8 +471,13 @@ class Context:
             strides = (out.shape[0] * out.shape[1],) + strides
         if stream is None:
             stream = torch.cuda.current_stream(device)
-        check(lib().repet_ctx_download_device_strided(self._h, C.c_void_p(out.data_ptr() or None), result_tensor_code(out),
-                                                      _strides(strides), _stream_handle(stream)))
+        out_code = result_tensor_code(out)
+        check(lib().repet_ctx_select_result(self._h, code))
+        try:
+            check(lib().repet_ctx_download_device_strided(self._h, C.c_void_p(out.data_ptr() or None), out_code,
+                                                          _strides(strides), _stream_handle(stream)))
+        finally:
+            lib().repet_ctx_select_result(self._h, OUT_BACKGROUND)
         return out
 
     def torch_stream(self):
@@ -616,9 +663,18 @@ def default_context(device=0):
     return ctx
 
 
+def _select_output(handle, codes, second=None, dtype=F64, strides=None):
+    """What the next emitting call of a live handle delivers: codes[0] in its own destination and, for a pair, codes[1] in
+    ``second`` (a pointer) by the same launch."""
+    check(lib().repet_online_set_output(handle, codes[0]))
+    if len(codes) == 2:
+        check(lib().repet_online_also_emit(handle, codes[1], second, dtype, strides))
+
+
 class OnlineSeparator:
     """Streaming online REPET-SIM: ``push(chunk)`` returns the background samples that became final,
-    ``finish()`` the rest; the concatenation equals ``repet.simonline`` of the whole signal."""
+    ``finish()`` the rest; the concatenation equals ``repet.simonline`` of the whole signal. ``which`` ("background",
+    "foreground", "mixture", "both") selects the signal of those samples, see ``repet.online``."""
 
     def __init__(self, params, n_channels, device=0):
         self._h = C.c_void_p()
@@ -628,28 +684,34 @@ class OnlineSeparator:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open(int(device), self._channels, C.byref(params), C.byref(self._h)))
 
-    def push(self, audio_chunk):
+    def push(self, audio_chunk, which="background"):
+        codes = which_codes(which)
         n, c = np.shape(audio_chunk)
         if c != self._channels:
             raise ValueError("chunk has %d channels, the stream %d" % (c, self._channels))
         a, code = as_input(audio_chunk)
         cap = n + self._window
-        out = np.empty((cap, c), dtype=np.float64)
+        outs = [np.empty((cap, c), dtype=np.float64) for _ in codes]
         written = C.c_int64()
-        check(lib().repet_online_push(self._h, ptr(a), code, n, ptr(out), cap, C.byref(written)))
-        return out[:written.value].copy()
+        _select_output(self._h, codes, ptr(outs[-1]))
+        check(lib().repet_online_push(self._h, ptr(a), code, n, ptr(outs[0]), cap, C.byref(written)))
+        outs = [o[:written.value].copy() for o in outs]
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
-    def finish(self):
+    def finish(self, which="background"):
+        codes = which_codes(which)
         cap = 4 * self._window + 16
         while True:
-            out = np.empty((cap, self._channels), dtype=np.float64)
+            outs = [np.empty((cap, self._channels), dtype=np.float64) for _ in codes]
             written = C.c_int64()
-            rc = lib().repet_online_finish(self._h, ptr(out), cap, C.byref(written))
+            _select_output(self._h, codes, ptr(outs[-1]))
+            rc = lib().repet_online_finish(self._h, ptr(outs[0]), cap, C.byref(written))
             if rc == ERR_BAD_ARG and b"capacity" in lib().repet_last_error():
                 cap *= 4
                 continue
             check(rc)
-            return out[:written.value].copy()
+            outs = [o[:written.value].copy() for o in outs]
+            return outs[0] if len(outs) == 1 else tuple(outs)
 
     def close(self):
         if self._h:
@@ -672,7 +734,12 @@ class OnlineStreams:
     The S streams are S *slots*: ``restart(slots)`` begins a new stream in each named slot at the handle's current sample (a
     multiple of the hop), ``finish_stream(slot)`` ends one and returns its tail, ``release(slots)`` drops them without output.
     An idle slot ignores what the lockstep chunks carry for it and emits zeros. A slot's output from its restart on, followed
-    by its ``finish_stream`` (or ``finish``) tail, equals ``repet.simonline`` of the samples pushed into it in between."""
+    by its ``finish_stream`` (or ``finish``) tail, equals ``repet.simonline`` of the samples pushed into it in between.
+
+    ``which`` of ``push`` / ``finish`` / ``finish_stream`` selects the signal of the emitted samples: "background" (default),
+    "foreground" (input - background), "mixture" (the input, aligned with the emission) or "both": the pair (background,
+    foreground) from one pass, with ``out=`` a pair of tensors. ``last_emission(which)`` returns another signal of the samples
+    the last of these calls emitted."""
 
     def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0):
         self._h = C.c_void_p()
@@ -687,6 +754,7 @@ class OnlineStreams:
         check(lib().repet_online_open_streams(self._device, self._streams, self._channels, C.byref(params),
                                               int(max_push_samples or 0), C.byref(self._h)))
         self._pushed = 0                              # samples per slot pushed so far
+        self._emitted_shape = (self._streams, 0, self._channels)
         self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
 
     @property
@@ -713,10 +781,18 @@ class OnlineStreams:
         if shape[2] != self._channels:
             raise ValueError(f"chunk has {shape[2]} channels, the streams {self._channels}")
 
-    def _device_out(self, out, n_emit):
+    def _device_outs(self, out, n_emit, codes, shape=None):
+        """The destination tensor(s) of a device call: (tensors, dtype code, list of strides); a pair for "both"."""
+        outs = [out] if len(codes) == 1 else list(out_pair(out))
+        checked = [self._device_out(o, n_emit, shape) for o in outs]
+        if len({c[1] for c in checked}) != 1:
+            raise ValueError("the two tensors of out have one dtype")
+        return [c[0] for c in checked], checked[0][1], [c[2] for c in checked]
+
+    def _device_out(self, out, n_emit, shape=None):
         import torch
         device = torch.device("cuda", self._device)
-        shape = (self._streams, n_emit, self._channels)
+        shape = shape or (self._streams, n_emit, self._channels)
         if out is None:
             out = torch.empty(shape, dtype=torch.float64, device=device)
         else:
@@ -728,10 +804,12 @@ class OnlineStreams:
                 raise ValueError("out has negative strides")
         return out, result_tensor_code(out), tuple(int(st) for st in out.stride())
 
-    def push(self, chunk, out=None):
-        """Feed ``(S, n, C)`` more samples; returns the ``(S, n_emit, C)`` background samples that became final."""
+    def push(self, chunk, out=None, which="background"):
+        """Feed ``(S, n, C)`` more samples; returns the ``(S, n_emit, C)`` samples that became final: their background, or
+        the signal ``which`` names (a pair of arrays / tensors for "both")."""
+        codes = which_codes(which)
         if is_device_tensor(chunk):
-            return self._push_device(chunk, out)
+            return self._push_device(chunk, out, codes)
         if out is not None:
             raise ValueError("out is for device chunks (a host chunk returns a new array)")
         if is_tensor(chunk):
@@ -740,14 +818,40 @@ class OnlineStreams:
         self._check_shape(a.shape)
         n = a.shape[1]
         n_emit = self.emit_count(n)
-        result = np.empty((self._streams, n_emit, self._channels), dtype=np.float64)
+        results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
         written = C.c_int64()
-        check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(result), n_emit, C.byref(written)))
+        _select_output(self._handle(), codes, ptr(results[-1]))
+        check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(results[0]), n_emit, C.byref(written)))
         self._pushed += n
         self._last_on_device = False
+        self._emitted_shape = results[0].shape
+        return results[0] if len(results) == 1 else tuple(results)
+
+    def last_emission(self, which="foreground", out=None):
+        """Another signal ("background", "foreground", "mixture") of exactly the samples the last ``push`` / ``finish`` /
+        ``finish_stream`` emitted: a float64 array, or a tensor on the device (``out``, or a fresh float64 one) when ``out`` is
+        given or the last push was a device chunk. ValueError once a push, finish, restart or release has followed."""
+        codes = which_codes(which)
+        if len(codes) != 1:
+            raise ValueError("last_emission returns one signal")
+        n = C.c_int64()
+        # (a call without a destination only asks: its refusal tells a stale emission from one that needs room)
+        rc = lib().repet_online_last_emission(self._handle(), codes[0], None, 1 << 62, C.byref(n))
+        if rc != ERR_BAD_ARG or b"capacity" not in lib().repet_last_error():
+            check(rc)
+        shape = self._emitted_shape
+        if out is not None or self._last_on_device:
+            import torch
+            (out,), out_code, (strides,) = self._device_outs(out, shape[1], codes, shape)
+            stream = torch.cuda.current_stream(out.device)
+            check(lib().repet_online_last_emission_device(self._handle(), codes[0], C.c_void_p(out.data_ptr() or None), out_code,
+                                                          _strides(strides), _stream_handle(stream), C.byref(n)))
+            return out
+        result = np.empty(shape, dtype=np.float64)
+        check(lib().repet_online_last_emission(self._handle(), codes[0], ptr(result), shape[1], C.byref(n)))
         return result
 
-    def _push_device(self, x, out):
+    def _push_device(self, x, out, codes):
         import torch
         if x.device.index != self._device:
             raise ValueError(f"tensor is on {x.device}, the streams on device {self._device}")
@@ -756,12 +860,15 @@ class OnlineStreams:
         self._check_shape(tuple(x.shape))
         x, code, shape, strides = tensor_layout(x, batched=True)
         n = shape[1]
-        out, out_code, out_strides = self._device_out(out, self.emit_count(n))
+        outs, out_code, out_strides = self._device_outs(out, self.emit_count(n), codes)
+        out = outs[0] if len(outs) == 1 else tuple(outs)
         stream = torch.cuda.current_stream(x.device)
         written = C.c_int64()
+        _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
         check(lib().repet_online_push_device(self._handle(), C.c_void_p(x.data_ptr() or None), code, n, _strides(strides),
-                                             _stream_handle(stream), C.c_void_p(out.data_ptr() or None), out_code,
-                                             _strides(out_strides), _stream_handle(stream), C.byref(written)))
+                                             _stream_handle(stream), C.c_void_p(outs[0].data_ptr() or None), out_code,
+                                             _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
+        self._emitted_shape = tuple(outs[0].shape)
         # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
         # recorded on it, the caching allocator hands its block out again only once the ingest has read it
         x.record_stream(stream)
@@ -810,55 +917,54 @@ class OnlineStreams:
         check(lib().repet_online_stream_emit_count(self._handle(), self._slot(slot), C.byref(n)))
         return n.value
 
-    def finish_stream(self, slot, out=None):
+    def finish_stream(self, slot, out=None, which="background"):
         """End the stream of one slot where the handle stands: its ``(n_rest, C)`` tail, as ``finish`` returns for all (a
-        tensor on the device when ``out`` is given or the last push was a device chunk). The other slots and the handle's
-        counters are untouched and the slot is idle afterwards. ValueError for an idle slot, or for a stream shorter than the
-        buffer (the slot then stays as it was)."""
+        tensor on the device when ``out`` is given or the last push was a device chunk; the signal ``which`` names, a pair
+        for "both"). The other slots and the handle's counters are untouched and the slot is idle afterwards. ValueError for
+        an idle slot, or for a stream shorter than the buffer (the slot then stays as it was)."""
+        codes = which_codes(which)
         slot = self._slot(slot)
         n_emit = self.stream_emit_count(slot)
         written = C.c_int64()
+        shape = (n_emit, self._channels)
         if out is not None or self._last_on_device:
             import torch
-            device = torch.device("cuda", self._device)
-            shape = (n_emit, self._channels)
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float64, device=device)
-            elif not is_device_tensor(out) or out.device != device:
-                raise ValueError(f"out must be a tensor on {device}")
-            elif tuple(out.shape) != shape:
-                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
-            elif any(st < 0 for st in out.stride()):
-                raise ValueError("out has negative strides")
-            stream = torch.cuda.current_stream(device)
-            strides = (C.c_int64 * 2)(*(int(st) for st in out.stride()))
-            check(lib().repet_online_finish_stream_device(self._handle(), slot, C.c_void_p(out.data_ptr() or None),
-                                                          result_tensor_code(out), strides, _stream_handle(stream),
+            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, shape)
+            stream = torch.cuda.current_stream(outs[0].device)
+            _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides((0,) + out_strides[-1]))
+            check(lib().repet_online_finish_stream_device(self._handle(), slot, C.c_void_p(outs[0].data_ptr() or None),
+                                                          out_code, (C.c_int64 * 2)(*out_strides[0]), _stream_handle(stream),
                                                           C.byref(written)))
             self._begun[slot] = None
-            return out
-        result = np.empty((n_emit, self._channels), dtype=np.float64)
-        check(lib().repet_online_finish_stream(self._handle(), slot, ptr(result), n_emit, C.byref(written)))
+            return outs[0] if len(outs) == 1 else tuple(outs)
+        results = [np.empty(shape, dtype=np.float64) for _ in codes]
+        _select_output(self._handle(), codes, ptr(results[-1]))
+        check(lib().repet_online_finish_stream(self._handle(), slot, ptr(results[0]), n_emit, C.byref(written)))
         self._begun[slot] = None
-        return result
+        return results[0] if len(results) == 1 else tuple(results)
 
-    def finish(self, out=None):
+    def finish(self, out=None, which="background"):
         """End every stream: the remaining samples, ``(S, n_rest, C)`` -- a float64 tensor on the device when ``out`` is given
-        or the last push was a device chunk, a NumPy array otherwise. ValueError if the handle has seen fewer samples than the
-        buffer holds. Every live slot ends with its own length; idle slots return zeros."""
+        or the last push was a device chunk, a NumPy array otherwise; the signal ``which`` names, a pair for "both". ValueError
+        if the handle has seen fewer samples than the buffer holds. Every live slot ends with its own length; idle slots
+        return zeros."""
+        codes = which_codes(which)
         n_emit = self.emit_count(0, finishing=True)
+        written = C.c_int64()
         if out is not None or self._last_on_device:
             import torch
-            out, out_code, out_strides = self._device_out(out, n_emit)
-            stream = torch.cuda.current_stream(out.device)
-            written = C.c_int64()
-            check(lib().repet_online_finish_device(self._handle(), C.c_void_p(out.data_ptr() or None), out_code,
-                                                   _strides(out_strides), _stream_handle(stream), C.byref(written)))
-            return out
-        result = np.empty((self._streams, n_emit, self._channels), dtype=np.float64)
-        written = C.c_int64()
-        check(lib().repet_online_finish_streams(self._handle(), ptr(result), n_emit, C.byref(written)))
-        return result
+            outs, out_code, out_strides = self._device_outs(out, n_emit, codes)
+            stream = torch.cuda.current_stream(outs[0].device)
+            _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
+            check(lib().repet_online_finish_device(self._handle(), C.c_void_p(outs[0].data_ptr() or None), out_code,
+                                                   _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
+            self._emitted_shape = tuple(outs[0].shape)
+            return outs[0] if len(outs) == 1 else tuple(outs)
+        results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
+        _select_output(self._handle(), codes, ptr(results[-1]))
+        check(lib().repet_online_finish_streams(self._handle(), ptr(results[0]), n_emit, C.byref(written)))
+        self._emitted_shape = results[0].shape
+        return results[0] if len(results) == 1 else tuple(results)
 
     def close(self):
         if self._h:

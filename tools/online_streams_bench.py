@@ -7,7 +7,10 @@ is active. Prints one JSON document (median and p95 in ms per push, and the audi
 K-th push one slot's stream is ended with ``finish_stream`` and a new one begun in it with ``restart`` (round robin over
 the slots). Reported: the latency of the pushes without a lifecycle call, of ``restart`` and of ``finish_stream`` (each
 call plus a synchronize), beside the same schedule on S separate ``repet.online`` handles, the only other way to end one
-stream and keep the rest: every hop is S pushes, a departure is one handle's ``finish`` and a new ``repet.online``."""
+stream and keep the rest: every hop is S pushes, a departure is one handle's ``finish`` and a new ``repet.online``.
+
+``--which background,foreground,both``: the one-handle device-chunk cases once per selection, one after another in the same
+session (``one_handle_device_chunks`` is the background's; the others carry their name)."""
 import argparse
 import json
 import sys
@@ -32,7 +35,7 @@ def stats(lat_s, n, fs):
             "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
 
 
-def one_handle(xs, fs, hops, device, timed, warm_s):
+def one_handle(xs, fs, hops, device, timed, warm_s, which="background"):
     import torch
     S, N, ch = xs.shape
     hop = repet.derive_params(fs).step_length
@@ -43,10 +46,10 @@ def one_handle(xs, fs, hops, device, timed, warm_s):
     h = repet.online_streams(fs, ch, S, max_push_samples=n)
     pos = 0
     while pos < warm_s * fs:                                   # fill the buffer in half-second pushes
-        h.push(src[:, pos:pos + fs // 2])
+        h.push(src[:, pos:pos + fs // 2], which=which)
         pos += fs // 2
     for _ in range(3):                                         # the per-push workspaces take their size
-        h.push(src[:, pos:pos + n])
+        h.push(src[:, pos:pos + n], which=which)
         pos += n
     torch.cuda.synchronize()
     held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
@@ -55,7 +58,7 @@ def one_handle(xs, fs, hops, device, timed, warm_s):
         if pos + n > N:
             break
         t0 = time.perf_counter()
-        h.push(src[:, pos:pos + n])
+        h.push(src[:, pos:pos + n], which=which)
         if device:
             torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
@@ -184,6 +187,8 @@ def main():
     ap.add_argument("--churn", type=int, default=0, metavar="K",
                     help="the churn leg: one finish_stream and one restart on every K-th push of one hop")
     ap.add_argument("--churn-separate", type=int, default=1, help="0: skip the separate-handles side of the churn leg")
+    ap.add_argument("--which", default="background",
+                    help="comma list of background / foreground / mixture / both: what the one-handle device pushes deliver")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
@@ -206,14 +211,17 @@ def main():
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
             case = {"streams": S, "hops_per_push": hops}
-            case["one_handle_device_chunks"] = one_handle(xs, fs, hops, True, args.timed, warm_s)
+            for which in args.which.split(","):
+                key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
+                case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s)
                 if S <= args.separate_max:
                     case["separate_handles_host"] = separate_handles(xs, fs, hops, args.timed, warm_s)
             result["cases"].append(case)
             print(json.dumps(case), file=sys.stderr, flush=True)
-    one = {(c["streams"], c["hops_per_push"]): c["one_handle_device_chunks"]["latency_ms_median"] for c in result["cases"]}
+    one = {(c["streams"], c["hops_per_push"]): c["one_handle_device_chunks"]["latency_ms_median"] for c in result["cases"]
+           if "one_handle_device_chunks" in c}
     result["device_push_ratio_to_S1"] = {f"S{S}_{h}hop": round(one[(S, h)] / one[(1, h)], 2)
                                          for (S, h) in one if (1, h) in one}
     print(json.dumps(result, indent=1))
