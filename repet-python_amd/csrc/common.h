@@ -282,12 +282,7 @@ struct PeakRefine {
     // queue of frames whose float64 unit rows are needed (frame = clip * frame_clip_stride + frame row)
     unsigned char* records; int32_t record_bytes; int32_t* lite_list; unsigned int* lite_flag;
     int32_t* frame_list; unsigned int* frame_flag; int64_t frame_clip_stride;
-    // (nullable) float64 norms of the fp32 unit rows, one per row of unit_rows (launch_unit_row_norms): with them the first
-    // pass's float64 similarities are one dot product per item instead of two and a square root
-    const double* unit_norms;
 };
-// float64 L2 norm of every fp32 row: norms[r] = sqrt(sum_k rows[r * pitch + k]^2), n_rows rows of `pitch` floats (pitch % 4 == 0)
-hipError_t launch_unit_row_norms(const float* rows, int64_t n_rows, int32_t pitch, double* norms, hipStream_t s);
 // batch (nullable): blockIdx.y = clip of a batch of equal-shape matrices; element strides between the clips
 // origin (nullable; modes 1 and 2, the streaming handle's slots): frame number at which clip b's own stream began. The clip's rows
 // are numbered from there (row0 and shift both count from origin[b]: circular positions are those of the clip's own frames,
@@ -383,11 +378,9 @@ hipError_t launch_fill_pad_rows(float* V, int64_t chan_stride, int32_t n_channel
                                 hipStream_t s, float* Z = nullptr, int64_t z_stride = 0, int64_t z_count = 0, int32_t n_z = 0,
                                 unsigned int* stats = nullptr, float* Z2 = nullptr);
 // max_count / min_period bound the list length so the launcher can pick the smallest compiled network.
-// side/fork/join (nullable): second stream and two events to run the Nyquist-bin kernel beside the main one.
 // parts: 1 = main kernel only, 2 = Nyquist-bin kernel only, 3 = both (chunked pipelines launch them separately).
 hipError_t launch_mask_sim(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count,
-                           int64_t first_frame, int32_t max_count, hipStream_t s, hipStream_t side = nullptr,
-                           hipEvent_t fork = nullptr, hipEvent_t join = nullptr, int parts = 3, bool lookups_by_caller = false);
+                           int64_t first_frame, int32_t max_count, hipStream_t s, int parts = 3, bool lookups_by_caller = false);
 int median_network_instructions(int max_n, int* net_size);
 // bit-sliced selection (mask_bits.hip): lists of at most 128 entries, at most 32 blocks of 64 ranked bins over all channels
 int code_planes_for(int64_t T);                       // planes of the codes of a T-frame clip (bits of T - 1, at least 11)
@@ -414,9 +407,6 @@ struct RankArgs {
     float* Vs; int64_t vs_pitch;          // Vs[c * n_cols + f][vs_pitch], vs_pitch = round_up(T, 32)
     unsigned short* codes;                // scratch: the codes column-major, [c * n_cols + f][vs_pitch]
     unsigned* P; int32_t n_planes;        // the codes bit-sliced INSTEAD of R (exactly one of R and P is set): MaskArgs::P
-    // phases of the chain a launch_rank_columns call runs: bit 0 the transpose V -> columns, bit 1 the sort and what follows
-    // (0 = both). The transpose needs V only and may run early (exec_sim, REPET_RANK_TRANSPOSE=early).
-    int32_t phases;
 };
 bool rank_columns_supported(int64_t T);
 // CPUs of the NUMA node device `dev` hangs off that this process may run on (hostio.hip; empty: unknown or nothing to choose)

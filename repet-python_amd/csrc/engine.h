@@ -83,7 +83,6 @@ struct repet_ctx {
     hipStream_t copy_stream = nullptr;   // the remainder plane of a float64 upload follows the samples here (created on first use)
     std::vector<hipStream_t> ballast_streams;   // candidates that shared the main stream's hardware queue (pick_side_stream)
     hipEvent_t fork_event = nullptr, join_event = nullptr;
-    hipEvent_t norms_fork = nullptr, norms_done = nullptr;      // exec_sim: the unit rows' float64 norms on the side stream beside the Gram kernel
     // resident clip
     DevBuf staging, audio, out, out64;
     StagingRing ring;             // pinned chunks the waveforms travel through (hostio.hip)
@@ -132,7 +131,6 @@ struct repet_ctx {
     // handed over, the table of float64 unit rows with its generation stamps, the row workspaces of the fixed grid
     DevBuf audio_lo; bool has_lo = false;
     DevBuf redo_list, redo_flag, u64, u64_gen, exact_scratch;
-    DevBuf unit_norms;            // float64 norms of the fp32 unit rows (PeakRefine::unit_norms)
     DevBuf lite_list, lite_flag, lite_records, frame_list, frame_flag;   // the wavefront kernel's fast path (peaks_wave.hip)
     unsigned int exact_gen = 0;
     bool refine_stats_cleared = false;   // ensure_spectra's housekeeping launch has zeroed them for the run being enqueued
@@ -212,7 +210,7 @@ int run_exact_rows(repet_ctx* c, const Tables* tb, const Geo& g, const float* M,
                    const PeakRefine& rf, const PeakBatch* batch, const float* hi, const float* lo, int64_t n_samples,
                    int64_t clip_stride, int64_t frame_sample0, int64_t n_frames, int clips);
 bool rank_median_enabled();
-int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count, int phases = 0);
+int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count);
 int exec_sim(repet_ctx* c, const repet_params* p);
 int exec_simonline(repet_ctx* c, const repet_params* p);
 int prepare_power_planes(repet_ctx* c, const Geo& g, int64_t T, int B);
@@ -257,7 +255,6 @@ MaskArgs mask_args(repet_ctx* c, const Geo& g, int cutoff);
 void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr);
 int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
               bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr = nullptr);
-bool split_in_stft(int B);
 // device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events
 int check_strides(const int64_t* strides);
 int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch);

@@ -229,8 +229,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         m.idx_batch_stride = std::max<int64_t>(n_active, 0) * KP; m.cnt_batch_stride = std::max<int64_t>(n_active, 0);
         const int64_t first_frame = Tw - std::max<int64_t>(n_active, 0);          // warm-up rows before it are zeroed
         const int max_peaks = (int)std::min<int64_t>(K, ceil_div(o->B, o->p.sim_distance_frames + 1));
-        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_frame, max_peaks, c->stream,
-                                c->side_stream, c->fork_event, c->join_event));
+        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_frame, max_peaks, c->stream));
     }
     if (n_emit > 0) {
         HIP_TRY(o->outf.ensure((size_t)S * n_emit * o->C * sizeof(float)));

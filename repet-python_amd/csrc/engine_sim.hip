@@ -120,7 +120,7 @@ static bool bits_median_enabled() {
 }
 
 // Sort every column of V and fill m's rank fields (bins [0, F-1); the lone Nyquist bin stays on the float kernel).
-int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count, int phases) {
+int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count) {
     const int n_cols = g.F - 1;
     const int64_t vs_pitch = round_up(g.T, 32);
     // (the bit-sliced selection reads the code planes only: no frame-major codes R then)
@@ -137,7 +137,6 @@ int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream
     a.V = c->V.as<float>(); a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.n_cols = n_cols;
     a.R = bits ? nullptr : c->R.as<unsigned short>(); a.r_chan_stride = g.chan_stride; a.Vs = c->Vs.as<float>(); a.vs_pitch = vs_pitch;
     a.codes = c->rank_codes.as<unsigned short>();
-    a.phases = phases;
     if (bits) {
         a.n_planes = code_planes_for(g.T);
         HIP_TRY(c->code_planes.ensure((size_t)g.T * a.n_planes * 64 * sizeof(unsigned)));
@@ -168,16 +167,17 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
     const int64_t T = repet_frame_count(N, p->window_length, p->step_length, 1);
     const Geo g = make_geo(p->window_length, p->step_length, T, c->n_channels);
     if (p->sim_number < 1) return fail(REPET_ERR_BAD_ARG, "similarity_number must be >= 1");
-    // (the same test as below: the median on rank codes multiplies X in place, the float path keeps the mask apart)
-    const bool ranks_ahead = rank_median_enabled() && g.F > 128 && ((g.F - 1) & 127) == 0 && rank_columns_supported(T) &&
-                             std::min<int64_t>(p->sim_number, ceil_div(T, p->sim_distance_frames + 1)) >= kRankMinList &&
-                             std::min<int64_t>(p->sim_number, ceil_div(T, p->sim_distance_frames + 1)) <= 128;
+    // peaks are more than d frames apart: at most ceil(T/(d+1)) of them, whatever similarity_number says
+    const int max_peaks = (int)std::min<int64_t>(p->sim_number, ceil_div(T, p->sim_distance_frames + 1));
+    // the median on rank codes (it multiplies X in place or leaves a plane; the float path keeps the mask apart)
+    const bool use_rank = rank_median_enabled() && g.F > 128 && ((g.F - 1) & 127) == 0 && rank_columns_supported(T) &&
+                          max_peaks >= kRankMinList && max_peaks <= 128;
     // Round 6: with the median on rank codes too the mask leaves the lookup kernel as a PLANE when the register inverse STFT will
     // apply it (W = 2048, mono / stereo). Rounds 3-5 masked X in place there (0.50 + 0.072 -> 0.50 + 0.091 ms with the kernels of
     // round 3); with the lookups a kernel of their own and the inverse merging in pairs the plane wins: lookups 0.1045 -> 0.0855,
     // inverse 0.0533 -> 0.0661, step 0.840 -> 0.829 ms (profiles/r06_mask_plane_ab.txt). REPET_MASK_PLANE=0 / p force either.
-    const bool plane_for_ranks = ranks_ahead && mask_plane_forced() < 0 && reg_fft_supported(g.W, g.C, true);
-    MaskPlaneScope plane(c, plane_for_ranks || mask_plane_wanted(ranks_ahead ? MaskKind::sim_ranks : MaskKind::sim_float));
+    const bool plane_for_ranks = use_rank && mask_plane_forced() < 0 && reg_fft_supported(g.W, g.C, true);
+    MaskPlaneScope plane(c, plane_for_ranks || mask_plane_wanted(use_rank ? MaskKind::sim_ranks : MaskKind::sim_float));
     RP_TRY(ensure_spectra(c, g, true, false));
     RP_TRY(run_stft(c, g, tb, 0, N, 1, true, false));
     const int64_t TS = round_up(T, 64);
@@ -188,37 +188,7 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
     if (with_seg) HIP_TRY(c->seg.ensure((size_t)T * 3 * seg_pitch * sizeof(float)));
     float* seg = with_seg ? c->seg.as<float>() : nullptr;
     bool seg_written = false;
-    // Experiment of round 6 (REPET_RANK_TRANSPOSE=early; measured: stage -12 us, step +13 us, profiles/r06_transpose_early_ab.txt -- off):
-    // the transpose that opens the column sort needs V only -- in line IN FRONT OF
-    // the Gram kernel (26 us alone) instead of squeezed in beside the first pass of the peak picking (55 us there), so that the sort
-    // itself is what the side stream starts with.
-    static const bool early_transpose = [] { const char* e = getenv("REPET_RANK_TRANSPOSE"); return e && e[0] == 'e'; }();
-    const int early_peaks = (int)std::min<int64_t>(p->sim_number, ceil_div(T, p->sim_distance_frames + 1));
-    const bool transposed_early = early_transpose && ranks_ahead;
-    if (transposed_early) {
-        MaskArgs m0 = mask_args(c, g, p->cutoff_bins);
-        RP_TRY(run_rank_columns(c, g, &m0, c->stream, false, early_peaks, 1));
-        mark(c, "columns_from_rows", (4.0 + 4.0) * (g.F - 1) * (double)g.T * g.C, 0);
-    }
-    // The float64 norms of the unit rows (the first pass's float64 similarities divide by them: peaks.h) need the unit rows only:
-    // they are computed on the side stream BESIDE the Gram kernel -- enqueued behind its launch, so the Gram's workgroups take the
-    // CUs first and the 1 939 small workgroups of this kernel run where its second round leaves CUs idle (496 tiles on 256 CUs).
-    // Measured (profiles/r06_peak_norms_ab.txt): the first pass is NOT faster with the table (98.6 -> 100.5 us: its span is the late
-    // start of its slow rows plus their sweep, not the arithmetic of their similarities), and the two events that tie the side
-    // stream's kernel in cost the Gram stage 13 us and the peak stage 12: 0.854 -> 0.881 ms per step. Off by default;
-    // REPET_PEAK_NORMS=1 turns it on (A/B).
-    static const bool use_norms = [] { const char* e = getenv("REPET_PEAK_NORMS"); return e && e[0] == '1'; }();
-    const bool norms_beside = use_norms && c->side_stream && peak_refine_delta(g.FS, gram_f16_enabled()) > 0.0f && (g.FS & 3) == 0 && g.FS <= 1280;
-    if (norms_beside) {
-        HIP_TRY(c->unit_norms.ensure((size_t)g.Tpad * sizeof(double)));
-        HIP_TRY(hipEventRecord(c->norms_fork, c->stream));               // the unit rows are there
-    }
     RP_TRY(run_gram_full(c, c->Vn.as<float>(), T, g.FS, c->S.as<float>(), TS, true, split_in_stft(1), seg, seg_pitch, &seg_written));
-    if (norms_beside) {
-        HIP_TRY(hipStreamWaitEvent(c->side_stream, c->norms_fork, 0));
-        HIP_TRY(launch_unit_row_norms(c->Vn.as<float>(), T, g.FS, c->unit_norms.as<double>(), c->side_stream));
-        HIP_TRY(hipEventRecord(c->norms_done, c->side_stream));
-    }
     {
         // flops as EXECUTED: upper-triangle 128 x 128 tiles over the padded K = FS, three f16 products per term on the
         // split kernel (hi hi' + hi lo' + lo hi'); bench.py prices them against the f16 (or fp32) matrix peak and
@@ -236,18 +206,10 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
     const int K = p->sim_number, KP = std::max(K, kMinIdxPitch);
     HIP_TRY(c->idx.ensure((size_t)T * KP * sizeof(int32_t)));
     HIP_TRY(c->cnt.ensure((size_t)T * sizeof(int32_t)));
-    // peaks are more than d frames apart: at most ceil(T/(d+1)) of them, whatever similarity_number says
-    const int max_peaks = (int)std::min<int64_t>(K, ceil_div(T, p->sim_distance_frames + 1));
     PeakRefine rf{};
     RP_TRY(make_refine(c, c->Vn.as<float>(), g.FS, p->sim_threshold, &rf, T, 1, (int)T, p->sim_distance_frames, T));
-    if (norms_beside) {
-        rf.unit_norms = c->unit_norms.as<double>();
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->norms_done, 0));
-    }
     {
         MaskArgs m = mask_args(c, g, p->cutoff_bins);
-        const bool use_rank = rank_median_enabled() && g.F > 128 && ((g.F - 1) & 127) == 0 && rank_columns_supported(T) &&
-                              max_peaks >= kRankMinList && max_peaks <= 128;
         // The column sort needs nothing of the similarity matrix: it runs on the side stream BESIDE the peak picking, whose
         // rows take 30 .. 140 us each -- the second half of that launch is a tail of fewer and fewer waves (spans of every
         // row: tools/peak_stamps.py), which the sort's workgroups fill. (Beside the Gram kernel it does not pay: a sort
@@ -259,15 +221,12 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
         static const bool overlap = [] { const char* e = getenv("REPET_RANK_OVERLAP"); return !(e && e[0] == '0'); }();
         const bool beside = use_rank && overlap;
         // (Measured and dropped: starting the sort behind the first pass of the peak picking, beside its second level --
-        // peaks + sort 0.446 against 0.419 ms: the second level's kernels hold a whole register file per wave and do not share
-        // a CU with the sort any better than the first pass does.)
-        // (Measured and dropped: starting the sort behind the first pass of the peak picking, beside its second level --
         // peaks + sort 0.416 against 0.373 ms: the sort fills the first pass's tail better than it shares the GPU with the
         // one-wave-per-SIMD kernels of the second level.)
         if (beside) {
             HIP_TRY(hipEventRecord(c->fork_event, c->stream));          // V is complete (so is S)
             HIP_TRY(hipStreamWaitEvent(c->side_stream, c->fork_event, 0));
-            RP_TRY(run_rank_columns(c, g, &m, c->side_stream, false, max_peaks, transposed_early ? 2 : 0));
+            RP_TRY(run_rank_columns(c, g, &m, c->side_stream, false, max_peaks));
             HIP_TRY(hipEventRecord(c->join_event, c->side_stream));
         }
         const size_t scratch = local_maxima_scratch_bytes(T, (int)T, p->sim_distance_frames);
@@ -292,10 +251,9 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
             mark(c, "peaks+rank_columns", 4.0 * T * T + 4.0 * K * T + (4.0 + 4.0 + 8.0 + 4.0 + 2.0 + 2.0 + 2.0) * (g.F - 1) * (double)g.T * g.C, 0);
         } else {
             mark(c, use_rank ? "local_maxima_level2" : "local_maxima", use_rank ? 0.0 : 4.0 * T * T + 4.0 * K * T, 0);
-            if (use_rank) RP_TRY(run_rank_columns(c, g, &m, c->stream, true, max_peaks, transposed_early ? 2 : 0));
+            if (use_rank) RP_TRY(run_rank_columns(c, g, &m, c->stream, true, max_peaks));
         }
-        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), 0, max_peaks, c->stream, c->side_stream,
-                                c->fork_event, c->join_event, 3, m.P != nullptr));
+        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), 0, max_peaks, c->stream, 3, m.P != nullptr));
         c->last_median_path = m.P ? 2 : m.R ? 1 : 0;
         c->last_FS = g.FS; c->last_chan_stride = g.chan_stride;
         if (m.P) {
@@ -364,8 +322,7 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     }
     MaskArgs m = mask_args(c, g, p->cutoff_bins);
     m.n_batch = nb; m.batch_stride = spec_stride; m.idx_batch_stride = rows_alloc * KP; m.cnt_batch_stride = rows_alloc;
-    HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), B - 1, max_peaks, c->stream, c->side_stream,
-                            c->fork_event, c->join_event));
+    HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), B - 1, max_peaks, c->stream));
     mark(c, "mask_sim", nb * (4.0 + 4.0 * K + (c->mask_plane ? 4.0 : 16.0)) * g.F * (double)rows * g.C, 0);
     if (nb == 1) {
         RP_TRY(run_istft(c, g, tb, 0, N, 0, false, 0, 0));

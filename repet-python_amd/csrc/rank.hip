@@ -81,69 +81,6 @@ struct HighTrips {
     }
 };
 
-// Round 6: trips of up to FIVE stages. The trip above takes its 32 keys as 8 x 4 (three stage bits and the two lowest index
-// bits, so that every access is 16 bytes): three stages per trip through LDS, 23 trips for 2^13 keys. A thread may as well hold
-// 16 x 2 (four stage bits, 8-byte accesses) or 32 x 1 (five stage bits, 4-byte accesses): the LDS moves the same bytes per
-// trip whatever the access width, and the merge phases 9 .. 13 then need one trip less each (19 trips). Built, validated
-// (the index algebra of both forms in NumPy for 2^11 .. 2^15 keys, the rank tests on the GPU) and measured: no faster (see
-// launch_rank_n) -- kept behind REPET_RANK_TRIPS=5.
-// NB = stage bits of the trip (3, 4, 5), VW = 32 >> NB consecutive keys per access.
-template <int LOG2N, int P, int QHI, int QLO, int NB, bool FLIP>
-__device__ __forceinline__ void trip_high_n(unsigned* s, int tid) {
-    constexpr int VW = 32 >> NB, LV = NB == 3 ? 2 : (NB == 4 ? 1 : 0), NU = 1 << NB;
-    constexpr int HB = QLO < LOG2N - NB ? QLO : LOG2N - NB;      // the thread's NB high bits are [HB, HB + NB)
-    static_assert(NB >= 3 && NB <= 5 && HB >= 5 && QHI < HB + NB && QLO >= HB, "stage bits must lie inside the thread's bit group");
-    const int low = tid & ((1 << (HB - LV)) - 1), high = tid >> (HB - LV);
-    const int base = (low << LV) | (high << (HB + NB));
-    unsigned r[NU][VW];
-    __syncthreads();                                           // the previous trip's stores
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const int i0 = base | (u << HB);
-        const bool mirrored = FLIP && ((u >> (P - 1 - HB)) & 1);   // upper half of a 2^P block: read mirrored below bit P - 1
-        const int src = mirrored ? ((i0 ^ ((1 << (P - 1)) - 1)) & ~(VW - 1)) : i0;
-        if constexpr (VW == 4) {
-            const uint4 v = *reinterpret_cast<const uint4*>(s + phys(src));
-            if (mirrored) { r[u][0] = v.w; r[u][1] = v.z; r[u][2] = v.y; r[u][3] = v.x; }
-            else { r[u][0] = v.x; r[u][1] = v.y; r[u][2] = v.z; r[u][3] = v.w; }
-        } else if constexpr (VW == 2) {
-            const uint2 v = *reinterpret_cast<const uint2*>(s + phys(src));
-            if (mirrored) { r[u][0] = v.y; r[u][1] = v.x; } else { r[u][0] = v.x; r[u][1] = v.y; }
-        } else r[u][0] = s[phys(src)];
-    }
-    if (FLIP) __syncthreads();                                 // mirrored reads touch other threads' keys: all read first
-#pragma unroll
-    for (int q = QHI; q >= QLO; --q) {
-        const int bit = 1 << (q - HB);
-#pragma unroll
-        for (int u = 0; u < NU; ++u)
-            if (!(u & bit)) {
-#pragma unroll
-                for (int w = 0; w < VW; ++w) cex(r[u][w], r[u | bit][w]);
-            }
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        unsigned* dst = s + phys(base | (u << HB));
-        if constexpr (VW == 4) *reinterpret_cast<uint4*>(dst) = make_uint4(r[u][0], r[u][1], r[u][2], r[u][3]);
-        else if constexpr (VW == 2) *reinterpret_cast<uint2*>(dst) = make_uint2(r[u][0], r[u][1]);
-        else dst[0] = r[u][0];
-    }
-}
-// how many of the n high stages (n >= 1) the next trip takes: all of them up to five, else about half (6: 3 + 3, 7: 4 + 3, 8: 4 + 4, 9: 5 + 4, 10: 5 + 5)
-constexpr int wide_trip_stages(int n) { return n <= 5 ? n : ((n + 1) / 2 > 5 ? 5 : (n + 1) / 2); }
-template <int LOG2N, int P, int QHI>
-struct WideTrips {
-    static __device__ __forceinline__ void run(unsigned* s, int tid) {
-        constexpr int n = QHI - 4;                             // stages QHI .. 5
-        constexpr int take = wide_trip_stages(n);
-        constexpr int QLO = QHI - take + 1;
-        constexpr int NB = take <= 3 ? 3 : take;
-        trip_high_n<LOG2N, P, QHI, QLO, NB, QHI == P - 1>(s, tid);
-        if constexpr (QLO > 5) WideTrips<LOG2N, P, QLO - 1>::run(s, tid);
-    }
-};
-
 // stages 4..0 on 32 contiguous keys in registers
 __device__ __forceinline__ void stages_low(unsigned (&k)[32]) {
 #pragma unroll
@@ -167,16 +104,15 @@ __device__ __forceinline__ void store_run(unsigned* s, int tid, const unsigned (
         *reinterpret_cast<uint4*>(s + phys(tid * 32 + v * 4)) = make_uint4(k[4 * v], k[4 * v + 1], k[4 * v + 2], k[4 * v + 3]);
 }
 
-template <int LOG2N, int P, bool WIDE>
+template <int LOG2N, int P>
 struct Phases {
     static __device__ __forceinline__ void run(unsigned* s, int tid, unsigned (&k)[32]) {
-        if constexpr (WIDE) WideTrips<LOG2N, P, P - 1>::run(s, tid);
-        else HighTrips<LOG2N, P, P - 1>::run(s, tid);
+        HighTrips<LOG2N, P, P - 1>::run(s, tid);
         __syncthreads();
         load_run(s, tid, k);
         stages_low(k);
         store_run(s, tid, k);
-        if constexpr (P < LOG2N) Phases<LOG2N, P + 1, WIDE>::run(s, tid, k);
+        if constexpr (P < LOG2N) Phases<LOG2N, P + 1>::run(s, tid, k);
     }
 };
 
@@ -184,12 +120,12 @@ struct Phases {
 
 // Tiled transposes either side of the column sort: the spectrogram is frame-major (a column is one float every FS),
 // the sort wants whole columns. in[c][t][FS] -> out[c * n_cols + f][pitch] (fp32, 64 x 64 tiles through LDS).
-// TF = frames per tile. 64 (the round-4 form): 16.6 KB of LDS per workgroup, eight workgroups per CU hold 133 KB. 32 (round 6):
-// half of that for the same 256 threads -- the stage this kernel opens is bound by the chip's LDS, and its
+// kColumnTileFrames = frames per tile: 32, 8.3 KB of LDS per workgroup for 256 threads (the 64-frame tiles of round 4 held 16.6 KB: measured
+// and dropped, profiles/HISTORY.md) -- the stage this kernel opens is bound by the chip's LDS, and its
 // workgroups have to find room beside the first pass of the peak picking. A column's 32 frames still leave as one 128-byte line.
-template <int TF>
+constexpr int kColumnTileFrames = 32;
 __global__ __launch_bounds__(256) void columns_from_rows_kernel(RankArgs a) {
-    static_assert(TF == 64 || TF == 32, "tile height");
+    constexpr int TF = kColumnTileFrames;
     constexpr int kRounds = TF / 16;                              // frame rows per thread on the way in
     constexpr int kOutLanes = TF / 4;                             // lanes that cover a column's frames on the way out
     constexpr int kOutRounds = 64 * kOutLanes / 256;              // columns per thread on the way out
@@ -216,7 +152,7 @@ __global__ __launch_bounds__(256) void columns_from_rows_kernel(RankArgs a) {
     float* out = a.Vs + ((int64_t)c * a.n_cols + f0) * a.vs_pitch;
     // thread -> (4 frames ox, column): a wave's reads of the tile must fall on 64 different banks (row pitch 65: bank = 4 ox + column)
     const int ox = threadIdx.x % kOutLanes, oy = threadIdx.x / kOutLanes;
-    const int col0 = TF == 64 ? oy : (oy & 3) + 32 * ((oy >> 2) & 1) + 4 * (threadIdx.x >> 6);
+    const int col0 = (oy & 3) + 32 * ((oy >> 2) & 1) + 4 * (threadIdx.x >> 6);
     if (t0 + 4 * ox < a.vs_pitch) {
 #pragma unroll
         for (int k = 0; k < kOutRounds; ++k) {
@@ -276,13 +212,13 @@ __device__ __forceinline__ void plane_transpose_stage(unsigned (&x)[16]) {
 // values of l -- 1 024 columns, 128 bytes of each, through LDS (column pitch 66 codes: lanes on adjacent l read adjacent
 // banks) -- and a thread builds the plane words of two (frame, l) with the transpose above, lanes adjacent in l so that a
 // wave writes two 128-byte halves of plane rows.
-// PF = frames per workgroup: 64 (round 4: 135 KB of LDS, one workgroup per CU -- it cannot start on a CU before the column sort
-// has left it altogether) or 32 (round 6: 70 KB, two per CU, a workgroup fits as soon as two of a CU's four sort workgroups
-// are gone; a plane row's words are still written 128 bytes at a time).
-template <int PF>
+// kPlaneFrames = frames per workgroup: 32 -- 70 KB of LDS, two per CU, a workgroup fits as soon as two of a CU's four sort workgroups are
+// gone (the 64-frame form of round 4 held 135 KB and could not start on a CU before the column sort had left it altogether:
+// measured and dropped, profiles/HISTORY.md); a plane row's words are still written 128 bytes at a time.
+constexpr int kPlaneFrames = 32;
 __global__ __launch_bounds__(1024) void code_planes_from_columns_kernel(RankArgs a) {
-    constexpr int kPlaneFrames = PF, kPlaneColPitch = PF + 2, kPieces = PF / 8;
-    extern __shared__ unsigned short plane_lds[];                 // [1024 columns][PF + 2]
+    constexpr int kPlaneColPitch = kPlaneFrames + 2, kPieces = kPlaneFrames / 8;
+    extern __shared__ unsigned short plane_lds[];                 // [1024 columns][kPlaneColPitch]
     const int64_t t0 = (int64_t)blockIdx.x * kPlaneFrames;
     const int l0 = blockIdx.y * 32;
     const int bpc = a.n_cols >> 6, n_bits = a.n_channels * bpc;
@@ -308,7 +244,7 @@ __global__ __launch_bounds__(1024) void code_planes_from_columns_kernel(RankArgs
     __syncthreads();
     const int l = threadIdx.x & 31;
 #pragma unroll
-    for (int k = 0; k < PF / 32; ++k) {
+    for (int k = 0; k < kPlaneFrames / 32; ++k) {
         const int tl = (threadIdx.x >> 5) + 32 * k;
         const int64_t t = t0 + tl;
         if (t >= a.T) continue;
@@ -334,7 +270,7 @@ __global__ __launch_bounds__(1024) void code_planes_from_columns_kernel(RankArgs
 // per thread and keeps the one-node-per-thread form
 constexpr int rank_leaf_bits(int log2n) { return log2n >= 15 ? 5 : REPET_RANK_LEAF_BITS; }
 
-template <int LOG2N, bool WIDE>
+template <int LOG2N>
 __global__ __launch_bounds__((1 << LOG2N) / 32) void rank_columns_kernel(RankArgs a) {
     constexpr int N = 1 << LOG2N, THREADS = N / 32;
     extern __shared__ uint4 rank_lds[];
@@ -370,7 +306,7 @@ __global__ __launch_bounds__((1 << LOG2N) / 32) void rank_columns_kernel(RankArg
         }
     }
     store_run(s, tid, k);
-    Phases<LOG2N, 6, WIDE>::run(s, tid, k);
+    Phases<LOG2N, 6>::run(s, tid, k);
     // code of every original key: 0x0400 + lower_bound(sorted, key), 32 independent binary searches per thread. The
     // keys are fetched again (cache-resident: this workgroup read them a few microseconds ago) rather than held in 32
     // registers through the whole sort.
@@ -466,51 +402,19 @@ template <int LOG2N>
 static hipError_t launch_rank_n(const RankArgs& a, hipStream_t s, RankStepHook hook, void* user) {
     constexpr int N = 1 << LOG2N;
     constexpr int lds = (N + N / 8) * 4 + (N >> rank_leaf_bits(LOG2N)) * 4;        // the padded keys + the breadth-first copy of the leaf ends
-    // REPET_RANK_TRIPS=5: the trips of up to five stages (WideTrips). Measured (profiles/r06_rank_trips_ab.txt): 19 trips instead of
-    // 23 and NOT faster -- rank_columns_kernel<13> 132.6 us beside the peak picking against 125-130, the stage 0.2411-0.2415 ms
-    // against 0.2392-0.2424: a trip's cost is its LDS INSTRUCTIONS (64 or 32 four- / eight-byte accesses per thread against 16
-    // sixteen-byte ones), not its bytes. Default: the three-stage trips.
-    // (2^15 keys: 1 024 threads at 128 registers each -- the wide trips spill there, that size keeps the three-stage form)
-    static const bool wide_env = [] { const char* t = getenv("REPET_RANK_TRIPS"); return t && t[0] == '5'; }();
-    constexpr bool kWideOk = LOG2N <= 14;
-    const bool wide = kWideOk && wide_env;
-    const void* fn = reinterpret_cast<const void*>(&rank_columns_kernel<LOG2N, false>);
-    if constexpr (kWideOk) { if (wide) fn = reinterpret_cast<const void*>(&rank_columns_kernel<LOG2N, true>); }
-    hipError_t e = ensure_dynamic_lds(fn, lds);
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_columns_kernel<LOG2N>), lds);
     if (e != hipSuccess) return e;
     const int64_t cols = (int64_t)a.n_channels * a.n_cols;
-    // REPET_RANK_TILE=64: the 64-frame tiles of round 4 (A/B)
-    static const bool tall = [] { const char* e = getenv("REPET_RANK_TILE"); return e && e[0] == '6'; }();
-    const bool do_transpose = a.phases == 0 || (a.phases & 1), do_sort = a.phases == 0 || (a.phases & 2);
-    if (do_transpose) {
-        if (tall)
-            hipLaunchKernelGGL(columns_from_rows_kernel<64>, dim3((unsigned)ceil_div(a.vs_pitch, 64), (unsigned)(a.n_cols / 64), (unsigned)a.n_channels),
-                               dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(columns_from_rows_kernel<32>, dim3((unsigned)ceil_div(a.vs_pitch, 32), (unsigned)(a.n_cols / 64), (unsigned)a.n_channels),
-                               dim3(256), 0, s, a);
-        if (hook) hook(user, 0);
-    }
-    if (!do_sort) return hipGetLastError();
-    bool launched = false;
-    if constexpr (kWideOk) {
-        if (wide) { hipLaunchKernelGGL((rank_columns_kernel<LOG2N, true>), dim3((unsigned)cols), dim3(N / 32), lds, s, a); launched = true; }
-    }
-    if (!launched) hipLaunchKernelGGL((rank_columns_kernel<LOG2N, false>), dim3((unsigned)cols), dim3(N / 32), lds, s, a);
+    hipLaunchKernelGGL(columns_from_rows_kernel, dim3((unsigned)ceil_div(a.vs_pitch, kColumnTileFrames), (unsigned)(a.n_cols / 64), (unsigned)a.n_channels),
+                       dim3(256), 0, s, a);
+    if (hook) hook(user, 0);
+    hipLaunchKernelGGL(rank_columns_kernel<LOG2N>, dim3((unsigned)cols), dim3(N / 32), lds, s, a);
     if (hook) hook(user, 1);
     if (a.P) {                           // the bit-sliced selection reads the planes only: no frame-major codes
-        // REPET_RANK_TILE=64: the 64-frame workgroups of round 4 (A/B)
-        if (tall) {
-            constexpr int plane_lds_bytes = 1024 * 66 * 2;
-            e = ensure_dynamic_lds(reinterpret_cast<const void*>(&code_planes_from_columns_kernel<64>), plane_lds_bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(code_planes_from_columns_kernel<64>, dim3((unsigned)ceil_div(a.T, 64), 2), dim3(1024), plane_lds_bytes, s, a);
-        } else {
-            constexpr int plane_lds_bytes = 1024 * 34 * 2;
-            e = ensure_dynamic_lds(reinterpret_cast<const void*>(&code_planes_from_columns_kernel<32>), plane_lds_bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(code_planes_from_columns_kernel<32>, dim3((unsigned)ceil_div(a.T, 32), 2), dim3(1024), plane_lds_bytes, s, a);
-        }
+        constexpr int plane_lds_bytes = 1024 * (kPlaneFrames + 2) * 2;
+        e = ensure_dynamic_lds(reinterpret_cast<const void*>(&code_planes_from_columns_kernel), plane_lds_bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(code_planes_from_columns_kernel, dim3((unsigned)ceil_div(a.T, kPlaneFrames), 2), dim3(1024), plane_lds_bytes, s, a);
         if (hook) hook(user, 2);
         return hipGetLastError();
     }
