@@ -239,6 +239,11 @@ bool gram_big_enabled();
 int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int64_t TS, bool unit_rows = false,
                   bool planes_ready = false, float* seg = nullptr, int seg_pitch = 0, bool* seg_written = nullptr);
 bool band_rows_on_f16(repet_ctx* c, int64_t T, int FS, int n_lags, int B, int64_t a_stride);
+// run_gram_band = the choice of a form (gram_band_form) + its execution (exec_gram_band)
+enum GramBandForm { kBandAuto = 0, kBandF32 = 1, kBandF16Rows = 2, kBandF16Unit = 3, kBandF16UnitLookback = 4 };
+int gram_band_form(repet_ctx* c, int64_t T, int FS, int n_lags, bool unit_rows, int B, int64_t a_stride, bool planes_ready, bool lookback);
+int exec_gram_band(repet_ctx* c, int form, const float* A, int64_t T, int FS, float* band, int n_lags, int LP, int B, int64_t a_stride,
+                   int64_t band_stride, bool planes_ready);
 int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, int n_lags, int LP, bool unit_rows = false,
                   int B = 1, int64_t a_stride = 0, int64_t band_stride = 0, bool planes_ready = false, bool lookback = false);
 void mark(repet_ctx* c, const char* name, double bytes, double flops);

@@ -206,20 +206,29 @@ bool band_rows_on_f16(repet_ctx* c, int64_t T, int FS, int n_lags, int B, int64_
 }
 
 // lookback (simonline): ask for band[j][l] = row j . row j - l; granted on the f16-split kernel only (c->band_lookback says so)
-int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, int n_lags, int LP, bool unit_rows,
-                  int B, int64_t a_stride, int64_t band_stride, bool planes_ready, bool lookback) {
-    c->band_lookback = false;
-    const int2* tiles; int n;
-    RP_TRY(get_tiles(c, T, gram_band_diagonals(n_lags), &tiles, &n));
+// The choice: which of the forms (GramBandForm, engine.h) run_gram_band takes for these arguments ...
+int gram_band_form(repet_ctx* c, int64_t T, int FS, int n_lags, bool unit_rows, int B, int64_t a_stride, bool planes_ready, bool lookback) {
     // power spectra (beat spectrum): any range, so the split is scaled by the matrix's largest magnitude. Two extra
     // passes over the matrix (max, split): worth it from about two rounds of tiles on (the batched segments of
     // `extended`: 0.58 -> 0.43 ms at cfg 3), not for one clip's narrow band (0.16 -> 0.17 ms at cfg 2 / cfg 4 sizes)
+    if (!unit_rows && (planes_ready || band_rows_on_f16(c, T, FS, n_lags, B, a_stride))) return kBandF16Rows;
+    if (unit_rows && gram_f16_enabled()) return lookback ? kBandF16UnitLookback : kBandF16Unit;
+    return kBandF32;
+}
+
+// ... and its execution (the stage entry repet_debug_gram_band_stage runs a form of its own choosing through this half)
+int exec_gram_band(repet_ctx* c, int form, const float* A, int64_t T, int FS, float* band, int n_lags, int LP, int B, int64_t a_stride,
+                   int64_t band_stride, bool planes_ready) {
+    c->band_lookback = false;
+    const int2* tiles; int n;
+    RP_TRY(get_tiles(c, T, gram_band_diagonals(n_lags), &tiles, &n));
     c->band_on_f16 = false;
-    if (!unit_rows && (planes_ready || band_rows_on_f16(c, T, FS, n_lags, B, a_stride))) {
+    const int64_t per_clip = round_up(T, kTile) * FS;
+    if (form == kBandF16Rows) {
         c->band_on_f16 = true;
-        const int64_t per_clip = round_up(T, kTile) * FS;
         const int64_t count = per_clip * B;
         const int64_t rows_per_clip = round_up(T, kTile);
+        if (B > 1 && a_stride != per_clip) return fail(REPET_ERR_BAD_ARG, "internal: the row-scaled planes of a batch are packed clip by clip");
         if (!planes_ready) {                                                         // (else: written by the STFT itself)
             HIP_TRY(c->Vh.ensure((size_t)count * 4));
             HIP_TRY(c->amax.ensure((size_t)rows_per_clip * B * sizeof(float)));      // one inverse scale per row
@@ -229,9 +238,8 @@ int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, 
                                      c->amax.as<float>(), rows_per_clip));
         return REPET_OK;
     }
-    if (unit_rows && gram_f16_enabled()) {
+    if (form == kBandF16Unit || form == kBandF16UnitLookback) {
         c->band_on_f16 = true;
-        const int64_t per_clip = round_up(T, kTile) * FS;
         // clips further apart than their padded rows (the streaming handle's windows): the split runs over the gaps too,
         // and the halves keep the clips' stride
         const int64_t clip_stride = B > 1 ? a_stride : per_clip;
@@ -242,13 +250,20 @@ int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, 
             HIP_TRY(c->Vh.ensure((size_t)count * 4));
             HIP_TRY(launch_split_f16(A, c->Vh.p, count, c->stream));
         }
-        c->band_lookback = lookback;
+        c->band_lookback = form == kBandF16UnitLookback;
         HIP_TRY(launch_gram_band_f16(c->Vh.p, T, FS, band, n_lags, LP, tiles, n, B, 2 * clip_stride, band_stride, c->stream, nullptr, 0,
                                      c->band_lookback));
         return REPET_OK;
     }
+    if (form != kBandF32) return fail(REPET_ERR_BAD_ARG, "internal: form of the banded Gram");
     HIP_TRY(launch_gram_band(A, T, FS, band, n_lags, LP, tiles, n, B, a_stride, band_stride, c->stream));
     return REPET_OK;
+}
+
+int run_gram_band(repet_ctx* c, const float* A, int64_t T, int FS, float* band, int n_lags, int LP, bool unit_rows,
+                  int B, int64_t a_stride, int64_t band_stride, bool planes_ready, bool lookback) {
+    return exec_gram_band(c, gram_band_form(c, T, FS, n_lags, unit_rows, B, a_stride, planes_ready, lookback), A, T, FS, band, n_lags, LP,
+                          B, a_stride, band_stride, planes_ready);
 }
 
 void mark(repet_ctx* c, const char* name, double bytes, double flops) {

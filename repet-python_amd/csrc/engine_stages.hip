@@ -248,6 +248,113 @@ int repet_debug_istft_stage(repet_ctx* c, const float* Y, int32_t n_spec, int32_
     return report_launch(info, kernel_out, kernel_cap, launch_out);
 }
 
+// ---- stage entries of the banded Gram and of the period chain (tests/test_gpu_gram_band_stages.py) ----------------------
+// exec_gram_band -- the second half of run_gram_band -- on rows laid out as the pipelines lay them out: B clips of T rows,
+// clip_stride_rows apart (at least Tpad = round_up(T, 128); more is the online handle's case), pitch FS, pad rows and pad
+// bins zero. form: 0 as gram_band_form picks from (unit_rows, lookback, planes_ready), 1 fp32, 2 f16 row-scaled planes, 3
+// f16 unit rows, 4 the same in the look-back layout. Every device buffer -- the rows' gaps, the band, the context's planes
+// and row inverses -- is filled with the byte `prefill` first. geo_out[8] = Tpad, FS, LP, the form that ran, band_on_f16,
+// band_lookback, the tile list's length, 0; with band_out null nothing runs and geo_out holds the form that WOULD run (the
+// only use of planes_ready: there are no planes to hand over). band_out (B, clip_stride_rows, LP); forms 2 - 4: planes_out
+// (B, Tpad, 2 FS) halves; form 2: inv_out (B, Tpad).
+int repet_debug_gram_band_stage(repet_ctx* c, const float* rows, int32_t B, int64_t T, int32_t F, int32_t n_lags, int64_t clip_stride_rows,
+                                int32_t form, int32_t unit_rows, int32_t lookback, int32_t planes_ready, int32_t prefill, int64_t* geo_out,
+                                float* band_out, uint16_t* planes_out, float* inv_out, char* kernel_out, int32_t kernel_cap) {
+    if (!c || !geo_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (B < 1 || T < 1 || F < 1 || n_lags < 1 || n_lags > T) return fail(REPET_ERR_BAD_ARG, "bad size");
+    if (form < kBandAuto || form > kBandF16UnitLookback)
+        return fail(REPET_ERR_BAD_ARG, "form: 0 as production picks, 1 fp32, 2 f16 row-scaled, 3 f16 unit rows, 4 f16 unit rows look-back");
+    const int FS = (int)round_up(F, kFreqAlign), LP = (int)round_up(n_lags, 64);
+    const int64_t Tpad = round_up(T, kTile);
+    if (clip_stride_rows < Tpad) return fail(REPET_ERR_BAD_ARG, "the clip stride is at least round_up(T, 128) rows");
+    DeviceGuard guard(c->device);
+    const int64_t a_stride = clip_stride_rows * FS, band_stride = clip_stride_rows * LP;
+    const int ran = form != kBandAuto ? form
+                                      : gram_band_form(c, T, FS, n_lags, unit_rows != 0, B, a_stride, planes_ready != 0, lookback != 0);
+    const int2* tiles; int n_tiles;
+    RP_TRY(get_tiles(c, T, gram_band_diagonals(n_lags), &tiles, &n_tiles));
+    int64_t geo[8] = {Tpad, FS, LP, ran, ran != kBandF32, ran == kBandF16UnitLookback, n_tiles, 0};
+    if (!band_out) { std::memcpy(geo_out, geo, sizeof(geo)); return REPET_OK; }
+    if (!rows || (ran != kBandF32 && !planes_out) || (ran == kBandF16Rows && !inv_out)) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (planes_ready) return fail(REPET_ERR_BAD_ARG, "planes_ready only asks for the choice: this entry has no planes to hand over");
+    if (ran == kBandF16Rows && B > 1 && clip_stride_rows != Tpad)
+        return fail(REPET_ERR_BAD_ARG, "the row-scaled planes of a batch are packed clip by clip: the stride is round_up(T, 128)");
+    const size_t a_count = (size_t)a_stride * (B - 1) + (size_t)Tpad * FS, band_count = (size_t)band_stride * B;
+    Scratch Ad, Bd;
+    HIP_TRY(Ad.b.ensure(a_count * sizeof(float)));
+    HIP_TRY(Bd.b.ensure(band_count * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(Ad.b.p, prefill & 255, a_count * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(Bd.b.p, prefill & 255, band_count * sizeof(float), c->stream));
+    for (int b = 0; b < B; ++b)
+        RP_TRY(h2d_pitched(c, Ad.b.as<float>() + (size_t)b * a_stride, FS, rows + (size_t)b * T * F, T, F, Tpad));
+    if (ran != kBandF32) {                            // what exec_gram_band will ask for: it then finds the buffers large enough
+        HIP_TRY(c->Vh.ensure(a_count * 4));
+        HIP_TRY(hipMemsetAsync(c->Vh.p, prefill & 255, a_count * 4, c->stream));
+        if (ran == kBandF16Rows) {
+            HIP_TRY(c->amax.ensure((size_t)Tpad * B * sizeof(float)));
+            HIP_TRY(hipMemsetAsync(c->amax.p, prefill & 255, (size_t)Tpad * B * sizeof(float), c->stream));
+        }
+    }
+    RP_TRY(exec_gram_band(c, ran, Ad.b.as<float>(), T, FS, Bd.b.as<float>(), n_lags, LP, B, a_stride, band_stride, false));
+    geo[4] = c->band_on_f16; geo[5] = c->band_lookback;
+    std::memcpy(geo_out, geo, sizeof(geo));
+    HIP_TRY(hipMemcpyAsync(band_out, Bd.b.p, band_count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (ran != kBandF32) {
+        const size_t clip_halves = (size_t)Tpad * FS * 2;
+        for (int b = 0; b < B; ++b)
+            HIP_TRY(hipMemcpyAsync(planes_out + (size_t)b * clip_halves, c->Vh.as<uint16_t>() + (size_t)b * a_stride * 2, clip_halves * sizeof(uint16_t),
+                                   hipMemcpyDeviceToHost, c->stream));
+        if (ran == kBandF16Rows)
+            HIP_TRY(hipMemcpyAsync(inv_out, c->amax.p, (size_t)Tpad * B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (kernel_out && kernel_cap > 0) {
+        std::strncpy(kernel_out, ran == kBandF32 ? "gram_kernel<GRAM_BAND>" : "gram_f16_kernel<true>", (size_t)kernel_cap - 1);
+        kernel_out[kernel_cap - 1] = 0;
+    }
+    return REPET_OK;
+}
+
+// run_band_window_sum -> launch_periods -> (T_expand > 0) launch_expand_periods on a band (B, T, LP) given as it is, LP a
+// multiple of 64: window w covers frames [start0 + w step, + len). beat_out (B, n_windows, LP), win_periods_out (B,
+// n_windows), frame_periods_out (T_expand) from the first clip's window periods (null with T_expand = 0). The beat rows
+// are filled with `prefill` first: a lag from n_lags on keeps it.
+int repet_debug_band_periods_stage(repet_ctx* c, const float* band, int32_t B, int64_t T, int32_t LP, int32_t n_lags, int32_t n_freq,
+                                   int64_t start0, int64_t step, int64_t len, int32_t n_windows, int32_t lo, int32_t hi,
+                                   int32_t n_lags_for_clamp, int64_t T_expand, int32_t prefill, float* beat_out,
+                                   int32_t* win_periods_out, int32_t* frame_periods_out) {
+    if (!c || !band || !beat_out || !win_periods_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (B < 1 || T < 1 || LP < 64 || (LP & 63) || n_lags < 1 || n_lags > LP || n_freq < 1 || step < 0 || len < 1 || n_windows < 1 ||
+        lo < 0 || T_expand < 0 || (T_expand > 0 && (!frame_periods_out || step < 1)))
+        return fail(REPET_ERR_BAD_ARG, "bad size");
+    const int h = std::min(hi, n_lags_for_clamp / 3);
+    if (h <= lo) return fail(REPET_ERR_TOO_SHORT, "attempt to get argmax of an empty sequence");
+    if (h > LP) return fail(REPET_ERR_BAD_ARG, "the searched lags end past the beat rows");
+    if (T_expand > 0 && ceil_div(T_expand, step) > n_windows) return fail(REPET_ERR_BAD_ARG, "T_expand needs more windows");
+    DeviceGuard guard(c->device);
+    const size_t band_count = (size_t)B * T * LP, beat_count = (size_t)B * n_windows * LP;
+    Scratch Bd, Be, Wp, Fp;
+    HIP_TRY(Bd.b.ensure(band_count * sizeof(float)));
+    HIP_TRY(Be.b.ensure(beat_count * sizeof(float)));
+    HIP_TRY(Wp.b.ensure((size_t)B * n_windows * sizeof(int32_t)));
+    HIP_TRY(Fp.b.ensure(std::max<size_t>((size_t)T_expand * sizeof(int32_t), 256)));
+    HIP_TRY(hipMemcpyAsync(Bd.b.p, band, band_count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(Be.b.p, prefill & 255, beat_count * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(Wp.b.p, prefill & 255, (size_t)B * n_windows * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(Fp.b.p, prefill & 255, std::max<size_t>((size_t)T_expand * sizeof(int32_t), 256), c->stream));
+    RP_TRY(run_band_window_sum(c, Bd.b.as<float>(), T, LP, n_lags, n_freq, start0, step, len, n_windows, Be.b.as<float>(), LP, B,
+                               (int64_t)T * LP, (int64_t)n_windows * LP));
+    HIP_TRY(launch_periods(Be.b.as<float>(), B * n_windows, LP, n_lags_for_clamp, lo, hi, Wp.b.as<int32_t>(), c->stream));
+    if (T_expand > 0) {
+        HIP_TRY(launch_expand_periods(Wp.b.as<int32_t>(), n_windows, (int32_t)step, T_expand, lo, Fp.b.as<int32_t>(), c->stream));
+        HIP_TRY(hipMemcpyAsync(frame_periods_out, Fp.b.p, (size_t)T_expand * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(beat_out, Be.b.p, beat_count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(win_periods_out, Wp.b.p, (size_t)B * n_windows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return REPET_OK;
+}
+
 static int stage_matrix_in(repet_ctx* c, DevBuf& buf, const float* host, int64_t T, int F, int FS, int64_t Tpad) {
     HIP_TRY(buf.ensure((size_t)Tpad * FS * sizeof(float)));
     return h2d_pitched(c, buf.as<float>(), FS, host, T, F, Tpad);

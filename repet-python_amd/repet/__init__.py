@@ -353,6 +353,8 @@ def _stage_entry(name):
             "repet_debug_stft_stage": [p, p, i64, i32, p, i32, i32, i32, i64, i64, i32, i64, i32, i32, i32, i32, p] + [p] * 8 + [p, i32, p],
             "repet_debug_istft_stage": [p, p, i32, i32, i64, i32, i64, i64, i64, C.c_float, p, p, p, i32, i32, i32, i64, i64,
                                         i32, i32, i32, i32, i32, i64, i64, i32, p, i64, p, i32, p],
+            "repet_debug_gram_band_stage": [p, p, i32, i64, i32, i32, i64, i32, i32, i32, i32, i32, p, p, p, p, p, i32],
+            "repet_debug_band_periods_stage": [p, p, i32, i64, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32, i64, i32, p, p, p],
         }[name]
         _stage_entries[name] = fn
     return _stage_entries[name]
@@ -440,6 +442,76 @@ def _istft_stage(spectra, window_length, out, trim, n_out, out_offset=0, scale=1
         int(fade_out), int(bt["n_batch"]), int(bt["batch_first"]), int(bt["batch_step"]), int(bt["batch_total"]), int(bt["batch_local0"]),
         int(bt["batch_out_stride"]), int(bt["overlap"]), FFT_PATHS[path], _native.ptr(buf), buf.shape[0], name, len(name), words))
     return buf, _launch_report(name, words)
+
+
+GRAM_BAND_FORMS = {"auto": 0, "f32": 1, "f16_rows": 2, "f16_unit": 3, "f16_unit_lookback": 4}
+_GRAM_BAND_FORM_NAMES = {v: k for k, v in GRAM_BAND_FORMS.items()}
+
+
+def _gram_band_stage(rows, n_lags, clip_stride=None, form="auto", unit_rows=False, lookback=False, planes_ready=False, prefill=0,
+                     choice_only=False):
+    """The banded Gram as the pipelines run it (``exec_gram_band``, the second half of ``run_gram_band``). ``rows`` (B, T, F) or
+    (T, F) fp32; ``clip_stride`` in rows, at least round_up(T, 128) (the default). ``form``: "auto" (what ``gram_band_form``
+    picks from ``unit_rows`` / ``lookback`` / ``planes_ready``), "f32", "f16_rows", "f16_unit", "f16_unit_lookback". Returns a
+    dict: "band" (B, clip_stride, LP) exactly as the kernel left it over the byte ``prefill``; for the f16 forms "planes"
+    (B, Tpad, 2 FS) float16, for "f16_rows" also "inv" (B, Tpad); "form" (the one that ran), "band_on_f16", "band_lookback",
+    "kernel", "n_tiles", "Tpad", "FS", "LP". ``choice_only``: nothing runs, only "form" (what would run) and the sizes come back;
+    ``rows`` may then be a (B, T, F) shape."""
+    import ctypes as C
+    if choice_only and isinstance(rows, tuple):
+        x, (b, t, f) = None, rows
+    else:
+        x = _f32(rows)
+        if x.ndim == 2:
+            x = x[None]
+        b, t, f = x.shape
+    tpad = -(-t // 128) * 128
+    stride = tpad if clip_stride is None else int(clip_stride)
+    geo = (C.c_int64 * 8)()
+    name = C.create_string_buffer(64)
+    fn = _stage_entry("repet_debug_gram_band_stage")
+    ctx = _native.default_context(_device).handle
+
+    def call(band, planes, inv):
+        opt = lambda a: None if a is None else _native.ptr(a)
+        _native.check(fn(ctx, opt(x), b, t, f, int(n_lags), stride, GRAM_BAND_FORMS[form], int(bool(unit_rows)), int(bool(lookback)),
+                         int(bool(planes_ready)), int(prefill), geo, opt(band), opt(planes), opt(inv), name, len(name)))
+
+    call(None, None, None)
+    _, fs, lp, ran = (int(v) for v in geo[:4])
+    out = {"form": _GRAM_BAND_FORM_NAMES[ran], "Tpad": tpad, "FS": fs, "LP": lp, "n_tiles": int(geo[6])}
+    if choice_only:
+        return out
+    band = np.empty((b, stride, lp), dtype=np.float32)
+    planes = np.empty((b, tpad, 2 * fs), dtype=np.float16) if ran != 1 else None
+    inv = np.empty((b, tpad), dtype=np.float32) if ran == 2 else None
+    call(band, planes, inv)
+    out.update(band=band, form=_GRAM_BAND_FORM_NAMES[int(geo[3])], band_on_f16=bool(geo[4]), band_lookback=bool(geo[5]),
+               kernel=name.value.decode())
+    if planes is not None:
+        out["planes"] = planes
+    if inv is not None:
+        out["inv"] = inv
+    return out
+
+
+def _band_periods_stage(band, n_freq, start0, step, length, n_windows, lo, hi, n_lags_for_clamp, n_lags=None, t_expand=0, prefill=0):
+    """``run_band_window_sum`` -> ``launch_periods`` -> (``t_expand`` > 0) ``launch_expand_periods`` on a band (B, T, LP) or
+    (T, LP) fp32, LP a multiple of 64 (``n_lags`` defaults to LP): window w covers frames [start0 + w step, + length). Returns
+    (beat rows (B, n_windows, LP) over the byte ``prefill``, window periods (B, n_windows), frame periods (t_expand,) of the first
+    clip or None)."""
+    x = _f32(band)
+    if x.ndim == 2:
+        x = x[None]
+    b, t, lp = x.shape
+    beat = np.empty((b, int(n_windows), lp), dtype=np.float32)
+    win = np.empty((b, int(n_windows)), dtype=np.int32)
+    frames = np.empty(int(t_expand), dtype=np.int32) if t_expand else None
+    _native.check(_stage_entry("repet_debug_band_periods_stage")(
+        _native.default_context(_device).handle, _native.ptr(x), b, t, lp, lp if n_lags is None else int(n_lags), int(n_freq), int(start0),
+        int(step), int(length), int(n_windows), int(lo), int(hi), int(n_lags_for_clamp), int(t_expand), int(prefill), _native.ptr(beat),
+        _native.ptr(win), None if frames is None else _native.ptr(frames)))
+    return beat, win, frames
 
 
 def _selfsimilaritymatrix(data_matrix):

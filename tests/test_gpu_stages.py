@@ -124,6 +124,16 @@ def test_beat_spectrogram_with_hole_quirk(clip):
     pr = [8, 80]
     assert np.array_equal(repet._periods(want.astype(np.float32), pr),
                           orc.periods(want.astype(np.float32).astype(np.float64), pr))
+    # a segment above 256 frames: its window sum is two chunks of band_chunk_sum_kernel, added by band_chunk_reduce_kernel
+    _, mag = orc.spectrogram_channels(x[:10 * fs], window, h)
+    p = np.power(np.mean(mag, axis=2), 2).astype(np.float32).astype(np.float64)
+    assert p.shape[1] > 257
+    for seg_len, seg_step in ((257, 100), (p.shape[1], 131)):
+        got = repet._beatspectrogram(p, seg_len, seg_step)
+        want = orc.beatspectrogram(p, seg_len, seg_step)
+        assert got.shape == want.shape
+        assert _rel(got, want) < 2e-5
+        assert np.all(got[:, seg_step - 1] == 0)
 
 
 def test_local_maxima_exact():
