@@ -489,6 +489,45 @@ int repet_online_finish_stream(repet_online* h, int32_t slot, double* out, int64
 int repet_online_finish_stream_device(repet_online* h, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
                                       void* signal_stream, int64_t* n_written);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) A live stream MOVED between handles. A slot's stream is
+ * its state -- the last B - 1 frames of magnitudes and unit rows, the overlap-add tail, the delay line of samples with their
+ * fp32 remainders -- and export_stream copies that state out as a value: a small host-side header and a dense payload whose
+ * size depends on W, H, B and the channel count alone. import_stream loads it into any slot of any handle opened with the same
+ * parameters (same GPU, another GPU, another process, now or later), and the stream goes on bit for bit as if it had never
+ * moved: what the exporting slot emitted before the export, then what the importing slot emits in lockstep, then its
+ * finish_stream / finish tail, equal repet.simonline of the stream's whole input.
+ * stream_state_size : bytes of the header (96) and of the payload for this handle's parameters.
+ * export_stream(_device): a SNAPSHOT of `slot` -- the slot lives on untouched, last_emission stays valid; migration is export +
+ *                   release_streams, and a snapshot may be imported any number of times (checkpoint, fork). Only where
+ *                   P % H == 0 and the slot is live (REPET_ERR_BAD_ARG otherwise). One launch gathers the slot's share of
+ *                   the handle's buffers; the host form returns once payload_out is written, the device form (payload_dev:
+ *                   payload bytes of device memory on the handle's device) enqueues only and orders signal_stream behind it.
+ *                   header_out is complete on return in both forms: the host knows it without touching the device.
+ * import_stream(_device): drops what lived in `slot`, as restart_streams does, and loads the state; last_emission becomes
+ *                   stale. Only where P % H == 0. REPET_ERR_BAD_ARG, before any launch, for a header with an unknown magic
+ *                   word or version, with a geometry (W, H, B, C, F), a parameter (cutoff_bins, sim_distance_frames,
+ *                   sim_number, sim_threshold, buffer_frames, flags) or a payload size other than the handle's, or with
+ *                   counts that contradict each other. One launch scatters the payload and writes the slot's first frame,
+ *                   which is the handle's next frame minus the stream's age: negative for a stream older than the handle.
+ *                   A handle younger than the state needs (fewer frames done than the state has history rows) is first
+ *                   read as if it had been opened that many hops earlier with every live slot idle until its own start
+ *                   (one more launch moves the held samples; buffers may grow, which waits); what the caller pushed per
+ *                   slot does not change, and every other slot's output is what it would have been (on a handle that has
+ *                   seen fewer than ceil(W / H) - 1 hops, behind as many hops of zeros as it lacked: the state brings
+ *                   samples that are held but not yet emitted, and emissions are in lockstep). The device form
+ *                   starts behind what wait_stream has enqueued and orders wait_stream behind its read of payload_dev.
+ * Header (little-endian, no padding): uint32 magic "REPS", uint32 version 1, int32 W, H, B, C, F, cutoff_bins,
+ * sim_distance_frames, sim_number, buffer_frames, flags, double sim_threshold, int64 age in frames (length / H - (ceil(W / H)
+ * - 1)), length in samples, valid history rows, pending samples, payload bytes. Payload (fp32, every part at a 16-byte
+ * aligned offset, rows right-aligned and zero where the stream is younger): Vn [B-1][FS] | V [C][B-1][FS] | X [C][FS] complex
+ * | samples [(B-1) H + (ceil(W / H) - 1) H][C] | their remainders likewise, FS = F rounded up to 32. */
+int repet_online_stream_state_size(repet_online* h, int64_t* header_bytes, int64_t* payload_bytes);
+int repet_online_export_stream(repet_online* h, int32_t slot, void* header_out, void* payload_out);
+int repet_online_export_stream_device(repet_online* h, int32_t slot, void* header_out, void* payload_dev, void* signal_stream);
+int repet_online_import_stream(repet_online* h, int32_t slot, const void* header, const void* payload);
+int repet_online_import_stream_device(repet_online* h, int32_t slot, const void* header, const void* payload_dev,
+                                      void* wait_stream);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) The FOREGROUND, aligned. The repeating background is the
  * means; audio - background is what most callers want, and a live handle returns its background behind the input (n_emit != n),
  * so only the handle knows which input samples an emission belongs to. One selector with one meaning everywhere: */

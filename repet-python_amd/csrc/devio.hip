@@ -406,6 +406,52 @@ __global__ __launch_bounds__(kIoThreads) void online_slot_reset(SlotResetArgs a)
     }
 }
 
+// Slot export / import (a live stream moved between handles): part z moves `blocks` runs of `len` floats between ONE slot's
+// share of the handle's strided buffers and the dense payload, slots of four floats as in the row copies. Element i of a run
+// is src[src_off + blk * src_block + i] for i >= zero_below and zero below it (the source is never read there: src_off may be
+// negative, the run right-aligned on what the source holds). The import also writes the slot's first frame and, where the
+// handle's epoch moved with it, adds `shift` to the first frame of every other live slot (one workgroup, plain stores).
+struct SlotMoveDev { const float* src; float* dst; int64_t src_off, len, slots_per_block, blocks, src_block, dst_block, zero_below; int32_t src_vec, dst_vec; };
+struct SlotMoveArgs { SlotMoveDev part[repet_eng::kRowCopyParts]; int64_t* slot_start; int64_t value, shift; int32_t slot, n_slots; };
+
+__device__ inline void slot_move_body(const SlotMoveDev& p) {
+    const int64_t slots = p.slots_per_block * p.blocks;
+    for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+        const int64_t blk = q / p.slots_per_block;
+        const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+        float* d = p.dst + blk * p.dst_block + i0;
+        const int64_t so = p.src_off + blk * p.src_block + i0;
+        if (i0 + 4 <= p.len && p.dst_vec) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i0 >= p.zero_below) {
+                if (p.src_vec) v = *reinterpret_cast<const float4*>(p.src + so);
+                else v = make_float4(p.src[so], p.src[so + 1], p.src[so + 2], p.src[so + 3]);
+            } else if (i0 + 4 > p.zero_below) {                   // the slot the boundary cuts
+                float e[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) e[k] = i0 + k >= p.zero_below ? p.src[so + k] : 0.f;
+                v = make_float4(e[0], e[1], e[2], e[3]);
+            }
+            *reinterpret_cast<float4*>(d) = v;
+        } else {
+            const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
+            for (int64_t k = 0; k < m; ++k) d[k] = i0 + k >= p.zero_below ? p.src[so + k] : 0.f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void online_slot_export(SlotMoveArgs a) { slot_move_body(a.part[blockIdx.y]); }
+
+__global__ __launch_bounds__(kIoThreads) void online_slot_import(SlotMoveArgs a) {
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        for (int32_t s = threadIdx.x; s < a.n_slots; s += kIoThreads) {
+            if (s == a.slot) a.slot_start[s] = a.value;
+            else if (a.shift != 0 && a.slot_start[s] < repet_eng::kSlotIdle) a.slot_start[s] += a.shift;
+        }
+    }
+    slot_move_body(a.part[blockIdx.y]);
+}
+
 int element_size(int dtype) {
     switch (dtype) {
         case REPET_F64: return 8;
@@ -506,6 +552,49 @@ hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// the parts of a slot move as the kernels take them; returns the slots of the longest part (-1: a part the kernels cannot take)
+static int64_t slot_move_args(const SlotMove* parts, int n_parts, SlotMoveArgs& a) {
+    int64_t most = 1;
+    for (int k = 0; k < kRowCopyParts; ++k) {
+        SlotMoveDev& d = a.part[k];
+        d = SlotMoveDev{nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, 0, 0};
+        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;
+        const SlotMove& p = parts[k];
+        const bool reads = p.src && p.zero_below < p.len;
+        if (!p.dst || p.zero_below < 0 || (!p.src && p.zero_below < p.len) || (reads && p.src_off + p.zero_below < 0)) return -1;
+        d.src = p.src; d.dst = p.dst; d.src_off = p.src_off; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
+        d.src_block = p.src_block; d.dst_block = p.dst_block; d.zero_below = std::min(p.zero_below, p.len);
+        d.dst_vec = !(reinterpret_cast<uintptr_t>(p.dst) & 15) && !(p.dst_block & 3) ? 1 : 0;
+        d.src_vec = reads && !(reinterpret_cast<uintptr_t>(p.src) & 15) && !(p.src_off & 3) && !(p.src_block & 3) ? 1 : 0;
+        most = std::max(most, d.slots_per_block * d.blocks);
+    }
+    return most;
+}
+
+static dim3 slot_move_grid(int64_t most) {
+    return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(most, kIoThreads), kMaxIoGroups / kRowCopyParts)), kRowCopyParts);
+}
+
+hipError_t launch_slot_export(const SlotMove* parts, int n_parts, hipStream_t s) {
+    if (n_parts <= 0 || n_parts > kRowCopyParts) return hipErrorInvalidValue;
+    SlotMoveArgs a{};
+    const int64_t most = slot_move_args(parts, n_parts, a);
+    if (most < 0) return hipErrorInvalidValue;
+    online_slot_export<<<slot_move_grid(most), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_slot_import(const SlotMove* parts, int n_parts, int64_t* slot_start, int32_t n_slots, int32_t slot, int64_t value,
+                              int64_t shift, hipStream_t s) {
+    if (n_parts < 0 || n_parts > kRowCopyParts || !slot_start || slot < 0 || slot >= n_slots) return hipErrorInvalidValue;
+    SlotMoveArgs a{};
+    const int64_t most = slot_move_args(parts, n_parts, a);
+    if (most < 0) return hipErrorInvalidValue;
+    a.slot_start = slot_start; a.value = value; a.shift = shift; a.slot = slot; a.n_slots = n_slots;
+    online_slot_import<<<slot_move_grid(most), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
 }
 
 hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,

@@ -279,6 +279,15 @@ constexpr int kSlotResetIds = 256;
 constexpr int64_t kSlotIdle = (int64_t)1 << 60;
 hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* slots, int32_t n_slots, const ZeroPart* parts,
                              int n_parts, hipStream_t s);
+//   export   ONE slot's share of the handle's buffers gathered into a dense payload, one launch: up to kRowCopyParts parts of
+//            `blocks` runs of `len` floats; element i of a run is src[src_off + blk * src_block + i] for i >= zero_below and
+//            zero below it (a run right-aligned on what the source holds: src_off may be negative, src null with zero_below = len)
+//   import   the same parts the other way (payload -> slot), slot_start[slot] = value and, where the handle's epoch moves
+//            with the import, slot_start[s] += shift for every other live slot: one launch
+struct SlotMove { const float* src; int64_t src_off; float* dst; int64_t len, blocks, src_block, dst_block, zero_below; };
+hipError_t launch_slot_export(const SlotMove* parts, int n_parts, hipStream_t s);
+hipError_t launch_slot_import(const SlotMove* parts, int n_parts, int64_t* slot_start, int32_t n_slots, int32_t slot, int64_t value,
+                              int64_t shift, hipStream_t s);
 hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
                                 float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s);
 hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s, const int64_t* slot_start = nullptr);

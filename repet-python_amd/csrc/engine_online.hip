@@ -44,6 +44,9 @@ struct repet_online {
     int64_t pend_cap = 0, pend_count = 0;   // samples per channel
     int64_t hist_valid = 0;         // valid history rows, right-aligned at row Hh
     int64_t frames_done = 0, total_in = 0, emitted = 0;
+    // hops by which imports of streams older than the handle moved its epoch (online_shift_epoch): the counters above read as
+    // if the handle had been opened `epoch` hops earlier, and total_in - epoch * H is what the caller pushed per slot
+    int64_t epoch = 0;
     int64_t max_push = 0;           // repet_online_open_streams: windows and pending buffers sized for pushes of this many samples
     bool finished = false;
     // What the emitting calls deliver (repet_online_set_output), the one-shot second destination of the next one
@@ -471,6 +474,178 @@ int online_plan_slot(const repet_online* o, int32_t slot, int64_t* n_new, int64_
     return online_plan(o, 0, true, n_new, n_emit);
 }
 
+// ---- a slot's stream as a value: repet_online_export_stream / import_stream --------------------------------------------------
+// On the hop grid a handle that has seen k >= m hops (m = ceil(W / H) - 1) has transformed k - m frames and holds m * H
+// unconsumed samples, so a stream of L samples has AGE L / H - m frames (negative while it is shorter than m hops), and a
+// slot's state is what online_reset_slots clears: the Hh history rows of Vn and V, the last masked spectrum, and the held
+// samples with their remainders. The payload is that, dense and right-aligned at its full size (zero where the stream is
+// younger), at pitches that depend on W, H, B and C alone:
+//   Vn [Hh][FS] | V [C][Hh][FS] | X [C][FS] float2 | pend [Hh * H + m * H][C] | pend_lo likewise      (fp32, parts padded to 16 bytes
+//   in FRONT of the samples). The header (host side, 96 bytes, little-endian) names the geometry, the parameters the online path
+//   reads and the stream's place in time.
+constexpr uint32_t kStateMagic = 0x53504552u;        // "REPS"
+constexpr uint32_t kStateVersion = 1;
+struct StateHeader {
+    uint32_t magic, version;
+    int32_t W, H, B, C, F, cutoff_bins, sim_distance_frames, sim_number, buffer_frames, flags;
+    double sim_threshold;
+    int64_t age_frames, length_samples, hist_rows, pending_samples, payload_bytes;
+};
+static_assert(sizeof(StateHeader) == 96, "the stream state header is 96 bytes");
+
+struct StateLayout { int64_t m, samples, rows, pend_len, vn, v, x, pend, pend_lo, floats; };
+static StateLayout state_layout(const repet_online* o) {
+    StateLayout l{};
+    l.m = ceil_div(o->W, o->H) - 1;
+    l.samples = ((int64_t)o->Hh + l.m) * o->H;
+    l.rows = (int64_t)o->Hh * o->FS;
+    l.pend_len = round_up(l.samples * o->C, 4);
+    l.vn = 0;
+    l.v = l.vn + round_up(l.rows, 4);
+    l.x = l.v + round_up(o->C * l.rows, 4);
+    l.pend = l.x + round_up((int64_t)o->C * 2 * o->FS, 4);
+    l.pend_lo = l.pend + l.pend_len;
+    l.floats = l.pend_lo + l.pend_len;
+    return l;
+}
+
+static void state_header(const repet_online* o, StateHeader* h) {
+    std::memset(h, 0, sizeof(*h));
+    h->magic = kStateMagic; h->version = kStateVersion;
+    h->W = o->W; h->H = o->H; h->B = o->B; h->C = o->C; h->F = o->F;
+    h->cutoff_bins = o->p.cutoff_bins; h->sim_distance_frames = o->p.sim_distance_frames; h->sim_number = o->p.sim_number;
+    h->buffer_frames = o->p.buffer_frames; h->flags = o->p.flags; h->sim_threshold = o->p.sim_threshold;
+    h->payload_bytes = state_layout(o).floats * (int64_t)sizeof(float);
+}
+
+static int64_t clamp_rows(const repet_online* o, int64_t age) { return std::min<int64_t>(std::max<int64_t>(age, 0), o->Hh); }
+
+// the header of slot's stream as it stands (host counters only); refusals before any launch
+int online_export_plan(const repet_online* o, int32_t slot, StateHeader* h) {
+    RP_TRY(online_check_slots(o, &slot, 1));
+    if (o->total_in % o->H)
+        return fail(REPET_ERR_BAD_ARG, "online: a stream can only be exported on a hop boundary (samples pushed % step_length == 0)");
+    const int64_t st = o->start[(size_t)slot];
+    if (st == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
+    const StateLayout l = state_layout(o);
+    state_header(o, h);
+    const int64_t L = o->total_in - st * (int64_t)o->H;
+    h->length_samples = L;
+    h->age_frames = L / o->H - l.m;
+    h->hist_rows = clamp_rows(o, h->age_frames);
+    h->pending_samples = std::min<int64_t>(L, l.m * o->H);
+    if (L < 0 || h->hist_rows > o->hist_valid || o->pend_hist + o->pend_count > l.samples)
+        return fail(REPET_ERR_LIMIT, "online: the slot's stream does not fit the handle's window");
+    return REPET_OK;
+}
+
+// one launch: the slot's share of the current window and pending buffers -> payload (device memory of h.payload_bytes)
+int online_export(repet_online* o, int32_t slot, const StateHeader& h, float* payload) {
+    const StateLayout l = state_layout(o);
+    const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), sb = slot;
+    const int64_t held = o->pend_hist + o->pend_count, valid = std::min(h.length_samples, held);
+    const bool win = o->rows_cap > 0 && h.hist_rows > 0, smp = o->pend_cap > 0 && valid > 0;
+    const int64_t row0 = win ? (o->Hh - h.hist_rows) * FS : l.rows;
+    const int64_t off = held * o->C - l.pend_len, below = smp ? l.pend_len - valid * o->C : l.pend_len;
+    const SlotMove parts[kRowCopyParts] = {
+        {win ? o->Vn[o->cur].as<float>() + sb * o->vn_stride() : nullptr, 0, payload + l.vn, l.rows, 1, 0, 0, row0},
+        {win ? o->V[o->cur].as<float>() + sb * spec : nullptr, 0, payload + l.v, l.rows, o->C, plane, l.rows, row0},
+        {win ? o->X[o->cur].as<float>() + 2 * (sb * spec + (o->Hh - 1) * FS) : nullptr, 0, payload + l.x, 2 * FS, o->C, 2 * plane, 2 * FS,
+         win ? 0 : 2 * FS},
+        {smp ? o->pend[o->pcur].as<float>() + sb * o->pend_stride() : nullptr, off, payload + l.pend, l.pend_len, 1, 0, 0, below},
+        {smp ? o->pend_lo[o->pcur].as<float>() + sb * o->pend_stride() : nullptr, off, payload + l.pend_lo, l.pend_len, 1, 0, 0, below}};
+    HIP_TRY(launch_slot_export(parts, kRowCopyParts, o->ctx->stream));
+    return REPET_OK;
+}
+
+// everything of a header against the handle and the slot, before any launch
+int online_import_check(const repet_online* o, int32_t slot, const StateHeader* h) {
+    RP_TRY(online_check_slots(o, &slot, 1));
+    if (h->magic != kStateMagic) return fail(REPET_ERR_BAD_ARG, "online: not a stream state (unknown magic word)");
+    if (h->version != kStateVersion) return fail(REPET_ERR_BAD_ARG, "online: unknown version of the stream state");
+    StateHeader mine;
+    state_header(o, &mine);
+    if (h->W != mine.W || h->H != mine.H || h->B != mine.B || h->C != mine.C || h->F != mine.F)
+        return fail(REPET_ERR_BAD_ARG, "online: the stream state has another geometry (window, hop, buffer, channels) than the handle");
+    if (h->cutoff_bins != mine.cutoff_bins || h->sim_distance_frames != mine.sim_distance_frames || h->sim_number != mine.sim_number ||
+        h->buffer_frames != mine.buffer_frames || h->flags != mine.flags || std::memcmp(&h->sim_threshold, &mine.sim_threshold, sizeof(double)))
+        return fail(REPET_ERR_BAD_ARG, "online: the stream state was made with other parameters than the handle's");
+    if (h->payload_bytes != mine.payload_bytes) return fail(REPET_ERR_BAD_ARG, "online: the stream state has another payload size");
+    const StateLayout l = state_layout(o);
+    const int64_t L = h->length_samples;
+    if (L < 0 || L % o->H || h->age_frames != L / o->H - l.m || h->hist_rows != clamp_rows(o, h->age_frames) ||
+        h->pending_samples != std::min<int64_t>(L, l.m * o->H))
+        return fail(REPET_ERR_BAD_ARG, "online: the stream state's age, length and held counts contradict each other");
+    if (o->total_in % o->H)
+        return fail(REPET_ERR_BAD_ARG, "online: a stream can only be imported on a hop boundary (samples pushed % step_length == 0)");
+    return REPET_OK;
+}
+
+// The handle read as if it had been opened `delta` hops earlier, with every live slot idle until its own start: the counters
+// move by delta hops (frames done and held samples as a handle of that age has them), every live slot's first frame moves with
+// them (the device table: by the import launch that follows), and the held samples of every slot move behind delta * H zeros
+// -- the samples before their starts -- into the other pending buffer: one launch. The history rows this exposes were never
+// written (zeroed at allocation, kept so by the slide and the resets). Only while the handle is younger than B - 1 frames.
+static int online_shift_epoch(repet_online* o, int64_t delta) {
+    repet_ctx* c = o->ctx;
+    const int64_t by = delta * o->H, old_held = o->pend_hist + o->pend_count;
+    const int64_t total = o->total_in + by;
+    const int64_t frames = total >= o->W ? (total - o->W) / o->H + 1 : 0;
+    const int64_t hist = std::min<int64_t>(o->Hh, frames);
+    const int64_t count = total - frames * (int64_t)o->H;
+    if (o->frames_done != o->hist_valid || frames != hist || hist * o->H + count != old_held + by || old_held + by > o->pend_cap)
+        return fail(REPET_ERR_LIMIT, "online: the handle is too old for an epoch shift");
+    const int64_t pst = o->pend_stride(), lead = by * o->C, len = old_held * o->C;
+    const int nxt = o->pcur ^ 1;
+    const RowCopy parts[4] = {{nullptr, o->pend[nxt].as<float>(), lead, 1, 0, 0, 0, pst},
+                              {nullptr, o->pend_lo[nxt].as<float>(), lead, 1, 0, 0, 0, pst},
+                              {o->pend[o->pcur].as<float>(), o->pend[nxt].as<float>() + lead, len, 1, 0, 0, pst, pst},
+                              {o->pend_lo[o->pcur].as<float>(), o->pend_lo[nxt].as<float>() + lead, len, 1, 0, 0, pst, pst}};
+    HIP_TRY(launch_row_copies(parts, 4, o->S, c->stream));
+    o->pcur = nxt;
+    o->total_in = total; o->frames_done = frames; o->hist_valid = hist; o->pend_hist = hist * o->H; o->pend_count = count;
+    o->emitted = frames * (int64_t)o->H;
+    for (int64_t& st : o->start)
+        if (st != kSlotIdle) st += delta;
+    o->latest_start += delta;
+    o->epoch += delta;
+    o->slots_on = true;
+    return REPET_OK;
+}
+
+// the checked state into `slot` (payload: device memory on the handle's device). The stream's frame `age` is the handle's next
+// frame: start[slot] = frames_done - age, negative for a stream older than the handle. A handle too young to hold the state
+// (fewer frames done than the state has history rows, or fewer held samples) is first moved back in time (online_shift_epoch).
+// One launch writes everything online_reset_slots clears, and the table.
+int online_import(repet_online* o, int32_t slot, const StateHeader& h, const float* payload) {
+    repet_ctx* c = o->ctx;
+    const StateLayout l = state_layout(o);
+    const int64_t delta = std::max<int64_t>(0, l.m + h.hist_rows - o->total_in / o->H);
+    o->em.valid = false;
+    RP_TRY(online_ensure_windows(o, std::max<int64_t>(o->max_push / o->H + 1, o->W / o->H + 1)));
+    RP_TRY(online_ensure_pending(o, delta * o->H));
+    if (delta > 0) RP_TRY(online_shift_epoch(o, delta));
+    const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), sb = slot;
+    const int64_t held = o->pend_hist + o->pend_count;
+    if (o->rows_cap < o->Hh || h.hist_rows > o->hist_valid || held > l.samples || held > o->pend_cap || o->pend_count != l.m * o->H)
+        return fail(REPET_ERR_LIMIT, "online: the stream state does not fit the handle's window");
+    const int64_t off = l.pend_len - held * o->C;
+    const SlotMove parts[kRowCopyParts] = {
+        {payload + l.vn, 0, o->Vn[o->cur].as<float>() + sb * o->vn_stride(), l.rows, 1, 0, 0, 0},
+        {payload + l.v, 0, o->V[o->cur].as<float>() + sb * spec, l.rows, o->C, l.rows, plane, 0},
+        {payload + l.x, 0, o->X[o->cur].as<float>() + 2 * (sb * spec + (o->Hh - 1) * FS), 2 * FS, o->C, 2 * FS, 2 * plane, 0},
+        {payload + l.pend, off, o->pend[o->pcur].as<float>() + sb * o->pend_stride(), held * o->C, 1, 0, 0, 0},
+        {payload + l.pend_lo, off, o->pend_lo[o->pcur].as<float>() + sb * o->pend_stride(), held * o->C, 1, 0, 0, 0}};
+    const int64_t first = o->frames_done - h.age_frames;
+    HIP_TRY(launch_slot_import(parts, kRowCopyParts, o->slot_start.as<int64_t>(), o->S, slot, first, delta, c->stream));
+    int64_t& st = o->start[(size_t)slot];
+    if (st == kSlotIdle) o->n_idle -= 1;
+    st = first;
+    o->latest_start = std::max(o->latest_start, first);
+    o->slots_on = true;
+    return REPET_OK;
+}
+
 }  // namespace repet_eng
 
 extern "C" {
@@ -599,6 +774,77 @@ int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, 
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
     RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
     *n_written = n_emit;
+    return REPET_OK;
+}
+
+int repet_online_stream_state_size(repet_online* o, int64_t* header_bytes, int64_t* payload_bytes) {
+    if (!o || !header_bytes || !payload_bytes) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *header_bytes = (int64_t)sizeof(StateHeader);
+    *payload_bytes = state_layout(o).floats * (int64_t)sizeof(float);
+    return REPET_OK;
+}
+
+int repet_online_export_stream(repet_online* o, int32_t slot, void* header_out, void* payload_out) {
+    if (!o || !header_out || !payload_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    StateHeader h;
+    RP_TRY(online_export_plan(o, slot, &h));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    const size_t bytes = (size_t)h.payload_bytes;
+    HIP_TRY(o->out64.ensure(bytes));
+    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, bytes));
+    RP_TRY(online_export(o, slot, h, o->out64.as<float>()));
+    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(payload_out, o->host_out, bytes);
+    std::memcpy(header_out, &h, sizeof(h));
+    return REPET_OK;
+}
+
+int repet_online_export_stream_device(repet_online* o, int32_t slot, void* header_out, void* payload_dev, void* signal_stream) {
+    if (!o || !header_out || !payload_dev) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(payload_dev) & 3) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
+    StateHeader h;
+    RP_TRY(online_export_plan(o, slot, &h));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_export(o, slot, h, static_cast<float*>(payload_dev)));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    std::memcpy(header_out, &h, sizeof(h));
+    return REPET_OK;
+}
+
+int repet_online_import_stream(repet_online* o, int32_t slot, const void* header, const void* payload) {
+    if (!o || !header || !payload) return fail(REPET_ERR_BAD_ARG, "null argument");
+    StateHeader h;
+    std::memcpy(&h, header, sizeof(h));
+    RP_TRY(online_import_check(o, slot, &h));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    const size_t bytes = (size_t)h.payload_bytes;
+    HIP_TRY(hipStreamSynchronize(c->stream));          // a device push may still be running; the pinned buffer is free
+    RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
+    HIP_TRY(o->staging.ensure(bytes));
+    std::memcpy(o->host_in, payload, bytes);
+    HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    return online_import(o, slot, h, o->staging.as<float>());
+}
+
+int repet_online_import_stream_device(repet_online* o, int32_t slot, const void* header, const void* payload_dev, void* wait_stream) {
+    if (!o || !header || !payload_dev) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(payload_dev) & 3) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
+    StateHeader h;
+    std::memcpy(&h, header, sizeof(h));
+    RP_TRY(online_import_check(o, slot, &h));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(wait_stream)));
+    RP_TRY(online_import(o, slot, h, static_cast<const float*>(payload_dev)));
+    // the caller's stream continues behind the import: the payload may be reused once that stream gets there
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(wait_stream), c->io_done, 0));
     return REPET_OK;
 }
 

@@ -22,6 +22,7 @@ import numpy as np
 from . import _native
 from ._native import Context  # noqa: F401  (device-resident API used by bench.py)
 from ._native import OnlineSeparator as _OnlineSeparator
+from ._native import StreamState  # noqa: F401  (what export_stream returns and import_stream takes)
 
 # ---- public parameters (repet.py:42-63) ----------------------------------------------------------------
 cutoff_frequency = 100
@@ -214,7 +215,11 @@ def online(sampling_frequency, number_channels):
     ``push(chunk, which=...)`` / ``finish(which=...)``: "background" (default), "foreground" -- the input minus the background
     of exactly the emitted samples (the output runs behind the input; the handle keeps the delay line) --, "mixture" (those
     input samples themselves) or "both", the pair ``(background, foreground)``. The concatenated foreground equals
-    ``x - simonline(x)``; during the 10-s warm-up, where ``simonline`` is silent, it is the input itself."""
+    ``x - simonline(x)``; during the 10-s warm-up, where ``simonline`` is silent, it is the input itself.
+
+    ``export_stream()`` returns the stream's state as a :class:`StreamState` (a snapshot; only where the samples pushed so
+    far are a multiple of the hop) and ``import_stream(state)`` loads one into this separator, which then goes on as the
+    exporting stream would have: see :func:`online_streams`."""
     return _OnlineSeparator(derive_params(sampling_frequency), number_channels, _device)
 
 
@@ -248,7 +253,22 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     input that is not float32 + float32 exact: within ``2**-47 * max(|x|, |background|)``); while a stream warms up its
     foreground is its input (nothing is removed before there is evidence); idle slots and the hop before a ``restart`` are
     zero in every signal, whatever the chunk held there. ``last_emission(which, out=None)`` returns another signal of the
-    samples the last ``push`` / ``finish`` emitted, until the next push, finish, restart or release."""
+    samples the last ``push`` / ``finish`` emitted, until the next push, finish, restart or release.
+
+    A stream can move between handles: ``export_stream(slot, device=False)`` returns a snapshot of the slot's state as a
+    :class:`StreamState` -- ``header``, a small ``bytes`` value the host knows at once, and ``payload``, a ``numpy.uint8``
+    array or (``device=True``, no host wait) a ``torch.uint8`` tensor on the handle's device, ``stream_state_nbytes`` bytes
+    -- and ``import_stream(slot, state)`` loads it into any slot of any handle opened with the same parameters, on this GPU,
+    another one (a tensor on another device is copied over first) or, through ``state.to_bytes()`` /
+    ``StreamState.from_bytes(b)``, another process or a later day. The exporting slot lives on untouched, so migration is
+    ``export_stream`` + ``release``, and a snapshot imported twice is a fork. Both calls need ``samples_pushed`` on the hop
+    grid; ``import_stream`` drops what lived in the slot, as ``restart`` does, and raises ValueError before anything runs
+    for a state of another sampling frequency, channel count or parameter set, a payload of the wrong size or dtype, or an
+    unknown magic word or version. What the exporting slot emitted before the export, then what the importing slot emits
+    in lockstep, then its ``finish_stream`` / ``finish`` tail, equal ``simonline`` of the stream's whole input bit for bit
+    -- on a handle of any age, other live slots undisturbed; the foreground's delay line moves with the stream. (A handle
+    on which nothing was pushed holds no sample yet, the state one hop that was never emitted: the first push after such
+    an import emits that hop, which is a hop of zeros in front of every other slot's own output.)"""
     return _native.OnlineStreams(derive_params(sampling_frequency), number_channels, number_streams, _device,
                                  max_push_samples or 0)
 

@@ -2,6 +2,7 @@
 is missing the calls raise, loudly."""
 import ctypes as C
 import os
+import struct
 import sys
 import threading
 import weakref
@@ -165,6 +166,11 @@ _SIGNATURES = {
     "repet_online_stream_emit_count": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "repet_online_finish_stream": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_finish_stream_device": (C.c_int, [_P, C.c_int32, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_online_stream_state_size": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "repet_online_export_stream": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "repet_online_export_stream_device": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    "repet_online_import_stream": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "repet_online_import_stream_device": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     "repet_online_set_output": (C.c_int, [_P, C.c_int]),
     "repet_online_also_emit": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "repet_online_last_emission": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
@@ -671,15 +677,147 @@ def _select_output(handle, codes, second=None, dtype=F64, strides=None):
         check(lib().repet_online_also_emit(handle, codes[1], second, dtype, strides))
 
 
+class StreamState:
+    """The state of one live stream as a value (``export_stream`` of a streaming handle): ``header``, a small ``bytes`` the
+    host knows without touching the device, and ``payload``, a ``numpy.uint8`` array or a ``torch.uint8`` tensor on a ROCm
+    device. ``import_stream`` of any handle opened with the same parameters takes it; ``to_bytes()`` / ``from_bytes(b)``
+    serve persistence (they may wait for the device). The header's fields are attributes (``window_length``, ``age_frames``,
+    ``length_samples``, ``payload_bytes``, ...), listed in ``StreamState.FIELDS``."""
+
+    MAGIC = 0x53504552                 # b"REPS", little-endian
+    VERSION = 1
+    _FORMAT = "<II10id5q"
+    HEADER_BYTES = struct.calcsize(_FORMAT)
+    FIELDS = ("magic", "version", "window_length", "step_length", "buffer_frames", "number_channels", "number_bins",
+              "cutoff_bins", "similarity_distance_frames", "similarity_number", "params_buffer_frames", "flags",
+              "similarity_threshold", "age_frames", "length_samples", "history_rows", "pending_samples", "payload_bytes")
+
+    def __init__(self, header, payload):
+        self.header = bytes(header)
+        self.fields = self.unpack_header(self.header)
+        self.payload = payload
+
+    def __getattr__(self, name):
+        fields = self.__dict__.get("fields")
+        if fields is not None and name in fields:
+            return fields[name]
+        raise AttributeError(name)
+
+    @classmethod
+    def pack_header(cls, fields):
+        """The header bytes of a dict with every name of ``FIELDS``."""
+        return struct.pack(cls._FORMAT, *(fields[name] for name in cls.FIELDS))
+
+    @classmethod
+    def unpack_header(cls, header):
+        """The fields of a header as a dict. ValueError for a wrong size, an unknown magic word or an unknown version."""
+        header = bytes(header)
+        if len(header) != cls.HEADER_BYTES:
+            raise ValueError(f"a stream state header is {cls.HEADER_BYTES} bytes, not {len(header)}")
+        fields = dict(zip(cls.FIELDS, struct.unpack(cls._FORMAT, header)))
+        if fields["magic"] != cls.MAGIC:
+            raise ValueError("not a stream state (unknown magic word)")
+        if fields["version"] != cls.VERSION:
+            raise ValueError(f"unknown version {fields['version']} of the stream state")
+        if fields["payload_bytes"] < 0:
+            raise ValueError("the stream state has a negative payload size")
+        return fields
+
+    def payload_array(self):
+        """The payload as a host ``numpy.uint8`` array (a device payload is copied: this waits)."""
+        p = self.payload
+        if is_tensor(p):
+            p = p.detach().cpu().numpy()
+        return np.ascontiguousarray(p)
+
+    def to_bytes(self):
+        """Header and payload as one ``bytes`` value."""
+        p = self.payload_array()
+        if p.dtype != np.uint8 or p.size != self.fields["payload_bytes"]:
+            raise ValueError("the payload is not the uint8 array the header describes")
+        return self.header + p.tobytes()
+
+    @classmethod
+    def from_bytes(cls, b):
+        """The state ``to_bytes`` wrote. ValueError for a truncated or padded value, an unknown magic word or version."""
+        b = bytes(b)
+        fields = cls.unpack_header(b[:cls.HEADER_BYTES])
+        if len(b) != cls.HEADER_BYTES + fields["payload_bytes"]:
+            raise ValueError(f"the stream state has {len(b) - cls.HEADER_BYTES} payload bytes, its header says {fields['payload_bytes']}")
+        return cls(b[:cls.HEADER_BYTES], np.frombuffer(b, dtype=np.uint8, offset=cls.HEADER_BYTES).copy())
+
+
+def _state_sizes(handle):
+    hb, pb = C.c_int64(), C.c_int64()
+    check(lib().repet_online_stream_state_size(handle, C.byref(hb), C.byref(pb)))
+    if hb.value != StreamState.HEADER_BYTES:
+        raise RuntimeError("librepet_hip.so writes another stream state header than this binding reads")
+    return hb.value, pb.value
+
+
+def _export_state(handle, slot, device=None):
+    """export_stream of ``slot``: a host payload (device None), or a tensor on cuda:``device`` behind its current stream."""
+    hb, pb = _state_sizes(handle)
+    header = C.create_string_buffer(hb)
+    if device is None:
+        payload = np.empty(pb, dtype=np.uint8)
+        check(lib().repet_online_export_stream(handle, slot, header, ptr(payload)))
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        payload = torch.empty(pb, dtype=torch.uint8, device=dev)
+        check(lib().repet_online_export_stream_device(handle, slot, header, C.c_void_p(payload.data_ptr()),
+                                                      _stream_handle(torch.cuda.current_stream(dev))))
+    return StreamState(header.raw, payload)
+
+
+def _import_state(handle, slot, state, device):
+    """import_stream of ``state`` into ``slot`` of a handle on cuda:``device``; returns the header's fields. Everything the
+    Python layer can refuse (header, payload dtype and size) is refused here, the rest by the library, before any launch."""
+    if not isinstance(state, StreamState):
+        raise ValueError("import_stream takes the StreamState that export_stream returned")
+    fields = StreamState.unpack_header(state.header)
+    _, pb = _state_sizes(handle)
+    payload = state.payload
+    if is_tensor(payload):
+        if str(payload.dtype) != "torch.uint8":
+            raise ValueError(f"the payload is a uint8 tensor, not {payload.dtype}")
+        size = payload.numel()
+    else:
+        payload = np.asarray(payload)
+        if payload.dtype != np.uint8:
+            raise ValueError(f"the payload is a uint8 array, not {payload.dtype}")
+        size = payload.size
+    if size != fields["payload_bytes"] or size != pb:
+        raise ValueError(f"the payload has {size} bytes, the header says {fields['payload_bytes']} and the handle takes {pb}")
+    if is_device_tensor(payload):
+        import torch
+        dev = torch.device("cuda", device)
+        # a payload on another GPU: a peer (or staged) copy into the handle's device, ordered by torch on the current streams
+        payload = payload.reshape(-1).to(dev, non_blocking=True).contiguous()
+        stream = torch.cuda.current_stream(dev)
+        check(lib().repet_online_import_stream_device(handle, slot, state.header, C.c_void_p(payload.data_ptr()),
+                                                      _stream_handle(stream)))
+        payload.record_stream(stream)
+    else:
+        if is_tensor(payload):
+            payload = payload.numpy()
+        payload = np.ascontiguousarray(payload).reshape(-1)
+        check(lib().repet_online_import_stream(handle, slot, state.header, ptr(payload)))
+    return fields
+
+
 class OnlineSeparator:
     """Streaming online REPET-SIM: ``push(chunk)`` returns the background samples that became final,
     ``finish()`` the rest; the concatenation equals ``repet.simonline`` of the whole signal. ``which`` ("background",
-    "foreground", "mixture", "both") selects the signal of those samples, see ``repet.online``."""
+    "foreground", "mixture", "both") selects the signal of those samples, see ``repet.online``. ``export_stream()`` returns
+    the stream's state as a ``StreamState`` and ``import_stream(state)`` loads one, see ``repet.online_streams``."""
 
     def __init__(self, params, n_channels, device=0):
         self._h = C.c_void_p()
         self._channels = int(n_channels)
         self._window = int(params.window_length)
+        self._device = int(device)
         if lib().repet_device_count() < 1:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open(int(device), self._channels, C.byref(params), C.byref(self._h)))
@@ -712,6 +850,16 @@ class OnlineSeparator:
             check(rc)
             outs = [o[:written.value].copy() for o in outs]
             return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def export_stream(self):
+        """A snapshot of the stream's state (a ``StreamState`` with a host payload); the stream goes on untouched. ValueError
+        unless the samples pushed so far are a multiple of the hop."""
+        return _export_state(self._h, 0)
+
+    def import_stream(self, state):
+        """Drop what the separator has heard and go on as the stream ``state`` was exported from (any handle opened with
+        the same parameters). ValueError, with nothing changed, for a state of other parameters or off the hop grid."""
+        _import_state(self._h, 0, state, self._device)
 
     def close(self):
         if self._h:
@@ -910,6 +1058,31 @@ class OnlineStreams:
         check(lib().repet_online_release_streams(self._handle(), arr, len(slots)))
         for s in slots:
             self._begun[s] = None
+
+    @property
+    def stream_state_nbytes(self):
+        """Bytes of the payload of a ``StreamState`` of this handle (they depend on the sampling frequency, the buffer
+        length and the channel count alone)."""
+        return _state_sizes(self._handle())[1]
+
+    def export_stream(self, slot, device=False):
+        """A snapshot of the stream that lives in ``slot`` as a ``StreamState``; the slot lives on untouched and
+        ``last_emission`` stays valid (migration is ``export_stream`` + ``release``; a snapshot imported twice is a fork).
+        ``device=True``: the payload is a ``torch.uint8`` tensor on the handle's device, ordered on the current torch stream
+        with no host wait; otherwise a ``numpy.uint8`` array (this form waits for its copy). ValueError for an idle slot or
+        unless ``samples_pushed`` is a multiple of the hop."""
+        return _export_state(self._handle(), self._slot(slot), self._device if device else None)
+
+    def import_stream(self, slot, state):
+        """Load ``state`` (a ``StreamState`` of a handle opened with the same parameters) into ``slot``, dropping what lived
+        there as ``restart`` does: the slot goes on bit for bit as the exporting one would have. The payload may be a host
+        array or a ROCm tensor on any device (a device payload enqueues only). ValueError, before any launch and with nothing
+        changed, unless ``samples_pushed`` is a multiple of the hop, and for a state of another geometry or other
+        parameters, a payload of the wrong size or dtype, or an unknown magic word or version. ``last_emission`` becomes
+        stale."""
+        slot = self._slot(slot)
+        fields = _import_state(self._handle(), slot, state, self._device)
+        self._begun[slot] = self._pushed - fields["length_samples"]
 
     def stream_emit_count(self, slot):
         """Samples ``finish_stream(slot)`` will return. ValueError for an idle slot or a stream shorter than the buffer."""

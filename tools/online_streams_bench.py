@@ -10,7 +10,14 @@ call plus a synchronize), beside the same schedule on S separate ``repet.online`
 stream and keep the rest: every hop is S pushes, a departure is one handle's ``finish`` and a new ``repet.online``.
 
 ``--which background,foreground,both``: the one-handle device-chunk cases once per selection, one after another in the same
-session (``one_handle_device_chunks`` is the background's; the others carry their name)."""
+session (``one_handle_device_chunks`` is the background's; the others carry their name).
+
+``--migrate 1``: instead, a stream moved between slots. One handle of S slots past its warm-up, device chunks of one hop; after
+every timed push one slot's stream is exported (``export_stream(slot, device=True)``) and imported into the spare slot
+(``import_stream``), each call timed with a synchronize; the host forms (payload through host memory) a few times beside them.
+In the same run, what a caller without these calls would do to keep a stream's background: replay its last ``buffer_frames``
+hops, here as one device push into a restarted one-slot handle (the cheapest form: on the S-slot handle the replay would be
+pushed in lockstep through every slot)."""
 import argparse
 import json
 import sys
@@ -177,8 +184,74 @@ def churn_separate_handles(xs, fs, every, timed, warm_s):
             "hops_timed": len(plain), "lifecycle_pairs": len(finish)}
 
 
+def migrate_one_handle(xs, fs, timed, warm_s):
+    import torch
+    S, N, ch = xs.shape
+    p = repet.derive_params(fs)
+    hop, B = p.step_length, p.buffer_frames
+    src = torch.tensor(xs, device="cuda:0")
+    h = repet.online_streams(fs, ch, S, max_push_samples=hop)
+    h.release(S - 1)                                           # the spare slot every export is imported into
+    pos = 0
+    while pos < warm_s * fs // hop * hop:
+        n = min(fs // 2 // hop * hop, warm_s * fs // hop * hop - pos)
+        h.push(src[:, pos:pos + n])
+        pos += n
+    out = torch.empty((S, hop, ch), dtype=torch.float64, device="cuda:0")
+    for _ in range(3):
+        h.push(src[:, pos:pos + hop], out=out)
+        pos += hop
+    h.import_stream(S - 1, h.export_stream(0, device=True))    # (both launches have run once before the clock starts)
+    torch.cuda.synchronize()
+    plain, export, load, k = [], [], [], 0
+    while k < timed and pos + hop <= N:
+        t0 = time.perf_counter()
+        h.push(src[:, pos:pos + hop], out=out)
+        torch.cuda.synchronize()
+        plain.append(time.perf_counter() - t0)
+        pos += hop
+        t0 = time.perf_counter()
+        state = h.export_stream(k % (S - 1), device=True)
+        torch.cuda.synchronize()
+        export.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        h.import_stream(S - 1, state)
+        torch.cuda.synchronize()
+        load.append(time.perf_counter() - t0)
+        k += 1
+    export_host, load_host = [], []
+    for k in range(5):
+        t0 = time.perf_counter()
+        state = h.export_stream(k, device=False)
+        export_host.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        h.import_stream(S - 1, state)
+        torch.cuda.synchronize()
+        load_host.append(time.perf_counter() - t0)
+    nbytes = h.stream_state_nbytes
+    h.close()
+    one = repet.online_streams(fs, ch, 1, max_push_samples=B * hop)
+    back = torch.empty((1, B * hop, ch), dtype=torch.float64, device="cuda:0")
+    one.push(src[:1, pos - B * hop:pos], out=back[:, :one.emit_count(B * hop)])
+    torch.cuda.synchronize()
+    replay = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        one.restart(0)
+        one.push(src[:1, pos - B * hop:pos], out=back[:, :one.emit_count(B * hop)])
+        torch.cuda.synchronize()
+        replay.append(time.perf_counter() - t0)
+    one.close()
+    ms = lambda v: round(float(np.median(np.array(v) * 1e3)), 3) if v else None
+    return {"payload_bytes": nbytes, "hop_ms": round(1e3 * hop / fs, 2), "push_ms_median": ms(plain),
+            "export_device_ms_median": ms(export), "import_device_ms_median": ms(load),
+            "export_host_ms_median": ms(export_host), "import_host_ms_median": ms(load_host),
+            "replay_buffer_one_slot_ms_median": ms(replay), "replay_hops": B, "calls_timed": len(export)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--migrate", type=int, default=0, help="1: the migrate leg (export_stream / import_stream per call)")
     ap.add_argument("--streams", default="1,8,64,256")
     ap.add_argument("--hops", default="1,4")
     ap.add_argument("--timed", type=int, default=60, help="pushes timed per case")
@@ -192,6 +265,14 @@ def main():
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
+    if args.migrate > 0:
+        hop = repet.derive_params(fs).step_length
+        result = {"fs": fs, "channels": ch, "cases": []}
+        for S in streams:
+            xs = stream_signals(S, warm_s + 1 + (args.timed + 8) * hop / fs, fs, ch)
+            result["cases"].append(dict({"streams": S}, **migrate_one_handle(xs, fs, args.timed, warm_s)))
+        print(json.dumps(result, indent=1))
+        return
     if args.churn > 0:
         hop = repet.derive_params(fs).step_length
         result = {"fs": fs, "channels": ch, "churn_every_pushes": args.churn, "cases": []}
