@@ -528,6 +528,37 @@ int repet_online_import_stream(repet_online* h, int32_t slot, const void* header
 int repet_online_import_stream_device(repet_online* h, int32_t slot, const void* header, const void* payload_dev,
                                       void* wait_stream);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) Separation that STARTS BEFORE THE BUFFER IS FULL. The
+ * reference writes nothing until its buffer holds B = buffer_frames frames (10 s at the defaults, repet.py:795-834) only because
+ * its warm-up loop is written that way; what it does at its first processed frame is well defined on a buffer that is still
+ * growing. With M = start_frames, 1 <= M <= B (M = B: the reference, the default everywhere), a stream's own frames j = 0, 1, ...:
+ *   j < M - 1        : a warm-up frame as before -- mask 0, nothing added to the background, the foreground is the input;
+ *   M - 1 <= j < B - 1 : a YOUNG frame. The buffer is the stream's own frames 0 .. j in columns 0 .. j (the circular position
+ *                      equals the frame number while j < B). The similarity vector has j + 1 elements and
+ *                      _localmaxima(vector, similarity_threshold, similarity_distance2, similarity_number) runs on exactly
+ *                      those: the columns past j are ABSENT, not zero (repet.py:1322-1326 clips its windows at the vector's
+ *                      ends). Median, np.minimum, mask, high-pass rule and overlap-add as in repet.py:869-898. Element for
+ *                      element this is what the reference computes for its first processed frame when buffer_length2 == j + 1.
+ *                      While j <= similarity_distance2 the frame's only similar frame is itself: its mask is 1, the whole
+ *                      input counts as background and the foreground is silent -- a sensible M is two or three times
+ *                      similarity_distance2 at least;
+ *   j >= B - 1       : unchanged, bit for bit.
+ * A stream is too short (REPET_ERR_TOO_SHORT of finish / finish_stream / execute) when it has fewer than (M - 2) H + W samples:
+ * the rule above with M in place of B. emit_count and stream_emit_count do not change (the warm-up emits its hops as zeros
+ * already), and a push enqueues the same launches whatever M is.
+ * repet_online_set_start_frames : M of the handle, for every slot and every later restart. Only before the handle's first push
+ *                   (REPET_ERR_BAD_ARG afterwards, and for a value outside [1, B]; nothing changes then).
+ * repet_online_start_frames     : the handle's M.
+ * repet_ctx_set_online_start    : M of REPET_SIMONLINE runs of this context alone (one clip or a batch); 0 = B, the reference.
+ *                   Checked against B when the run executes (REPET_ERR_BAD_ARG for M > B). repet_ctx_last_sim_indices then
+ *                   returns T - M + 1 rows, for frames M - 1 .. T - 1.
+ * Migration: M belongs to the HANDLE, not to the stream. The 96-byte header and the payload are unchanged; export_stream of a young
+ * stream works as for any other (the state holds right-aligned history rows, zero where the stream is younger), and an imported
+ * stream goes on under the importing handle's M -- bit for bit where both handles have the same M. */
+int repet_online_set_start_frames(repet_online* h, int32_t start_frames);
+int repet_online_start_frames(repet_online* h, int32_t* out);
+int repet_ctx_set_online_start(repet_ctx* ctx, int32_t start_frames);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) The FOREGROUND, aligned. The repeating background is the
  * means; audio - background is what most callers want, and a live handle returns its background behind the input (n_emit != n),
  * so only the handle knows which input samples an emission belongs to. One selector with one meaning everywhere: */

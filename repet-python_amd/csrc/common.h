@@ -286,8 +286,10 @@ struct PeakRefine {
 // batch (nullable): blockIdx.y = clip of a batch of equal-shape matrices; element strides between the clips
 // origin (nullable; modes 1 and 2, the streaming handle's slots): frame number at which clip b's own stream began. The clip's rows
 // are numbered from there (row0 and shift both count from origin[b]: circular positions are those of the clip's own frames,
-// the band rows stay where they are), and a row younger than n_cols - 1 frames is not active: count 0, no list.
-struct PeakBatch { int32_t n_batch; int64_t m_stride, idx_stride, cnt_stride, unit_stride; const int64_t* origin; };
+// the band rows stay where they are), and a row younger than start - 1 frames is not active: count 0, no list.
+// start (0: n_cols): the clip's row j >= start - 1 is decided on min(n_cols, j + 1) columns, the frames 0 .. j of its own stream
+// while its buffer is still filling (peaks.h: row_columns). Modes 1 and 2 count their columns so with or without a batch.
+struct PeakBatch { int32_t n_batch; int64_t m_stride, idx_stride, cnt_stride, unit_stride; const int64_t* origin; int32_t start; };
 hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int32_t n_cols, int64_t pitch,
                                int32_t mode, float min_value, int32_t d, int32_t number, int32_t* idx,
                                int32_t idx_pitch, int32_t* count, hipStream_t s, int64_t shift = 0,

@@ -737,6 +737,13 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     return REPET_OK;
 }
 
+int repet_ctx_set_online_start(repet_ctx* c, int32_t start_frames) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (start_frames < 0) return fail(REPET_ERR_BAD_ARG, "start_frames must be >= 0 (0: buffer_frames, the reference)");
+    c->online_start = start_frames;
+    return REPET_OK;
+}
+
 int repet_ctx_select_result(repet_ctx* c, int which) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     if (which < REPET_OUT_BACKGROUND || which > REPET_OUT_MIXTURE)

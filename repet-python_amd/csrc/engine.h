@@ -117,6 +117,7 @@ struct repet_ctx {
     hipEvent_t io_wait = nullptr, io_done = nullptr;
     DevBuf nonfinite_word;
     int result_which = REPET_OUT_BACKGROUND;   // what repet_ctx_download_device_strided writes (repet_ctx_select_result)
+    int online_start = 0;         // simonline: start_frames of this context (repet_ctx_set_online_start; 0: buffer_frames, the reference)
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
     DevBuf X, V, Vn, P, S, band, beat, idx, cnt, periods, win_periods, frames, tmp_a, tmp_b, tmp_c;

@@ -30,6 +30,9 @@ struct repet_online {
     bool slots_on = false;
     int64_t latest_start = 0, n_idle = 0;
     int C = 0, W = 0, H = 0, F = 0, FS = 0, B = 0, Hh = 0, LP = 0;
+    // start_frames (repet_online_set_start_frames; B: the reference): a stream's frames M-1 .. B-2 are separated on its buffer as
+    // far as it has filled (peaks.h: row_columns). The handle's, for every slot and restart; the launches are the same for any M.
+    int M = 0;
     // per stream s, at the strides below: X / V [C planes of rows_cap + kPadRows rows][FS], Vn [rows_cap rows][FS], the
     // pending samples [pend_cap][C] (pend_lo: their fp32 remainders), and in the per-push workspaces band / idx / cnt / outf
     DevBuf X[2], V[2], Vn[2], pend[2], pend_lo[2], band, outf, out64, staging;
@@ -197,7 +200,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
             {nullptr, reinterpret_cast<float*>(Xb) + 2 * hv, 2 * nn, o->C, 0, 2 * plane, 0, 2 * spec, 2 * (int64_t)o->FS, o->frames_done}};
         HIP_TRY(launch_row_copies(zero, early ? 4 : 1, S, c->stream, starts));
 
-        const int64_t first_active = std::max<int64_t>(o->frames_done, o->B - 1);     // global frame number
+        const int64_t first_active = std::max<int64_t>(o->frames_done, o->M - 1);     // global frame number
         const int64_t n_active = o->frames_done + n_new - first_active;
         const int K = o->p.sim_number, KP = std::max(K, kMinIdxPitch);
         if (n_active > 0) {
@@ -209,7 +212,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
             HIP_TRY(c->cnt.ensure((size_t)S * n_active * sizeof(int32_t)));
             PeakRefine rf{};
             RP_TRY(make_refine(c, Vnb, o->FS, o->p.sim_threshold, &rf, n_active, S, o->B, o->p.sim_distance_frames, Tpad));
-            const PeakBatch pb{S, band_stride, n_active * KP, n_active, vns, starts};
+            const PeakBatch pb{S, band_stride, n_active * KP, n_active, vns, starts, o->M};
             const PeakBatch* batch = (S > 1 || starts) ? &pb : nullptr;
             hipError_t e = launch_local_maxima(o->band.as<float>(), n_active, first_active, o->B, o->LP, peak_mode, (float)o->p.sim_threshold,
                                                o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), c->stream,
@@ -228,7 +231,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         m.V = Vb; m.chan_stride = plane; m.n_channels = o->C; m.T = Tw; m.F = o->F; m.FS = o->FS; m.X = Xb; m.mask = nullptr;
         m.cutoff = o->p.cutoff_bins; m.pad_row = o->rows_cap - r0; m.frame0 = o->hist_valid;
         m.n_batch = S; m.batch_stride = spec;
-        m.slot_start = starts; m.slot_bias = first_global - (o->B - 1);     // row t is the slot's frame first_global + t - start
+        m.slot_start = starts; m.slot_bias = first_global - (o->M - 1);     // row t is the slot's frame first_global + t - start
         m.idx_batch_stride = std::max<int64_t>(n_active, 0) * KP; m.cnt_batch_stride = std::max<int64_t>(n_active, 0);
         const int64_t first_frame = Tw - std::max<int64_t>(n_active, 0);          // warm-up rows before it are zeroed
         const int max_peaks = (int)std::min<int64_t>(K, ceil_div(o->B, o->p.sim_distance_frames + 1));
@@ -282,7 +285,7 @@ int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (finishing) {
         const int64_t N = o->total_in;
-        if (N < (int64_t)(o->B - 2) * o->H + o->W)      // the reference's warm-up needs B-1 whole frames (repet.py:795-810)
+        if (N < (int64_t)(o->M - 2) * o->H + o->W)      // the warm-up needs M-1 whole frames (the reference's, M = B: repet.py:795-810)
             return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
         const int64_t T = repet_frame_count(N, o->W, o->H, 0);                   // repet.py:781, last frame zero-padded
         *n_new = std::max<int64_t>(T - o->frames_done, 0);
@@ -469,7 +472,7 @@ int online_plan_slot(const repet_online* o, int32_t slot, int64_t* n_new, int64_
     const int64_t st = o->start[(size_t)slot];
     if (st == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
     const int64_t N = o->total_in - st * (int64_t)o->H;
-    if (N < (int64_t)(o->B - 2) * o->H + o->W)
+    if (N < (int64_t)(o->M - 2) * o->H + o->W)
         return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
     return online_plan(o, 0, true, n_new, n_emit);
 }
@@ -585,7 +588,8 @@ int online_import_check(const repet_online* o, int32_t slot, const StateHeader* 
 // move by delta hops (frames done and held samples as a handle of that age has them), every live slot's first frame moves with
 // them (the device table: by the import launch that follows), and the held samples of every slot move behind delta * H zeros
 // -- the samples before their starts -- into the other pending buffer: one launch. The history rows this exposes were never
-// written (zeroed at allocation, kept so by the slide and the resets). Only while the handle is younger than B - 1 frames.
+// written (zeroed at allocation, kept so by the slide and the resets). Only while the handle is younger than B - 1 frames, whatever start_frames is: a slot's own
+// frame numbers do not move with the epoch, so its young rows (from its frame M - 1 on) are the same rows before and after.
 static int online_shift_epoch(repet_online* o, int64_t delta) {
     repet_ctx* c = o->ctx;
     const int64_t by = delta * o->H, old_held = o->pend_hist + o->pend_count;
@@ -719,6 +723,20 @@ int repet_online_last_emission_device(repet_online* o, int which, void* dst, int
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
     *n_written = o->em.n;
+    return REPET_OK;
+}
+
+int repet_online_set_start_frames(repet_online* o, int32_t start_frames) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->total_in != 0 || o->epoch != 0 || o->finished) return fail(REPET_ERR_BAD_ARG, "online: start_frames can only be set before the first push");
+    if (start_frames < 1 || start_frames > o->B) return fail(REPET_ERR_BAD_ARG, "online: start_frames must lie in [1, buffer_frames]");
+    o->M = start_frames;
+    return REPET_OK;
+}
+
+int repet_online_start_frames(repet_online* o, int32_t* out) {
+    if (!o || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *out = o->M;
     return REPET_OK;
 }
 
@@ -860,7 +878,7 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
     int rc = repet_ctx_create(device, &o->ctx);
     if (rc != REPET_OK) { delete o; return rc; }
     o->p = *p; o->S = n_streams; o->C = n_channels; o->W = p->window_length; o->H = p->step_length; o->F = o->W / 2 + 1;
-    o->FS = (int)round_up(o->F, kFreqAlign); o->B = p->buffer_frames; o->Hh = o->B - 1; o->LP = (int)round_up(o->B, 64);
+    o->FS = (int)round_up(o->F, kFreqAlign); o->B = p->buffer_frames; o->M = o->B; o->Hh = o->B - 1; o->LP = (int)round_up(o->B, 64);
     o->max_push = max_push_samples;
     o->start.assign((size_t)n_streams, 0);
     {   // every slot's stream begins with the handle's until a restart or release says otherwise

@@ -277,7 +277,11 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     const int64_t N = c->n_samples;
     const int W = p->window_length, H = p->step_length, B = p->buffer_frames;
     if (B < 1) return fail(REPET_ERR_BAD_ARG, "buffer length must be >= 1 frame");
-    if (N < (int64_t)(B - 2) * H + W)   // the warm-up slices B-1 whole frames (repet.py:795-810)
+    // start_frames M (repet_hip.h: repet_online_set_start_frames): frames M-1 .. B-2 are separated on the buffer as far as it has
+    // filled, min(B, j + 1) columns for frame j; M = B is the reference
+    const int M = c->online_start > 0 ? c->online_start : B;
+    if (M > B) return fail(REPET_ERR_BAD_ARG, "simonline: start_frames must lie in [1, buffer_frames]");
+    if (N < (int64_t)(M - 2) * H + W)   // the warm-up slices M-1 whole frames (repet.py:795-810 with M = B)
         return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
     const int64_t T = repet_frame_count(N, W, H, 0);
     const Geo g = make_geo(W, H, T, c->n_channels);
@@ -293,36 +297,36 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     const int peak_mode = c->band_lookback ? 2 : 1;
     mark(c, c->band_on_f16 ? "similarity_band_f16x3" : "similarity_band", nb * (4.0 * g.F * T + 4.0 * T * B), nb * 2.0 * g.F * (double)T * B);
     const int K = p->sim_number, KP = std::max(K, kMinIdxPitch);
-    const int64_t rows = T >= B ? T - B + 1 : 0;
+    const int64_t rows = T >= M ? T - M + 1 : 0;
     const int64_t rows_alloc = std::max<int64_t>(rows, 1);
     HIP_TRY(c->idx.ensure((size_t)nb * rows_alloc * KP * sizeof(int32_t)));
     HIP_TRY(c->cnt.ensure((size_t)nb * rows_alloc * sizeof(int32_t)));
     PeakRefine rf{};
     RP_TRY(make_refine(c, c->Vn.as<float>(), g.FS, p->sim_threshold, &rf, rows, nb, B, p->sim_distance_frames, T));
     const PeakBatch pb{nb, band_stride, rows_alloc * KP, rows_alloc, mean_stride};
-    hipError_t e = launch_local_maxima(c->band.as<float>(), rows, B - 1, B, LP, peak_mode, (float)p->sim_threshold,
+    hipError_t e = launch_local_maxima(c->band.as<float>(), rows, M - 1, B, LP, peak_mode, (float)p->sim_threshold,
                                        p->sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), c->stream, 0, &rf,
                                        nb > 1 ? &pb : nullptr);
     if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "simonline: buffer too long for the peak-picking kernel");
     HIP_TRY(e);
     if (rows > 0)
-        RP_TRY(run_exact_rows(c, tb, g, c->band.as<float>(), B - 1, B, LP, peak_mode, (float)p->sim_threshold, p->sim_distance_frames, K,
+        RP_TRY(run_exact_rows(c, tb, g, c->band.as<float>(), M - 1, B, LP, peak_mode, (float)p->sim_threshold, p->sim_distance_frames, K,
                               c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), 0, rf, nb > 1 ? &pb : nullptr,
                               c->audio.as<float>() + c->clip_base * g.C, c->has_lo ? c->audio_lo.as<float>() + c->clip_base * g.C : nullptr,
                               N, N * g.C, 0, T, nb));
     mark(c, "local_maxima", nb * (4.0 * rows * B + 4.0 * K * rows), 0);
     const int max_peaks = (int)std::min<int64_t>(K, ceil_div(B, p->sim_distance_frames + 1));
-    if (c->nonfinite_passes() && B > 1) {
+    if (c->nonfinite_passes() && M > 1) {
         // strict reference mode: repet.py never writes the warm-up frames (repet.py:834: its background stays 0 there); the engine
         // gives them the mask 0, and 0 x NaN would be NaN -- their spectra (which only the inverse STFT still reads) are cleared
         for (int b = 0; b < nb; ++b)
             for (int ch = 0; ch < g.C; ++ch)
                 HIP_TRY(hipMemsetAsync(c->X.as<float2>() + b * spec_stride + ch * g.chan_stride, 0,
-                                       (size_t)std::min<int64_t>(B - 1, T) * g.FS * sizeof(float2), c->stream));
+                                       (size_t)std::min<int64_t>(M - 1, T) * g.FS * sizeof(float2), c->stream));
     }
     MaskArgs m = mask_args(c, g, p->cutoff_bins);
     m.n_batch = nb; m.batch_stride = spec_stride; m.idx_batch_stride = rows_alloc * KP; m.cnt_batch_stride = rows_alloc;
-    HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), B - 1, max_peaks, c->stream));
+    HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), M - 1, max_peaks, c->stream));
     mark(c, "mask_sim", nb * (4.0 + 4.0 * K + (c->mask_plane ? 4.0 : 16.0)) * g.F * (double)rows * g.C, 0);
     if (nb == 1) {
         RP_TRY(run_istft(c, g, tb, 0, N, 0, false, 0, 0));

@@ -6,6 +6,11 @@ namespace repet {
 
 // mode: 0 = rows of a full matrix; 1 = simonline on band[t][l] = sim(t, t + l): element i of row j is frame j - ((j - i) mod n),
 // a walk down a diagonal; 2 = the same elements in the look-back band[j][l] = sim(j, j - l): row j is contiguous
+// n: the launch's row length on the host; in the kernels of modes 1 and 2 it is OVERWRITTEN with the row's own length
+// (row_columns) once the row is known, AFTER the LDS has been carved from groups / peak_cap, which stay sized by the launch's n.
+// Nothing sized from n may be added behind that point. Who does which: local_maxima_wave_kernel and local_maxima_lite_kernel
+// (peaks_wave.hip) overwrite a.n itself, because wave_finish_row and the record path read it; local_maxima_kernel (peaks.hip)
+// and local_maxima_exact_kernel (peaks_exact.hip) keep the row's length in a local `n` and leave a.n launch-wide.
 struct PeakArgs {
     const float* M; int64_t row0; int n; int64_t pitch; int mode; float min_value; int d; int number;
     int* idx; int idx_pitch; int* count; int dl; int groups; int peak_cap; int64_t shift;
@@ -31,6 +36,7 @@ struct PeakArgs {
     // only where a window's edge cuts a segment whose maximum lies outside it, and around near-ties.
     const float* seg; int seg_pitch;
     const int64_t* origin;         // (nullable) PeakBatch::origin
+    int start;                     // PeakBatch::start (n when the batch names none): with an origin, rows before start - 1 have no list
 };
 
 // diagnostics counters (common.h: kStatShards): the copy of this workgroup
@@ -46,6 +52,13 @@ __device__ __forceinline__ void apply_origin(PeakArgs& a, int clip) {
     const int64_t o = a.origin[clip];
     a.row0 -= o;
     a.shift -= o;
+}
+// Columns of row j (modes 1 and 2). The buffer of a stream holds its own frames only: while it is still filling, row j has the
+// j + 1 columns 0 .. j (circular position = frame number), and the columns past j are ABSENT, not zero -- the windows are
+// clipped at column j as they are at column n - 1 of a full buffer (repet.py:1322-1326). From row n - 1 on this is n. The row
+// is uniform per wavefront (block index, origin), so the result lives in a scalar register; LDS stays sized by n.
+__device__ __forceinline__ int row_columns(const PeakArgs& a, int64_t j) {
+    return (a.mode != 0 && j + 1 < (int64_t)a.n) ? (int)(j + 1) : a.n;
 }
 __device__ __forceinline__ void flag_row_for_exact(const PeakArgs& a, int64_t r, int clip) {
     if (!a.redo_list) return;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
     __shared__ unsigned char amb_ok[kAmbCap], amb_lose[kAmbCap];
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int n = a.n, d = a.d, dl = a.dl;
+    const int d = a.d, dl = a.dl;
     const int groups = (STAGE == 2) ? 0 : a.groups;      // stage 2 has no row: every row loop below is empty
     a.M += blockIdx.y * a.m_stride;
     a.idx += blockIdx.y * a.idx_stride;
@@ -75,12 +75,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
     if (a.unit) a.unit += blockIdx.y * a.unit_stride;
     const int64_t r = blockIdx.x;           // row within this launch
     apply_origin(a, blockIdx.y);
-    if (a.origin && a.row0 + r < n - 1) {   // a slot of the streaming handle still warming up (or idle): no list
+    if (a.origin && a.row0 + r < a.start - 1) {   // a slot of the streaming handle still warming up (or idle): no list
         for (int k = tid; k < a.number; k += 256) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
         if (tid == 0) a.count[r] = 0;
         return;
     }
     const int64_t j = a.row0 + r;           // absolute row (mode 1: current frame)
+    const int n = row_columns(a, j);        // (uniform per workgroup) a.n, or j + 1 while the stream's buffer is filling
     if (tid == 0) { n_peak = 0; n_amb = 0; n_riv = 0; n_unl = 0; n_close = 0; }
     float dlt = a.delta;                    // 0: no refinement
     const int seg = (STAGE == 1) ? (int)blockIdx.z : 0;
@@ -536,6 +537,7 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
     a.number = number; a.idx = idx; a.idx_pitch = idx_pitch; a.count = count; a.shift = shift;
     a.min_value64 = min_value;
     a.seg = seg; a.seg_pitch = seg_pitch;
+    a.start = (batch && batch->start > 0) ? batch->start : n_cols;
     if (refine && refine->unit_rows && refine->delta > 0.0f && (refine->pitch & 3) == 0) {
         a.unit = refine->unit_rows; a.unit_pitch = refine->pitch; a.delta = refine->delta;
         a.min_value64 = refine->min_value; a.stats = refine->stats;

@@ -687,8 +687,9 @@ __global__ __launch_bounds__(kExactThreads) void local_maxima_exact_kernel(Exact
         a.count += clip * a.cnt_stride;
         a.unit += clip * a.unit_stride;
         apply_origin(a, clip);
-        const int n = a.n, d = a.d;
+        const int d = a.d;
         const int64_t j = a.row0 + r;
+        const int n = row_columns(a, j);                        // (the scratch row stays sized by a.n: x.n4)
         const float dlt = a.delta;
         const double d2 = x.delta2, thr64 = a.min_value64;
         auto lag_of = [&](int i) -> int { int l = (int)(j - i) % n; return l < 0 ? l + n : l; };
@@ -1040,6 +1041,7 @@ hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_col
     a.number = number; a.idx = idx; a.idx_pitch = idx_pitch; a.count = count; a.shift = shift;
     a.unit = refine->unit_rows; a.unit_pitch = refine->pitch; a.delta = refine->delta;
     a.min_value64 = refine->min_value; a.stats = refine->stats;
+    a.start = (batch && batch->start > 0) ? batch->start : n_cols;
     if (batch && batch->n_batch > 0) {
         a.m_stride = batch->m_stride; a.idx_stride = batch->idx_stride; a.cnt_stride = batch->cnt_stride;
         a.unit_stride = batch->unit_stride;

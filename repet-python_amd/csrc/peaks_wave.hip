@@ -532,18 +532,19 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
     const int64_t r = (int64_t)blockIdx.x;                   // row within this launch
     if (r >= n_rows) return;
     const WaveLds L = carve(wave_smem + (size_t)wave * lds_per_wave, a.peak_cap, a.groups);
-    const int n = a.n, d = a.d;
+    const int d = a.d;
     a.M += blockIdx.y * a.m_stride;
     a.idx += blockIdx.y * a.idx_stride;
     a.count += blockIdx.y * a.cnt_stride;
     if (a.unit) a.unit += blockIdx.y * a.unit_stride;
     apply_origin(a, blockIdx.y);
-    if (a.origin && a.row0 + r < n - 1) {                    // a slot of the streaming handle still warming up (or idle): no list
+    if (a.origin && a.row0 + r < a.start - 1) {              // a slot of the streaming handle still warming up (or idle): no list
         for (int k = lane; k < a.number; k += 64) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
         if (lane == 0) a.count[r] = 0;
         return;
     }
     const int64_t j = a.row0 + r;                            // absolute row (mode 1: current frame)
+    const int n = a.n = row_columns(a, j);                   // (uniform per wavefront) everything below, wave_finish_row included, sees the row's own length
     float dlt = a.delta;                                     // 0: no refinement
 
     // element i of the row for an index known to lie in [0, n), without a branch: loads of a batch must not each sit behind
@@ -1124,6 +1125,7 @@ __global__ __launch_bounds__(64) void local_maxima_lite_kernel(PeakArgs a0, Lite
         a.unit += clip * a.unit_stride;
         apply_origin(a, clip);
         const int64_t j = a.row0 + r;
+        a.n = row_columns(a, j);                               // the record's elements are columns of the row's own length
         const LiteRecord q = carve_record(a.records + (size_t)slot * a.record_bytes, a.peak_cap);
         const LiteHeader h = *q.h;
         bool missing = false, unchanged = false;

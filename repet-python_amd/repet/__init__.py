@@ -207,7 +207,7 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which)
 
 
-def online(sampling_frequency, number_channels):
+def online(sampling_frequency, number_channels, start_length=None):
     """Streaming form of :func:`simonline` (the reference needs the whole signal up front): returns an object with
     ``push(chunk) -> newly final background samples`` and ``finish() -> the remaining ones``. The module parameters are
     snapshotted now; the concatenated output equals ``simonline`` of the concatenated input.
@@ -219,11 +219,22 @@ def online(sampling_frequency, number_channels):
 
     ``export_stream()`` returns the stream's state as a :class:`StreamState` (a snapshot; only where the samples pushed so
     far are a multiple of the hop) and ``import_stream(state)`` loads one into this separator, which then goes on as the
-    exporting stream would have: see :func:`online_streams`."""
-    return _OnlineSeparator(derive_params(sampling_frequency), number_channels, _device)
+    exporting stream would have: see :func:`online_streams`.
+
+    ``start_length`` (seconds; None: ``buffer_length``, the reference): separate before the buffer has filled. The reference
+    writes nothing until its buffer holds ``buffer_length`` (10 s) of frames; with ``start_frames = min(buffer_frames, max(1,
+    round(start_length * fs / step_length)))`` (the ``start_frames`` property) a stream's frame ``j >= start_frames - 1`` is
+    separated on the ``min(buffer_frames, j + 1)`` frames it has heard so far -- exactly what the reference computes for its
+    first processed frame with a buffer of ``j + 1`` frames -- and from frame ``buffer_frames - 1`` on nothing changes, bit for
+    bit. Below ``start_length`` the foreground is still the input, as today, and a stream can be finished once it has
+    ``(start_frames - 2) * step_length + window_length`` samples. While ``j <= similarity_distance`` (in frames) a young
+    frame's only similar frame is itself: its mask is 1, so the whole input counts as background and the foreground is
+    silent. A sensible ``start_length`` is therefore at least two or three times ``similarity_distance``."""
+    params = derive_params(sampling_frequency)
+    return _OnlineSeparator(params, number_channels, _device, _native.start_frames_for(params, sampling_frequency, start_length))
 
 
-def online_streams(sampling_frequency, number_channels, number_streams, max_push_samples=None):
+def online_streams(sampling_frequency, number_channels, number_streams, max_push_samples=None, start_length=None):
     """Many live streams at once: ``number_streams`` streams of ``number_channels`` channels at one sampling frequency in ONE
     streaming handle on the device of :func:`set_device`, pushed in lockstep. ``push(chunk, out=None)`` takes a chunk
     ``(number_streams, n, number_channels)`` -- a host array, or a ROCm tensor (the dtypes :func:`separate` takes, any strides)
@@ -268,9 +279,19 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     in lockstep, then its ``finish_stream`` / ``finish`` tail, equal ``simonline`` of the stream's whole input bit for bit
     -- on a handle of any age, other live slots undisturbed; the foreground's delay line moves with the stream. (A handle
     on which nothing was pushed holds no sample yet, the state one hop that was never emitted: the first push after such
-    an import emits that hop, which is a hop of zeros in front of every other slot's own output.)"""
-    return _native.OnlineStreams(derive_params(sampling_frequency), number_channels, number_streams, _device,
-                                 max_push_samples or 0)
+    an import emits that hop, which is a hop of zeros in front of every other slot's own output.)
+
+    ``start_length`` (seconds; None: ``buffer_length``, the reference) lets every slot separate before its 10-s buffer has
+    filled, from its own frame ``start_frames - 1`` on (see :func:`online`; the ``start_frames`` property), after every
+    ``restart`` too: each life then equals the one-stream handle's output with the same ``start_length``, a stream of
+    ``(start_frames - 2) * step_length + window_length`` samples can be finished, and a push costs the launches it always
+    cost. While a young frame's number is at most ``similarity_distance`` (in frames) its only similar frame is itself: the
+    mask is 1, the whole input counts as background and the foreground is silent, so a sensible ``start_length`` is at least
+    two or three times ``similarity_distance``; below ``start_length`` the foreground is still the input. The value belongs
+    to the handle, not to a stream: an imported stream goes on under the importing handle's."""
+    params = derive_params(sampling_frequency)
+    return _native.OnlineStreams(params, number_channels, number_streams, _device, max_push_samples or 0,
+                                 _native.start_frames_for(params, sampling_frequency, start_length))
 
 
 def run_batch(algo, audio_signals, sampling_frequency, n_devices=1, transport="host", device=None, depth=None):

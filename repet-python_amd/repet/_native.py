@@ -176,6 +176,9 @@ _SIGNATURES = {
     "repet_online_last_emission": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_last_emission_device": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(C.c_int64)]),
     "repet_ctx_select_result": (C.c_int, [_P, C.c_int]),
+    "repet_online_set_start_frames": (C.c_int, [_P, C.c_int32]),
+    "repet_online_start_frames": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "repet_ctx_set_online_start": (C.c_int, [_P, C.c_int32]),
     "repet_select_run_result": (C.c_int, [C.c_int, C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -652,6 +655,12 @@ class Context:
         return {"rows_exact": out[0], "elements_exact": out[1], "rows_changed": out[2], "level2_max_diff": out[3] * 1e-12,
                 "unit_rows_f64": out[4], "input_has_remainders": bool(out[5]), "rows_fast_path": out[6], "rows_handed_on": out[7]}
 
+    def set_online_start(self, start_frames):
+        """``start_frames`` M of this context's ``simonline`` runs (see ``repet.online``): frames M - 1 .. buffer_frames - 2 are
+        separated on the buffer as far as it has filled, and ``last_sim_indices`` then has ``T - M + 1`` rows. 0: the reference
+        (buffer_frames). Checked against buffer_frames when a run executes (ValueError for a larger value)."""
+        check(lib().repet_ctx_set_online_start(self._h, int(start_frames)))
+
     def last_sim_indices(self, n_rows, number):
         idx = np.empty((max(n_rows, 1), number), dtype=np.int32)
         cnt = np.empty(max(n_rows, 1), dtype=np.int32)
@@ -667,6 +676,32 @@ def default_context(device=0):
     if ctx is None:
         ctx = _default_ctx[device] = Context(device)
     return ctx
+
+
+def start_frames_for(params, sampling_frequency, start_length):
+    """``start_length`` in seconds as frames, derived as buffer_frames is and clamped to [1, buffer_frames]; None stays None (the
+    handle is then opened as it always was)."""
+    if start_length is None:
+        return None
+    frames = int(round(start_length * sampling_frequency / params.step_length))
+    return min(int(params.buffer_frames), max(1, frames))
+
+
+def _set_start_frames(owner, start_frames):
+    """start_frames of a handle that was just opened (None: left alone); a refusal closes the handle before it is raised."""
+    if start_frames is None:
+        return
+    try:
+        check(lib().repet_online_set_start_frames(owner._h, int(start_frames)))
+    except Exception:
+        owner.close()
+        raise
+
+
+def _start_frames(handle):
+    out = C.c_int32()
+    check(lib().repet_online_start_frames(handle, C.byref(out)))
+    return out.value
 
 
 def _select_output(handle, codes, second=None, dtype=F64, strides=None):
@@ -813,7 +848,7 @@ class OnlineSeparator:
     "foreground", "mixture", "both") selects the signal of those samples, see ``repet.online``. ``export_stream()`` returns
     the stream's state as a ``StreamState`` and ``import_stream(state)`` loads one, see ``repet.online_streams``."""
 
-    def __init__(self, params, n_channels, device=0):
+    def __init__(self, params, n_channels, device=0, start_frames=None):
         self._h = C.c_void_p()
         self._channels = int(n_channels)
         self._window = int(params.window_length)
@@ -821,6 +856,12 @@ class OnlineSeparator:
         if lib().repet_device_count() < 1:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open(int(device), self._channels, C.byref(params), C.byref(self._h)))
+        _set_start_frames(self, start_frames)
+
+    @property
+    def start_frames(self):
+        """The stream's frame count from which it is separated (``start_length`` of ``repet.online``; buffer_frames: the reference)."""
+        return _start_frames(self._h)
 
     def push(self, audio_chunk, which="background"):
         codes = which_codes(which)
@@ -889,7 +930,7 @@ class OnlineStreams:
     foreground) from one pass, with ``out=`` a pair of tensors. ``last_emission(which)`` returns another signal of the samples
     the last of these calls emitted."""
 
-    def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0):
+    def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0, start_frames=None):
         self._h = C.c_void_p()
         self._channels = int(n_channels)
         self._streams = int(n_streams)
@@ -901,6 +942,7 @@ class OnlineStreams:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open_streams(self._device, self._streams, self._channels, C.byref(params),
                                               int(max_push_samples or 0), C.byref(self._h)))
+        _set_start_frames(self, start_frames)
         self._pushed = 0                              # samples per slot pushed so far
         self._emitted_shape = (self._streams, 0, self._channels)
         self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
@@ -909,6 +951,12 @@ class OnlineStreams:
     def shape(self):
         """(number_streams, number_channels)"""
         return self._streams, self._channels
+
+    @property
+    def start_frames(self):
+        """Frames of its own after which every slot's stream is separated (``start_length`` of ``repet.online_streams``;
+        buffer_frames: the reference). The handle's, for every slot and every restart."""
+        return _start_frames(self._handle())
 
     def _handle(self):
         if not self._h:

@@ -181,6 +181,11 @@ static void check_context_calls(void) {
     CHECK(repet_ctx_last_median_codes(NULL, NULL, 1, 1) != REPET_OK);
     CHECK(repet_ctx_download_input(NULL, fout, fout, &n32) != REPET_OK);
     CHECK(repet_mask_sim_ranked(NULL, fout, 2000, 1025, &n32, &n32, 100, 2, fout, NULL) != REPET_OK);
+    /* start_frames: the three calls refuse null handles and leave their output alone */
+    n32 = 7;
+    CHECK(repet_online_set_start_frames(NULL, 40) != REPET_OK);
+    CHECK(repet_online_start_frames(NULL, &n32) != REPET_OK && n32 == 7);
+    CHECK(repet_ctx_set_online_start(NULL, 40) != REPET_OK);
 
     const int devices = repet_device_count();
     repet_ctx* ctx = NULL;

@@ -17,7 +17,11 @@ every timed push one slot's stream is exported (``export_stream(slot, device=Tru
 (``import_stream``), each call timed with a synchronize; the host forms (payload through host memory) a few times beside them.
 In the same run, what a caller without these calls would do to keep a stream's background: replay its last ``buffer_frames``
 hops, here as one device push into a restarted one-slot handle (the cheapest form: on the S-slot handle the replay would be
-pushed in lockstep through every slot)."""
+pushed in lockstep through every slot).
+
+``--start-length SECONDS``: the one-handle cases on handles opened with ``start_length`` (separation from that age on, before
+the 10-s buffer has filled). The streams are then pushed only half a second past the start length, so the timed pushes are
+those of YOUNG frames, each decided on the frames heard so far; keep ``--timed`` x hops inside the buffer's first 10 s."""
 import argparse
 import json
 import sys
@@ -42,7 +46,7 @@ def stats(lat_s, n, fs):
             "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
 
 
-def one_handle(xs, fs, hops, device, timed, warm_s, which="background"):
+def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None):
     import torch
     S, N, ch = xs.shape
     hop = repet.derive_params(fs).step_length
@@ -50,7 +54,9 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background"):
     src = torch.tensor(xs, device="cuda:0") if device else xs
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info(0)[0]
-    h = repet.online_streams(fs, ch, S, max_push_samples=n)
+    h = repet.online_streams(fs, ch, S, max_push_samples=n, start_length=start_length)
+    if start_length is not None:
+        warm_s = start_length + 0.5                            # past the start length, far from a full buffer
     pos = 0
     while pos < warm_s * fs:                                   # fill the buffer in half-second pushes
         h.push(src[:, pos:pos + fs // 2], which=which)
@@ -70,9 +76,13 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background"):
             torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
         pos += n
+    h_start = h.start_frames
     h.close()
     out = stats(lat, n, fs)
     out["device_mb_per_stream"] = round(held / S / 2**20, 1)
+    if start_length is not None:
+        out["start_frames"] = h_start
+        out["stream_age_s_at_last_timed_push"] = round(pos / fs, 2)
     return out
 
 
@@ -262,6 +272,8 @@ def main():
     ap.add_argument("--churn-separate", type=int, default=1, help="0: skip the separate-handles side of the churn leg")
     ap.add_argument("--which", default="background",
                     help="comma list of background / foreground / mixture / both: what the one-handle device pushes deliver")
+    ap.add_argument("--start-length", type=float, default=None, metavar="SECONDS",
+                    help="open the one-handle cases with this start_length and time pushes of young frames (see above)")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
@@ -288,15 +300,17 @@ def main():
     hop = repet.derive_params(fs).step_length
     seconds = warm_s + 1 + (args.timed + 4) * max(hops_list) * hop / fs
     result = {"fs": fs, "channels": ch, "cases": []}
+    if args.start_length is not None:
+        result["start_length_s"] = args.start_length
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
             case = {"streams": S, "hops_per_push": hops}
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
-                case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which)
+                case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length)
             if args.only == "all":
-                case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s)
+                case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length)
                 if S <= args.separate_max:
                     case["separate_handles_host"] = separate_handles(xs, fs, hops, args.timed, warm_s)
             result["cases"].append(case)
