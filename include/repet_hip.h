@@ -593,6 +593,39 @@ int repet_online_last_emission_device(repet_online* h, int which, void* dst, int
 int repet_ctx_select_result(repet_ctx* ctx, int which);
 int repet_select_run_result(int device, int which);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) KEEP A CHOSEN SHARE OF THE BACKGROUND in the foreground.
+ * Dialogue enhancement, ducking and karaoke attenuate the repeating background by some decibels instead of removing it. A
+ * background gain g in [0, 1] changes what REPET_OUT_FOREGROUND means, wherever that selector already works (push*, finish*,
+ * finish_stream*, last_emission*, the second destination of also_emit, host and device forms, F64 and F32 destinations):
+ *     foreground = x - a * bg,   a = (float)(1.0 - (double)g)   (an fp32 value)
+ * computed as fma(-a, bg, x) in float64 by the egress launch itself: a * bg is fp32 x fp32 and exact, so the foreground is
+ * x - a * bg rounded once (an F32 destination rounds once more). g = 0, the default, is the foreground as it was, bit for bit
+ * (-12 dB of background: g = pow(10, -12.0 / 20)); g = 1 returns the input, except where bg is NaN or infinite (0 * NaN). The
+ * background and mixture signals, every counter and the exported stream state do not change; samples before a slot's own
+ * stream began stay zero.
+ * repet_online_set_background_gain : gains[k] for slots[k], k < n_slots; slots == NULL: gains[0] for every slot (n_slots is
+ *                   ignored). A slot named twice takes the last value. REPET_ERR_BAD_ARG, before anything is enqueued and with
+ *                   nothing changed, for a slot out of range or a gain that is NaN, infinite or outside [0, 1]. Enqueues only
+ *                   (one small launch per 256 slots named), no host wait. The gain is the SLOT's setting, not the stream's: it
+ *                   survives restart_streams, release_streams, finish_stream and import_stream, and it is not part of an
+ *                   exported state. A CHANGE IS A FADE: the first emitting call that covers the slot after a set (every slot
+ *                   for push* / finish*, the one slot for finish_stream*) moves a linearly from the value in force to the
+ *                   new one over its first R = min(step_length, n_emit) samples -- sample k (0-based, per stream) takes
+ *                   fma(a_new - a_old, (double)(k + 1) / R, a_old) in float64 for k + 1 < R and a_new itself from k + 1 == R
+ *                   on -- so the fade is complete when that call returns; it costs that call one small launch more, and a
+ *                   push in steady state enqueues exactly what it enqueued before. last_emission(REPET_OUT_FOREGROUND) returns
+ *                   what the emission's own gain and fade produced, whatever was set since. Before the first set on a
+ *                   handle no kernel is given a gain and everything is as it was.
+ * repet_online_background_gain     : the g last set for `slot` (0 before any set), from the host's copy: no device work.
+ * repet_ctx_set_background_gain    : g for the foreground repet_ctx_download_device_strided writes from now on (a scalar for
+ *                   every clip, no fade); the same range rule. 0 restores the original path.
+ * repet_set_run_background_gain    : the same for the calling thread's repet_run_device context of `device`, with the lifetime
+ *                   repet_select_run_result has (the value is checked before a context is made). */
+int repet_online_set_background_gain(repet_online* h, const int32_t* slots, int32_t n_slots, const float* gains);
+int repet_online_background_gain(repet_online* h, int32_t slot, float* gain_out);
+int repet_ctx_set_background_gain(repet_ctx* ctx, float gain);
+int repet_set_run_background_gain(int device, float gain);
+
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,
  * fp32 -> float64; non-temporal AVX-512 / AVX2 lines where the CPU has them) against scalar loops on n values with NaN,
  * infinities, denormals, PCM-exact runs and every misalignment. No GPU needed. Returns the number of values that differ

@@ -197,6 +197,11 @@ __global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, 
 // other sample is zero in all three signals by a select, so NaN in an idle slot's share of a chunk never shows.
 // EPT consecutive interleaved elements per thread as in egress_body: vector accesses on bg, on hi / lo where the run lies in
 // one stream and is aligned, on a dense destination.
+// Background gain (`gain` != 0; 0 is the path above, untouched): foreground = fma(-a, bg, x) in float64 with a an fp32 value, so
+// a * bg is exact and the foreground is x - a * bg rounded once. kGainScalar: a = `a` for every sample (offline contexts).
+// kGainTables: per stream s, for its sample j (0-based within this emission): a = a_tgt[s] where j + 1 >= ramp (a select), else
+// the fade fma(a_tgt[s] - a_cur[s], (j + 1) / ramp, a_cur[s]); a slot whose two entries are equal fades nowhere.
+constexpr int32_t kGainScalar = 1, kGainTables = 2;
 struct EmitOut { void* p; int64_t s_clip, s_sample, s_channel; int32_t which, dense; };
 struct EmitArgs {
     const float* bg; const float* hi; const float* lo;
@@ -204,6 +209,7 @@ struct EmitArgs {
     const int64_t* slot_start; int64_t pos0, hop;
     int32_t n_channels, n_out;
     EmitOut out[2];
+    const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
 };
 
 template <typename T, int EPT>
@@ -256,13 +262,36 @@ __device__ inline void emit_body(const EmitArgs& a) {
             live[k] = start < repet_eng::kSlotIdle && a.pos0 + r / a.n_channels >= start * a.hop;
         }
     }
+    double ak[EPT];
+    if (a.gain) {
+        int64_t s_of = -1;
+        double at = (double)a.a, ac = at;
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+            ak[k] = at;
+            if (a.gain == kGainTables && k < m) {
+                int64_t s = s0, r = r0 + k;
+                if (r >= a.per) { s += r / a.per; r %= a.per; }
+                if (s != s_of) {                                  // (one or two streams per thread: one or two reads per table)
+                    at = (double)a.a_tgt[s];
+                    ac = a.ramp > 0 ? (double)a.a_cur[s] : at;
+                    s_of = s;
+                }
+                const int64_t j1 = r / a.n_channels + 1;
+                ak[k] = at;
+                // (only inside a fade: no call in steady state, ramp == 0, reaches the float64 divide)
+                if (j1 < a.ramp) ak[k] = fma(at - ac, (double)j1 / (double)a.ramp, ac);
+            }
+        }
+    }
     double bgv[EPT], fgv[EPT], mix[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
         // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi)
         const double x = fabsf(h[k]) <= 3.402823466e38f || h[k] != h[k] ? (double)h[k] + (double)l[k] : (double)h[k];
         mix[k] = live[k] ? x : 0.0;
-        fgv[k] = live[k] ? x - (double)b[k] : 0.0;
+        const double f = a.gain ? fma(-ak[k], (double)b[k], x) : x - (double)b[k];
+        fgv[k] = live[k] ? f : 0.0;
         bgv[k] = live[k] ? (double)b[k] : 0.0;
     }
 #pragma unroll
@@ -452,6 +481,20 @@ __global__ __launch_bounds__(kIoThreads) void online_slot_import(SlotMoveArgs a)
     slot_move_body(a.part[blockIdx.y]);
 }
 
+// Background gains of the streaming handle: fp32 tables [S] of a = (float)(1 - gain). One workgroup each.
+__global__ __launch_bounds__(kIoThreads) void online_gain_fill(float* table, int32_t n, float a) {
+    for (int32_t i = threadIdx.x; i < n; i += kIoThreads) table[i] = a;
+}
+
+struct GainSetArgs { float* tgt; int32_t n; unsigned short slot[repet_eng::kSlotResetIds]; float a[repet_eng::kSlotResetIds]; };
+__global__ __launch_bounds__(kIoThreads) void online_gain_set(GainSetArgs g) {
+    for (int32_t i = threadIdx.x; i < g.n; i += kIoThreads) g.tgt[g.slot[i]] = g.a[i];
+}
+
+__global__ __launch_bounds__(kIoThreads) void online_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n, int32_t slot) {
+    for (int32_t i = threadIdx.x; i < n; i += kIoThreads) cur_new[i] = slot < 0 || i == slot ? tgt[i] : cur_old[i];
+}
+
 int element_size(int dtype) {
     switch (dtype) {
         case REPET_F64: return 8;
@@ -612,13 +655,50 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
     return hipGetLastError();
 }
 
+hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!table) return hipErrorInvalidValue;
+    online_gain_fill<<<1, kIoThreads, 0, s>>>(table, n, a);
+    return hipGetLastError();
+}
+
+// (the slots of one call are distinct: two threads never write one entry)
+hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int32_t n_slots, hipStream_t s) {
+    if (n_slots <= 0) return hipSuccess;
+    if (!tgt || !slots || !a) return hipErrorInvalidValue;
+    GainSetArgs g{};
+    g.tgt = tgt;
+    for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
+        g.n = std::min<int32_t>(kSlotResetIds, n_slots - first);
+        for (int32_t k = 0; k < g.n; ++k) { g.slot[k] = (unsigned short)slots[first + k]; g.a[k] = a[first + k]; }
+        online_gain_set<<<1, kIoThreads, 0, s>>>(g);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s) {
+    if (n_slots <= 0) return hipSuccess;
+    if (!tgt || !cur_old || !cur_new || cur_old == cur_new || slot >= n_slots) return hipErrorInvalidValue;
+    online_gain_commit<<<1, kIoThreads, 0, s>>>(tgt, cur_old, cur_new, n_slots, slot);
+    return hipGetLastError();
+}
+
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s) {
+                              int n_dsts, hipStream_t s, const EmitGain* gain) {
     const int64_t count = (int64_t)n_streams * n * ch;
     if (count <= 0 || n_dsts <= 0) return hipSuccess;
     if (n_dsts > 2 || !bg || !hi) return hipErrorInvalidValue;
     EmitArgs a{};
+    if (gain) {
+        if (gain->scalar) { a.gain = kGainScalar; a.a = gain->a; }
+        else {
+            if (!gain->a_tgt || gain->ramp < 0 || (gain->ramp > 0 && !gain->a_cur)) return hipErrorInvalidValue;
+            a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
+        }
+    }
     a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts;
     for (int k = 0; k < n_dsts; ++k) {
@@ -663,6 +743,13 @@ int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t
     }
     return REPET_OK;
 }
+
+int check_background_gain(float gain) {
+    if (!(gain >= 0.f && gain <= 1.f)) return fail(REPET_ERR_BAD_ARG, "the background gain must lie in [0, 1] (NaN and infinities are refused)");
+    return REPET_OK;
+}
+
+float background_gain_factor(float gain) { return (float)(1.0 - (double)gain); }
 
 int ensure_io_events(repet_ctx* c) {
     if (!c->io_wait) HIP_TRY(hipEventCreateWithFlags(&c->io_wait, hipEventDisableTiming));
@@ -752,6 +839,14 @@ int repet_ctx_select_result(repet_ctx* c, int which) {
     return REPET_OK;
 }
 
+int repet_ctx_set_background_gain(repet_ctx* c, float gain) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    RP_TRY(check_background_gain(gain));
+    c->result_gain = gain != 0.f;                       // (0, the default: the foreground as it always was, by the path it always took)
+    c->result_a = background_gain_factor(gain);
+    return REPET_OK;
+}
+
 int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const int64_t strides[3], void* signal_stream) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
@@ -770,9 +865,11 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
         // foreground / mixture: the resident samples and, where a float64 upload left them, their remainders beside the result
         if (c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
         EmitDst d{dst, c->result_which, {strides[0], strides[1], strides[2]}};
+        EmitGain gain;
+        gain.scalar = true; gain.a = c->result_a;
         HIP_TRY(launch_stream_emit(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
                                    c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels, dtype, &d, 1,
-                                   c->stream));
+                                   c->stream, c->result_gain ? &gain : nullptr));
     } else if (count > 0) {
         IoGeo g{count, c->n_samples, c->n_channels, strides[0], strides[1], strides[2]};
         const float* in = c->out.as<float>();

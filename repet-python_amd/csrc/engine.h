@@ -117,6 +117,8 @@ struct repet_ctx {
     hipEvent_t io_wait = nullptr, io_done = nullptr;
     DevBuf nonfinite_word;
     int result_which = REPET_OUT_BACKGROUND;   // what repet_ctx_download_device_strided writes (repet_ctx_select_result)
+    // repet_ctx_set_background_gain: the foreground it writes is x - result_a * bg, result_a = (float)(1 - gain); off: x - bg as ever
+    float result_a = 1.f; bool result_gain = false;
     int online_start = 0;         // simonline: start_frames of this context (repet_ctx_set_online_start; 0: buffer_frames, the reference)
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
@@ -265,6 +267,9 @@ int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_
 int check_strides(const int64_t* strides);
 int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch);
 int ensure_io_events(repet_ctx* c);
+// a background gain g in [0, 1] (BAD_ARG otherwise, NaN included) and what the egress multiplies the background by: (float)(1 - g)
+int check_background_gain(float gain);
+float background_gain_factor(float gain);
 // the streaming handle's per-push data movement (devio.hip), n_streams streams at per-stream element strides:
 //   append   chunk [S][n][C] (strided, any device dtype) -> hi / lo at s * dst_stream + dst_off (fp32 + fp32 remainder)
 //   copies   up to kRowCopyParts parts of `blocks` runs of `len` floats per stream (src null: zeros), one launch
@@ -296,10 +301,20 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
                                 const int64_t strides[3], hipStream_t s);
 //   emit     background / foreground / mixture of an emission (or of an offline result) into one or two strided destinations
 //            of one dtype, one launch: bg fp32 [S][n][C]; the input hi (+ lo, nullable) with stream s at s * in_stream floats
+//            gain (nullable: the foreground is x - bg as ever): the foreground is x - a * bg, with a the scalar (offline) or
+//            per stream from fp32 tables [n_streams]: a_tgt[s] from sample `ramp` - 1 of the emission on, a linear fade from
+//            a_cur[s] before it (ramp 0: a_tgt everywhere)
 struct EmitDst { void* p = nullptr; int which = -1; int64_t strides[3] = {0, 0, 0}; };
+struct EmitGain { const float* a_cur = nullptr; const float* a_tgt = nullptr; int64_t ramp = 0; float a = 1.f; bool scalar = false; };
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s);
+                              int n_dsts, hipStream_t s, const EmitGain* gain = nullptr);
+//   gains    the background gains of the streaming handle, fp32 [S] tables of a = (float)(1 - gain). fill: n entries = a.
+//            set: tgt[slots[k]] = a[k], one launch per kSlotResetIds slots named. commit: cur_new[s] = tgt[s] for the slots an
+//            emission covers (slot < 0: all), cur_old[s] for the others; one launch
+hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s);
+hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int32_t n_slots, hipStream_t s);
+hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s);
 int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int64_t* st1, int elem_bytes, int32_t n_clips, int64_t n,
                    int32_t ch);
 constexpr int kRankMinList = 24;     // shortest list bound for which the column sort is worth its time

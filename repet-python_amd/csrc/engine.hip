@@ -1184,6 +1184,13 @@ int repet_select_run_result(int device, int which) {
     return repet_ctx_select_result(c, which);
 }
 
+int repet_set_run_background_gain(int device, float gain) {
+    RP_TRY(check_background_gain(gain));
+    repet_ctx* c = nullptr;
+    RP_TRY(thread_ctx(device, &c));
+    return repet_ctx_set_background_gain(c, gain);
+}
+
 int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t in_strides[3],
                      void* dst, int out_dtype, const int64_t out_strides[3], const repet_params* p, int device, void* stream) {
     repet_ctx* c = nullptr;

@@ -58,7 +58,24 @@ struct repet_online {
     // share). Nothing writes that buffer before the next push's slide; restart / release and the next append end its validity.
     int out_which = REPET_OUT_BACKGROUND;
     struct Also { int which = -1; void* dst = nullptr; int dtype = REPET_F64; int64_t strides[3] = {0, 0, 0}; } also;
-    struct Emission { bool valid = false; int buf = 0, S = 0, slot = -1; int64_t off = 0, n = 0, pos0 = 0; } em;
+    // (g0, g1, ramp: the gain tables of that emission, see below -- a fade from table g0 to table g1 over its first `ramp` samples)
+    struct Emission { bool valid = false; int buf = 0, S = 0, slot = -1; int64_t off = 0, n = 0, pos0 = 0; int g0 = 0, g1 = 0; int64_t ramp = 0; } em;
+    // Background gains (repet_online_set_background_gain): the foreground of slot s is x - a[s] * bg, a = (float)(1 - gain). The
+    // gain is the SLOT's: no restart, release, finish_stream or import touches it. gain[s] is the host mirror of what was set;
+    // gain_tab holds three fp32 tables [S] on the device, all 1 at open: the target (written by a set, entry for entry, with no
+    // host wait) and two current tables, of which `gcur` is in force. A set marks its slots dirty; the first emitting call that
+    // covers a dirty slot writes the OTHER current table (target where it covers, the table in force elsewhere: one small
+    // launch), fades from the one to the other over min(H, n_emit) samples and puts the other in force. Both stay as they are
+    // until the next fade, so last_emission replays a fade from the tables that made it, whatever was set since. Until the first
+    // set (gains_on) no kernel is given a table.
+    std::vector<float> gain;
+    std::vector<unsigned char> gain_dirty;
+    int64_t n_dirty = 0;
+    DevBuf gain_tab;
+    int gcur = 0;
+    bool gains_on = false;
+    float* gain_target() const { return gain_tab.as<float>(); }
+    float* gain_current(int k) const { return gain_tab.as<float>() + (int64_t)(1 + k) * S; }
 
     int64_t plane() const { return (rows_cap + kPadRows) * FS; }        // elements between channel planes of X and V
     int64_t spec_stride() const { return (int64_t)C * plane(); }      // ... between streams in X and V
@@ -159,6 +176,7 @@ int online_ensure_pending(repet_online* o, int64_t n) {
 int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1) {
     repet_ctx* c = o->ctx;
     o->em = repet_online::Emission{true, o->pcur, slot < 0 ? o->S : 1, slot, o->pend_hist, std::max<int64_t>(n_emit, 0), o->emitted};
+    o->em.g0 = o->em.g1 = o->gcur;
     if (n_new <= 0 && n_emit <= 0) return REPET_OK;
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, o->W, &tb));
@@ -249,6 +267,17 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
         HIP_TRY(e);
     }
+    if (n_emit > 0 && o->gains_on && (all ? o->n_dirty > 0 : o->gain_dirty[(size_t)slot] != 0)) {
+        // a gain was set since these slots last emitted: this emission fades to it, and it is in force afterwards
+        // (the min below is a guard only: online_plan emits whole hops from a push and H + ((N - W) mod H) samples, or all N >=
+        // H of a short stream, from a finish, so n_emit >= H wherever n_emit > 0 and no emission is shorter than a fade)
+        const int nxt = o->gcur ^ 1;
+        HIP_TRY(launch_gain_commit(o->gain_target(), o->gain_current(o->gcur), o->gain_current(nxt), o->S, all ? -1 : slot, c->stream));
+        o->em.g0 = o->gcur; o->em.g1 = nxt; o->em.ramp = std::min<int64_t>(o->H, n_emit);
+        o->gcur = nxt;
+        if (all) { std::fill(o->gain_dirty.begin(), o->gain_dirty.end(), 0); o->n_dirty = 0; }
+        else { o->gain_dirty[(size_t)slot] = 0; o->n_dirty -= 1; }
+    }
     if (n_new > 0 && all) {
         // slide, one launch for every stream and channel: the last min(Hh, Tw) rows of V and Vn and the last masked spectrum
         // (overlap-add tail of the next hop) become the history of the other window; the samples of the window's frames
@@ -326,9 +355,11 @@ int online_emit(repet_online* o, const EmitDst* dsts, int n_dsts, int dtype) {
     }
     if (em.off + em.n > o->pend_cap) return fail(REPET_ERR_LIMIT, "online: the emitted range is not in the pending buffer");
     const int64_t sb = em.slot < 0 ? 0 : em.slot, at = sb * o->pend_stride() + em.off * o->C;
+    EmitGain gain;
+    if (o->gains_on) { gain.a_cur = o->gain_current(em.g0) + sb; gain.a_tgt = o->gain_current(em.g1) + sb; gain.ramp = em.ramp; }
     HIP_TRY(launch_stream_emit(o->outf.as<float>(), o->pend[em.buf].as<float>() + at, o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
                                o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dtype, dsts,
-                               n_dsts, c->stream));
+                               n_dsts, c->stream, o->gains_on ? &gain : nullptr));
     return REPET_OK;
 }
 
@@ -726,6 +757,49 @@ int repet_online_last_emission_device(repet_online* o, int which, void* dst, int
     return REPET_OK;
 }
 
+int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int32_t n_slots, const float* gains) {
+    if (!o || !gains) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
+    const int32_t n = slots ? n_slots : 1;
+    for (int32_t k = 0; k < n; ++k) {
+        if (slots && (slots[k] < 0 || slots[k] >= o->S)) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        RP_TRY(check_background_gain(gains[k]));
+    }
+    if (n == 0) return REPET_OK;
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    if (!slots) {
+        HIP_TRY(launch_gain_fill(o->gain_target(), o->S, background_gain_factor(gains[0]), c->stream));
+        std::fill(o->gain.begin(), o->gain.end(), gains[0]);
+        std::fill(o->gain_dirty.begin(), o->gain_dirty.end(), 1);
+        o->n_dirty = o->S;
+    } else {
+        // a slot named twice takes the last value given for it: the launch gets every slot once
+        std::vector<int32_t> ids;
+        std::vector<float> a;
+        std::vector<unsigned char> seen((size_t)o->S, 0);
+        for (int32_t k = 0; k < n; ++k) o->gain[(size_t)slots[k]] = gains[k];
+        for (int32_t k = 0; k < n; ++k) {
+            const size_t s = (size_t)slots[k];
+            if (seen[s]) continue;
+            seen[s] = 1;
+            ids.push_back(slots[k]);
+            a.push_back(background_gain_factor(o->gain[s]));
+            if (!o->gain_dirty[s]) { o->gain_dirty[s] = 1; o->n_dirty += 1; }
+        }
+        HIP_TRY(launch_gain_set(o->gain_target(), ids.data(), a.data(), (int32_t)ids.size(), c->stream));
+    }
+    o->gains_on = true;
+    return REPET_OK;
+}
+
+int repet_online_background_gain(repet_online* o, int32_t slot, float* gain_out) {
+    if (!o || !gain_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    *gain_out = o->gain[(size_t)slot];
+    return REPET_OK;
+}
+
 int repet_online_set_start_frames(repet_online* o, int32_t start_frames) {
     if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->total_in != 0 || o->epoch != 0 || o->finished) return fail(REPET_ERR_BAD_ARG, "online: start_frames can only be set before the first push");
@@ -885,6 +959,11 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
         DeviceGuard guard(o->ctx->device);
         hipError_t e = o->slot_start.ensure((size_t)n_streams * sizeof(int64_t));
         if (e == hipSuccess) e = hipMemsetAsync(o->slot_start.p, 0, (size_t)n_streams * sizeof(int64_t), o->ctx->stream);
+        // the background gains: 0 for every slot, which is a = 1 in the target table and in both current ones
+        o->gain.assign((size_t)n_streams, 0.f);
+        o->gain_dirty.assign((size_t)n_streams, 0);
+        if (e == hipSuccess) e = o->gain_tab.ensure((size_t)3 * n_streams * sizeof(float));
+        if (e == hipSuccess) e = launch_gain_fill(o->gain_tab.as<float>(), 3 * n_streams, 1.f, o->ctx->stream);
         if (e != hipSuccess) { repet_online_close(o); return fail(e == hipErrorOutOfMemory ? REPET_ERR_OOM : REPET_ERR_HIP, hipGetErrorString(e)); }
     }
     if (max_push_samples > 0) {
@@ -910,7 +989,7 @@ int repet_online_close(repet_online* o) {
         DeviceGuard guard(o->ctx->device);
         (void)hipStreamSynchronize(o->ctx->stream);
         for (int k = 0; k < 2; ++k) { o->X[k].release(); o->V[k].release(); o->Vn[k].release(); o->pend[k].release(); o->pend_lo[k].release(); }
-        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release();
+        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release();
         free_pinned(o->host_in, o->host_in_cap);
         free_pinned(o->host_out, o->host_out_cap);
     }

@@ -118,10 +118,11 @@ def release_workspaces():
     _native.release_tensor_contexts()
 
 
-def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background"):
+def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
-    selects what the egress writes; "both" is two egress launches behind one run."""
+    selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
+    has checked, or None."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
@@ -143,7 +144,15 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     stream = torch.cuda.current_stream(x.device)
     ctx.upload_layout(*layout, stream=stream)
     ctx.execute_async(algo, params)
-    results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+    if background_gain is None:
+        results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+    else:
+        # on this thread's cached context for this call alone: later calls are the plain foreground again, whatever happens here
+        try:
+            ctx.set_background_gain(background_gain)
+            results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+        finally:
+            ctx.set_background_gain(0.0)
     return results if which == "both" else results[0]
 
 
@@ -187,7 +196,7 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None, which="background"):
+def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
     clips one after another). Returns a float64 tensor on the tensor's device -- or fills ``out``, a float32 / float64 tensor
@@ -198,13 +207,23 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     from the samples as the engine holds them (exact for float32 / float16 / bfloat16 / int16 tensors; 48 bits of a float64
     sample, so within ``2**-47 * max(|x|, |background|)`` of the float64 subtraction), rounded once more for a float32
     ``out`` --, "mixture" (the input as the engine holds it) or "both": the pair ``(background, foreground)``, with ``out`` a
-    pair of tensors that share no memory."""
+    pair of tensors that share no memory.
+
+    ``background_gain`` (a number in [0, 1], with ``which="foreground"`` or ``"both"`` only): keep that share of the background,
+    ``foreground = x - float32(1 - background_gain) * background``, rounded once in float64 by the same egress (-12 dB of
+    background: ``10 ** (-12 / 20)``; 0 is the plain foreground, 1 the input). For this call alone. ValueError for a value
+    outside [0, 1] (NaN included) or with another ``which``."""
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
     _native.which_codes(which)
+    if background_gain is not None:
+        if which not in ("foreground", "both"):
+            raise ValueError('background_gain changes the foreground: it goes with which="foreground" or "both"')
+        background_gain = float(_native.background_gains(background_gain)[0])
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
-    return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which)
+    return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
+                            background_gain=background_gain)
 
 
 def online(sampling_frequency, number_channels, start_length=None):
@@ -220,6 +239,9 @@ def online(sampling_frequency, number_channels, start_length=None):
     ``export_stream()`` returns the stream's state as a :class:`StreamState` (a snapshot; only where the samples pushed so
     far are a multiple of the hop) and ``import_stream(state)`` loads one into this separator, which then goes on as the
     exporting stream would have: see :func:`online_streams`.
+
+    ``set_background_gain(gain)`` keeps ``gain`` (in [0, 1]) of the background in the foreground, ``x - float32(1 - gain) *
+    background``, fading to it over at most one hop; ``background_gain()`` reads it back: see :func:`online_streams`.
 
     ``start_length`` (seconds; None: ``buffer_length``, the reference): separate before the buffer has filled. The reference
     writes nothing until its buffer holds ``buffer_length`` (10 s) of frames; with ``start_frames = min(buffer_frames, max(1,
@@ -265,6 +287,16 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     foreground is its input (nothing is removed before there is evidence); idle slots and the hop before a ``restart`` are
     zero in every signal, whatever the chunk held there. ``last_emission(which, out=None)`` returns another signal of the
     samples the last ``push`` / ``finish`` emitted, until the next push, finish, restart or release.
+
+    ``set_background_gain(gain, slots=None)`` keeps a share ``gain`` in [0, 1] of the background in the foreground of the named
+    slots (None: all; a scalar, or one value per named slot): ``foreground = x - a * background`` with ``a = float32(1 -
+    gain)``, rounded once in float64 by the same launch, wherever "foreground" is delivered ("both" and ``last_emission``
+    included). 0 is the default and the plain foreground bit for bit, 1 returns the input (except where the background is NaN
+    or infinite), -12 dB of background is ``10 ** (-12 / 20)``. A change is a fade: the next emission moves ``a`` linearly
+    from the old value to the new one over its first ``min(step_length, n_emit)`` samples and is at the new value from there
+    on. The gain is the slot's, not the stream's -- ``restart``, ``release``, ``finish_stream`` and ``import_stream`` leave it,
+    and an exported state does not carry it --; ``background_gain(slot)`` reads it back. No host wait; a push in steady state
+    costs the launches it always cost. ValueError for a value outside [0, 1] (NaN included) or a slot out of range.
 
     A stream can move between handles: ``export_stream(slot, device=False)`` returns a snapshot of the slot's state as a
     :class:`StreamState` -- ``header``, a small ``bytes`` value the host knows at once, and ``payload``, a ``numpy.uint8``

@@ -37,6 +37,27 @@ def which_codes(which):
     return (WHICH_CODES[which],)
 
 
+def background_gains(gain, count=None):
+    """``gain`` as a float32 array: a scalar (``count`` None), or one value per named slot -- a scalar is repeated ``count``
+    times. ValueError, before any device is touched, for a value that is NaN, infinite or outside [0, 1] (checked on the float32
+    value the library takes) or for another number of values than slots."""
+    try:
+        g = np.asarray(gain, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"background_gain must be a number in [0, 1], not {gain!r}") from None
+    if count is None:
+        if g.ndim != 0:
+            raise ValueError("background_gain is one number here")
+        g = g.reshape(1)
+    elif g.ndim == 0:
+        g = np.full(count, g, dtype=np.float32)
+    elif g.ndim != 1 or g.size != count:
+        raise ValueError(f"{g.size} background gains for {count} slots")
+    if not np.all((g >= 0) & (g <= 1)):
+        raise ValueError(f"background_gain must lie in [0, 1] (NaN and infinities are refused), not {gain!r}")
+    return np.ascontiguousarray(g)
+
+
 class Params(C.Structure):
     _fields_ = [("window_length", C.c_int32), ("step_length", C.c_int32), ("period_lo", C.c_int32),
                 ("period_hi", C.c_int32), ("cutoff_bins", C.c_int32), ("filter_order", C.c_int32),
@@ -180,6 +201,10 @@ _SIGNATURES = {
     "repet_online_start_frames": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "repet_ctx_set_online_start": (C.c_int, [_P, C.c_int32]),
     "repet_select_run_result": (C.c_int, [C.c_int, C.c_int]),
+    "repet_online_set_background_gain": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "repet_online_background_gain": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float)]),
+    "repet_ctx_set_background_gain": (C.c_int, [_P, C.c_float]),
+    "repet_set_run_background_gain": (C.c_int, [C.c_int, C.c_float]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -488,6 +513,12 @@ class Context:
         finally:
             lib().repet_ctx_select_result(self._h, OUT_BACKGROUND)
         return out
+
+    def set_background_gain(self, gain):
+        """The foreground ``download_tensor`` writes from now on keeps ``gain`` (in [0, 1]) of the background:
+        ``x - float32(1 - gain) * background``. 0, the default, is the plain foreground. ValueError outside [0, 1]."""
+        g = background_gains(gain)
+        check(lib().repet_ctx_set_background_gain(self._h, float(g[0])))
 
     def torch_stream(self):
         """The context's stream as a ``torch.cuda.ExternalStream`` (cached)."""
@@ -892,6 +923,17 @@ class OnlineSeparator:
             outs = [o[:written.value].copy() for o in outs]
             return outs[0] if len(outs) == 1 else tuple(outs)
 
+    def set_background_gain(self, gain):
+        """Keep ``gain`` (in [0, 1]) of the background in the foreground from the next emission on, see ``repet.online``."""
+        g = background_gains(gain)
+        check(lib().repet_online_set_background_gain(self._h, None, 0, ptr(g)))
+
+    def background_gain(self):
+        """The background gain last set (0: the plain foreground)."""
+        out = C.c_float()
+        check(lib().repet_online_background_gain(self._h, 0, C.byref(out)))
+        return out.value
+
     def export_stream(self):
         """A snapshot of the stream's state (a ``StreamState`` with a host payload); the stream goes on untouched. ValueError
         unless the samples pushed so far are a multiple of the hop."""
@@ -1091,6 +1133,24 @@ class OnlineStreams:
     def _slot_list(self, slots):
         slots = [self._slot(s) for s in ([slots] if np.isscalar(slots) else slots)]
         return slots, (C.c_int32 * max(len(slots), 1))(*slots)
+
+    def set_background_gain(self, gain, slots=None):
+        """Keep ``gain`` (in [0, 1]) of the background in the foreground of the named slots (None: every slot): a scalar, or
+        one value per named slot. The next emission fades to it over at most one hop; see ``repet.online_streams``. No host
+        wait. ValueError, with nothing changed, for a value outside [0, 1] (NaN included) or a slot out of range."""
+        if slots is None:
+            g = background_gains(gain)
+            check(lib().repet_online_set_background_gain(self._handle(), None, 0, ptr(g)))
+            return
+        slots, arr = self._slot_list(slots)
+        g = background_gains(gain, len(slots))
+        check(lib().repet_online_set_background_gain(self._handle(), arr, len(slots), ptr(g)))
+
+    def background_gain(self, slot):
+        """The background gain last set for ``slot`` (0: the plain foreground)."""
+        out = C.c_float()
+        check(lib().repet_online_background_gain(self._handle(), self._slot(slot), C.byref(out)))
+        return out.value
 
     def restart(self, slots):
         """Begin a new stream in every named slot: its sample 0 is the handle's sample ``samples_pushed``, which must be a

@@ -21,7 +21,11 @@ pushed in lockstep through every slot).
 
 ``--start-length SECONDS``: the one-handle cases on handles opened with ``start_length`` (separation from that age on, before
 the 10-s buffer has filled). The streams are then pushed only half a second past the start length, so the timed pushes are
-those of YOUNG frames, each decided on the frames heard so far; keep ``--timed`` x hops inside the buffer's first 10 s."""
+those of YOUNG frames, each decided on the frames heard so far; keep ``--timed`` x hops inside the buffer's first 10 s.
+
+``--background-gain G``: the one-handle cases with ``set_background_gain(G)`` made right after the open, so every timed push is
+one of the steady state with gains set. ``--gain-change-every K`` (with it): a new gain is also set before every K-th timed push
+(outside the clock), so those pushes are each the first one after a set, the ones that fade."""
 import argparse
 import json
 import sys
@@ -46,7 +50,7 @@ def stats(lat_s, n, fs):
             "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
 
 
-def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None):
+def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0):
     import torch
     S, N, ch = xs.shape
     hop = repet.derive_params(fs).step_length
@@ -55,6 +59,8 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info(0)[0]
     h = repet.online_streams(fs, ch, S, max_push_samples=n, start_length=start_length)
+    if gain is not None:
+        h.set_background_gain(gain)
     if start_length is not None:
         warm_s = start_length + 0.5                            # past the start length, far from a full buffer
     pos = 0
@@ -67,9 +73,11 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
     torch.cuda.synchronize()
     held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
     lat = []
-    for _ in range(timed):
+    for k in range(timed):
         if pos + n > N:
             break
+        if gain is not None and gain_every > 0 and k % gain_every == 0:
+            h.set_background_gain((gain + 0.01 * (k + 1)) % 1.0)
         t0 = time.perf_counter()
         h.push(src[:, pos:pos + n], which=which)
         if device:
@@ -274,6 +282,10 @@ def main():
                     help="comma list of background / foreground / mixture / both: what the one-handle device pushes deliver")
     ap.add_argument("--start-length", type=float, default=None, metavar="SECONDS",
                     help="open the one-handle cases with this start_length and time pushes of young frames (see above)")
+    ap.add_argument("--background-gain", type=float, default=None, metavar="G",
+                    help="set this background gain on the one-handle cases right after the open (see above)")
+    ap.add_argument("--gain-change-every", type=int, default=0, metavar="K",
+                    help="with --background-gain: set a new gain before every K-th timed push")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
@@ -302,15 +314,20 @@ def main():
     result = {"fs": fs, "channels": ch, "cases": []}
     if args.start_length is not None:
         result["start_length_s"] = args.start_length
+    if args.background_gain is not None:
+        result["background_gain"] = args.background_gain
+        result["gain_change_every"] = args.gain_change_every
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
             case = {"streams": S, "hops_per_push": hops}
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
-                case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length)
+                case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
+                                       args.gain_change_every)
             if args.only == "all":
-                case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length)
+                case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
+                                                            gain=args.background_gain, gain_every=args.gain_change_every)
                 if S <= args.separate_max:
                     case["separate_handles_host"] = separate_handles(xs, fs, hops, args.timed, warm_s)
             result["cases"].append(case)
