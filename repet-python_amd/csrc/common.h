@@ -376,13 +376,24 @@ struct MaskArgs {
 };
 constexpr int kPadRows = 8;       // rows kept behind the Tpad frame rows of V (2 used)
 constexpr int kMinIdxPitch = 128; // index lists are readable up to the largest network size
+// What a mask launcher launched (nullable trailing argument of the three launchers; the stage entry of engine_stages.hip
+// returns it, the pipelines pass nothing): the kernel of the main bins and the one of the lone Nyquist bin (launch_mask_sim,
+// split shapes), as template name + arguments. net: the network size compiled in (0: bisection, -1: mask_period_kernel's
+// switch); flag: SPLIT (mask_sim_kernel), the planes NP (mask_sim_bits_kernel, net = H); parts: the workgroups that share a
+// position's bins (mask_period_kernel). An empty name: that kernel was not launched.
+struct MaskLaunch {
+    const char* kernel = ""; int32_t net = 0, flag = 0, parts = 0; uint32_t grid[3] = {0, 0, 0};
+    const char* nyquist = ""; int32_t nyquist_net = 0, nyquist_preload = 0; uint32_t nyquist_grid[3] = {0, 0, 0};
+    void set_main(const char* name, int n, int fl, int pa, dim3 g) { kernel = name; net = n; flag = fl; parts = pa; grid[0] = g.x; grid[1] = g.y; grid[2] = g.z; }
+};
 hipError_t launch_fill_pad_rows(float* V, int64_t chan_stride, int32_t n_channels, int64_t pad_row, int32_t FS,
                                 hipStream_t s, float* Z = nullptr, int64_t z_stride = 0, int64_t z_count = 0, int32_t n_z = 0,
                                 unsigned int* stats = nullptr, float* Z2 = nullptr);
 // max_count / min_period bound the list length so the launcher can pick the smallest compiled network.
 // parts: 1 = main kernel only, 2 = Nyquist-bin kernel only, 3 = both (chunked pipelines launch them separately).
 hipError_t launch_mask_sim(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count,
-                           int64_t first_frame, int32_t max_count, hipStream_t s, int parts = 3, bool lookups_by_caller = false);
+                           int64_t first_frame, int32_t max_count, hipStream_t s, int parts = 3, bool lookups_by_caller = false,
+                           MaskLaunch* info = nullptr);
 int median_network_instructions(int max_n, int* net_size);
 // bit-sliced selection (mask_bits.hip): lists of at most 128 entries, at most 32 blocks of 64 ranked bins over all channels
 int code_planes_for(int64_t T);                       // planes of the codes of a T-frame clip (bits of T - 1, at least 11)
@@ -391,11 +402,11 @@ int mask_sim_bits_instructions(int32_t max_count, int32_t n_planes);
 // the selection (codes of both medians per cell into m.median_codes), and the lookups + mask from those codes (the caller
 // launches the second behind the first; launch_mask_sim does both unless told that the caller will)
 hipError_t launch_mask_sim_bits(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count, int32_t max_count,
-                                unsigned n_launch, hipStream_t s);
+                                unsigned n_launch, hipStream_t s, MaskLaunch* info = nullptr);
 hipError_t launch_mask_from_codes(const MaskArgs& m, const int32_t* count, hipStream_t s);
-hipError_t launch_mask_adaptive(const MaskArgs& m, const int32_t* periods, int32_t order, hipStream_t s);
+hipError_t launch_mask_adaptive(const MaskArgs& m, const int32_t* periods, int32_t order, hipStream_t s, MaskLaunch* info = nullptr);
 hipError_t launch_mask_period(const MaskArgs& m, const int32_t* period_dev, int32_t period_host,
-                              int32_t min_period, hipStream_t s);
+                              int32_t min_period, hipStream_t s, MaskLaunch* info = nullptr);
 
 // Rank transform of V for the rank-domain median of `sim` (rank.hip): every column (bin f of channel c over the T
 // frames) is sorted once; R gets 0x0400 + the number of strictly smaller magnitudes of the column, Vs the sorted column.

@@ -620,6 +620,195 @@ int repet_mask_sim_ranked(repet_ctx* c, const float* v, int64_t T, int32_t F, co
     return d2h_pitched(c, mask_out, c->tmp_c.as<float>(), FS, T, F);
 }
 
+// ---- stage entry of the production mask launchers (tests/test_gpu_mask_stages.py) --------------------------------------
+// The four exports above fix one channel, one clip, no cutoff, no X, a host period, first_frame = frame0 = 0 and pad_row = T:
+// no pipeline launches the kernels that way. This one lays V (and X) out as make_geo does -- FS = round_up(F, 32), Tpad =
+// round_up(T, 128), Tpad + kPadRows rows per channel, pad_row = Tpad, clips C * chan_stride apart --, runs launch_fill_pad_rows
+// over all B * C planes as ensure_spectra does and then exactly ONE of launch_mask_period (kind 0), launch_mask_adaptive (1)
+// and launch_mask_sim (2) with a MaskArgs the caller controls. V (B, C, T, F), X (nullable; B, C, T, F, 2). want: 1 the mask
+// plane, 2 X in place, 4 the model (period only, and then nothing else: the kernel writes nothing else). Every device buffer
+// -- V and X outside the caller's cells, the mask plane, the model, the median codes -- holds the byte `prefill` before the
+// launch, and every output comes back whole: mask / X (B, C, Tpad + kPadRows, FS), model (B, C, T / 3 + 2, FS), codes (C, Tpad +
+// kPadRows, FS). Everything a kernel indexes with is checked on the host first: bad input is REPET_ERR_BAD_ARG, a shape the
+// median path asked for does not take REPET_ERR_LIMIT, never an out-of-range gather.
+//   period    periods null: the host period `period_host`; else B device periods, min_period <= periods[b] <= T / 3 + 2
+//   adaptive  periods (T), order
+//   sim       idx (B, rows, width), cnt (B, rows), rows >= T - first_frame list rows numbered from first_frame; idx_pitch >= max(128,
+//             width), any alignment; slot_start (nullable, B) + slot_bias; median_path 0 floats, 1 packed network on rank
+//             codes, 2 bit-sliced selection (1 and 2: B = 1, first_frame = 0; the column sort runs on all C channels, with the
+//             calls of run_rank_columns)
+// geo_out[8] = Tpad, rows per channel, FS, chan_stride, model rows, 0, 0, 0. launch_out[16] = net, flag, parts, grid x y z,
+// Nyquist net, preload, grid x y z, 1 if mask_from_codes_kernel ran behind the selection, 0...; kernel_out / nyquist_out: the
+// template names (MaskLaunch, common.h).
+int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const float* X, int32_t B, int32_t C, int64_t T, int32_t F,
+                           int32_t cutoff, int32_t prefill, int32_t want, int32_t period_host, const int32_t* periods,
+                           int32_t min_period, int32_t order, const int32_t* idx, const int32_t* cnt, int64_t rows, int32_t width,
+                           int64_t first_frame, int32_t max_count, int64_t frame0, int64_t frame_end, int32_t parts,
+                           const int64_t* slot_start, int64_t slot_bias, int32_t idx_pitch, int32_t median_path, int64_t* geo_out,
+                           float* mask_out, float* X_out, float* model_out, uint32_t* codes_out, char* kernel_out,
+                           int32_t kernel_cap, char* nyquist_out, int32_t nyquist_cap, int64_t* launch_out) {
+    if (!c || !V || !geo_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (kind < 0 || kind > 2) return fail(REPET_ERR_BAD_ARG, "kind: 0 period, 1 adaptive, 2 sim");
+    if (B < 1 || C < 1 || C > 64 || T < 1 || F < 1 || cutoff < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
+    const int FS = (int)round_up(F, kFreqAlign);
+    const int64_t Tpad = round_up(T, kTile), n_rows = Tpad + kPadRows, chan_stride = n_rows * FS, batch_stride = (int64_t)C * chan_stride;
+    const int64_t model_rows = T / 3 + 2;
+    if (chan_stride * 8 >= ((int64_t)1 << 31) || (int64_t)B * batch_stride > ((int64_t)1 << 27)) return fail(REPET_ERR_LIMIT, "too many cells for a stage test");
+    const int64_t geo[8] = {Tpad, n_rows, FS, chan_stride, model_rows, 0, 0, 0};
+    std::memcpy(geo_out, geo, sizeof(geo));
+    if (!(want & 7) || (want & ~7)) return fail(REPET_ERR_BAD_ARG, "want: 1 mask plane, 2 X in place, 4 model");
+    if ((want & 4) && (kind != 0 || (want & 3))) return fail(REPET_ERR_BAD_ARG, "the model is the period family's, and comes alone");
+    if (((want & 1) && !mask_out) || ((want & 2) && (!X || !X_out)) || ((want & 4) && !model_out)) return fail(REPET_ERR_BAD_ARG, "null output");
+    if (kind == 0) {
+        if (periods) {
+            if (min_period < 1) return fail(REPET_ERR_BAD_ARG, "min_period must be >= 1");
+            for (int b = 0; b < B; ++b)
+                if (periods[b] < min_period || periods[b] > model_rows) return fail(REPET_ERR_BAD_ARG, "a period outside [min_period, T / 3 + 2]");
+        } else if (period_host < 1 || period_host > T || ((want & 4) && period_host > model_rows))
+            return fail(REPET_ERR_BAD_ARG, "period must be in [1, T] (with a model: [1, T / 3 + 2])");
+    } else if (kind == 1) {
+        if (!periods || order < 1 || order > 1024) return fail(REPET_ERR_BAD_ARG, "adaptive: periods and an order in [1, 1024]");
+        if (B != 1) return fail(REPET_ERR_BAD_ARG, "adaptive: one clip");
+        for (int64_t t = 0; t < T; ++t)
+            if (periods[t] < 1 || periods[t] > (1 << 20)) return fail(REPET_ERR_BAD_ARG, "a period outside [1, 2^20]");
+    } else {
+        if (!idx || !cnt) return fail(REPET_ERR_BAD_ARG, "null argument");
+        if (width < 1 || max_count < 1 || max_count > width || idx_pitch < kMinIdxPitch || idx_pitch < width || idx_pitch > (1 << 16))
+            return fail(REPET_ERR_BAD_ARG, "sim: 1 <= max_count <= width <= idx_pitch, idx_pitch >= 128");
+        if (first_frame < 0 || first_frame > T || rows < 1 || rows < T - first_frame || rows > T)
+            return fail(REPET_ERR_BAD_ARG, "sim: first_frame in [0, T], max(1, T - first_frame) <= rows <= T");
+        if (frame_end == 0) frame_end = T;
+        if (frame0 < 0 || frame0 > frame_end || frame_end > T) return fail(REPET_ERR_BAD_ARG, "sim: 0 <= frame0 <= frame_end <= T");
+        if (parts < 1 || parts > 3) return fail(REPET_ERR_BAD_ARG, "parts: 1 main bins, 2 Nyquist bin, 3 both");
+        if (median_path < 0 || median_path > 2) return fail(REPET_ERR_BAD_ARG, "median_path: 0 floats, 1 packed rank codes, 2 bit-sliced");
+        for (int64_t k = 0; k < (int64_t)B * rows; ++k)
+            if (cnt[k] < 0 || cnt[k] > max_count) return fail(REPET_ERR_BAD_ARG, "a list length outside [0, max_count]");
+        for (int64_t k = 0; k < (int64_t)B * rows * width; ++k)
+            if (idx[k] < 0 || idx[k] >= T) return fail(REPET_ERR_BAD_ARG, "a list entry outside [0, T)");
+        if (median_path > 0) {
+            if (B != 1 || first_frame != 0 || slot_start) return fail(REPET_ERR_BAD_ARG, "the rank paths take one clip from frame 0");
+            if (F <= 128 || ((F - 1) & 127) || !rank_columns_supported(T) || max_count < 2 || max_count > 128)
+                return fail(REPET_ERR_LIMIT, "rank-domain median: 1024 < n_frames <= 30720, n_freq - 1 a multiple of 128, lists of 2..128 entries");
+            if (median_path == 2 && !mask_sim_bits_supported(T, C, F - 1, max_count))
+                return fail(REPET_ERR_LIMIT, "bit-sliced selection: at most 32 blocks of 64 bins over all channels, a power of two per channel");
+            if (median_path == 2 && !codes_out) return fail(REPET_ERR_BAD_ARG, "null output");
+        }
+    }
+    DeviceGuard guard(c->device);
+    const size_t planes = (size_t)B * C, cells = planes * chan_stride;
+    const int fill = prefill & 255;
+    Scratch Vd, Xd, Md, Wd, Pd, Id, Nd, Sd, Rd, Vsd, RCd, CPd, MCd;
+    HIP_TRY(Vd.b.ensure(cells * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(Vd.b.p, fill, cells * sizeof(float), c->stream));
+    for (size_t p = 0; p < planes; ++p)
+        HIP_TRY(hipMemcpy2DAsync(Vd.b.as<float>() + p * chan_stride, (size_t)FS * sizeof(float), V + p * (size_t)T * F, (size_t)F * sizeof(float),
+                                 (size_t)F * sizeof(float), T, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_fill_pad_rows(Vd.b.as<float>(), chan_stride, (int32_t)planes, Tpad, FS, c->stream));
+    if (want & 2) {
+        HIP_TRY(Xd.b.ensure(cells * sizeof(float2)));
+        HIP_TRY(hipMemsetAsync(Xd.b.p, fill, cells * sizeof(float2), c->stream));
+        for (size_t p = 0; p < planes; ++p)
+            HIP_TRY(hipMemcpy2DAsync(Xd.b.as<float2>() + p * chan_stride, (size_t)FS * sizeof(float2), X + p * (size_t)T * F * 2,
+                                     (size_t)F * sizeof(float2), (size_t)F * sizeof(float2), T, hipMemcpyHostToDevice, c->stream));
+    }
+    if (want & 1) {
+        HIP_TRY(Md.b.ensure(cells * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Md.b.p, fill, cells * sizeof(float), c->stream));
+    }
+    const size_t model_cells = planes * model_rows * FS;
+    if (want & 4) {
+        HIP_TRY(Wd.b.ensure(model_cells * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Wd.b.p, fill, model_cells * sizeof(float), c->stream));
+    }
+    MaskArgs m{};
+    m.V = Vd.b.as<float>(); m.chan_stride = chan_stride; m.n_channels = C; m.T = T; m.F = F; m.FS = FS;
+    m.X = (want & 2) ? Xd.b.as<float2>() : nullptr; m.mask = (want & 1) ? Md.b.as<float>() : nullptr;
+    m.cutoff = cutoff; m.pad_row = Tpad; m.n_batch = B; m.batch_stride = batch_stride;
+    if (want & 4) { m.model = Wd.b.as<float>(); m.model_batch_stride = (int64_t)C * model_rows * FS; m.model_chan_stride = model_rows * FS; }
+    MaskLaunch info;
+    bool from_codes = false;
+    if (kind == 0) {
+        if (periods) {
+            HIP_TRY(Pd.b.ensure((size_t)B * sizeof(int32_t)));
+            HIP_TRY(hipMemcpyAsync(Pd.b.p, periods, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(launch_mask_period(m, Pd.b.as<int32_t>(), 0, min_period, c->stream, &info));
+        } else
+            HIP_TRY(launch_mask_period(m, nullptr, period_host, period_host, c->stream, &info));
+    } else if (kind == 1) {
+        HIP_TRY(Pd.b.ensure((size_t)T * sizeof(int32_t)));
+        HIP_TRY(hipMemcpyAsync(Pd.b.p, periods, (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_mask_adaptive(m, Pd.b.as<int32_t>(), order, c->stream, &info));
+    } else {
+        const size_t list_rows = (size_t)B * rows;
+        HIP_TRY(Id.b.ensure(list_rows * idx_pitch * sizeof(int32_t)));
+        HIP_TRY(Nd.b.ensure(list_rows * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(Id.b.p, 0, list_rows * idx_pitch * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemcpy2DAsync(Id.b.p, (size_t)idx_pitch * sizeof(int32_t), idx, (size_t)width * sizeof(int32_t), (size_t)width * sizeof(int32_t),
+                                 list_rows, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(Nd.b.p, cnt, list_rows * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        m.idx_batch_stride = rows * idx_pitch; m.cnt_batch_stride = rows; m.frame0 = frame0; m.frame_end = frame_end;
+        if (slot_start) {
+            HIP_TRY(Sd.b.ensure((size_t)B * sizeof(int64_t)));
+            HIP_TRY(hipMemcpyAsync(Sd.b.p, slot_start, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            m.slot_start = Sd.b.as<int64_t>(); m.slot_bias = slot_bias;
+        }
+        if (median_path > 0) {                               // run_rank_columns' calls, the path forced instead of read from the environment
+            const int n_cols = F - 1;
+            const int64_t vs_pitch = round_up(T, 32);
+            const bool bits = median_path == 2;
+            HIP_TRY(Vsd.b.ensure((size_t)C * n_cols * vs_pitch * sizeof(float)));
+            HIP_TRY(RCd.b.ensure((size_t)C * n_cols * vs_pitch * sizeof(unsigned short)));
+            RankArgs a{};
+            a.V = Vd.b.as<float>(); a.chan_stride = chan_stride; a.n_channels = C; a.T = T; a.FS = FS; a.n_cols = n_cols;
+            a.r_chan_stride = chan_stride; a.Vs = Vsd.b.as<float>(); a.vs_pitch = vs_pitch; a.codes = RCd.b.as<unsigned short>();
+            if (bits) {
+                a.n_planes = code_planes_for(T);
+                HIP_TRY(CPd.b.ensure((size_t)T * a.n_planes * 64 * sizeof(unsigned)));
+                HIP_TRY(hipMemsetAsync(CPd.b.p, 0, (size_t)T * a.n_planes * 64 * sizeof(unsigned), c->stream));
+                a.P = CPd.b.as<unsigned>();
+                HIP_TRY(MCd.b.ensure((size_t)C * chan_stride * sizeof(unsigned)));
+                HIP_TRY(hipMemsetAsync(MCd.b.p, fill, (size_t)C * chan_stride * sizeof(unsigned), c->stream));
+                m.median_codes = MCd.b.as<unsigned>();
+            } else {
+                HIP_TRY(Rd.b.ensure((size_t)C * chan_stride * sizeof(unsigned short)));
+                HIP_TRY(hipMemsetAsync(Rd.b.p, 0, (size_t)C * chan_stride * sizeof(unsigned short), c->stream));
+                HIP_TRY(launch_fill_rank_pad_rows(Rd.b.as<unsigned short>(), chan_stride, C, Tpad, FS, c->stream));
+                a.R = Rd.b.as<unsigned short>();
+            }
+            HIP_TRY(launch_rank_columns(a, c->stream));
+            m.R = a.R; m.r_chan_stride = a.r_chan_stride; m.Vs = a.Vs; m.vs_pitch = vs_pitch; m.n_rank_cols = n_cols;
+            m.P = a.P; m.n_planes = a.n_planes;
+        }
+        // (as exec_sim: the lookups of the bit-sliced selection are the caller's launch)
+        HIP_TRY(launch_mask_sim(m, Id.b.as<int32_t>(), idx_pitch, Nd.b.as<int32_t>(), first_frame, max_count, c->stream, parts, m.P != nullptr, &info));
+        if (median_path > 0 && (parts & 1) && frame_end > frame0) {
+            const char* expect = median_path == 2 ? "mask_sim_bits_kernel" : "mask_sim_rank_kernel";
+            if (std::strcmp(info.kernel, expect) != 0) {
+                (void)hipStreamSynchronize(c->stream);
+                return fail(REPET_ERR_LIMIT, "the launcher did not take the median path asked for");
+            }
+            if (median_path == 2) { HIP_TRY(launch_mask_from_codes(m, Nd.b.as<int32_t>(), c->stream)); from_codes = true; }
+        }
+    }
+    if (want & 1) HIP_TRY(hipMemcpyAsync(mask_out, Md.b.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (want & 2) HIP_TRY(hipMemcpyAsync(X_out, Xd.b.p, cells * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    if (want & 4) HIP_TRY(hipMemcpyAsync(model_out, Wd.b.p, model_cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (kind == 2 && median_path == 2)
+        HIP_TRY(hipMemcpyAsync(codes_out, MCd.b.p, (size_t)C * chan_stride * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    auto put = [](char* out, int32_t cap, const char* name) {
+        if (out && cap > 0) { std::strncpy(out, name, (size_t)cap - 1); out[cap - 1] = 0; }
+    };
+    put(kernel_out, kernel_cap, info.kernel);
+    put(nyquist_out, nyquist_cap, info.nyquist);
+    if (launch_out) {
+        const int64_t v[16] = {info.net, info.flag, info.parts, info.grid[0], info.grid[1], info.grid[2], info.nyquist_net, info.nyquist_preload,
+                               info.nyquist_grid[0], info.nyquist_grid[1], info.nyquist_grid[2], from_codes, 0, 0, 0, 0};
+        std::memcpy(launch_out, v, sizeof(v));
+    }
+    return REPET_OK;
+}
+
 int repet_rank_columns(repet_ctx* c, const float* v, int64_t T, int32_t F, uint16_t* codes_out, float* sorted_out) {
     if (!c || !v || !codes_out || !sorted_out) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (F < 128) return fail(REPET_ERR_BAD_ARG, "needs at least 128 bins");

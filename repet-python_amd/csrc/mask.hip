@@ -512,7 +512,9 @@ __global__ __launch_bounds__(64) void mask_sim_nyquist_kernel(MaskArgs a, const 
     const int64_t n_rows = a.T - first_frame;       // first_frame >= frame0: rows before it are warm-up frames
     const int64_t r = r0 < n_rows ? r0 : n_rows - 1;
     const int64_t t = first_frame + r;
-    const bool active = r0 < n_rows && t >= warm_up_end(a, first_frame, blockIdx.z);   // (a slot's warm-up rows: the main kernel's)
+    // (a slot's warm-up rows: the main kernel's; rows outside [frame0, frame_end) are not this launch's)
+    const int64_t t_end = a.frame_end > 0 ? a.frame_end : a.T;
+    const bool active = r0 < n_rows && t >= warm_up_end(a, first_frame, blockIdx.z) && t >= a.frame0 && t < t_end;
     const float* Vc = a.V + c * a.chan_stride;
     const int n = count[r];
     const int* list = idx + r * (int64_t)idx_pitch;
@@ -547,7 +549,7 @@ static bool nyquist_entry_by_entry() {
 }
 
 hipError_t launch_mask_sim(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count,
-                           int64_t first_frame, int32_t max_count, hipStream_t s, int parts, bool lookups_by_caller) {
+                           int64_t first_frame, int32_t max_count, hipStream_t s, int parts, bool lookups_by_caller, MaskLaunch* info) {
     const int64_t t_end = m.frame_end > 0 ? m.frame_end : m.T;
     if (t_end - m.frame0 <= 0) return hipSuccess;
     // Round 6: the Nyquist-bin kernel runs on the MAIN stream, in front of the selection. With its list fetched up front it is short,
@@ -562,39 +564,50 @@ hipError_t launch_mask_sim(const MaskArgs& m, const int32_t* idx, int32_t idx_pi
         constexpr int NET = decltype(net)::value;
         if (split) {
             if (rows > 0 && (parts & 2)) {
-                if (NET >= 2 && idx_pitch >= 128 && (idx_pitch & 3) == 0 && !nyquist_entry_by_entry())
-                    hipLaunchKernelGGL((mask_sim_nyquist_kernel<NET, true>), dim3((unsigned)ceil_div(rows, 64), (unsigned)m.n_channels, nb),
-                                       dim3(64), 0, s, m, idx, idx_pitch, count, first_frame);
+                const dim3 grid((unsigned)ceil_div(rows, 64), (unsigned)m.n_channels, nb);
+                const bool preload = NET >= 2 && idx_pitch >= 128 && (idx_pitch & 3) == 0 && !nyquist_entry_by_entry();
+                if (preload)
+                    hipLaunchKernelGGL((mask_sim_nyquist_kernel<NET, true>), grid, dim3(64), 0, s, m, idx, idx_pitch, count, first_frame);
                 else
-                    hipLaunchKernelGGL(mask_sim_nyquist_kernel<NET>, dim3((unsigned)ceil_div(rows, 64), (unsigned)m.n_channels, nb),
-                                       dim3(64), 0, s, m, idx, idx_pitch, count, first_frame);
+                    hipLaunchKernelGGL(mask_sim_nyquist_kernel<NET>, grid, dim3(64), 0, s, m, idx, idx_pitch, count, first_frame);
+                if (info) {
+                    info->nyquist = "mask_sim_nyquist_kernel"; info->nyquist_net = NET; info->nyquist_preload = preload;
+                    info->nyquist_grid[0] = grid.x; info->nyquist_grid[1] = grid.y; info->nyquist_grid[2] = grid.z;
+                }
             }
             if (parts & 1) {
                 if constexpr (NET >= 2) {
                     if (m.P != nullptr && nb == 1 && first_frame == 0 &&
                         mask_sim_bits_supported(m.T, m.n_channels, m.n_rank_cols, max_count) && m.n_rank_cols == m.F - 1) {
-                        bits_error = launch_mask_sim_bits(m, idx, idx_pitch, count, max_count, n_launch, s);
+                        bits_error = launch_mask_sim_bits(m, idx, idx_pitch, count, max_count, n_launch, s, info);
                         if (bits_error == hipSuccess && !lookups_by_caller) bits_error = launch_mask_from_codes(m, count, s);
                     } else if (m.R != nullptr && ((m.F - 1) & 127) == 0 && nb == 1 && first_frame == 0) {
                         const int n_quads = (int)ceil_div(n_launch, 4);
                         const int combos = m.n_channels * ((m.F - 1) >> 7);
-                        hipLaunchKernelGGL(mask_sim_rank_kernel<NET>, dim3((unsigned)(8 * ceil_div(combos, 8) * n_quads)), dim3(256), 0, s,
-                                           m, idx, idx_pitch, count, n_quads);
+                        const dim3 grid((unsigned)(8 * ceil_div(combos, 8) * n_quads));
+                        hipLaunchKernelGGL(mask_sim_rank_kernel<NET>, grid, dim3(256), 0, s, m, idx, idx_pitch, count, n_quads);
+                        if (info) info->set_main("mask_sim_rank_kernel", NET, 0, 0, grid);
                     } else if (NET <= 16 && ((m.F - 1) & 255) == 0 && (m.FS & 3) == 0 && mask_wide_enabled()) {
-                        if constexpr (NET <= 16)
-                            hipLaunchKernelGGL(mask_sim_wide_kernel<NET>, dim3((unsigned)ceil_div(n_launch, kWideRun), (unsigned)m.n_channels, nb), dim3(256), 0, s,
-                                               m, idx, idx_pitch, count, first_frame, n_launch);
-                    } else
+                        if constexpr (NET <= 16) {
+                            const dim3 grid((unsigned)ceil_div(n_launch, kWideRun), (unsigned)m.n_channels, nb);
+                            hipLaunchKernelGGL(mask_sim_wide_kernel<NET>, grid, dim3(256), 0, s, m, idx, idx_pitch, count, first_frame, n_launch);
+                            if (info) info->set_main("mask_sim_wide_kernel", NET, 0, 0, grid);
+                        }
+                    } else {
                         hipLaunchKernelGGL((mask_sim_kernel<NET, true>), dim3(n_launch, (unsigned)m.n_channels, nb), dim3(256), 0, s,
                                            m, idx, idx_pitch, count, first_frame);
+                        if (info) info->set_main("mask_sim_kernel", NET, 1, 0, dim3(n_launch, (unsigned)m.n_channels, nb));
+                    }
                 } else {
                     hipLaunchKernelGGL((mask_sim_kernel<NET, true>), dim3(n_launch, (unsigned)m.n_channels, nb), dim3(256), 0, s,
                                        m, idx, idx_pitch, count, first_frame);
+                    if (info) info->set_main("mask_sim_kernel", NET, 1, 0, dim3(n_launch, (unsigned)m.n_channels, nb));
                 }
             }
         } else if (parts & 1) {
             hipLaunchKernelGGL((mask_sim_kernel<NET, false>), dim3(n_launch, (unsigned)m.n_channels, nb), dim3(256), 0, s,
                                m, idx, idx_pitch, count, first_frame);
+            if (info) info->set_main("mask_sim_kernel", NET, 0, 0, dim3(n_launch, (unsigned)m.n_channels, nb));
         }
     });
     if (bits_error != hipSuccess) return bits_error;
@@ -643,11 +656,12 @@ __global__ __launch_bounds__(256) void mask_adaptive_kernel(MaskArgs a, const in
     }
 }
 
-hipError_t launch_mask_adaptive(const MaskArgs& m, const int32_t* periods, int32_t order, hipStream_t s) {
+hipError_t launch_mask_adaptive(const MaskArgs& m, const int32_t* periods, int32_t order, hipStream_t s, MaskLaunch* info) {
     if (m.T <= 0) return hipSuccess;
     dispatch_net(order, [&](auto net) {
         hipLaunchKernelGGL(mask_adaptive_kernel<decltype(net)::value>, dim3((unsigned)m.T, (unsigned)m.n_channels),
                            dim3(256), 0, s, m, periods, order);
+        if (info) info->set_main("mask_adaptive_kernel", decltype(net)::value, 0, 0, dim3((unsigned)m.T, (unsigned)m.n_channels));
     });
     return hipGetLastError();
 }
@@ -738,7 +752,7 @@ __global__ __launch_bounds__(256) void mask_period_kernel(MaskArgs a, const int*
 }
 
 hipError_t launch_mask_period(const MaskArgs& m, const int32_t* period_dev, int32_t period_host,
-                              int32_t min_period, hipStream_t s) {
+                              int32_t min_period, hipStream_t s, MaskLaunch* info) {
     if (m.T <= 0) return hipSuccess;
     // the period lives on the device when it was just estimated there; the grid covers the largest
     // admissible period (a third of the frames, repet.py:1266) and surplus workgroups exit
@@ -756,9 +770,11 @@ hipError_t launch_mask_period(const MaskArgs& m, const int32_t* period_dev, int3
     if (max_segments <= 32) {        // a tight bound and a small network: the single-network kernel
         dispatch_net(max_segments, [&](auto net) {
             hipLaunchKernelGGL(mask_period_kernel<decltype(net)::value>, grid, dim3(256), 0, s, m, period_dev, period_host, parts);
+            if (info) info->set_main("mask_period_kernel", decltype(net)::value, 0, parts, grid);
         });
     } else {
         hipLaunchKernelGGL(mask_period_kernel<-1>, grid, dim3(256), 0, s, m, period_dev, period_host, parts);
+        if (info) info->set_main("mask_period_kernel", -1, 0, parts, grid);
     }
     return hipGetLastError();
 }

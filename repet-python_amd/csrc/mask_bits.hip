@@ -272,13 +272,14 @@ __global__ __launch_bounds__(256) void mask_from_codes_kernel(MaskArgs a, const 
 
 template <int H>
 hipError_t launch_bits_h(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count, unsigned n_launch, int bpc_shift,
-                         hipStream_t s) {
+                         hipStream_t s, MaskLaunch* info) {
 #define REPET_BITS_CASE(NP) case NP: hipLaunchKernelGGL((mask_sim_bits_kernel<H, NP>), dim3(8 * ((n_launch + 7) / 8)), dim3(256), 0, s, m, idx, idx_pitch, count, bpc_shift); break;
     switch (m.n_planes) {
         REPET_BITS_CASE(11) REPET_BITS_CASE(12) REPET_BITS_CASE(13) REPET_BITS_CASE(14) REPET_BITS_CASE(15)
         default: return hipErrorInvalidValue;
     }
 #undef REPET_BITS_CASE
+    if (info) info->set_main("mask_sim_bits_kernel", H, m.n_planes, 0, dim3(8 * ((n_launch + 7) / 8)));
     return hipGetLastError();
 }
 
@@ -304,14 +305,14 @@ int mask_sim_bits_instructions(int32_t max_count, int32_t n_planes) {
 }
 
 hipError_t launch_mask_sim_bits(const MaskArgs& m, const int32_t* idx, int32_t idx_pitch, const int32_t* count, int32_t max_count,
-                                unsigned n_launch, hipStream_t s) {
+                                unsigned n_launch, hipStream_t s, MaskLaunch* info) {
     if (!m.P || !mask_sim_bits_supported(m.T, m.n_channels, m.n_rank_cols, max_count) || m.n_planes != code_planes_for(m.T) ||
         idx_pitch < 128 || !m.median_codes || (int64_t)m.n_channels * m.chan_stride * 4 >= ((int64_t)1 << 31))
         return hipErrorInvalidValue;
     int bpc_shift = 0;
     while ((64 << bpc_shift) < m.n_rank_cols) ++bpc_shift;
-    return max_count <= 100 ? launch_bits_h<25>(m, idx, idx_pitch, count, n_launch, bpc_shift, s)
-                            : launch_bits_h<32>(m, idx, idx_pitch, count, n_launch, bpc_shift, s);
+    return max_count <= 100 ? launch_bits_h<25>(m, idx, idx_pitch, count, n_launch, bpc_shift, s, info)
+                            : launch_bits_h<32>(m, idx, idx_pitch, count, n_launch, bpc_shift, s, info);
 }
 
 hipError_t launch_mask_from_codes(const MaskArgs& m, const int32_t* count, hipStream_t s) {

@@ -428,6 +428,8 @@ def _stage_entry(name):
                                         i32, i32, i32, i32, i32, i64, i64, i32, p, i64, p, i32, p],
             "repet_debug_gram_band_stage": [p, p, i32, i64, i32, i32, i64, i32, i32, i32, i32, i32, p, p, p, p, p, i32],
             "repet_debug_band_periods_stage": [p, p, i32, i64, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32, i64, i32, p, p, p],
+            "repet_debug_mask_stage": [p, i32, p, p, i32, i32, i64, i32, i32, i32, i32, i32, p, i32, i32, p, p, i64, i32, i64, i32, i64, i64,
+                                       i32, p, i64, i32, i32, p, p, p, p, p, p, i32, p, i32, p],
         }[name]
         _stage_entries[name] = fn
     return _stage_entries[name]
@@ -585,6 +587,80 @@ def _band_periods_stage(band, n_freq, start0, step, length, n_windows, lo, hi, n
         int(step), int(length), int(n_windows), int(lo), int(hi), int(n_lags_for_clamp), int(t_expand), int(prefill), _native.ptr(beat),
         _native.ptr(win), None if frames is None else _native.ptr(frames)))
     return beat, win, frames
+
+
+MASK_KINDS = {"period": 0, "adaptive": 1, "sim": 2}
+MEDIAN_PATHS = {"float": 0, "rank": 1, "bits": 2}
+
+
+def _mask_stage(kind, V, X=None, want=("mask",), cutoff=0, prefill=0, period=None, periods=None, min_period=1, order=1, idx=None,
+                cnt=None, first_frame=0, max_count=None, frame0=0, frame_end=0, parts=3, slot_start=None, slot_bias=0, idx_pitch=None,
+                median_path="float"):
+    """One of ``launch_mask_period`` / ``launch_mask_adaptive`` / ``launch_mask_sim`` as the pipelines call them, on buffers laid
+    out as ``make_geo`` lays them out (``repet_debug_mask_stage``). ``V`` (B, C, T, F) fp32, ``X`` (B, C, T, F) complex64 or None.
+    ``want``: any of "mask", "X" -- or "model" alone (period). ``kind`` "period": ``period`` (host) or ``periods`` (B,) device
+    periods + ``min_period``; "adaptive": ``periods`` (T,) + ``order``; "sim": ``idx`` (B, rows, width), ``cnt`` (B, rows),
+    ``first_frame``, ``max_count`` (default width), ``frame0``, ``frame_end`` (0: T), ``parts`` 1 main bins / 2 Nyquist bin / 3 both,
+    ``slot_start`` (B,) + ``slot_bias``, ``idx_pitch`` (default max(width, 128)), ``median_path`` "float" / "rank" / "bits".
+    Returns a dict: "mask" (B, C, rows, FS), "X" (B, C, rows, FS) complex64, "model" (B, C, T // 3 + 2, FS), "codes" (C, rows, FS)
+    uint32 (bit-sliced path) -- each whole, as the kernel left it over the byte ``prefill`` --, "Tpad", "rows", "FS" and "launch":
+    the kernel of the main bins ("kernel", e.g. "mask_sim_kernel<10, true>", with "name", "net", "flag", "parts", "grid"), of the
+    Nyquist bin ("nyquist", "nyquist_net", "nyquist_preload", "nyquist_grid") and "lookups" (mask_from_codes_kernel ran). Input
+    that would index out of range raises ValueError; a shape the median path does not take RuntimeError."""
+    import ctypes as C
+    v = _f32(V)
+    assert v.ndim == 4
+    b, ch, t, f = v.shape
+    x = None if X is None else np.ascontiguousarray(X, dtype=np.complex64)
+    assert x is None or x.shape == v.shape
+    bits = sum({"mask": 1, "X": 2, "model": 4}[k] for k in want)
+    fs, tpad = -(-f // 32) * 32, -(-t // 128) * 128
+    rows_all, model_rows = tpad + 8, t // 3 + 2
+    per = None if periods is None else np.ascontiguousarray(periods, dtype=np.int32)
+    if kind == "period":
+        assert (per is None) != (period is None) and (per is None or per.shape == (b,))
+    elif kind == "adaptive":
+        assert per is not None and per.shape == (t,)
+    ix = nn = ss = None
+    n_list_rows = width = 0
+    if kind == "sim":
+        ix, nn = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(cnt, dtype=np.int32)
+        assert ix.ndim == 3 and ix.shape[0] == b and nn.shape == ix.shape[:2]
+        n_list_rows, width = ix.shape[1:]
+        max_count = width if max_count is None else max_count
+        idx_pitch = max(width, 128) if idx_pitch is None else idx_pitch
+        if slot_start is not None:
+            ss = np.ascontiguousarray(slot_start, dtype=np.int64)
+            assert ss.shape == (b,)
+    mask = np.empty((b, ch, rows_all, fs), dtype=np.float32) if bits & 1 else None
+    xo = np.empty((b, ch, rows_all, fs), dtype=np.complex64) if bits & 2 else None
+    model = np.empty((b, ch, model_rows, fs), dtype=np.float32) if bits & 4 else None
+    codes = np.empty((ch, rows_all, fs), dtype=np.uint32) if kind == "sim" and median_path == "bits" else None
+    geo, words = (C.c_int64 * 8)(), (C.c_int64 * 16)()
+    name, nyq = C.create_string_buffer(64), C.create_string_buffer(64)
+    opt = lambda a: None if a is None else _native.ptr(a)
+    _native.check(_stage_entry("repet_debug_mask_stage")(
+        _native.default_context(_device).handle, MASK_KINDS[kind], _native.ptr(v), opt(x), b, ch, t, f, int(cutoff), int(prefill), bits,
+        int(period or 0), opt(per), int(min_period), int(order), opt(ix), opt(nn), n_list_rows, width, int(first_frame), int(max_count or 0),
+        int(frame0), int(frame_end), int(parts), opt(ss), int(slot_bias), int(idx_pitch or 0), MEDIAN_PATHS[median_path], geo, opt(mask),
+        opt(xo), opt(model), opt(codes), name, len(name), nyq, len(nyq), words))
+    assert (int(geo[0]), int(geo[1]), int(geo[2]), int(geo[4])) == (tpad, rows_all, fs, model_rows)
+    w = [int(k) for k in words]
+    main = name.value.decode()
+    if main == "mask_sim_kernel":
+        full = "%s<%d, %s>" % (main, w[0], "true" if w[1] else "false")
+    elif main == "mask_sim_bits_kernel":
+        full = "%s<%d, %d>" % (main, w[0], w[1])
+    else:
+        full = "%s<%d>" % (main, w[0]) if main else ""
+    nyquist = "%s<%d, %s>" % (nyq.value.decode(), w[6], "true" if w[7] else "false") if nyq.value else ""
+    out = {"Tpad": tpad, "rows": rows_all, "FS": fs,
+           "launch": {"kernel": full, "name": main, "net": w[0], "flag": w[1], "parts": w[2], "grid": tuple(w[3:6]), "nyquist": nyquist,
+                      "nyquist_net": w[6], "nyquist_preload": bool(w[7]), "nyquist_grid": tuple(w[8:11]), "lookups": bool(w[11])}}
+    for key, a in (("mask", mask), ("X", xo), ("model", model), ("codes", codes)):
+        if a is not None:
+            out[key] = a
+    return out
 
 
 def _selfsimilaritymatrix(data_matrix):
