@@ -25,9 +25,12 @@
 // mask exactly as mask_sim_rank_kernel does: same codes, same table, same soft_mask -- the same bits
 // (tests/test_gpu_variants.py::test_median_paths_agree_bit_for_bit, tests/test_gpu_stages.py::
 // test_median_selection_on_rank_codes_against_numpy). What bounds it (tools/microbench/bitslice_select.hip, gather_rate.hip):
-// the gathers -- 1 300 dword wave-loads per frame, of which a CU's vector memory path takes one every ~11 cycles whatever the
-// cache says -- rather than the wave instructions.
+// the gathers -- 13 planes x 100 entries + the frame's own 13 rows = 1 313 dword wave-loads per frame, every plane row of every
+// entry fetched exactly once, of which a CU's vector memory path takes one every 8.4 cycles whatever the cache says -- rather
+// than the wave instructions.
 #include "common.h"
+
+#include <type_traits>
 
 namespace repet {
 
@@ -108,8 +111,10 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
     const unsigned even = (n & 1) ? 0u : ~0u;
 #pragma unroll
     for (int d = 0; d < kR; ++d) r1[d] = ((((n - 1) >> 1) >> d) & 1) ? ~0u : 0u;
-#pragma unroll 1
-    for (int p = NP - 1; p >= 0; --p) {
+    // One round of the descent, on plane p (ln: the lane). Every round but the last ends with the gathers of plane p - 1; the
+    // last one has no plane left to fetch: every plane row of every entry is fetched exactly once, NP * 4 H wave-loads per frame.
+    auto round = [&](const int p, const int ln, auto last_round) {
+        constexpr bool kLast = decltype(last_round)::value;
         unsigned c1[kD];
         BitsliceCount<H>::run([&](int k) { return bs_andn(A1[k], B[k]); }, c1);
         unsigned any2 = 0u;
@@ -126,8 +131,8 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
             unsigned v[8];
 #pragma unroll
             for (int d = 0; d < 8; ++d) v[d] = d < kD ? c1[d] : d == kD ? any2 : 0u;
-            xch[w][0][lane] = make_uint4(v[0], v[1], v[2], v[3]);
-            xch[w][1][lane] = make_uint4(v[4], v[5], v[6], v[7]);
+            xch[w][0][ln] = make_uint4(v[0], v[1], v[2], v[3]);
+            xch[w][1][ln] = make_uint4(v[4], v[5], v[6], v[7]);
         }
         __syncthreads();
         if (w == lead) {                                    // the leader adds the partial counts up and decides for everybody
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
 #pragma unroll
             for (int oi = 0; oi < 3; ++oi) {
                 const int ow = (lead + 1 + oi) & 3;
-                const uint4 lo = xch[ow][0][lane], hi = xch[ow][1][lane];
+                const uint4 lo = xch[ow][0][ln], hi = xch[ow][1][ln];
                 q[oi][0] = lo.x; q[oi][1] = lo.y; q[oi][2] = lo.z; q[oi][3] = lo.w;
                 q[oi][4] = hi.x; q[oi][5] = hi.y; q[oi][6] = hi.z; q[oi][7] = hi.w;
             }
@@ -175,23 +180,33 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
             D = bs_or_andn(D, s1, s2);
 #pragma unroll
             for (int d = 0; d < kR; ++d) r1[d] = bs_sel(bw, r1[d], diff[d]);
-            dec[0][lane] = s1; dec[1][lane] = s2;
-            lu[0][p][lane] = ~s1; lu[1][p][lane] = ~s2;
+            dec[0][ln] = s1; dec[1][ln] = s2;
+            lu[0][p][ln] = ~s1; lu[1][p][ln] = ~s2;
             __builtin_amdgcn_s_setprio(0);
         }
         __syncthreads();
-        const unsigned s1 = dec[0][lane], s2 = dec[1][lane];
+        const unsigned s1 = dec[0][ln], s2 = dec[1][ln];
         // The entry's row offset is ADDED to the lanes' offset (one v_add per load) rather than handed over as the load's scalar
         // offset: with a scalar offset operand the CU takes a dword wave-load every 11.4 cycles, without one every 8.4
         // (tools/microbench/gather_rate.hip) -- 0.206 -> 0.190 ms.
-        const int next = lane * 4 + (p > 0 ? p - 1 : 0) * (kRowWords * 4);     // (the last round reads plane 0 again rather than branching)
+        // (`next` is opaque to the compiler: otherwise it keeps lane * 4 + off[k] in 25 VGPRs over the loop and adds the plane's
+        // offset as the scalar -- 149 VGPRs, three waves per SIMD. An empty statement: nothing is emitted for it.)
+        int next = ln * 4 + (p - 1) * (kRowWords * 4);
+        if constexpr (!kLast) asm volatile("" : "+v"(next));
 #pragma unroll
         for (int k = 0; k < H; ++k) {
             A1[k] = bs_keep(A1[k], B[k], s1);
             A2[k] = bs_keep(A2[k], B[k], s2);
-            B[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, next + off[k], 0, 0);
+            if constexpr (!kLast) B[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, next + off[k], 0, 0);
         }
-    }
+    };
+#pragma unroll 1
+    for (int p = NP - 1; p > 0; --p) round(p, lane, std::false_type{});
+    // The last round is peeled (chosen at compile time: no branch around the loads). From here on the lane comes from
+    // v_mbcnt: with the thread index's the compiler carries lane, 4 lane and 16 lane through the loop for the addresses of
+    // the peeled copy -- 120 / 147 VGPRs instead of 118 / 145 (tests/test_select_registers.py holds the kernel to its counts).
+    const int lane_t = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    round(0, lane_t, std::true_type{});
     // ---- the two code images back into numbers: wave w for the cells of bits [8 w, 8 w + 8) ----
     // One word per cell goes to median_codes (V's geometry): upper code << 16 | lower code, bit 15 = "the lower median is
     // below the frame's own value" (codes have 15 bits at most). mask_from_codes_kernel turns them into magnitudes: its
@@ -200,14 +215,14 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
     const int n_bits = a.n_channels << bpc_shift;           // blocks of 64 bins over all channels (<= 32)
     unsigned own[NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) own[p] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(t * kRowBytes) + lane * 4, p * (kRowWords * 4), 0);
+    for (int p = 0; p < NP; ++p) own[p] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (unsigned)(t * kRowBytes) + lane_t * 4, p * (kRowWords * 4), 0);
     // need = lower median < own code: the borrow of (lower - own), least significant plane first
     unsigned need = 0u, x[16];
     const unsigned pick = 0x0C040C00u + 0x00010001u * w;   // v_perm_b32: byte w of the upper image | byte w of the lower one
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
         if (p < NP) {
-            const unsigned lo = lu[0][p][lane], hi = lu[1][p][lane];
+            const unsigned lo = lu[0][p][lane_t], hi = lu[1][p][lane_t];
             need = bs_borrow(lo, own[p], need);
             x[p] = __builtin_amdgcn_perm(hi, lo, pick);
         } else x[p] = 0u;
@@ -221,7 +236,7 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
             const int c = b >> bpc_shift, fb = b - (c << bpc_shift);
             const int row = (int)(c * a.chan_stride + t * a.FS) + fb * 64;            // elements; the lane adds itself
             const unsigned flag = ((need >> b) & 1u) << 15;
-            __builtin_amdgcn_raw_buffer_store_b32(x[j] | flag, c_rsrc, lane * 4, row * 4, 2);      // nt: read once, by the next kernel
+            __builtin_amdgcn_raw_buffer_store_b32(x[j] | flag, c_rsrc, lane_t * 4, row * 4, 2);      // nt: read once, by the next kernel
         }
     }
 }

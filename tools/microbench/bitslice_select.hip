@@ -10,13 +10,16 @@
 // prefetched into a second register set 0.246 against 0.202 (a wave per SIMD less); planes in groups of four behind
 // buffer_load_dwordx4 0.28 (two waves per SIMD). What bounds all of them: gather_rate.hip -- the CU takes one dword wave-load
 // per 11.4 cycles whatever the cache says when the row comes as the load's scalar offset, per 8.4 when it is added into the
-// lanes' offset (0.218 -> 0.20 here), and a frame needs 1 300 of them.
+// lanes' offset (0.218 -> 0.20 here), and a frame needs 1 300 of them: 13 planes x 100 entries, the last round of the descent
+// fetches no further plane. All figures above are those of the build that fetched plane 0 twice and held 168 VGPRs, three
+// waves per SIMD; this one holds 120 and four (local lists 0.200 -> 0.164, uniform 0.272 -> 0.276: profiles/select_rounds_ab.txt).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <type_traits>
 #include <vector>
 
 template <int IMM>
@@ -46,8 +49,9 @@ __device__ unsigned long long g_phase[8192][4][8];
 #define ST(i)
 #endif
 
-// the selection of mask_sim_bits_kernel (mask_bits.hip) without what follows it: the two code images go to `out` (the compiler
-// gives this copy 168 VGPRs -- three waves per SIMD -- where the kernel in the library has 118 and four)
+// the selection of mask_sim_bits_kernel (mask_bits.hip) without what follows it: the two code images go to `out` (with the
+// plane offset opaque as in the library the compiler gives this copy 120 VGPRs, four waves per SIMD like the library's 118;
+// before, it kept lane * 4 + off[k] in registers here: 168 and three)
 template <int NP>
 __global__ __launch_bounds__(256) void select_kernel(const unsigned* __restrict__ planes, const int* __restrict__ idx, int idx_pitch,
                                                      const int* __restrict__ count, unsigned* __restrict__ out, int T) {
@@ -80,8 +84,9 @@ __global__ __launch_bounds__(256) void select_kernel(const unsigned* __restrict_
 #pragma unroll
     for (int d = 0; d < kR; ++d) r1[d] = (((n - 1) >> 1) >> d & 1) ? ~0u : 0u;
     unsigned* o = out + (long)t * 2 * NP * 64;
-#pragma unroll 1
-    for (int p = NP - 1; p >= 0; --p) {
+    // one round of the descent on plane p; the last one (peeled, chosen at compile time) has no further plane to fetch
+    auto round = [&](const int p, auto last_round) {
+        constexpr bool kLast = decltype(last_round)::value;
 #ifdef STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ST(0)                                   // waiting for the plane
@@ -154,15 +159,19 @@ __global__ __launch_bounds__(256) void select_kernel(const unsigned* __restrict_
         __syncthreads();
         ST(4)                                   // second barrier
         const unsigned s1 = dec[0][lane], s2 = dec[1][lane];
-        const int next = lane * 4 + (p > 0 ? p - 1 : 0) * (kRowWords * 4);
+        int next = lane * 4 + (p - 1) * (kRowWords * 4);
+        if constexpr (!kLast) asm volatile("" : "+v"(next));     // (opaque, as in mask_bits.hip: the entries' offsets stay scalar)
 #pragma unroll
         for (int k = 0; k < kH; ++k) {          // (the row in the lane offset: gather_rate.hip)
             A1[k] = bs_keep(A1[k], B[k], s1);
             A2[k] = bs_keep(A2[k], B[k], s2);
-            B[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, next + off[k], 0, 0);
+            if constexpr (!kLast) B[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, next + off[k], 0, 0);
         }
         ST(5)                                   // update, issue of the next plane's loads
-    }
+    };
+#pragma unroll 1
+    for (int p = NP - 1; p > 0; --p) round(p, std::false_type{});
+    round(0, std::true_type{});
 #ifdef STAMPS
     if (blockIdx.x < 8192 && lane == 0) {
         acc[6] = __builtin_amdgcn_s_memtime() - start;
