@@ -290,12 +290,17 @@ struct PeakRefine {
 // start (0: n_cols): the clip's row j >= start - 1 is decided on min(n_cols, j + 1) columns, the frames 0 .. j of its own stream
 // while its buffer is still filling (peaks.h: row_columns). Modes 1 and 2 count their columns so with or without a batch.
 struct PeakBatch { int32_t n_batch; int64_t m_stride, idx_stride, cnt_stride, unit_stride; const int64_t* origin; int32_t start; };
+// What the peak-picking launchers launched (nullable trailing argument; the stage entry of engine_stages.hip returns it, the
+// pipelines pass nothing). family: "wave" (local_maxima_wave_kernel<rd, false>), "wave+records" (<0, true>), "block"
+// (local_maxima_kernel<qmax, 0>), "block two-stage" (<qmax, 1> + <1, 2>); lite: local_maxima_lite_kernel ran on the recorded
+// rows; unit_kq: the unit_rows_f64_wg_kernel variant (0: not launched); exact_fft: the FFT plan of local_maxima_exact_kernel (0: not launched)
+struct PeakLaunch { const char* family = ""; int32_t qmax = 0, rd = -1, unit_kq = 0, lite = 0, exact_fft = 0; };
 hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int32_t n_cols, int64_t pitch,
                                int32_t mode, float min_value, int32_t d, int32_t number, int32_t* idx,
                                int32_t idx_pitch, int32_t* count, hipStream_t s, int64_t shift = 0,
                                const PeakRefine* refine = nullptr, const PeakBatch* batch = nullptr,
                                void* scratch = nullptr, const struct ExactSource* lite_src = nullptr,
-                               const float* seg = nullptr, int32_t seg_pitch = 0);
+                               const float* seg = nullptr, int32_t seg_pitch = 0, PeakLaunch* info = nullptr);
 //   seg (mode 0, nullable): the rows' segment records (peaks.h: launch_segment_maxima, or the Gram kernel's epilogue), row r
 //           of M at seg + (row0 + r) * 3 * seg_pitch: the wavefront kernel then takes its candidates from them.
 //   lite_src (second level, fast path): instead of the first pass, the rows it left records of (PeakRefine::records)
@@ -310,7 +315,7 @@ constexpr int kSegWidth = 32;
 hipError_t launch_segment_maxima(const float* M, int64_t n_rows, int n_cols, int64_t pitch, float* seg, int seg_pitch, hipStream_t s);
 int segment_pitch(int n_cols);
 bool local_maxima_segments_apply(int n_cols, int d, int64_t pitch, int mode, int n_batch);
-hipError_t launch_unit_rows_f64(const struct ExactSource& src, const PeakRefine* refine, hipStream_t s);
+hipError_t launch_unit_rows_f64(const struct ExactSource& src, const PeakRefine* refine, hipStream_t s, PeakLaunch* info = nullptr);
 //   scratch (nullable): local_maxima_scratch_bytes(n_rows, n_cols, d) bytes (0 for rows that fit one workgroup). With
 //           it, rows of any length are handled in segments; without it the limit is about 40 000 elements per row.
 size_t local_maxima_scratch_bytes(int64_t n_rows, int32_t n_cols, int32_t d);
@@ -331,7 +336,7 @@ size_t local_maxima_exact_scratch_bytes(int32_t n_cols, int* grid_out = nullptr)
 hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_cols, int64_t pitch, int32_t mode, float min_value,
                                      int32_t d, int32_t number, int32_t* idx, int32_t idx_pitch, int32_t* count, hipStream_t s,
                                      int64_t shift, const PeakRefine* refine, const PeakBatch* batch, const ExactSource& src,
-                                     void* scratch);
+                                     void* scratch, PeakLaunch* info = nullptr);
 
 // K5/K8/K8b: gather-median masks. V[c][t][FS] -> (optional) mask[c][t][FS]; if X != null it is
 // multiplied in place by the mask after the high-pass override mask[1..cutoff] = 1 (repet.py:185).

@@ -211,7 +211,7 @@ int make_refine(repet_ctx* c, const float* unit_rows, int FS, double threshold, 
 int run_exact_rows(repet_ctx* c, const Tables* tb, const Geo& g, const float* M, int64_t row0, int n_cols, int64_t pitch, int mode,
                    float min_value, int d, int number, int32_t* idx, int idx_pitch, int32_t* count, int64_t shift,
                    const PeakRefine& rf, const PeakBatch* batch, const float* hi, const float* lo, int64_t n_samples,
-                   int64_t clip_stride, int64_t frame_sample0, int64_t n_frames, int clips);
+                   int64_t clip_stride, int64_t frame_sample0, int64_t n_frames, int clips, PeakLaunch* info = nullptr);
 bool rank_median_enabled();
 int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count);
 int exec_sim(repet_ctx* c, const repet_params* p);

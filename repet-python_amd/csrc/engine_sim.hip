@@ -76,7 +76,7 @@ int make_refine(repet_ctx* c, const float* unit_rows, int FS, double threshold, 
 int run_exact_rows(repet_ctx* c, const Tables* tb, const Geo& g, const float* M, int64_t row0, int n_cols, int64_t pitch, int mode,
                    float min_value, int d, int number, int32_t* idx, int idx_pitch, int32_t* count, int64_t shift,
                    const PeakRefine& rf, const PeakBatch* batch, const float* hi, const float* lo, int64_t n_samples,
-                   int64_t clip_stride, int64_t frame_sample0, int64_t n_frames, int clips) {
+                   int64_t clip_stride, int64_t frame_sample0, int64_t n_frames, int clips, PeakLaunch* info) {
     if (!rf.redo_list) return REPET_OK;
     hipStream_t stream = c->stream;
     if (lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(stream, c->ring.lo_done, 0));       // the remainder plane has arrived
@@ -95,14 +95,14 @@ int run_exact_rows(repet_ctx* c, const Tables* tb, const Geo& g, const float* M,
     src.u64_gen = c->u64_gen.as<unsigned int>(); src.gen_clip_stride = n_frames;
     if (rf.lite_list) {
         // fast path: the float64 unit rows of the queued frames, then the recorded rows again with them
-        HIP_TRY(launch_unit_rows_f64(src, &rf, stream));
+        HIP_TRY(launch_unit_rows_f64(src, &rf, stream, info));
         HIP_TRY(launch_local_maxima(M, 0, row0, n_cols, pitch, mode, min_value, d, number, idx, idx_pitch, count, stream, shift,
-                                    &rf, batch, nullptr, &src));
+                                    &rf, batch, nullptr, &src, nullptr, 0, info));
     }
     // general path: flat rows, rows of the workgroup kernel, rows the fast path handed on
     HIP_TRY(c->exact_scratch.ensure(local_maxima_exact_scratch_bytes(n_cols)));
     HIP_TRY(launch_local_maxima_exact(M, row0, n_cols, pitch, mode, min_value, d, number, idx, idx_pitch, count, stream, shift,
-                                      &rf, batch, src, c->exact_scratch.p));
+                                      &rf, batch, src, c->exact_scratch.p, info));
     return REPET_OK;
 }
 

@@ -937,4 +937,156 @@ int repet_ctx_last_refine_stats(repet_ctx* c, int64_t out[4]) {
     return REPET_OK;
 }
 
+// ---- stage entry of the production peak-picking launchers (tests/test_gpu_peaks_stages.py) -----------------------------
+// repet_local_maxima above is launch_local_maxima in mode 0 without refinement, batch, origin, shift or scratch: no pipeline
+// launches the kernels that way. This one runs the chain of exec_sim / exec_simonline / the live handles -- launch_segment_maxima
+// where local_maxima_segments_apply says so, make_refine, launch_local_maxima, run_exact_rows -- on buffers the caller lays out:
+//   M     (n_batch, m_rows, n_cols) fp32, copied to rows of `pitch` floats (mode 0: matrix rows; modes 1 and 2: the band as
+//         run_gram_band lays it out, band row = frame - shift)
+//   unit  (n_batch, n_frames, F) fp32 unit rows, copied to pitch FS = round_up(F, 32) with zero pad bins (PeakRefine::unit_rows;
+//         mode 0: row = frame = column; modes 1 and 2: row = band row)
+//   hi, lo (nullable) (n_batch, n_samples, C) fp32: the ExactSource; frame row fr starts at sample frame_sample0 + fr * W / 2
+//   refine 0: none (unit, hi unused); 1: level 1 only (make_refine with no rows for the second level); 2: both levels
+//   origin (nullable, n_batch) and start: PeakBatch; the batch is passed when n_batch > 1, origin is given or start > 0
+// idx, count, the float64 unit-row table and every cell of the device copy of M the caller did not supply hold the byte
+// `prefill` before the launch. Every row the launch can touch is walked on the host first, with the cells it may read: a
+// band row or unit row outside the buffers is REPET_ERR_BAD_ARG, never an out-of-range load.
+// Out: idx (n_batch, n_rows + 1, KP) and count (n_batch, n_rows + 1) whole (the last row of a clip is a guard no launch owns),
+// stats[32] the counters added up ([8] a maximum), delta[2] = delta, delta2 of the launch, u64 (n_batch, n_frames, FS) and
+// stamped (n_batch, n_frames; 1: the row's stamp is this launch's generation) when refine == 2, family (PeakLaunch),
+// launch[8] = QMAX, RD, unit_rows_f64_wg_kernel variant, lite relaunch, FFT plan of local_maxima_exact_kernel, KP, FS, 0.
+int repet_debug_peaks_stage(repet_ctx* c, const float* M, int32_t n_batch, int64_t m_rows, int32_t n_cols, int64_t pitch,
+                            const float* unit, int64_t n_frames, int32_t F, const float* hi, const float* lo, int64_t n_samples,
+                            int32_t C, int32_t W, int64_t frame_sample0, int32_t mode, int64_t row0, int64_t n_rows, double min_value,
+                            int32_t d, int32_t number, int64_t shift, const int64_t* origin, int32_t start, int32_t with_scratch,
+                            int32_t refine, int32_t prefill, int32_t* idx_out, int32_t* count_out, int64_t* stats_out,
+                            double* delta_out, double* u64_out, int32_t* stamped_out, char* family_out, int32_t family_cap,
+                            int64_t* launch_out) {
+    if (!c || !M || !idx_out || !count_out || !stats_out || !delta_out || !launch_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (mode < 0 || mode > 2 || refine < 0 || refine > 2) return fail(REPET_ERR_BAD_ARG, "mode in 0..2, refine in 0..2");
+    if (n_batch < 1 || n_batch > 64 || m_rows < 1 || n_cols < 1 || pitch < n_cols || pitch > (1 << 20) || n_rows < 1 || row0 < 0 || d < 0 ||
+        number < 1 || number > (1 << 16) || row0 + n_rows > ((int64_t)1 << 30))
+        return fail(REPET_ERR_BAD_ARG, "bad size");
+    if ((int64_t)n_batch * m_rows * pitch > ((int64_t)1 << 27)) return fail(REPET_ERR_LIMIT, "too many cells for a stage test");
+    const int FS = refine ? (int)round_up(F, kFreqAlign) : 0;
+    if (refine) {
+        if (!unit || n_frames < 1 || F < 1 || (int64_t)n_batch * n_frames * FS > ((int64_t)1 << 27)) return fail(REPET_ERR_BAD_ARG, "refinement: unit rows");
+    }
+    if (refine == 2) {
+        if (!hi || !u64_out || !stamped_out || n_samples < 1 || C < 1 || C > 64 || W < 64 || W > 8192 || (W & (W - 1)) || F != W / 2 + 1 ||
+            (int64_t)n_batch * n_samples * C > ((int64_t)1 << 27) || frame_sample0 < -(int64_t)W || frame_sample0 > n_samples)
+            return fail(REPET_ERR_BAD_ARG, "second level: audio (n_batch, n_samples, C), W a power of two, F = W / 2 + 1");
+    }
+    if (mode == 0) {
+        if (origin || start != 0 || shift != 0) return fail(REPET_ERR_BAD_ARG, "mode 0 takes no origin, start or shift");
+        if (row0 + n_rows > m_rows) return fail(REPET_ERR_BAD_ARG, "mode 0: rows outside the matrix");
+        if (refine && n_frames < std::max<int64_t>(n_cols, row0 + n_rows)) return fail(REPET_ERR_BAD_ARG, "mode 0: a unit row per row and column");
+    } else {
+        if (start < 0 || start > n_cols) return fail(REPET_ERR_BAD_ARG, "start in [0, n_cols]");
+        const int64_t first_active = (start > 0 ? start : n_cols) - 1;
+        for (int b = 0; b < n_batch; ++b) {
+            const int64_t o = origin ? origin[b] : 0;
+            if (o < -((int64_t)1 << 61) || o > ((int64_t)1 << 61)) return fail(REPET_ERR_BAD_ARG, "origin out of range");
+            for (int64_t r = 0; r < n_rows; ++r) {
+                const int64_t jl = row0 + r - o;                      // the row counted from the clip's own first frame
+                if (origin && jl < first_active) continue;             // inactive: no list, nothing read
+                if (jl < 0) return fail(REPET_ERR_BAD_ARG, "a row before the clip's first frame");
+                const int64_t cols = std::min<int64_t>(n_cols, jl + 1), top = row0 + r - shift, bottom = top - (cols - 1);
+                if (bottom < 0 || top >= m_rows || (refine && top >= n_frames)) return fail(REPET_ERR_BAD_ARG, "a band row outside the band");
+            }
+        }
+    }
+    DeviceGuard guard(c->device);
+    const int fill = prefill & 255;
+    const int KP = std::max(number, kMinIdxPitch);
+    const int64_t rows_alloc = n_rows + 1;
+    const size_t m_cells = (size_t)n_batch * m_rows * pitch + 4096;     // (slack behind the last row for 16-byte loads up to the pitch)
+    Scratch Md, Ud, Hd, Ld, Id, Nd, Od, Sd, Pd;
+    HIP_TRY(Md.b.ensure(m_cells * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(Md.b.p, fill, m_cells * sizeof(float), c->stream));
+    HIP_TRY(hipMemcpy2DAsync(Md.b.p, (size_t)pitch * sizeof(float), M, (size_t)n_cols * sizeof(float), (size_t)n_cols * sizeof(float),
+                             (size_t)n_batch * m_rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(Id.b.ensure((size_t)n_batch * rows_alloc * KP * sizeof(int32_t)));
+    HIP_TRY(Nd.b.ensure((size_t)n_batch * rows_alloc * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(Id.b.p, fill, (size_t)n_batch * rows_alloc * KP * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(Nd.b.p, fill, (size_t)n_batch * rows_alloc * sizeof(int32_t), c->stream));
+    if (refine) {
+        const size_t u_cells = (size_t)n_batch * n_frames * FS;
+        HIP_TRY(Ud.b.ensure(u_cells * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Ud.b.p, 0, u_cells * sizeof(float), c->stream));
+        HIP_TRY(hipMemcpy2DAsync(Ud.b.p, (size_t)FS * sizeof(float), unit, (size_t)F * sizeof(float), (size_t)F * sizeof(float),
+                                 (size_t)n_batch * n_frames, hipMemcpyHostToDevice, c->stream));
+    }
+    Tables* tb = nullptr;
+    if (refine == 2) {
+        const size_t a_bytes = (size_t)n_batch * n_samples * C * sizeof(float);
+        RP_TRY(get_tables(c, W, &tb));
+        HIP_TRY(Hd.b.ensure(a_bytes));
+        HIP_TRY(hipMemcpyAsync(Hd.b.p, hi, a_bytes, hipMemcpyHostToDevice, c->stream));
+        if (lo) {
+            HIP_TRY(Ld.b.ensure(a_bytes));
+            HIP_TRY(hipMemcpyAsync(Ld.b.p, lo, a_bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(c->u64.ensure((size_t)n_batch * n_frames * FS * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(c->u64.p, fill, (size_t)n_batch * n_frames * FS * sizeof(double), c->stream));
+    }
+    if (origin) {
+        HIP_TRY(Od.b.ensure((size_t)n_batch * sizeof(int64_t)));
+        HIP_TRY(hipMemcpyAsync(Od.b.p, origin, (size_t)n_batch * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    }
+    float* seg = nullptr;
+    const int seg_pitch = segment_pitch((int)pitch);
+    if (local_maxima_segments_apply(n_cols, d, pitch, mode, n_batch)) {                  // as exec_sim: records of every row of M
+        HIP_TRY(Sd.b.ensure((size_t)m_rows * 3 * seg_pitch * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(Sd.b.p, fill, (size_t)m_rows * 3 * seg_pitch * sizeof(float), c->stream));
+        seg = Sd.b.as<float>();
+        HIP_TRY(launch_segment_maxima(Md.b.as<float>(), m_rows, n_cols, pitch, seg, seg_pitch, c->stream));
+    }
+    PeakRefine rf{};
+    if (refine)
+        RP_TRY(make_refine(c, Ud.b.as<float>(), FS, min_value, &rf, refine == 2 ? n_rows : 0, n_batch, n_cols, d, refine == 2 ? n_frames : 0));
+    const PeakBatch pb{n_batch, m_rows * pitch, rows_alloc * KP, rows_alloc, n_frames * (int64_t)FS, origin ? Od.b.as<int64_t>() : nullptr, start};
+    const PeakBatch* batch = (n_batch > 1 || origin || start > 0) ? &pb : nullptr;
+    void* scratch = nullptr;
+    if (with_scratch) {
+        const size_t bytes = local_maxima_scratch_bytes(n_rows, n_cols, d);
+        if (bytes > 0) { HIP_TRY(Pd.b.ensure(bytes)); HIP_TRY(hipMemsetAsync(Pd.b.p, fill, bytes, c->stream)); scratch = Pd.b.p; }
+    }
+    PeakLaunch info;
+    hipError_t e = launch_local_maxima(Md.b.as<float>(), n_rows, row0, n_cols, pitch, mode, (float)min_value, d, number, Id.b.as<int32_t>(), KP,
+                                       Nd.b.as<int32_t>(), c->stream, shift, refine ? &rf : nullptr, batch, scratch, nullptr, seg, seg_pitch, &info);
+    if (e == hipErrorInvalidValue) { (void)hipStreamSynchronize(c->stream); return fail(REPET_ERR_LIMIT, "row too long for the peak-picking kernel"); }
+    HIP_TRY(e);
+    if (refine == 2) {
+        const Geo g = make_geo(W, W / 2, n_frames, C);
+        if (g.FS != FS || g.F != F) { (void)hipStreamSynchronize(c->stream); return fail(REPET_ERR_BAD_ARG, "F does not match W"); }
+        RP_TRY(run_exact_rows(c, tb, g, Md.b.as<float>(), row0, n_cols, pitch, mode, (float)min_value, d, number, Id.b.as<int32_t>(), KP,
+                              Nd.b.as<int32_t>(), shift, rf, batch, Hd.b.as<float>(), lo ? Ld.b.as<float>() : nullptr, n_samples,
+                              n_samples * C, frame_sample0, n_frames, n_batch, &info));
+    }
+    HIP_TRY(hipMemcpyAsync(idx_out, Id.b.p, (size_t)n_batch * rows_alloc * KP * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(count_out, Nd.b.p, (size_t)n_batch * rows_alloc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < kRefineStats; ++k) stats_out[k] = 0;
+    if (refine) {
+        unsigned int total[kRefineStats] = {};
+        RP_TRY(read_stats(c, total));
+        for (int k = 0; k < kRefineStats; ++k) stats_out[k] = total[k];
+    }
+    if (refine == 2 && rf.redo_list) {
+        const size_t n_gen = (size_t)n_batch * n_frames;
+        std::vector<unsigned int> gens(n_gen);
+        HIP_TRY(hipMemcpyAsync(u64_out, c->u64.p, n_gen * FS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(gens.data(), c->u64_gen.p, n_gen * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k < n_gen; ++k) stamped_out[k] = gens[k] == rf.gen ? 1 : 0;
+    } else if (refine == 2)
+        return fail(REPET_ERR_LIMIT, "the second level is switched off");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    delta_out[0] = rf.delta; delta_out[1] = rf.delta2;
+    if (family_out && family_cap > 0) { std::strncpy(family_out, info.family, (size_t)family_cap - 1); family_out[family_cap - 1] = 0; }
+    const int64_t v[8] = {info.qmax, info.rd, info.unit_kq, info.lite, info.exact_fft, KP, FS, 0};
+    std::memcpy(launch_out, v, sizeof(v));
+    return REPET_OK;
+}
+
 }  // extern "C"

@@ -295,7 +295,7 @@ __device__ __forceinline__ float4 max4(float4 a, float4 b) {
 __device__ __forceinline__ float nan_to_inf(float v) { return (v != v) ? INFINITY : v; }
 
 // the wavefront-per-row kernel (peaks_wave.hip); hipErrorNotSupported when the shape is outside its range
-hipError_t launch_local_maxima_wave(const PeakArgs& a, int64_t n_rows, int n_batch, hipStream_t s);
+hipError_t launch_local_maxima_wave(const PeakArgs& a, int64_t n_rows, int n_batch, hipStream_t s, PeakLaunch* info = nullptr);
 // does launch_local_maxima_wave take this shape (then the fast second level applies), and its record size
 bool local_maxima_wave_supported(int n_cols, int d, int* record_bytes);
 

@@ -493,16 +493,21 @@ static hipError_t launch_one(const PeakArgs& a, dim3 grid, size_t bytes, hipStre
 }
 
 template <int STAGE>
-static hipError_t launch_by_size(const PeakArgs& a, dim3 grid, size_t bytes, hipStream_t s) {
+static hipError_t launch_by_size(const PeakArgs& a, dim3 grid, size_t bytes, hipStream_t s, int* qmax_out) {
     const int per_thread = (int)ceil_div(a.groups, 256);
     if (bytes > 160 * 1024 - 4096 || per_thread > 32) return hipErrorInvalidValue;
-    if (per_thread <= 1) return launch_one<1, STAGE>(a, grid, bytes, s);
-    if (per_thread <= 2) return launch_one<2, STAGE>(a, grid, bytes, s);
-    if (per_thread <= 4) return launch_one<4, STAGE>(a, grid, bytes, s);
-    if (per_thread <= 8) return launch_one<8, STAGE>(a, grid, bytes, s);
+    auto go = [&](auto tag) -> hipError_t {
+        constexpr int QMAX = decltype(tag)::value;
+        if (qmax_out) *qmax_out = QMAX;
+        return launch_one<QMAX, STAGE>(a, grid, bytes, s);
+    };
+    if (per_thread <= 1) return go(std::integral_constant<int, 1>{});
+    if (per_thread <= 2) return go(std::integral_constant<int, 2>{});
+    if (per_thread <= 4) return go(std::integral_constant<int, 4>{});
+    if (per_thread <= 8) return go(std::integral_constant<int, 8>{});
     if constexpr (STAGE == 0) {
-        if (per_thread <= 16) return launch_one<16, 0>(a, grid, bytes, s);
-        return launch_one<32, 0>(a, grid, bytes, s);
+        if (per_thread <= 16) return go(std::integral_constant<int, 16>{});
+        return go(std::integral_constant<int, 32>{});
     }
     return hipErrorInvalidValue;      // segments are sized for at most 8 groups per thread
 }
@@ -529,7 +534,7 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
                                int32_t mode, float min_value, int32_t d, int32_t number, int32_t* idx,
                                int32_t idx_pitch, int32_t* count, hipStream_t s, int64_t shift, const PeakRefine* refine,
                                const PeakBatch* batch, void* scratch, const ExactSource* lite_src, const float* seg,
-                               int32_t seg_pitch) {
+                               int32_t seg_pitch, PeakLaunch* info) {
     if (n_rows <= 0 && !lite_src) return hipSuccess;
     if (d > n_cols) d = n_cols;                                       // a wider window changes nothing
     PeakArgs a{};
@@ -556,9 +561,12 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
         a.m_stride = batch->m_stride; a.idx_stride = batch->idx_stride; a.cnt_stride = batch->cnt_stride;
         a.unit_stride = batch->unit_stride;
     }
-    if (lite_src) return launch_local_maxima_lite(a, *lite_src, s);      // (the rows the first pass left records of)
+    if (lite_src) {                                                       // (the rows the first pass left records of)
+        if (info) info->lite = 1;
+        return launch_local_maxima_lite(a, *lite_src, s);
+    }
     {   // one wavefront per row where the shape allows it (peaks_wave.hip); this kernel is the general fallback
-        const hipError_t ew = launch_local_maxima_wave(a, n_rows, n_batch, s);
+        const hipError_t ew = launch_local_maxima_wave(a, n_rows, n_batch, s, info);
         if (ew != hipErrorNotSupported) return ew;
     }
     a.dl = (int)round_up(d, 4);
@@ -578,7 +586,8 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
         a1.groups = (int)(round_up(a.dl + seg_len + d, 4) / 4 + 3);
         a1.peak_cap = cap;
         const size_t bytes1 = (size_t)(4 * a1.groups + 2 * a1.peak_cap) * 4;
-        hipError_t e = launch_by_size<1>(a1, dim3((unsigned)n_rows, 1, (unsigned)n_seg), bytes1, s);
+        if (info) info->family = "block two-stage";
+        hipError_t e = launch_by_size<1>(a1, dim3((unsigned)n_rows, 1, (unsigned)n_seg), bytes1, s, info ? &info->qmax : nullptr);
         if (e != hipSuccess) return e;
         PeakArgs a2 = a;
         a2.peak_cap = (int)round_up(total_cap + n_seg, 4);
@@ -589,7 +598,8 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
     a.groups = (int)(round_up(a.dl + n_cols + d, 4) / 4 + 3);      // slack for the aligned window reads past the end
     a.peak_cap = total_cap;
     const size_t bytes = (size_t)(4 * a.groups + 2 * a.peak_cap) * 4;
-    return launch_by_size<0>(a, dim3((unsigned)n_rows, (unsigned)n_batch), bytes, s);
+    if (info) info->family = "block";
+    return launch_by_size<0>(a, dim3((unsigned)n_rows, (unsigned)n_batch), bytes, s, info ? &info->qmax : nullptr);
 }
 
 #ifdef REPET_PEAK_STAMPS

@@ -1032,7 +1032,7 @@ size_t local_maxima_exact_scratch_bytes(int32_t n_cols, int* grid_out) {
 hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_cols, int64_t pitch, int32_t mode, float min_value,
                                      int32_t d, int32_t number, int32_t* idx, int32_t idx_pitch, int32_t* count, hipStream_t s,
                                      int64_t shift, const PeakRefine* refine, const PeakBatch* batch, const ExactSource& src,
-                                     void* scratch) {
+                                     void* scratch, PeakLaunch* info) {
     if (!refine || !refine->unit_rows || !(refine->delta > 0.0f) || !refine->redo_list || !refine->stats) return hipSuccess;
     if (d > n_cols) d = n_cols;
     ExactArgs x{};
@@ -1079,11 +1079,12 @@ hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_col
         hipLaunchKernelGGL(local_maxima_exact_kernel<V>, dim3((unsigned)grid), dim3(kExactThreads), lds, s, x);
         return hipGetLastError();
     };
+    if (info) info->exact_fft = plan.variant == kFftLds4 ? kFftLds4 : kFftLdsAcc;
     if (plan.variant == kFftLds4) return go(std::integral_constant<int, kFftLds4>{});
     return go(std::integral_constant<int, kFftLdsAcc>{});
 }
 
-hipError_t launch_unit_rows_f64(const ExactSource& src, const PeakRefine* refine, hipStream_t s) {
+hipError_t launch_unit_rows_f64(const ExactSource& src, const PeakRefine* refine, hipStream_t s, PeakLaunch* info) {
     if (!refine || !refine->frame_list || !refine->stats) return hipSuccess;
     UnitRowsArgs x{};
     x.src = src; x.frame_list = refine->frame_list; x.stats = refine->stats; x.gen = refine->gen;
@@ -1100,6 +1101,7 @@ hipError_t launch_unit_rows_f64(const ExactSource& src, const PeakRefine* refine
         hipLaunchKernelGGL(unit_rows_f64_wg_kernel<KQ>, dim3(1024), dim3(256), lds, s, x);
         return hipGetLastError();
     };
+    if (info) info->unit_kq = Mh <= 1024 ? 1 : 4;
     return Mh <= 1024 ? go_wg(std::integral_constant<int, 1>{}) : go_wg(std::integral_constant<int, 4>{});
 }
 

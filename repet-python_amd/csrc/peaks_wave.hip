@@ -1278,7 +1278,7 @@ bool local_maxima_wave_supported(int n_cols, int d, int* record_bytes) {
     return true;
 }
 
-hipError_t launch_local_maxima_wave(const PeakArgs& a0, int64_t n_rows, int n_batch, hipStream_t s) {
+hipError_t launch_local_maxima_wave(const PeakArgs& a0, int64_t n_rows, int n_batch, hipStream_t s, PeakLaunch* info) {
     if (wave_kernel_off()) return hipErrorNotSupported;
     PeakArgs a = a0;
     int cap = 0;
@@ -1291,6 +1291,7 @@ hipError_t launch_local_maxima_wave(const PeakArgs& a0, int64_t n_rows, int n_ba
         a.groups = std::max<int>(kBufGroups, (int)ceil_div(5 * (int64_t)a.seg_pitch * 4, 16));    // three planes + the waiting list
         const int seg_bytes = (int)round_up((int64_t)wave_lds_bytes(cap, a.groups), 16);
         e = launch_wave_rd<0, true>(a, n_rows, n_batch, seg_bytes, seg_bytes, s);
+        if (info) { info->family = "wave+records"; info->rd = 0; }
     } else {
         a.seg = nullptr;
         const int per_wave = (int)round_up((int64_t)wave_lds_bytes(cap), 16);
@@ -1301,6 +1302,7 @@ hipError_t launch_local_maxima_wave(const PeakArgs& a0, int64_t n_rows, int n_ba
             case 2: e = launch_wave_rd<2>(a, n_rows, n_batch, bytes, per_wave, s); break;
             default: e = launch_wave_rd<3>(a, n_rows, n_batch, bytes, per_wave, s); break;
         }
+        if (info) { info->family = "wave"; info->rd = a.d & 3; }
     }
     return e;
 }

@@ -430,6 +430,8 @@ def _stage_entry(name):
             "repet_debug_band_periods_stage": [p, p, i32, i64, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32, i64, i32, p, p, p],
             "repet_debug_mask_stage": [p, i32, p, p, i32, i32, i64, i32, i32, i32, i32, i32, p, i32, i32, p, p, i64, i32, i64, i32, i64, i64,
                                        i32, p, i64, i32, i32, p, p, p, p, p, p, i32, p, i32, p],
+            "repet_debug_peaks_stage": [p, p, i32, i64, i32, i64, p, i64, i32, p, p, i64, i32, i32, i64, i32, i64, i64, C.c_double, i32, i32,
+                                        i64, p, i32, i32, i32, i32, p, p, p, p, p, p, p, i32, p],
         }[name]
         _stage_entries[name] = fn
     return _stage_entries[name]
@@ -660,6 +662,75 @@ def _mask_stage(kind, V, X=None, want=("mask",), cutoff=0, prefill=0, period=Non
     for key, a in (("mask", mask), ("X", xo), ("model", model), ("codes", codes)):
         if a is not None:
             out[key] = a
+    return out
+
+
+PEAK_REFINE_STATS = ("rows_refined", "near_tied", "decisions_changed", "flat_rows", "rows_to_level2", "level2_cursor", "elements_level2",
+                     "rows_changed_level2", "level2_max_diff_1e12", "unit_rows_f64", "frames_queued", "queue_cursor", "rows_recorded",
+                     "record_cursor", "rows_handed_on")
+
+
+def _peaks_stage(M, n_cols=None, pitch=None, mode=0, row0=0, n_rows=None, min_value=0.0, d=1, number=1, shift=0, origin=None, start=0,
+                 with_scratch=False, refine=0, unit=None, hi=None, lo=None, W=0, frame_sample0=0, prefill=0):
+    """The peak picking as ``exec_sim``, ``exec_simonline`` and the live handles run it (``repet_debug_peaks_stage``):
+    ``launch_segment_maxima`` where the launcher will use the records, ``make_refine``, ``launch_local_maxima`` and -- ``refine`` 2
+    -- ``run_exact_rows``. ``M`` (n_batch, m_rows, n_cols) or (m_rows, n_cols) fp32: matrix rows (mode 0) or the band (modes 1, 2),
+    copied to rows of ``pitch`` floats (default round_up(n_cols, 64)). ``unit`` (n_batch, n_frames, F) fp32 unit rows (``refine``
+    >= 1), ``hi`` / ``lo`` (n_batch, n_samples, C) fp32 audio with ``W`` and ``frame_sample0`` (``refine`` 2). ``origin`` (n_batch,)
+    int64 or None and ``start``: ``PeakBatch``. Returns a dict: "idx" (n_batch, n_rows + 1, KP) and "count" (n_batch, n_rows + 1)
+    whole, as the kernels left them over the byte ``prefill`` (the last row of every clip belongs to no launch), "KP", "stats" (the
+    32 counters) and "counters" (the named ones), "delta", "delta2", "u64" (n_batch, n_frames, FS) float64 and "stamped" (n_batch,
+    n_frames) bool (``refine`` 2), and "launch": "family" ("wave", "wave+records", "block", "block two-stage"), "qmax", "rd",
+    "unit_rows_variant" (0: not launched), "lite", "exact_fft" (0: the general kernel was not launched). Input that would index
+    out of range raises ValueError."""
+    import ctypes as C
+    m = _f32(M)
+    if m.ndim == 2:
+        m = m[None]
+    nb, m_rows, cols = m.shape
+    assert n_cols is None or n_cols == cols
+    pitch = -(-cols // 64) * 64 if pitch is None else int(pitch)
+    n_rows = m_rows - row0 if n_rows is None else int(n_rows)
+    u = h = l = org = None
+    n_frames = f = n_samples = ch = 0
+    if refine:
+        u = _f32(unit)
+        if u.ndim == 2:
+            u = u[None]
+        assert u.ndim == 3 and u.shape[0] == nb
+        n_frames, f = u.shape[1:]
+    if refine == 2:
+        h = _f32(hi)
+        assert h.ndim == 3 and h.shape[0] == nb
+        n_samples, ch = h.shape[1:]
+        if lo is not None:
+            l = _f32(lo)
+            assert l.shape == h.shape
+    if origin is not None:
+        org = np.ascontiguousarray(origin, dtype=np.int64)
+        assert org.shape == (nb,)
+    kp = max(int(number), 128)
+    fs = -(-f // 32) * 32
+    idx = np.empty((nb, n_rows + 1, kp), dtype=np.int32)
+    cnt = np.empty((nb, n_rows + 1), dtype=np.int32)
+    u64 = np.empty((nb, n_frames, fs), dtype=np.float64) if refine == 2 else None
+    stamped = np.empty((nb, n_frames), dtype=np.int32) if refine == 2 else None
+    stats, delta, words = (C.c_int64 * 32)(), (C.c_double * 2)(), (C.c_int64 * 8)()
+    family = C.create_string_buffer(32)
+    opt = lambda a: None if a is None else _native.ptr(a)
+    _native.check(_stage_entry("repet_debug_peaks_stage")(
+        _native.default_context(_device).handle, _native.ptr(m), nb, m_rows, cols, pitch, opt(u), n_frames, f, opt(h), opt(l), n_samples, ch,
+        int(W), int(frame_sample0), int(mode), int(row0), n_rows, float(min_value), int(d), int(number), int(shift), opt(org), int(start),
+        int(bool(with_scratch)), int(refine), int(prefill), _native.ptr(idx), _native.ptr(cnt), stats, delta, opt(u64), opt(stamped),
+        family, len(family), words))
+    w = [int(k) for k in words]
+    assert w[5] == kp and (not refine or w[6] == fs)
+    st = [int(k) for k in stats]
+    out = {"idx": idx, "count": cnt, "KP": kp, "stats": st, "counters": dict(zip(PEAK_REFINE_STATS, st)), "delta": float(delta[0]),
+           "delta2": float(delta[1]),
+           "launch": {"family": family.value.decode(), "qmax": w[0], "rd": w[1], "unit_rows_variant": w[2], "lite": bool(w[3]), "exact_fft": w[4]}}
+    if refine == 2:
+        out["u64"], out["stamped"] = u64, stamped.astype(bool)
     return out
 
 
