@@ -400,7 +400,11 @@ int repet_ctx_last_median_path(repet_ctx* ctx, int32_t* path);
 /* After a run on path 2: what the selection left per cell, out[channel][frame][bin] for the first n_bins bins (n_bins <=
  * n_freq - 1: the Nyquist bin is not ranked): bits 0-14 the rank code (number of strictly smaller magnitudes of the bin over
  * the clip, rank.hip, without its 0x0400 base) of the lower median of the frame's similar frames, bit 15 set where that is
- * below the frame's own code, bits 16-30 the code of the upper median (equal to the lower one for an odd list). */
+ * below the frame's own code, bits 16-30 the code of the upper median (equal to the lower one for an odd list).
+ * Bin 1 is the exception when the high-pass cutoff covers at least one bin (cutoff_bins >= 1, the default): its mask is 1
+ * whatever its median, so its column of the rank transform carries the Nyquist bin instead, and the words at bin 1 are
+ * those of bin n_freq - 1 -- codes among the Nyquist magnitudes, the flag against the frame's own Nyquist code.
+ * (REPET_NYQUIST_COLUMN=0, or a cutoff of 0 bins: bin 1's own.) */
 int repet_ctx_last_median_codes(repet_ctx* ctx, uint32_t* out, int64_t n_frames, int32_t n_bins);
 /* sim / simonline: counters of the near-tie refinement of the last run's peak picking (_localmaxima,
  * repet.py:1294-1345): out[0] rows with a decision inside the fp32 tolerance, out[1] near-tied elements

@@ -369,10 +369,17 @@ struct MaskArgs {
     // 0x7C00 at pad_row, pad_row+1) and the rank -> value table Vs[c][f][vs_pitch] of the first n_rank_cols bins of
     // every channel. R == nullptr: select on the floats themselves.
     const unsigned short* R; int64_t r_chan_stride; const float* Vs; int64_t vs_pitch; int32_t n_rank_cols;
+    // mask_from_codes_kernel only (0: off; RankArgs::swap_col): ranked column swap_col of every channel was built from bin
+    // swap_bin, so the word and the table at bin swap_col are bin swap_bin's, and the lane that owns bin swap_col finishes
+    // that cell too. swap_col lies in 1 .. cutoff (soft_mask is 1 there whatever the median), swap_bin in [n_rank_cols, F):
+    // the Nyquist bin F - 1 in `sim`. (The two fields sit in alignment holes: no other field, and no argument behind the
+    // struct, moves.)
+    int32_t swap_col;
     // the same codes (minus their base) bit-sliced, for the bit-sliced selection (mask_bits.hip): P[t][plane][64] words,
     // bit b of word l = bit `plane` of the code of cell 64 b + l, cells numbered channel-major over the ranked bins.
     // P == nullptr: the packed network on R.
     const unsigned* P; int32_t n_planes;
+    int32_t swap_bin;
     unsigned* median_codes;       // bit-sliced selection: one word per cell, V's geometry (upper code << 16 | lower code | flag)
     // mask_sim only (nullable; the streaming handle's slots): clip b's own stream began at frame slot_start[b], and frame row t
     // is frame slot_bias + t + (warm-up length) of the handle: rows with t + slot_bias < slot_start[b] are warm-up rows of that
@@ -425,6 +432,10 @@ struct RankArgs {
     float* Vs; int64_t vs_pitch;          // Vs[c * n_cols + f][vs_pitch], vs_pitch = round_up(T, 32)
     unsigned short* codes;                // scratch: the codes column-major, [c * n_cols + f][vs_pitch]
     unsigned* P; int32_t n_planes;        // the codes bit-sliced INSTEAD of R (exactly one of R and P is set): MaskArgs::P
+    // swap_col > 0 (0: none): column swap_col of every channel is built from bin swap_bin of V (any bin below FS) instead
+    // of its own -- a ranked bin whose median nobody reads (1 .. cutoff: soft_mask) lends its column, its codes and its
+    // selection to a bin outside the ranked ones (exec_sim: bin 1 to the Nyquist bin)
+    int32_t swap_col, swap_bin;
 };
 bool rank_columns_supported(int64_t T);
 // CPUs of the NUMA node device `dev` hangs off that this process may run on (hostio.hip; empty: unknown or nothing to choose)

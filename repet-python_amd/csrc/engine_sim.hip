@@ -119,7 +119,19 @@ static bool bits_median_enabled() {
     return on;
 }
 
-// Sort every column of V and fill m's rank fields (bins [0, F-1); the lone Nyquist bin stays on the float kernel).
+// The Nyquist bin F - 1 is the one bin outside the 64-bin blocks of the rank chain, and bin 1 is a ranked column whose median
+// nobody reads (soft_mask is 1 in bins 1 .. cutoff whatever the model says: the high-pass rule). On the bit-sliced path with
+// a cutoff of at least one bin, column 1 is therefore built from the Nyquist magnitudes (RankArgs::swap_col): the sort, the
+// code planes and the selection carry them as they carry any column, the lookups finish the Nyquist cell (MaskArgs::swap_col),
+// and mask_sim_nyquist_kernel -- 10.6 us in line for 2 of 2 050 cells per frame at cfg 2 -- is not launched.
+// REPET_NYQUIST_COLUMN=0 (A/B, agreement test): the float kernel as before.
+static bool nyquist_column_enabled() {
+    static const bool on = [] { const char* e = getenv("REPET_NYQUIST_COLUMN"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// Sort every column of V and fill m's rank fields (bins [0, F-1); the lone Nyquist bin stays on the float kernel unless bin
+// 1's column takes it: m->swap_col says so afterwards).
 int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream, bool with_mark, int max_count) {
     const int n_cols = g.F - 1;
     const int64_t vs_pitch = round_up(g.T, 32);
@@ -143,6 +155,7 @@ int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream
         a.P = c->code_planes.as<unsigned>();
         HIP_TRY(c->median_codes.ensure((size_t)g.C * g.chan_stride * sizeof(unsigned)));
         m->median_codes = c->median_codes.as<unsigned>();
+        if (m->cutoff >= 1 && nyquist_column_enabled()) { a.swap_col = m->swap_col = 1; a.swap_bin = m->swap_bin = g.F - 1; }
     }
     // (with_mark: the chain runs alone on the main stream and every kernel gets its own timing mark -- bench.py's per-kernel rows)
     struct HookCtx { repet_ctx* c; double cells; double plane_bytes; } hc{c, (double)n_cols * (double)g.T * g.C, bits ? (double)g.T * a.n_planes * 256.0 : 0.0};
@@ -253,7 +266,8 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
             mark(c, use_rank ? "local_maxima_level2" : "local_maxima", use_rank ? 0.0 : 4.0 * T * T + 4.0 * K * T, 0);
             if (use_rank) RP_TRY(run_rank_columns(c, g, &m, c->stream, true, max_peaks));
         }
-        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), 0, max_peaks, c->stream, 3, m.P != nullptr));
+        // (parts 1: no Nyquist-bin kernel where bin 1's column carries that bin)
+        HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), 0, max_peaks, c->stream, m.swap_col > 0 ? 1 : 3, m.P != nullptr));
         c->last_median_path = m.P ? 2 : m.R ? 1 : 0;
         c->last_FS = g.FS; c->last_chan_stride = g.chan_stride;
         if (m.P) {

@@ -635,8 +635,10 @@ int repet_mask_sim_ranked(repet_ctx* c, const float* v, int64_t T, int32_t F, co
 //   adaptive  periods (T), order
 //   sim       idx (B, rows, width), cnt (B, rows), rows >= T - first_frame list rows numbered from first_frame; idx_pitch >= max(128,
 //             width), any alignment; slot_start (nullable, B) + slot_bias; median_path 0 floats, 1 packed network on rank
-//             codes, 2 bit-sliced selection (1 and 2: B = 1, first_frame = 0; the column sort runs on all C channels, with the
-//             calls of run_rank_columns)
+//             codes, 2 bit-sliced selection, 3 the bit-sliced selection with the Nyquist bin in the ranked column of bin 1, as
+//             exec_sim runs it (RankArgs / MaskArgs::swap_col = 1, swap_bin = F - 1; cutoff >= 1 and parts = 1, else
+//             REPET_ERR_BAD_ARG: the lookups write that bin) (1 .. 3: B = 1, first_frame = 0; the column sort runs on all C
+//             channels, with the calls of run_rank_columns)
 // geo_out[8] = Tpad, rows per channel, FS, chan_stride, model rows, 0, 0, 0. launch_out[16] = net, flag, parts, grid x y z,
 // Nyquist net, preload, grid x y z, 1 if mask_from_codes_kernel ran behind the selection, 0...; kernel_out / nyquist_out: the
 // template names (MaskLaunch, common.h).
@@ -680,7 +682,9 @@ int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const flo
         if (frame_end == 0) frame_end = T;
         if (frame0 < 0 || frame0 > frame_end || frame_end > T) return fail(REPET_ERR_BAD_ARG, "sim: 0 <= frame0 <= frame_end <= T");
         if (parts < 1 || parts > 3) return fail(REPET_ERR_BAD_ARG, "parts: 1 main bins, 2 Nyquist bin, 3 both");
-        if (median_path < 0 || median_path > 2) return fail(REPET_ERR_BAD_ARG, "median_path: 0 floats, 1 packed rank codes, 2 bit-sliced");
+        if (median_path < 0 || median_path > 3) return fail(REPET_ERR_BAD_ARG, "median_path: 0 floats, 1 packed rank codes, 2 bit-sliced, 3 bit-sliced with the Nyquist column");
+        if (median_path == 3 && (cutoff < 1 || parts != 1))
+            return fail(REPET_ERR_BAD_ARG, "median_path 3: the Nyquist bin takes the column of bin 1, which needs cutoff >= 1, and parts = 1");
         for (int64_t k = 0; k < (int64_t)B * rows; ++k)
             if (cnt[k] < 0 || cnt[k] > max_count) return fail(REPET_ERR_BAD_ARG, "a list length outside [0, max_count]");
         for (int64_t k = 0; k < (int64_t)B * rows * width; ++k)
@@ -689,9 +693,9 @@ int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const flo
             if (B != 1 || first_frame != 0 || slot_start) return fail(REPET_ERR_BAD_ARG, "the rank paths take one clip from frame 0");
             if (F <= 128 || ((F - 1) & 127) || !rank_columns_supported(T) || max_count < 2 || max_count > 128)
                 return fail(REPET_ERR_LIMIT, "rank-domain median: 1024 < n_frames <= 30720, n_freq - 1 a multiple of 128, lists of 2..128 entries");
-            if (median_path == 2 && !mask_sim_bits_supported(T, C, F - 1, max_count))
+            if (median_path >= 2 && !mask_sim_bits_supported(T, C, F - 1, max_count))
                 return fail(REPET_ERR_LIMIT, "bit-sliced selection: at most 32 blocks of 64 bins over all channels, a power of two per channel");
-            if (median_path == 2 && !codes_out) return fail(REPET_ERR_BAD_ARG, "null output");
+            if (median_path >= 2 && !codes_out) return fail(REPET_ERR_BAD_ARG, "null output");
         }
     }
     DeviceGuard guard(c->device);
@@ -755,7 +759,7 @@ int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const flo
         if (median_path > 0) {                               // run_rank_columns' calls, the path forced instead of read from the environment
             const int n_cols = F - 1;
             const int64_t vs_pitch = round_up(T, 32);
-            const bool bits = median_path == 2;
+            const bool bits = median_path >= 2;
             HIP_TRY(Vsd.b.ensure((size_t)C * n_cols * vs_pitch * sizeof(float)));
             HIP_TRY(RCd.b.ensure((size_t)C * n_cols * vs_pitch * sizeof(unsigned short)));
             RankArgs a{};
@@ -769,6 +773,7 @@ int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const flo
                 HIP_TRY(MCd.b.ensure((size_t)C * chan_stride * sizeof(unsigned)));
                 HIP_TRY(hipMemsetAsync(MCd.b.p, fill, (size_t)C * chan_stride * sizeof(unsigned), c->stream));
                 m.median_codes = MCd.b.as<unsigned>();
+                if (median_path == 3) { a.swap_col = m.swap_col = 1; a.swap_bin = m.swap_bin = F - 1; }
             } else {
                 HIP_TRY(Rd.b.ensure((size_t)C * chan_stride * sizeof(unsigned short)));
                 HIP_TRY(hipMemsetAsync(Rd.b.p, 0, (size_t)C * chan_stride * sizeof(unsigned short), c->stream));
@@ -782,18 +787,18 @@ int repet_debug_mask_stage(repet_ctx* c, int32_t kind, const float* V, const flo
         // (as exec_sim: the lookups of the bit-sliced selection are the caller's launch)
         HIP_TRY(launch_mask_sim(m, Id.b.as<int32_t>(), idx_pitch, Nd.b.as<int32_t>(), first_frame, max_count, c->stream, parts, m.P != nullptr, &info));
         if (median_path > 0 && (parts & 1) && frame_end > frame0) {
-            const char* expect = median_path == 2 ? "mask_sim_bits_kernel" : "mask_sim_rank_kernel";
+            const char* expect = median_path >= 2 ? "mask_sim_bits_kernel" : "mask_sim_rank_kernel";
             if (std::strcmp(info.kernel, expect) != 0) {
                 (void)hipStreamSynchronize(c->stream);
                 return fail(REPET_ERR_LIMIT, "the launcher did not take the median path asked for");
             }
-            if (median_path == 2) { HIP_TRY(launch_mask_from_codes(m, Nd.b.as<int32_t>(), c->stream)); from_codes = true; }
+            if (median_path >= 2) { HIP_TRY(launch_mask_from_codes(m, Nd.b.as<int32_t>(), c->stream)); from_codes = true; }
         }
     }
     if (want & 1) HIP_TRY(hipMemcpyAsync(mask_out, Md.b.p, cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (want & 2) HIP_TRY(hipMemcpyAsync(X_out, Xd.b.p, cells * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     if (want & 4) HIP_TRY(hipMemcpyAsync(model_out, Wd.b.p, model_cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (kind == 2 && median_path == 2)
+    if (kind == 2 && median_path >= 2)
         HIP_TRY(hipMemcpyAsync(codes_out, MCd.b.p, (size_t)C * chan_stride * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     auto put = [](char* out, int32_t cap, const char* name) {

@@ -244,6 +244,7 @@ __global__ __launch_bounds__(256) void mask_sim_bits_kernel(MaskArgs a, const in
 // Codes -> magnitudes -> mask: the tail of mask_sim_rank_kernel on the words the selection left. Same scheduling: the unit of
 // work is (channel, block of 128 bins, 4 consecutive frames), and XCD x is given the combinations x, x + 8, ... one after
 // the other over all frames, so its L2 holds the 4 MB of sorted columns of one combination while the lookups go there.
+// With MaskArgs::swap_col set, one lane of the frame finishes two cells: its own and the one whose codes its column carried.
 __global__ __launch_bounds__(256) void mask_from_codes_kernel(MaskArgs a, const int* __restrict__ count, int n_quads) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nfb = a.n_rank_cols >> 7;
@@ -269,6 +270,16 @@ __global__ __launch_bounds__(256) void mask_from_codes_kernel(MaskArgs a, const 
     const uint2 cw = make_uint2(c_nt.x, c_nt.y);
     float4 x_own = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.X) { const f4 x_nt = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.X + o)); x_own = make_float4(x_nt.x, x_nt.y, x_nt.z, x_nt.w); }
+    // MaskArgs::swap_col: the workgroups of its block of 128 bins fetch bin swap_bin of their frame too (one address per wave:
+    // a broadcast), with the streams above and ahead of the table reads
+    const bool swap = a.swap_col > 0 && fb == (a.swap_col >> 7);         // workgroup-uniform
+    const int64_t o_sw = c * a.chan_stride + t * a.FS + a.swap_bin;
+    float v_sw = 0.f;
+    float2 x_sw = make_float2(0.f, 0.f);
+    if (swap) {
+        v_sw = __builtin_nontemporal_load(a.V + o_sw);
+        if (a.X) { const f2 x_nt = __builtin_nontemporal_load(reinterpret_cast<const f2*>(a.X + o_sw)); x_sw = make_float2(x_nt.x, x_nt.y); }
+    }
     // lower median >= own value  =>  min(V, median) = V and the mask is exactly 1: V itself stands in for the model.
     // (One branch per bin, two table reads in each: 0.12 ms at cfg 2; all four behind one branch 0.133; two or four frames per
     // wave with all their loads up front 0.14.)
@@ -283,6 +294,19 @@ __global__ __launch_bounds__(256) void mask_from_codes_kernel(MaskArgs a, const 
     if (a.mask) *reinterpret_cast<float2*>(a.mask + o) = make_float2(m0, m1);
     // (X itself is stored the ordinary way: the inverse STFT reads it next -- a non-temporal store gave the lookups 4 us and took 3 from it)
     if (a.X) *reinterpret_cast<float4*>(a.X + o) = make_float4(x_own.x * m0, x_own.y * m0, x_own.z * m1, x_own.w * m1);
+    // The lane of column swap_col finishes the cell of bin swap_bin: the word it read at bin swap_col and the table entries
+    // behind it are that bin's (bin swap_col itself got its 1.0 from soft_mask above: 1 <= swap_col <= cutoff). Where the
+    // flag is clear the stand-in for the median is bin swap_bin's own magnitude, not the lane's.
+    if (swap && f0 == (a.swap_col & ~1)) {
+        const bool second = a.swap_col & 1;
+        const bool need = second ? need1 : need0;
+        const float lo = second ? a1 : a0, hi = second ? b1 : b0;
+        float med = need ? ((n & 1) ? lo : 0.5f * (lo + hi)) : v_sw;
+        if (n <= 0) med = __uint_as_float(0x7fc00000u);
+        const float m = soft_mask(v_sw, med, a.swap_bin, a.cutoff);
+        if (a.mask) a.mask[o_sw] = m;
+        if (a.X) a.X[o_sw] = make_float2(x_sw.x * m, x_sw.y * m);
+    }
 }
 
 template <int H>
@@ -333,6 +357,9 @@ hipError_t launch_mask_sim_bits(const MaskArgs& m, const int32_t* idx, int32_t i
 hipError_t launch_mask_from_codes(const MaskArgs& m, const int32_t* count, hipStream_t s) {
     const int64_t t_end = m.frame_end > 0 ? m.frame_end : m.T;
     if (!m.median_codes || !m.Vs || t_end <= m.frame0 || (m.n_rank_cols & 127)) return hipErrorInvalidValue;
+    // a lent column: one whose own mask is 1 whatever its median, for a bin that has no column of its own
+    if (m.swap_col < 0 || (m.swap_col > 0 && (m.swap_col > m.cutoff || m.swap_col >= m.n_rank_cols || m.swap_bin < m.n_rank_cols || m.swap_bin >= m.F)))
+        return hipErrorInvalidValue;
     const int n_quads = (int)ceil_div(t_end - m.frame0, 4);
     const int combos = m.n_channels * (m.n_rank_cols >> 7);
     hipLaunchKernelGGL(mask_from_codes_kernel, dim3((unsigned)(8 * ceil_div(combos, 8) * n_quads)), dim3(256), 0, s, m, count, n_quads);

@@ -142,6 +142,23 @@ __global__ __launch_bounds__(256) void columns_from_rows_kernel(RankArgs a) {
         const int64_t t = t0 + ty + 16 * k;
         r[k] = *reinterpret_cast<const float4*>(in + (t < a.T ? t : a.T - 1) * a.FS + f0 + 4 * tx);
     }
+    // RankArgs::swap_col: the workgroups whose 64 columns hold it fetch bin swap_bin of their rows as well (one address per
+    // row: a broadcast), with the loads above, and the lane of column swap_col takes it for its own bin
+    const bool swap = a.swap_col > 0 && f0 == (a.swap_col & ~63);      // workgroup-uniform
+    float sw[kRounds];
+    if (swap) {
+#pragma unroll
+        for (int k = 0; k < kRounds; ++k) {
+            const int64_t t = t0 + ty + 16 * k;
+            sw[k] = in[(t < a.T ? t : a.T - 1) * a.FS + a.swap_bin];
+        }
+        const int comp = tx == ((a.swap_col & 63) >> 2) ? (a.swap_col & 3) : -1;
+#pragma unroll
+        for (int k = 0; k < kRounds; ++k) {
+            r[k].x = comp == 0 ? sw[k] : r[k].x; r[k].y = comp == 1 ? sw[k] : r[k].y;
+            r[k].z = comp == 2 ? sw[k] : r[k].z; r[k].w = comp == 3 ? sw[k] : r[k].w;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < kRounds; ++k) {
         const bool live = t0 + ty + 16 * k < a.T;
@@ -428,6 +445,7 @@ hipError_t launch_rank_columns(const RankArgs& a0, hipStream_t s, RankStepHook h
     if (!rank_columns_supported(a0.T) || a0.n_cols <= 0 || (a0.n_cols & 127) || (a0.vs_pitch & 31) || (a0.FS & 1)) return hipErrorInvalidValue;
     if (a0.P && (a0.R || a0.n_planes != code_planes_for(a0.T) || a0.n_planes > 15 || a0.n_channels * (a0.n_cols >> 6) > 32)) return hipErrorInvalidValue;
     if (!a0.P && !a0.R) return hipErrorInvalidValue;
+    if (a0.swap_col < 0 || a0.swap_col >= a0.n_cols || (a0.swap_col > 0 && (a0.swap_bin < 0 || a0.swap_bin >= a0.FS))) return hipErrorInvalidValue;
     RankArgs a = a0;
     if (a.T <= 2048) return launch_rank_n<11>(a, s, hook, user);
     if (a.T <= 4096) return launch_rank_n<12>(a, s, hook, user);

@@ -592,7 +592,7 @@ def _band_periods_stage(band, n_freq, start0, step, length, n_windows, lo, hi, n
 
 
 MASK_KINDS = {"period": 0, "adaptive": 1, "sim": 2}
-MEDIAN_PATHS = {"float": 0, "rank": 1, "bits": 2}
+MEDIAN_PATHS = {"float": 0, "rank": 1, "bits": 2, "bits+nyquist": 3}
 
 
 def _mask_stage(kind, V, X=None, want=("mask",), cutoff=0, prefill=0, period=None, periods=None, min_period=1, order=1, idx=None,
@@ -603,7 +603,9 @@ def _mask_stage(kind, V, X=None, want=("mask",), cutoff=0, prefill=0, period=Non
     ``want``: any of "mask", "X" -- or "model" alone (period). ``kind`` "period": ``period`` (host) or ``periods`` (B,) device
     periods + ``min_period``; "adaptive": ``periods`` (T,) + ``order``; "sim": ``idx`` (B, rows, width), ``cnt`` (B, rows),
     ``first_frame``, ``max_count`` (default width), ``frame0``, ``frame_end`` (0: T), ``parts`` 1 main bins / 2 Nyquist bin / 3 both,
-    ``slot_start`` (B,) + ``slot_bias``, ``idx_pitch`` (default max(width, 128)), ``median_path`` "float" / "rank" / "bits".
+    ``slot_start`` (B,) + ``slot_bias``, ``idx_pitch`` (default max(width, 128)), ``median_path`` "float" / "rank" / "bits" /
+    "bits+nyquist" (the bit-sliced path with the Nyquist bin in the ranked column of bin 1, as ``exec_sim`` runs it: ``cutoff`` >= 1,
+    ``parts`` 1).
     Returns a dict: "mask" (B, C, rows, FS), "X" (B, C, rows, FS) complex64, "model" (B, C, T // 3 + 2, FS), "codes" (C, rows, FS)
     uint32 (bit-sliced path) -- each whole, as the kernel left it over the byte ``prefill`` --, "Tpad", "rows", "FS" and "launch":
     the kernel of the main bins ("kernel", e.g. "mask_sim_kernel<10, true>", with "name", "net", "flag", "parts", "grid"), of the
@@ -637,7 +639,7 @@ def _mask_stage(kind, V, X=None, want=("mask",), cutoff=0, prefill=0, period=Non
     mask = np.empty((b, ch, rows_all, fs), dtype=np.float32) if bits & 1 else None
     xo = np.empty((b, ch, rows_all, fs), dtype=np.complex64) if bits & 2 else None
     model = np.empty((b, ch, model_rows, fs), dtype=np.float32) if bits & 4 else None
-    codes = np.empty((ch, rows_all, fs), dtype=np.uint32) if kind == "sim" and median_path == "bits" else None
+    codes = np.empty((ch, rows_all, fs), dtype=np.uint32) if kind == "sim" and median_path in ("bits", "bits+nyquist") else None
     geo, words = (C.c_int64 * 8)(), (C.c_int64 * 16)()
     name, nyq = C.create_string_buffer(64), C.create_string_buffer(64)
     opt = lambda a: None if a is None else _native.ptr(a)
