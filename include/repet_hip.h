@@ -630,6 +630,49 @@ int repet_online_background_gain(repet_online* h, int32_t slot, float* gain_out)
 int repet_ctx_set_background_gain(repet_ctx* ctx, float gain);
 int repet_set_run_background_gain(int device, float gain);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) LEVELS of what a live handle or a tensor call emitted:
+ * how loud the input, the background and the foreground of every slot were, whether anything repeating was found, whether a
+ * stream clips or carries NaN -- reduced on the device, so that a server need not pull three signals to the host per hop. For
+ * every stream s and channel c of an emission of n samples there are REPET_LEVEL_FIELDS float64 values, dense [S][C][8]: */
+#define REPET_LEVEL_FIELDS 8
+#define REPET_LEVEL_MIX_ENERGY 0   /* sum of mix^2 */
+#define REPET_LEVEL_BG_ENERGY 1    /* sum of bg^2 */
+#define REPET_LEVEL_FG_ENERGY 2    /* sum of fg^2 */
+#define REPET_LEVEL_MIX_PEAK 3     /* max |mix| */
+#define REPET_LEVEL_BG_PEAK 4      /* max |bg| */
+#define REPET_LEVEL_FG_PEAK 5      /* max |fg| */
+#define REPET_LEVEL_LIVE 6         /* number of live samples */
+#define REPET_LEVEL_NONFINITE 7    /* number of live samples whose mixture is NaN or +-inf */
+#define REPET_LEVEL_CHUNK 4096     /* samples of one stream a workgroup of the reduction takes */
+/* mix, bg and fg are the float64 values the emission kernel forms for the sample BEFORE it rounds to the destination dtype, by
+ * the same device function: mix = hi + lo (hi for an infinite hi), bg the fp32 background widened, fg = mix - bg or
+ * fma(-a, bg, mix) with the gain that was in force for THAT emission, its fade included. The record therefore depends neither on
+ * the output the handle has selected nor on a destination dtype. A sample that is not live -- every sample of an idle slot, the
+ * samples before a slot's own first frame -- adds zero to every field and is not counted in LIVE, whatever the chunk carried
+ * there. While a stream warms up BG_ENERGY is 0 and the FG fields equal the MIX fields. Energies are plain IEEE sums (NaN and
+ * inf propagate); peaks skip NaN (fmax), are inf for an infinite sample and 0 with nothing live.
+ * DETERMINISTIC: no floating-point atomics. The reduction has one fixed shape -- a thread's accumulators in element order, a wave
+ * by __shfl_xor, the waves of a workgroup through LDS in wave order, the REPET_LEVEL_CHUNK-sample chunks of a long emission
+ * through a partials buffer folded in a fixed order by a second small launch -- so two calls on one emission, the host form and
+ * the device form, return identical bits. One launch for an emission of one chunk, two otherwise, a memset for an empty one
+ * (a push that emitted nothing: all zeros). Computed ON DEMAND: a push that nobody asks about enqueues what it always did.
+ * repet_online_last_levels        : host form, out[S][C][8] through the pinned buffer (one copy, one wait). out == NULL (or a
+ *                   capacity too small) only asks: REPET_ERR_BAD_ARG with *n_written = the doubles needed.
+ * repet_online_last_levels_device : dense float64 [S][C][8] at `dst` on the handle's device, ordered behind `signal_stream` by
+ *                   events as last_emission_device is; no host wait.
+ * Both are valid where last_emission is: after a push or finish, until the next push, finish, restart, release or import
+ * (REPET_ERR_BAD_ARG, the same message); REPET_ERR_LIMIT where the emitted range is no longer in the pending buffer. S is the
+ * handle's stream count. finish_stream drops its slot's samples, so it measures its tail itself ([C][8], S = 1: one launch more
+ * in that call) -- but only on a handle that has been asked for levels before (any earlier call of either form, the asking one
+ * included); on any other handle a finish_stream enqueues what it always did and the levels calls refuse as stale after it.
+ * repet_ctx_result_levels_device  : the same record of the resident result of an offline context, [n_clips][C][8]: every
+ *                   sample is live, the gain is the context's (repet_ctx_set_background_gain). Ordered as
+ *                   repet_ctx_download_device_strided is (it waits for the remainder plane of a float64 upload where that does);
+ *                   REPET_ERR_BAD_ARG for a context with no clip. More than 1024 channels: REPET_ERR_LIMIT (all three). */
+int repet_online_last_levels(repet_online* h, double* out, int64_t capacity_doubles, int64_t* n_written);
+int repet_online_last_levels_device(repet_online* h, void* dst, void* signal_stream);
+int repet_ctx_result_levels_device(repet_ctx* ctx, void* dst, void* signal_stream);
+
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,
  * fp32 -> float64; non-temporal AVX-512 / AVX2 lines where the CPU has them) against scalar loops on n values with NaN,
  * infinities, denormals, PCM-exact runs and every misalignment. No GPU needed. Returns the number of values that differ

@@ -212,6 +212,24 @@ struct EmitArgs {
     const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
 };
 
+// The per-sample arithmetic of an emission, shared by the kernels that write it (emit_body) and that measure it (devio_levels):
+// a of sample j1 - 1 of a stream whose tables say at (target) and ac (current), inside a fade of `ramp` samples or behind it
+__device__ inline double emit_gain_at(double at, double ac, int64_t j1, int64_t ramp) {
+    // (only inside a fade: no call in steady state, ramp == 0, reaches the float64 divide)
+    return j1 < ramp ? fma(at - ac, (double)j1 / (double)ramp, ac) : at;
+}
+
+// the three float64 signals of one sample: h + l (or h, infinite), the fp32 background widened, x - bg or fma(-ak, bg, x); a
+// sample that is not live is zero in all three by a select
+__device__ inline void emit_sample(float h, float l, float b, bool live, bool gain, double ak, double& mix, double& bgv, double& fgv) {
+    // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi)
+    const double x = fabsf(h) <= 3.402823466e38f || h != h ? (double)h + (double)l : (double)h;
+    mix = live ? x : 0.0;
+    const double f = gain ? fma(-ak, (double)b, x) : x - (double)b;
+    fgv = live ? f : 0.0;
+    bgv = live ? (double)b : 0.0;
+}
+
 template <typename T, int EPT>
 __device__ inline void emit_body(const EmitArgs& a) {
     const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * EPT;
@@ -278,22 +296,13 @@ __device__ inline void emit_body(const EmitArgs& a) {
                     s_of = s;
                 }
                 const int64_t j1 = r / a.n_channels + 1;
-                ak[k] = at;
-                // (only inside a fade: no call in steady state, ramp == 0, reaches the float64 divide)
-                if (j1 < a.ramp) ak[k] = fma(at - ac, (double)j1 / (double)a.ramp, ac);
+                ak[k] = emit_gain_at(at, ac, j1, a.ramp);
             }
         }
     }
     double bgv[EPT], fgv[EPT], mix[EPT];
 #pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi)
-        const double x = fabsf(h[k]) <= 3.402823466e38f || h[k] != h[k] ? (double)h[k] + (double)l[k] : (double)h[k];
-        mix[k] = live[k] ? x : 0.0;
-        const double f = a.gain ? fma(-ak[k], (double)b[k], x) : x - (double)b[k];
-        fgv[k] = live[k] ? f : 0.0;
-        bgv[k] = live[k] ? (double)b[k] : 0.0;
-    }
+    for (int k = 0; k < EPT; ++k) emit_sample(h[k], l[k], b[k], live[k], a.gain != 0, a.gain ? ak[k] : 0.0, mix[k], bgv[k], fgv[k]);
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         if (d >= a.n_out) break;
@@ -321,6 +330,186 @@ __device__ inline void emit_body(const EmitArgs& a) {
 
 __global__ __launch_bounds__(kIoThreads) void devio_emit_f64(EmitArgs a) { emit_body<double, 2>(a); }
 __global__ __launch_bounds__(kIoThreads) void devio_emit_f32(EmitArgs a) { emit_body<float, 4>(a); }
+
+// Levels of an emission (or of an offline result): per stream s and channel c the REPET_LEVEL_FIELDS float64 values of
+// include/repet_hip.h -- sums of squares and largest magnitudes of the three signals emit_sample forms, the live samples and
+// those whose mixture is not finite -- reduced in ONE fixed shape, so that every call on the same emission returns the same bits
+// (no floating-point atomics anywhere):
+//   workgroup (x: chunk of kLevelChunk samples, y: stream) walks its chunk's interleaved elements in tiles of `tile` elements, a
+//   multiple of the channel count (and of 4 where that leaves a tile of at most 1024: then every full run is one dwordx4 load per
+//   plane, where its addresses are aligned). Thread t owns elements 4t .. 4t+3 of every tile: element i of a tile is channel
+//   i % C in every tile, so the thread keeps one accumulator set per element of its run, whatever C is (C = 3 never aligns to a
+//   vector: the runs simply start on different channels).
+//   Then, four fields at a time: the 1024 accumulators go to LDS in tile order; for each channel every thread folds the entries
+//   c + C * (t + 256 m) in order of m, the wave folds its 64 values by __shfl_xor (32, 16, .. 1), lane 0 leaves the wave's value
+//   in LDS and one thread per field folds the four waves in wave order.
+//   A single chunk writes the record itself; otherwise the workgroup writes partial[s][c][chunk][8] and devio_levels_fold (one
+//   wave per stream and channel) folds the chunks: lane (u, f) the u-th eighth of them in index order, then u = 0 .. 7 in order.
+// Sums are plain IEEE additions (NaN and inf propagate), peaks fmax (NaN skipped, inf kept, 0 with nothing live); unused
+// accumulators hold +0, which changes neither.
+constexpr int kLevelSlots = kIoThreads * 4;
+struct LevelArgs {
+    const float* bg; const float* hi; const float* lo;
+    int64_t in_stream, per;
+    const int64_t* slot_start; int64_t pos0, hop;
+    int32_t n_channels, n_chunks, tile;
+    const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
+    double* dst; double* partial;
+};
+
+template <int F> __device__ inline double level_fold(double x, double y) {
+    if constexpr (F >= REPET_LEVEL_MIX_PEAK && F <= REPET_LEVEL_FG_PEAK) return fmax(x, y);
+    else return x + y;
+}
+
+__device__ inline double level_fold_rt(int f, double x, double y) {
+    return f >= REPET_LEVEL_MIX_PEAK && f <= REPET_LEVEL_FG_PEAK ? fmax(x, y) : x + y;
+}
+
+// fields 4 * G .. 4 * G + 3 of every channel, from the threads' accumulators v[field][element of the run]
+template <int G>
+__device__ inline void level_regroup(const LevelArgs& a, const double (&v)[4][4], double (*slots)[kLevelSlots], double (*waves)[4][4]) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, C = a.n_channels;
+    __syncthreads();                                              // (the previous group's entries have been read)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) slots[q][4 * t + k] = v[q][k];
+    }
+    __syncthreads();
+    const int64_t s = blockIdx.y;
+    for (int c = 0; c < C; ++c) {
+        double r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = 0.0;
+        for (int i = c + C * t; i < a.tile; i += C * kIoThreads) {
+            r[0] = level_fold<4 * G + 0>(r[0], slots[0][i]); r[1] = level_fold<4 * G + 1>(r[1], slots[1][i]);
+            r[2] = level_fold<4 * G + 2>(r[2], slots[2][i]); r[3] = level_fold<4 * G + 3>(r[3], slots[3][i]);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            r[0] = level_fold<4 * G + 0>(r[0], __shfl_xor(r[0], d)); r[1] = level_fold<4 * G + 1>(r[1], __shfl_xor(r[1], d));
+            r[2] = level_fold<4 * G + 2>(r[2], __shfl_xor(r[2], d)); r[3] = level_fold<4 * G + 3>(r[3], __shfl_xor(r[3], d));
+        }
+        double (*w)[4] = waves[c & 1];                            // (two images: the fold of channel c reads one while c + 1 fills the other)
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) w[wave][q] = r[q];
+        }
+        __syncthreads();
+        if (t < 4) {
+            const int f = 4 * G + t;
+            double x = w[0][t];
+            for (int k = 1; k < kIoThreads / 64; ++k) x = level_fold_rt(f, x, w[k][t]);
+            const int64_t sc = s * C + c;
+            if (a.n_chunks == 1) a.dst[sc * REPET_LEVEL_FIELDS + f] = x;
+            else a.partial[(sc * a.n_chunks + blockIdx.x) * REPET_LEVEL_FIELDS + f] = x;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
+    __shared__ double slots[4][kLevelSlots];
+    __shared__ double waves[2][kIoThreads / 64][4];
+    const int t = threadIdx.x, C = a.n_channels;
+    const int64_t s = blockIdx.y;
+    const int64_t e0 = (int64_t)blockIdx.x * repet_eng::kLevelChunk * C;                    // the chunk's elements of this stream: [e0, e1)
+    const int64_t e1 = e0 + repet_eng::kLevelChunk * C < a.per ? e0 + repet_eng::kLevelChunk * C : a.per;
+    // the first live sample of this stream within the emission (emit_body's rule: slot_start and pos0)
+    int64_t live_from = 0;
+    bool any_live = true;
+    if (a.slot_start) {
+        const int64_t start = a.slot_start[s];
+        any_live = start < repet_eng::kSlotIdle;
+        live_from = any_live ? start * a.hop - a.pos0 : 0;
+    }
+    double at = (double)a.a, ac = at;
+    if (a.gain == kGainTables) {
+        at = (double)a.a_tgt[s];
+        ac = a.ramp > 0 ? (double)a.a_cur[s] : at;
+    }
+    const float* bg_s = a.bg + s * a.per;
+    const float* hi_s = a.hi + s * a.in_stream;
+    const float* lo_s = a.lo ? a.lo + s * a.in_stream : nullptr;
+    double energy[3][4], peak[3][4];
+    unsigned int n_live[4], n_bad[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { energy[q][k] = 0.0; peak[q][k] = 0.0; }
+        n_live[k] = 0u; n_bad[k] = 0u;
+    }
+    if (4 * t < a.tile) {
+        for (int64_t base = e0; base < e1; base += a.tile) {
+            const int64_t r0 = base + 4 * t;
+            if (r0 >= e1) break;
+            int m = a.tile - 4 * t < 4 ? a.tile - 4 * t : 4;
+            if (e1 - r0 < m) m = (int)(e1 - r0);
+            float b[4], h[4], l[4];
+            const float* pb = bg_s + r0;
+            const float* ph = hi_s + r0;
+            if (m == 4 && !((reinterpret_cast<uintptr_t>(pb) | reinterpret_cast<uintptr_t>(ph)) & 15)) {
+                const float4 vb = *reinterpret_cast<const float4*>(pb);
+                const float4 vh = *reinterpret_cast<const float4*>(ph);
+                b[0] = vb.x; b[1] = vb.y; b[2] = vb.z; b[3] = vb.w;
+                h[0] = vh.x; h[1] = vh.y; h[2] = vh.z; h[3] = vh.w;
+                if (lo_s) {                                          // (hi and lo are laid out alike: aligned together)
+                    const float4 vl = *reinterpret_cast<const float4*>(lo_s + r0);
+                    l[0] = vl.x; l[1] = vl.y; l[2] = vl.z; l[3] = vl.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) l[k] = 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    b[k] = 0.f; h[k] = 0.f; l[k] = 0.f;
+                    if (k < m) {
+                        b[k] = pb[k]; h[k] = ph[k];
+                        if (lo_s) l[k] = lo_s[r0 + k];
+                    }
+                }
+            }
+            int64_t j = r0 / C;                                   // sample of the run's first element, and its channel
+            int c = (int)(r0 - j * C);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool live = k < m && any_live && j >= live_from;
+                const double ak = a.gain == kGainTables ? emit_gain_at(at, ac, j + 1, a.ramp) : at;
+                double mix, bgv, fgv;
+                emit_sample(h[k], l[k], b[k], live, a.gain != 0, ak, mix, bgv, fgv);
+                energy[0][k] += mix * mix; energy[1][k] += bgv * bgv; energy[2][k] += fgv * fgv;
+                peak[0][k] = fmax(peak[0][k], fabs(mix)); peak[1][k] = fmax(peak[1][k], fabs(bgv)); peak[2][k] = fmax(peak[2][k], fabs(fgv));
+                n_live[k] += live ? 1u : 0u;
+                n_bad[k] += live && !(fabs(mix) <= 1.7976931348623157e308) ? 1u : 0u;
+                if (++c == C) { c = 0; ++j; }
+            }
+        }
+    }
+    double v[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[0][k] = energy[0][k]; v[1][k] = energy[1][k]; v[2][k] = energy[2][k]; v[3][k] = peak[0][k]; }
+    level_regroup<0>(a, v, slots, waves);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[0][k] = peak[1][k]; v[1][k] = peak[2][k]; v[2][k] = (double)n_live[k]; v[3][k] = (double)n_bad[k]; }
+    level_regroup<1>(a, v, slots, waves);
+}
+
+__global__ __launch_bounds__(64) void devio_levels_fold(const double* __restrict__ partial, int32_t n_chunks, double* __restrict__ dst) {
+    const int f = threadIdx.x & 7, u = threadIdx.x >> 3;
+    const int64_t sc = blockIdx.x;
+    const int per = (n_chunks + 7) / 8;
+    const int first = u * per, last = first + per < n_chunks ? first + per : n_chunks;
+    double x = 0.0;
+    for (int k = first; k < last; ++k) x = level_fold_rt(f, x, partial[(sc * n_chunks + k) * REPET_LEVEL_FIELDS + f]);
+    double r = x;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        const double y = __shfl(x, 8 * k + f);
+        r = level_fold_rt(f, r, y);
+    }
+    if (u == 0) dst[sc * REPET_LEVEL_FIELDS + f] = r;
+}
 
 // ---- the streaming handle's per-push data movement (engine_online.hip): S streams at a per-stream stride -------------------
 // Grids are streams (y) x four-element slots (x), both capped and walked grid-stride; every store of a whole slot is one
@@ -710,6 +899,47 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
     return hipGetLastError();
 }
 
+// elements of a tile of the level reduction: a multiple of the channel count, and of 4 where that fits (0: too many channels)
+static int32_t level_tile(int32_t ch) {
+    const int64_t both = std::lcm<int64_t>(4, ch);
+    if (both <= kLevelSlots) return (int32_t)(kLevelSlots / both * both);
+    return ch <= kLevelSlots ? kLevelSlots / ch * ch : 0;
+}
+
+int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch) {
+    const int64_t chunks = ceil_div(n, kLevelChunk);
+    return chunks > 1 ? (int64_t)n_streams * ch * chunks * REPET_LEVEL_FIELDS : 0;
+}
+
+hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
+                                int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
+                                hipStream_t s, const EmitGain* gain) {
+    if (n_streams <= 0 || ch <= 0) return hipSuccess;
+    if (!dst) return hipErrorInvalidValue;
+    const int64_t count = (int64_t)n_streams * n * ch;
+    if (count <= 0) return hipMemsetAsync(dst, 0, (size_t)n_streams * ch * REPET_LEVEL_FIELDS * sizeof(double), s);
+    const int64_t chunks = ceil_div(n, kLevelChunk);
+    if (!bg || !hi || (chunks > 1 && !partials) || chunks > 0x7fffffff || n_streams > 65535) return hipErrorInvalidValue;
+    LevelArgs a{};
+    a.tile = level_tile(ch);
+    if (a.tile <= 0) return hipErrorNotSupported;
+    if (gain) {
+        if (gain->scalar) { a.gain = kGainScalar; a.a = gain->a; }
+        else {
+            if (!gain->a_tgt || gain->ramp < 0 || (gain->ramp > 0 && !gain->a_cur)) return hipErrorInvalidValue;
+            a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
+        }
+    }
+    a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
+    a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_chunks = (int32_t)chunks;
+    a.dst = dst; a.partial = partials;
+    devio_levels<<<dim3((unsigned)chunks, (unsigned)n_streams), kIoThreads, 0, s>>>(a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || chunks == 1) return e;
+    devio_levels_fold<<<dim3((unsigned)(n_streams * ch)), 64, 0, s>>>(partials, (int32_t)chunks, dst);
+    return hipGetLastError();
+}
+
 // two destinations of one emission must not share memory: their address ranges (first to last element) must not intersect
 int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int64_t* st1, int elem_bytes, int32_t n_clips, int64_t n,
                    int32_t ch) {
@@ -883,6 +1113,33 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
         HIP_TRY(hipGetLastError());
     }
     // the caller's stream continues behind the egress
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
+    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    DeviceGuard guard(c->device);
+    RP_TRY(ensure_io_events(c));
+    // the destination belongs to the caller's stream, as in repet_ctx_download_device_strided
+    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(signal_stream)));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    const int64_t count = c->n_samples * c->n_channels * c->n_clips;
+    if (count > 0 && c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
+    const int64_t partials = stream_levels_partials(c->n_clips, c->n_samples, c->n_channels);
+    if (partials > 0) HIP_TRY(c->levels_ws.ensure((size_t)partials * sizeof(double)));
+    EmitGain gain;
+    gain.scalar = true; gain.a = c->result_a;
+    // every sample of a resident clip is live: no table, one hop
+    const hipError_t e = launch_stream_levels(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
+                                              c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels,
+                                              static_cast<double*>(dst), partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream,
+                                              c->result_gain ? &gain : nullptr);
+    if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
+    HIP_TRY(e);
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
     return REPET_OK;

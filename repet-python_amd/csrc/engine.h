@@ -116,6 +116,7 @@ struct repet_ctx {
     // caller's stream, the caller's stream on io_done recorded behind the egress; the refusal mode's non-finite flag word
     hipEvent_t io_wait = nullptr, io_done = nullptr;
     DevBuf nonfinite_word;
+    DevBuf levels_ws;             // level records on their way to the host and the chunk partials of the level reduction (devio.hip)
     int result_which = REPET_OUT_BACKGROUND;   // what repet_ctx_download_device_strided writes (repet_ctx_select_result)
     // repet_ctx_set_background_gain: the foreground it writes is x - result_a * bg, result_a = (float)(1 - gain); off: x - bg as ever
     float result_a = 1.f; bool result_gain = false;
@@ -309,6 +310,16 @@ struct EmitGain { const float* a_cur = nullptr; const float* a_tgt = nullptr; in
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
                               int n_dsts, hipStream_t s, const EmitGain* gain = nullptr);
+//   levels   the REPET_LEVEL_FIELDS float64 values per stream and channel of the emission the same arguments describe to
+//            launch_stream_emit (include/repet_hip.h: energies, peaks, live and non-finite samples), dense [n_streams][ch][8]
+//            into dst: one launch over (chunk of kLevelChunk samples, stream), and for more than one chunk a second small one
+//            that folds partials [n_streams][ch][chunks][8] (stream_levels_partials doubles; 0: not needed) in a fixed order.
+//            No element at all: dst is zeroed by a memset. hipErrorNotSupported: more channels than a tile holds (1024)
+constexpr int64_t kLevelChunk = REPET_LEVEL_CHUNK;
+int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch);
+hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
+                                int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
+                                hipStream_t s, const EmitGain* gain = nullptr);
 //   gains    the background gains of the streaming handle, fp32 [S] tables of a = (float)(1 - gain). fill: n entries = a.
 //            set: tgt[slots[k]] = a[k], one launch per kSlotResetIds slots named. commit: cur_new[s] = tgt[s] for the slots an
 //            emission covers (slot < 0: all), cur_old[s] for the others; one launch

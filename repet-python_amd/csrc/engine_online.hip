@@ -68,6 +68,13 @@ struct repet_online {
     // launch), fades from the one to the other over min(H, n_emit) samples and puts the other in force. Both stay as they are
     // until the next fade, so last_emission replays a fade from the tables that made it, whatever was set since. Until the first
     // set (gains_on) no kernel is given a table.
+    // Levels (repet_online_last_levels*): computed on demand from what `em` describes, so a handle that is never asked runs
+    // nothing for them. `levels` holds the record on its way to the host ([S][C][8] float64) and behind it the record of a
+    // finish_stream tail ([C][8]): that call drops its slot's samples, so it measures the tail itself -- on a handle that has
+    // been asked for levels before (levels_on) -- and tail_valid says the kept record is the last emission's.
+    DevBuf levels;
+    bool levels_on = false, tail_valid = false;
+    double* tail_levels() const { return levels.as<double>() + (int64_t)S * C * REPET_LEVEL_FIELDS; }
     std::vector<float> gain;
     std::vector<unsigned char> gain_dirty;
     int64_t n_dirty = 0;
@@ -176,6 +183,7 @@ int online_ensure_pending(repet_online* o, int64_t n) {
 int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1) {
     repet_ctx* c = o->ctx;
     o->em = repet_online::Emission{true, o->pcur, slot < 0 ? o->S : 1, slot, o->pend_hist, std::max<int64_t>(n_emit, 0), o->emitted};
+    o->tail_valid = false;
     o->em.g0 = o->em.g1 = o->gcur;
     if (n_new <= 0 && n_emit <= 0) return REPET_OK;
     Tables* tb = nullptr;
@@ -332,7 +340,7 @@ int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new
 // the chunk's samples (already where `src` says, device memory) appended to every stream's pending buffer
 int online_append(repet_online* o, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
     if (n <= 0) return REPET_OK;
-    o->em.valid = false;
+    o->em.valid = false; o->tail_valid = false;
     RP_TRY(online_ensure_pending(o, n));
     hipError_t e = launch_stream_append(src, dtype, o->S, n, o->C, strides, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
                                         o->pend_stride(), (o->pend_hist + o->pend_count) * o->C, o->ctx->stream);
@@ -360,6 +368,45 @@ int online_emit(repet_online* o, const EmitDst* dsts, int n_dsts, int dtype) {
     HIP_TRY(launch_stream_emit(o->outf.as<float>(), o->pend[em.buf].as<float>() + at, o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
                                o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dtype, dsts,
                                n_dsts, c->stream, o->gains_on ? &gain : nullptr));
+    return REPET_OK;
+}
+
+// The level record of the last emission (o->em) into dst, dense float64 [em.S][C][REPET_LEVEL_FIELDS] on the device: the
+// arguments online_emit gives the emission kernel, so the gain and fade are the emission's own. Enqueues only (one launch, two
+// for an emission of several chunks); an empty emission is a memset.
+static int online_levels(repet_online* o, double* dst) {
+    repet_ctx* c = o->ctx;
+    const repet_online::Emission& em = o->em;
+    if (!em.valid) return fail(REPET_ERR_BAD_ARG, "online: no emission to measure");
+    const bool empty = (int64_t)em.S * em.n * o->C <= 0;
+    if (!empty && em.off + em.n > o->pend_cap) return fail(REPET_ERR_LIMIT, "online: the emitted range is not in the pending buffer");
+    const int64_t sb = em.slot < 0 ? 0 : em.slot, at = sb * o->pend_stride() + em.off * o->C;
+    const int64_t partials = stream_levels_partials(em.S, em.n, o->C);
+    if (partials > 0) HIP_TRY(c->levels_ws.ensure((size_t)partials * sizeof(double)));
+    EmitGain gain;
+    if (o->gains_on) { gain.a_cur = o->gain_current(em.g0) + sb; gain.a_tgt = o->gain_current(em.g1) + sb; gain.ramp = em.ramp; }
+    const hipError_t e = launch_stream_levels(o->outf.as<float>(), empty ? nullptr : o->pend[em.buf].as<float>() + at,
+                                              empty ? nullptr : o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
+                                              o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dst,
+                                              partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream, o->gains_on ? &gain : nullptr);
+    if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
+    HIP_TRY(e);
+    return REPET_OK;
+}
+
+static int online_ensure_levels(repet_online* o) {
+    HIP_TRY(o->levels.ensure((size_t)(o->S + 1) * o->C * REPET_LEVEL_FIELDS * sizeof(double)));
+    return REPET_OK;
+}
+
+// finish_stream is about to drop its slot's samples: on a handle that has been asked for levels, the tail is measured now.
+// (A tail the pending buffer no longer holds is not measured: last_levels then refuses as last_emission does.)
+static int online_keep_tail_levels(repet_online* o, bool* kept) {
+    *kept = false;
+    if (!o->levels_on || !o->em.valid || o->em.off + o->em.n > o->pend_cap) return REPET_OK;
+    RP_TRY(online_ensure_levels(o));
+    RP_TRY(online_levels(o, o->tail_levels()));
+    *kept = true;
     return REPET_OK;
 }
 
@@ -461,7 +508,7 @@ int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
 // spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
 int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t first_frame) {
     repet_ctx* c = o->ctx;
-    o->em.valid = false;
+    o->em.valid = false; o->tail_valid = false;
     if (n <= 0) return REPET_OK;
     const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), held = (o->pend_hist + o->pend_count) * o->C;
     ZeroPart parts[kRowCopyParts] = {};
@@ -656,7 +703,7 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     repet_ctx* c = o->ctx;
     const StateLayout l = state_layout(o);
     const int64_t delta = std::max<int64_t>(0, l.m + h.hist_rows - o->total_in / o->H);
-    o->em.valid = false;
+    o->em.valid = false; o->tail_valid = false;
     RP_TRY(online_ensure_windows(o, std::max<int64_t>(o->max_push / o->H + 1, o->W / o->H + 1)));
     RP_TRY(online_ensure_pending(o, delta * o->H));
     if (delta > 0) RP_TRY(online_shift_epoch(o, delta));
@@ -757,6 +804,50 @@ int repet_online_last_emission_device(repet_online* o, int which, void* dst, int
     return REPET_OK;
 }
 
+static const char* const kStaleLevels = "online: the last emission is stale (a push, finish, restart or release came after it)";
+
+int repet_online_last_levels(repet_online* o, double* out, int64_t capacity_doubles, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    o->levels_on = true;
+    if (!o->em.valid && !o->tail_valid) return fail(REPET_ERR_BAD_ARG, kStaleLevels);
+    const int64_t count = (int64_t)(o->tail_valid ? 1 : o->em.S) * o->C * REPET_LEVEL_FIELDS;
+    *n_written = count;
+    if (!out || capacity_doubles < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    *n_written = 0;
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_ensure_levels(o));
+    const double* record = o->tail_levels();
+    if (!o->tail_valid) {
+        RP_TRY(online_levels(o, o->levels.as<double>()));
+        record = o->levels.as<double>();
+    }
+    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(o->host_out, record, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    *n_written = count;
+    return REPET_OK;
+}
+
+int repet_online_last_levels_device(repet_online* o, void* dst, void* signal_stream) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    o->levels_on = true;
+    if (!o->em.valid && !o->tail_valid) return fail(REPET_ERR_BAD_ARG, kStaleLevels);
+    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    if (o->tail_valid)
+        HIP_TRY(hipMemcpyAsync(dst, o->tail_levels(), (size_t)o->C * REPET_LEVEL_FIELDS * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    else
+        RP_TRY(online_levels(o, static_cast<double*>(dst)));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
 int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int32_t n_slots, const float* gains) {
     if (!o || !gains) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
@@ -844,7 +935,10 @@ int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64
     o->slots_on = true;
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_host_result(o, n_emit, out, 1));
+    bool kept = false;
+    RP_TRY(online_keep_tail_levels(o, &kept));
     RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
+    o->tail_valid = kept;
     *n_written = n_emit;
     return REPET_OK;
 }
@@ -864,7 +958,10 @@ int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, 
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
+    bool kept = false;
+    RP_TRY(online_keep_tail_levels(o, &kept));
     RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
+    o->tail_valid = kept;
     *n_written = n_emit;
     return REPET_OK;
 }
@@ -989,7 +1086,7 @@ int repet_online_close(repet_online* o) {
         DeviceGuard guard(o->ctx->device);
         (void)hipStreamSynchronize(o->ctx->stream);
         for (int k = 0; k < 2; ++k) { o->X[k].release(); o->V[k].release(); o->Vn[k].release(); o->pend[k].release(); o->pend_lo[k].release(); }
-        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release();
+        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release(); o->levels.release();
         free_pinned(o->host_in, o->host_in_cap);
         free_pinned(o->host_out, o->host_out_cap);
     }

@@ -23,6 +23,7 @@ from . import _native
 from ._native import Context  # noqa: F401  (device-resident API used by bench.py)
 from ._native import OnlineSeparator as _OnlineSeparator
 from ._native import StreamState  # noqa: F401  (what export_stream returns and import_stream takes)
+from ._native import LEVELS  # noqa: F401  (the eight fields of a level record, in index order)
 
 # ---- public parameters (repet.py:42-63) ----------------------------------------------------------------
 cutoff_frequency = 100
@@ -118,11 +119,13 @@ def release_workspaces():
     _native.release_tensor_contexts()
 
 
-def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None):
+def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
+                     levels=False):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
-    has checked, or None."""
+    has checked, or None. ``levels``: also the level record of the result (one reduction launch more, two for a long clip), under
+    the same gain."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
@@ -144,16 +147,22 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     stream = torch.cuda.current_stream(x.device)
     ctx.upload_layout(*layout, stream=stream)
     ctx.execute_async(algo, params)
+    record = None
     if background_gain is None:
         results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+        if levels:
+            record = ctx.result_levels(stream=stream)
     else:
         # on this thread's cached context for this call alone: later calls are the plain foreground again, whatever happens here
         try:
             ctx.set_background_gain(background_gain)
             results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+            if levels:
+                record = ctx.result_levels(stream=stream)
         finally:
             ctx.set_background_gain(0.0)
-    return results if which == "both" else results[0]
+    results = results if which == "both" else results[0]
+    return (results, record) if levels else results
 
 
 def _separate(algo, audio_signal, sampling_frequency):
@@ -196,7 +205,7 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None):
+def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
     clips one after another). Returns a float64 tensor on the tensor's device -- or fills ``out``, a float32 / float64 tensor
@@ -212,7 +221,13 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     ``background_gain`` (a number in [0, 1], with ``which="foreground"`` or ``"both"`` only): keep that share of the background,
     ``foreground = x - float32(1 - background_gain) * background``, rounded once in float64 by the same egress (-12 dB of
     background: ``10 ** (-12 / 20)``; 0 is the plain foreground, 1 the input). For this call alone. ValueError for a value
-    outside [0, 1] (NaN included) or with another ``which``."""
+    outside [0, 1] (NaN included) or with another ``which``.
+
+    ``levels=True`` returns ``(result, levels)``: the level record of the call (``repet.LEVELS``: per channel the sums of squares
+    and the largest magnitudes of mixture, background and foreground, the samples and those whose mixture is not finite), a
+    float64 tensor ``(C, 8)`` -- ``(B, C, 8)`` for a batch -- on the tensor's device, reduced there from the float64 values the
+    egress forms (whatever ``which`` and the dtype of ``out`` are, under this call's ``background_gain``), with no host wait.
+    Deterministic: the same call returns the same bits. See :func:`online_streams` for the fields."""
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
     _native.which_codes(which)
@@ -223,7 +238,7 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
-                            background_gain=background_gain)
+                            background_gain=background_gain, levels=bool(levels))
 
 
 def online(sampling_frequency, number_channels, start_length=None):
@@ -297,6 +312,21 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     on. The gain is the slot's, not the stream's -- ``restart``, ``release``, ``finish_stream`` and ``import_stream`` leave it,
     and an exported state does not carry it --; ``background_gain(slot)`` reads it back. No host wait; a push in steady state
     costs the launches it always cost. ValueError for a value outside [0, 1] (NaN included) or a slot out of range.
+
+    ``last_levels(out=None)`` tells what the handle just did to every slot without pulling a signal to the host: for the
+    samples the last ``push`` / ``finish`` emitted, per stream and channel the eight float64 values ``repet.LEVELS`` names --
+    the sums of squares and the largest magnitudes of mixture, background and foreground (the float64 values of the emission
+    itself, its gain and fade included, whatever ``which`` was), the live samples and the live samples whose mixture is NaN or
+    infinite -- as ``(number_streams, number_channels, 8)``: a NumPy array, or a float64 tensor on the device (no host wait)
+    when ``out`` is given or the last push was a device chunk. Samples that are not live (idle slots, the hop before a
+    ``restart``) add nothing and are not counted; while a stream warms up its background energy is 0 and its foreground
+    fields equal its mixture fields; energies are plain sums (NaN and inf propagate), peaks skip NaN. A background energy of 0
+    says nothing repeating was found (bypass, or drive ``set_background_gain`` as a ducker); a peak above 1 clips in PCM.
+    Reduced by one launch on demand (two for an emission longer than 4096 samples, none for an empty one: all zeros), in a
+    fixed order: repeated calls return identical bits, and a push that nobody asks about costs what it always cost. After
+    ``finish_stream`` it returns that tail's ``(number_channels, 8)`` -- the call measures its tail itself, since it drops the
+    slot's samples, on a handle that ``last_levels`` has been called on before; ValueError otherwise, and once a push,
+    finish, restart or release has followed.
 
     A stream can move between handles: ``export_stream(slot, device=False)`` returns a snapshot of the slot's state as a
     :class:`StreamState` -- ``header``, a small ``bytes`` value the host knows at once, and ``payload``, a ``numpy.uint8``

@@ -27,6 +27,32 @@ OUT_BACKGROUND, OUT_FOREGROUND, OUT_MIXTURE = 0, 1, 2
 WHICH_CODES = {"background": OUT_BACKGROUND, "foreground": OUT_FOREGROUND, "mixture": OUT_MIXTURE}
 
 
+# the fields of a level record (REPET_LEVEL_* of include/repet_hip.h, in index order): per stream and channel the sums of
+# squares and the largest magnitudes of the three signals of an emission, its live samples and those whose mixture is not finite
+LEVELS = ("mixture_energy", "background_energy", "foreground_energy", "mixture_peak", "background_peak", "foreground_peak",
+          "live_samples", "nonfinite_samples")
+LEVEL_FIELDS = len(LEVELS)
+LEVEL_CHUNK = 4096             # REPET_LEVEL_CHUNK: samples of one stream per workgroup of the reduction
+
+
+def levels_out(out, shape, device):
+    """``out=`` of a levels call: None (a fresh float64 tensor of ``shape`` on cuda:``device``), or a dense float64 tensor of
+    that shape there. ValueError otherwise, before anything runs."""
+    import torch
+    dev = torch.device("cuda", device)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+    if not is_device_tensor(out) or out.device != dev:
+        raise ValueError(f"out must be a tensor on {dev}")
+    if out.dtype != torch.float64:
+        raise ValueError(f"levels are float64, out is {out.dtype}")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"out has shape {tuple(out.shape)}, the levels {tuple(shape)}")
+    if not out.is_contiguous():
+        raise ValueError("out must be dense (contiguous)")
+    return out
+
+
 def which_codes(which):
     """The REPET_OUT_* code(s) of ``which``: one for "background" / "foreground" / "mixture", the pair for "both".
     ValueError for anything else -- raised before any device is touched."""
@@ -205,6 +231,9 @@ _SIGNATURES = {
     "repet_online_background_gain": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float)]),
     "repet_ctx_set_background_gain": (C.c_int, [_P, C.c_float]),
     "repet_set_run_background_gain": (C.c_int, [C.c_int, C.c_float]),
+    "repet_online_last_levels": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_last_levels_device": (C.c_int, [_P, _P, _P]),
+    "repet_ctx_result_levels_device": (C.c_int, [_P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -512,6 +541,21 @@ class Context:
                                                           _strides(strides), _stream_handle(stream)))
         finally:
             lib().repet_ctx_select_result(self._h, OUT_BACKGROUND)
+        return out
+
+    def result_levels(self, out=None, stream=None):
+        """The levels of the resident result (``repet.LEVELS``): a float64 tensor ``(C, 8)``, or ``(B, C, 8)`` for a batch, on
+        this context's device -- ``out`` (dense float64 of that shape) or a fresh one --, reduced on the engine's stream and
+        ordered on ``stream`` (default: the current one) like ``download_tensor``. Every sample is live; the foreground is
+        the one ``set_background_gain`` describes. No host wait."""
+        import torch
+        if self.shape is None:
+            raise ValueError("no clip uploaded")
+        shape = tuple(self.shape[:-2]) + (self.shape[-1], LEVEL_FIELDS)
+        out = levels_out(out, shape, self._device)
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        check(lib().repet_ctx_result_levels_device(self._h, C.c_void_p(out.data_ptr()), _stream_handle(stream)))
         return out
 
     def set_background_gain(self, gain):
@@ -923,6 +967,14 @@ class OnlineSeparator:
             outs = [o[:written.value].copy() for o in outs]
             return outs[0] if len(outs) == 1 else tuple(outs)
 
+    def last_levels(self):
+        """The levels (``repet.LEVELS``) of what the last ``push`` / ``finish`` emitted: a float64 array ``(C, 8)``, reduced on
+        the device; see ``repet.online_streams``. ValueError once another call has followed."""
+        result = np.empty((self._channels, LEVEL_FIELDS), dtype=np.float64)
+        n = C.c_int64()
+        check(lib().repet_online_last_levels(self._h, ptr(result), result.size, C.byref(n)))
+        return result
+
     def set_background_gain(self, gain):
         """Keep ``gain`` (in [0, 1]) of the background in the foreground from the next emission on, see ``repet.online``."""
         g = background_gains(gain)
@@ -987,6 +1039,7 @@ class OnlineStreams:
         _set_start_frames(self, start_frames)
         self._pushed = 0                              # samples per slot pushed so far
         self._emitted_shape = (self._streams, 0, self._channels)
+        self._tail_emitted = False                    # the last emitting call was a finish_stream: one slot's record
         self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
 
     @property
@@ -1063,6 +1116,7 @@ class OnlineStreams:
         self._pushed += n
         self._last_on_device = False
         self._emitted_shape = results[0].shape
+        self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
 
     def last_emission(self, which="foreground", out=None):
@@ -1089,6 +1143,24 @@ class OnlineStreams:
         check(lib().repet_online_last_emission(self._handle(), codes[0], ptr(result), shape[1], C.byref(n)))
         return result
 
+    def last_levels(self, out=None):
+        """The levels (``repet.LEVELS``, eight float64 values per stream and channel) of exactly the samples the last ``push`` /
+        ``finish`` emitted, ``(S, C, 8)``, or of the tail the last ``finish_stream`` returned, ``(C, 8)``: a NumPy array, or a
+        tensor on the device (``out``, a dense float64 tensor of that shape, or a fresh one) when ``out`` is given or the last
+        push was a device chunk -- then with no host wait. Reduced on the device on demand; see ``repet.online_streams``.
+        ValueError for a wrong ``out`` (before anything runs) and once a push, finish, restart or release has followed."""
+        shape = (self._channels, LEVEL_FIELDS) if self._tail_emitted else (self._streams, self._channels, LEVEL_FIELDS)
+        if out is not None or self._last_on_device:
+            import torch
+            out = levels_out(out, shape, self._device)
+            stream = torch.cuda.current_stream(out.device)
+            check(lib().repet_online_last_levels_device(self._handle(), C.c_void_p(out.data_ptr()), _stream_handle(stream)))
+            return out
+        result = np.empty(shape, dtype=np.float64)
+        n = C.c_int64()
+        check(lib().repet_online_last_levels(self._handle(), ptr(result), result.size, C.byref(n)))
+        return result
+
     def _push_device(self, x, out, codes):
         import torch
         if x.device.index != self._device:
@@ -1112,6 +1184,7 @@ class OnlineStreams:
         x.record_stream(stream)
         self._pushed += n
         self._last_on_device = True
+        self._tail_emitted = False
         return out
 
     @property
@@ -1217,11 +1290,13 @@ class OnlineStreams:
                                                           out_code, (C.c_int64 * 2)(*out_strides[0]), _stream_handle(stream),
                                                           C.byref(written)))
             self._begun[slot] = None
+            self._tail_emitted = True
             return outs[0] if len(outs) == 1 else tuple(outs)
         results = [np.empty(shape, dtype=np.float64) for _ in codes]
         _select_output(self._handle(), codes, ptr(results[-1]))
         check(lib().repet_online_finish_stream(self._handle(), slot, ptr(results[0]), n_emit, C.byref(written)))
         self._begun[slot] = None
+        self._tail_emitted = True
         return results[0] if len(results) == 1 else tuple(results)
 
     def finish(self, out=None, which="background"):
@@ -1240,11 +1315,13 @@ class OnlineStreams:
             check(lib().repet_online_finish_device(self._handle(), C.c_void_p(outs[0].data_ptr() or None), out_code,
                                                    _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
             self._emitted_shape = tuple(outs[0].shape)
+            self._tail_emitted = False
             return outs[0] if len(outs) == 1 else tuple(outs)
         results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
         _select_output(self._handle(), codes, ptr(results[-1]))
         check(lib().repet_online_finish_streams(self._handle(), ptr(results[0]), n_emit, C.byref(written)))
         self._emitted_shape = results[0].shape
+        self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
 
     def close(self):

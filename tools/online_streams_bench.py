@@ -25,7 +25,11 @@ those of YOUNG frames, each decided on the frames heard so far; keep ``--timed``
 
 ``--background-gain G``: the one-handle cases with ``set_background_gain(G)`` made right after the open, so every timed push is
 one of the steady state with gains set. ``--gain-change-every K`` (with it): a new gain is also set before every K-th timed push
-(outside the clock), so those pushes are each the first one after a set, the ones that fade."""
+(outside the clock), so those pushes are each the first one after a set, the ones that fade.
+
+``--levels host|device``: the one-handle cases with a levels call after every timed push, inside the clock: ``device`` is
+``last_levels()`` into a preallocated tensor on the device (no host wait of its own), ``host`` the C ABI's host form (one copy
+through the pinned buffer and one wait), whatever the chunks are."""
 import argparse
 import json
 import sys
@@ -50,8 +54,10 @@ def stats(lat_s, n, fs):
             "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
 
 
-def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0):
+def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None):
+    import ctypes
     import torch
+    from repet import _native
     S, N, ch = xs.shape
     hop = repet.derive_params(fs).step_length
     n = hops * hop
@@ -72,6 +78,8 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
         pos += n
     torch.cuda.synchronize()
     held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
+    record_dev = torch.empty((S, ch, len(repet.LEVELS)), dtype=torch.float64, device="cuda:0") if levels == "device" else None
+    record_host, written = np.empty((S, ch, len(repet.LEVELS))), ctypes.c_int64()
     lat = []
     for k in range(timed):
         if pos + n > N:
@@ -80,6 +88,11 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
             h.set_background_gain((gain + 0.01 * (k + 1)) % 1.0)
         t0 = time.perf_counter()
         h.push(src[:, pos:pos + n], which=which)
+        if levels == "device":
+            h.last_levels(out=record_dev)
+        elif levels == "host":
+            _native.check(_native.lib().repet_online_last_levels(h._handle(), _native.ptr(record_host), record_host.size,
+                                                                 ctypes.byref(written)))
         if device:
             torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
@@ -286,6 +299,8 @@ def main():
                     help="set this background gain on the one-handle cases right after the open (see above)")
     ap.add_argument("--gain-change-every", type=int, default=0, metavar="K",
                     help="with --background-gain: set a new gain before every K-th timed push")
+    ap.add_argument("--levels", choices=["host", "device"], default=None,
+                    help="a levels call after every timed push of the one-handle cases, inside the clock (see above)")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
@@ -317,6 +332,8 @@ def main():
     if args.background_gain is not None:
         result["background_gain"] = args.background_gain
         result["gain_change_every"] = args.gain_change_every
+    if args.levels is not None:
+        result["levels"] = args.levels
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
@@ -324,10 +341,11 @@ def main():
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
                 case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
-                                       args.gain_change_every)
+                                       args.gain_change_every, args.levels)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
-                                                            gain=args.background_gain, gain_every=args.gain_change_every)
+                                                            gain=args.background_gain, gain_every=args.gain_change_every,
+                                                            levels=args.levels)
                 if S <= args.separate_max:
                     case["separate_handles_host"] = separate_handles(xs, fs, hops, args.timed, warm_s)
             result["cases"].append(case)
