@@ -47,8 +47,19 @@ typedef enum repet_algo {
 } repet_algo;
 
 /* REPET_F16 / REPET_BF16: the device-side entries only (repet_ctx_upload_device_strided, repet_run_device); the host entries
- * refuse them. */
+ * refuse them.
+ * As a DESTINATION dtype of a device-side entry (repet_ctx_download_device_strided, out_dtype of repet_run_device, dst_dtype of
+ * the repet_online_*_device calls, repet_online_also_emit armed for one) each of the five is the inverse of the same source
+ * dtype: a cast of the float64 value the engine holds, never a rescale. REPET_I16 ingest is the raw (float) cast, so REPET_I16
+ * egress returns the same units (a +-1.0 float stream emitted as int16 is 0 / +-1): round to nearest, ties to even, saturated
+ * to [-32768, 32767], NaN 0. REPET_F16 / REPET_BF16: the nearest value of the format, ties to even, rounded ONCE from float64
+ * (not through float32): +-inf beyond the largest finite, subnormals produced, NaN stays NaN, the sign of zero is kept. The
+ * host-array results stay float64. */
 typedef enum repet_dtype { REPET_F32 = 0, REPET_F64 = 1, REPET_I16 = 2, REPET_F16 = 3, REPET_BF16 = 4 } repet_dtype;
+/* (still ABI 4: an addition -- look the symbol up to detect it) 1 where `dtype` is a destination dtype of the device-side
+ * entries (the five codes above), 0 for anything else. Touches no device. A library without this symbol writes REPET_F64 and
+ * REPET_F32 only. */
+int repet_emit_dtype_supported(int dtype);
 
 /* The reference's nine module globals (repet.py:42-63), already converted to frames/bins/samples. */
 typedef struct repet_params {
@@ -170,7 +181,8 @@ int repet_ctx_download_device(repet_ctx* ctx, float* dev_out);
  *     values leaves, bit for bit. The context is left as repet_ctx_upload_device_split leaves it (the planes are not scanned).
  *     REPET_FLAG_REFUSE_NONFINITE (repet_ctx_set_strict_reference(ctx, 0)) is the one case that waits: the ingest notes a
  *     sample that is not finite and the call reads that note back (one host wait) to refuse such a clip as the host path does.
- * repet_ctx_download_device_strided : the result widened into `dst` (REPET_F64: (double)v; or REPET_F32) of shape
+ * repet_ctx_download_device_strided : the result into `dst` (REPET_F64: (double)v; REPET_F32; or REPET_I16 / F16 / BF16, the
+ *     value rounded once as repet_dtype describes) of shape
  *     [n_clips][n_samples][n_channels] with the given strides (elements must not overlap), enqueued on the context's stream
  *     behind what `signal_stream` has enqueued so far; `signal_stream` then waits for it, so the caller's next work on that
  *     stream sees the result. */
@@ -274,7 +286,7 @@ int repet_run(int algo, const void* audio, int dtype, int64_t n_samples, int32_t
               const repet_params* p, double* out, int device, repet_timing* timing /* nullable */);
 /* The device-side twin of repet_run, for a host that keeps its audio on the GPU and has a HIP stream of its own: the same
  * per-thread, per-device context; ingest (repet_ctx_upload_device_strided, waiting for `stream`), repet_ctx_execute_async and
- * egress into `dst` (out_dtype REPET_F64 or REPET_F32, signalling `stream`), all ordered on `stream` without a host wait
+ * egress into `dst` (out_dtype REPET_F64 / F32 / I16 / F16 / BF16, signalling `stream`), all ordered on `stream` without a host wait
  * (except for REPET_FLAG_REFUSE_NONFINITE, see above, and the one-time growth of workspaces on a new shape). */
 int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n_samples, int32_t n_channels,
                      const int64_t in_strides[3], void* dst, int out_dtype, const int64_t out_strides[3],
@@ -452,7 +464,8 @@ int repet_online_close(repet_online* h);
  *                stream); returns once out is written. For S = 1 this is exactly repet_online_push.
  * push_device  : device chunk with element strides [stream, sample, channel] (F64 / F32 / I16 / F16 / BF16, as
  *                repet_ctx_upload_device_strided), read behind what wait_stream has enqueued; the result is widened into dst
- *                (F32 / F64, element strides, elements must not overlap) and signal_stream is made to wait for it. No host wait.
+ *                (F64 / F32, or I16 / F16 / BF16 rounded once as repet_dtype describes; element strides, elements must not
+ *                overlap) and signal_stream is made to wait for it. No host wait. A 16-bit destination costs no launch more.
  * finish_*     : the end of every stream, to the host or into a device destination like push_device's. */
 int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p,
                               int64_t max_push_samples, repet_online** out);
@@ -571,7 +584,8 @@ int repet_ctx_set_online_start(repet_ctx* ctx, int32_t start_frames);
 #define REPET_OUT_MIXTURE 2      /* the input samples themselves, aligned with what was emitted (the delay-compensated input) */
 /* With x the sample as the engine holds it (fp32 sample + fp32 remainder: exact for F32 / F16 / BF16 / I16 input and for
  * float64 input that came from PCM or fp32, 48 bits of any other float64 sample) and bg the fp32 background: mixture =
- * (double)x, foreground = (double)x - (double)bg, rounded once; an F32 destination takes that value rounded once more. A sample
+ * (double)x, foreground = (double)x - (double)bg, rounded once; an F32 / I16 / F16 / BF16 destination takes that value rounded
+ * once more (straight from float64: see repet_dtype). A sample
  * before its slot's own stream began (the hop emitted behind a restart, every sample of an idle slot) is zero in all three
  * signals, whatever the chunk carried there; from the slot's first own sample on, foreground and mixture are its input, the
  * warm-up included (the background is zero there: nothing is removed before there is evidence).

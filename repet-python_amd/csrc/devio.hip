@@ -6,7 +6,8 @@
 //           remainders: hi = (float)x, lo = (float)(x - (double)hi) -- exactly what narrow_f64 / split_part of hostio.hip
 //           produce, so the planes equal a host upload's bit for bit. I16 is the raw (float) cast of narrow_i16; F16 / BF16
 //           widen exactly. With a flag word it also notes a sample that is not finite (the refusal mode reads it).
-//   egress  out [clip][n][c] fp32 -> destination (F64: (double)v as widen_f32 does, or F32), strided.
+//   egress  out [clip][n][c] fp32 -> destination (F64: (double)v as widen_f32 does, F32, or I16 / F16 / BF16: the inverse of
+//           the ingest's cast, never a rescale -- the value rounded ONCE to nearest, ties to even, see narrow()), strided.
 // Both are bandwidth kernels: every thread owns a few consecutive elements of the interleaved side, which it reads or writes
 // with one vector access, so that each 128-byte line of that side is moved whole by one instruction of one wave; the strided
 // side takes element accesses, vector ones when it is the same dense layout and aligned.
@@ -152,30 +153,91 @@ __device__ inline void ingest_body(const T* __restrict__ src, IoGeo g, int dense
     if (bad) *nonfinite = 1u;                                     // (every writer stores the same value)
 }
 
+// The last store of an emission: the float64 value the engine holds -> the destination's type. A destination dtype is the
+// inverse of the same source dtype: a cast, never a rescale (I16 ingest is the raw (float) cast, so I16 egress returns the
+// same units: a +-1.0 float stream emitted as int16 is 0 / +-1).
+//   F64 / F32  the C++ conversion, as ever.
+//   F16 / BF16 the nearest value of the format, ties to even, rounded ONCE from float64 (through float32 it would be rounded
+//              twice): beyond the largest finite +-inf, subnormals produced, NaN a quiet NaN, the sign of zero kept. An integer
+//              sequence on the double's bits, E exponent and M fraction bits (binary16: 5, 10; bfloat16: 8, 7): the
+//              significand shifted down to the format's last place -- further below its smallest normal --, then
+//              incremented where the bits shifted out are above half a place, or exactly half with an odd last place; the
+//              carry of that increment runs into the exponent field by itself, up to infinity.
+//   I16        round to nearest, ties to even (v_rndne_f64), saturated to [-32768, 32767]; NaN is 0.
+template <int E, int M> __host__ __device__ inline uint16_t round_f64_bits(double v) {
+    constexpr int kMax = (1 << E) - 1, kBias = (1 << (E - 1)) - 1;
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t sign = (uint32_t)(u >> 48) & 0x8000u;
+    const int e = (int)(u >> 52) & 0x7ff;
+    const uint64_t frac = u & 0xfffffffffffffull;
+    if (e == 0x7ff) return (uint16_t)(sign | (uint32_t)(kMax << M) | (frac ? 1u << (M - 1) : 0u));
+    const int te = e - 1023 + kBias;                              // the exponent field of a normal result
+    if (te >= kMax) return (uint16_t)(sign | (uint32_t)(kMax << M));
+    const uint64_t sig = frac | (e ? 1ull << 52 : 0ull);
+    int sh = 52 - M + (te >= 1 ? 0 : 1 - te);                     // (54 and more: below half the smallest subnormal, all alike)
+    sh = sh < 54 ? sh : 54;
+    uint32_t r = (te >= 1 ? (uint32_t)(te - 1) << M : 0u) + (uint32_t)(sig >> sh);      // (the hidden bit completes the field)
+    const uint64_t rem = sig & ((1ull << sh) - 1), half = 1ull << (sh - 1);
+    r += rem > half || (rem == half && (r & 1u)) ? 1u : 0u;
+    return (uint16_t)(sign | r);
+}
+
+template <typename T> __device__ inline T narrow(double v) { return (T)v; }
+template <> __device__ inline int16_t narrow<int16_t>(double v) {
+    return (int16_t)(int32_t)(v != v ? 0.0 : fmin(fmax(rint(v), -32768.0), 32767.0));
+}
+template <> __device__ inline Half narrow<Half>(double v) { return Half{round_f64_bits<5, 10>(v)}; }
+template <> __device__ inline BHalf narrow<BHalf>(double v) { return BHalf{round_f64_bits<8, 7>(v)}; }
+
+__device__ inline uint32_t bits16(int16_t v) { return (uint16_t)v; }
+__device__ inline uint32_t bits16(Half v) { return v.bits; }
+__device__ inline uint32_t bits16(BHalf v) { return v.bits; }
+
+// Elements per thread of the kernels that write a 16-bit type: four, an 8-byte store per lane on a dense destination beside the
+// 16-byte loads of the fp32 planes. (Eight -- a 16-byte store -- costs devio_emit_* 74 VGPRs against the 48 of devio_emit_f32 and
+// of the four-element form: six waves per SIMD instead of eight; profiles/HISTORY.md.)
+constexpr int kEpt16 = 4;
+
+// EPT consecutive fp32 values by one vector load (2: a float2; 4: a float4), p aligned for it
+template <int EPT> __device__ inline void load_run(const float* p, float (&v)[EPT]) {
+    if constexpr (EPT == 2) { const float2 a = *reinterpret_cast<const float2*>(p); v[0] = a.x; v[1] = a.y; }
+    else { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
+}
+
+// EPT consecutive elements of a dense destination by ONE vector store (F64: double2, F32: float4, 16-bit types: four elements
+// in a uint2), p aligned for it
+template <typename T, int EPT> __device__ inline void store_run(T* p, const T (&v)[EPT]) {
+    if constexpr (sizeof(T) == 8) *reinterpret_cast<double2*>(p) = make_double2(v[0], v[1]);
+    else if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *reinterpret_cast<uint2*>(p) = make_uint2(bits16(v[0]) | bits16(v[1]) << 16, bits16(v[2]) | bits16(v[3]) << 16);
+}
+
 // Egress: EPT consecutive interleaved elements per thread, read with one vector load (F64: 2 -> float2 in, double2 out;
-// F32: 4 -> float4 in and out), so that the interleaved side and a dense destination move whole lines per instruction.
+// F32: 4 -> float4 in and out; I16 / F16 / BF16: 4 -> float4 in, 8 bytes out), so that the interleaved side and a dense
+// destination move whole lines per instruction. (An fp32 value widens exactly: narrow() rounds it once.)
 template <typename T, int EPT>
 __device__ inline void egress_body(const float* __restrict__ in, IoGeo g, int dense, T* __restrict__ dst) {
     const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * EPT;
     if (i0 >= g.count) return;
     if (i0 + EPT <= g.count) {
         float v[EPT];
-        if constexpr (EPT == 2) { const float2 a = *reinterpret_cast<const float2*>(in + i0); v[0] = a.x; v[1] = a.y; }
-        else { const float4 a = *reinterpret_cast<const float4*>(in + i0); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
+        load_run<EPT>(in + i0, v);
         if (dense) {
-            if constexpr (EPT == 2) *reinterpret_cast<double2*>(dst + i0) = make_double2((double)v[0], (double)v[1]);
-            else *reinterpret_cast<float4*>(dst + i0) = make_float4(v[0], v[1], v[2], v[3]);
+            T t[EPT];
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) t[k] = narrow<T>((double)v[k]);
+            store_run<T, EPT>(dst + i0, t);
         } else {
             Walker w(g, i0);
 #pragma unroll
             for (int k = 0; k < EPT; ++k) {
-                dst[w.off] = (T)v[k];
+                dst[w.off] = narrow<T>((double)v[k]);
                 if (k < EPT - 1) w.next(g);
             }
         }
     } else {
         Walker w(g, i0);
-        for (int64_t i = i0; i < g.count; ++i) { dst[w.off] = (T)in[i]; w.next(g); }
+        for (int64_t i = i0; i < g.count; ++i) { dst[w.off] = narrow<T>((double)in[i]); w.next(g); }
     }
 }
 
@@ -187,12 +249,16 @@ __global__ __launch_bounds__(kIoThreads) void devio_ingest_f16(const Half* src, 
 __global__ __launch_bounds__(kIoThreads) void devio_ingest_bf16(const BHalf* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<BHalf>(src, g, dense, hi, lo, nf); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f64(const float* in, IoGeo g, int dense, double* dst) { egress_body<double, 2>(in, g, dense, dst); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, IoGeo g, int dense, float* dst) { egress_body<float, 4>(in, g, dense, dst); }
+__global__ __launch_bounds__(kIoThreads) void devio_egress_i16(const float* in, IoGeo g, int dense, int16_t* dst) { egress_body<int16_t, kEpt16>(in, g, dense, dst); }
+__global__ __launch_bounds__(kIoThreads) void devio_egress_f16(const float* in, IoGeo g, int dense, Half* dst) { egress_body<Half, kEpt16>(in, g, dense, dst); }
+__global__ __launch_bounds__(kIoThreads) void devio_egress_bf16(const float* in, IoGeo g, int dense, BHalf* dst) { egress_body<BHalf, kEpt16>(in, g, dense, dst); }
 
 // Emission of the streaming handle, and the selected result of an offline context: what was emitted as background (`bg`, fp32
 // [S][n][C] dense), as foreground (input - background) or as mixture (the input itself, aligned with what was emitted), into
 // one or two strided destinations in ONE pass. The input is read where the engine holds it: fp32 samples `hi` and, where
 // present, their fp32 remainders `lo`, stream s at s * in_stream floats. In float64: mixture = hi + lo (exact),
-// foreground = mixture - bg (rounded once); an F32 destination takes that value rounded once more. A sample of stream s is
+// foreground = mixture - bg (rounded once); an F32 / I16 / F16 / BF16 destination takes that value rounded once more, by
+// narrow(): the destination dtype is a property of the last store alone. A sample of stream s is
 // LIVE from handle sample slot_start[s] * hop on (pos0: handle sample of the emission's first one; no table: always); every
 // other sample is zero in all three signals by a select, so NaN in an idle slot's share of a chunk never shows.
 // EPT consecutive interleaved elements per thread as in egress_body: vector accesses on bg, on hi / lo where the run lies in
@@ -222,8 +288,9 @@ __device__ inline double emit_gain_at(double at, double ac, int64_t j1, int64_t 
 // the three float64 signals of one sample: h + l (or h, infinite), the fp32 background widened, x - bg or fma(-ak, bg, x); a
 // sample that is not live is zero in all three by a select
 __device__ inline void emit_sample(float h, float l, float b, bool live, bool gain, double ak, double& mix, double& bgv, double& fgv) {
-    // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi)
-    const double x = fabsf(h) <= 3.402823466e38f || h != h ? (double)h + (double)l : (double)h;
+    // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi. So it is with a zero
+    // remainder, which adds nothing and must not: -0 + +0 is +0, and the mixture of a negative zero is a negative zero)
+    const double x = (fabsf(h) <= 3.402823466e38f || h != h) && l != 0.f ? (double)h + (double)l : (double)h;
     mix = live ? x : 0.0;
     const double f = gain ? fma(-ak, (double)b, x) : x - (double)b;
     fgv = live ? f : 0.0;
@@ -239,8 +306,7 @@ __device__ inline void emit_body(const EmitArgs& a) {
     float b[EPT], h[EPT], l[EPT];
     bool live[EPT];
     if (m == EPT) {
-        if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(a.bg + i0); b[0] = v.x; b[1] = v.y; }
-        else { const float4 v = *reinterpret_cast<const float4*>(a.bg + i0); b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w; }
+        load_run<EPT>(a.bg + i0, b);
     } else {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) b[k] = k < m ? a.bg[i0 + k] : 0.f;
@@ -248,12 +314,9 @@ __device__ inline void emit_body(const EmitArgs& a) {
     const float* ph = a.hi + s0 * a.in_stream + r0;
     const bool one_stream = m == EPT && r0 + EPT <= a.per;
     if (one_stream && !(reinterpret_cast<uintptr_t>(ph) & (EPT * 4 - 1))) {
-        if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(ph); h[0] = v.x; h[1] = v.y; }
-        else { const float4 v = *reinterpret_cast<const float4*>(ph); h[0] = v.x; h[1] = v.y; h[2] = v.z; h[3] = v.w; }
+        load_run<EPT>(ph, h);
         if (a.lo) {
-            const float* pl = a.lo + s0 * a.in_stream + r0;         // (hi and lo are laid out alike: aligned together)
-            if constexpr (EPT == 2) { const float2 v = *reinterpret_cast<const float2*>(pl); l[0] = v.x; l[1] = v.y; }
-            else { const float4 v = *reinterpret_cast<const float4*>(pl); l[0] = v.x; l[1] = v.y; l[2] = v.z; l[3] = v.w; }
+            load_run<EPT>(a.lo + s0 * a.in_stream + r0, l);         // (hi and lo are laid out alike: aligned together)
         } else {
 #pragma unroll
             for (int k = 0; k < EPT; ++k) l[k] = 0.f;
@@ -310,10 +373,9 @@ __device__ inline void emit_body(const EmitArgs& a) {
         T* dst = static_cast<T*>(o.p);
         T v[EPT];
 #pragma unroll
-        for (int k = 0; k < EPT; ++k) v[k] = (T)(o.which == REPET_OUT_BACKGROUND ? bgv[k] : (o.which == REPET_OUT_FOREGROUND ? fgv[k] : mix[k]));
+        for (int k = 0; k < EPT; ++k) v[k] = narrow<T>(o.which == REPET_OUT_BACKGROUND ? bgv[k] : (o.which == REPET_OUT_FOREGROUND ? fgv[k] : mix[k]));
         if (m == EPT && o.dense) {
-            if constexpr (EPT == 2) *reinterpret_cast<double2*>(dst + i0) = make_double2(v[0], v[1]);
-            else *reinterpret_cast<float4*>(dst + i0) = make_float4(v[0], v[1], v[2], v[3]);
+            store_run<T, EPT>(dst + i0, v);
         } else {
             const IoGeo g{a.count, a.n_samples, a.n_channels, o.s_clip, o.s_sample, o.s_channel};
             Walker w(g, i0);
@@ -330,6 +392,9 @@ __device__ inline void emit_body(const EmitArgs& a) {
 
 __global__ __launch_bounds__(kIoThreads) void devio_emit_f64(EmitArgs a) { emit_body<double, 2>(a); }
 __global__ __launch_bounds__(kIoThreads) void devio_emit_f32(EmitArgs a) { emit_body<float, 4>(a); }
+__global__ __launch_bounds__(kIoThreads) void devio_emit_i16(EmitArgs a) { emit_body<int16_t, kEpt16>(a); }
+__global__ __launch_bounds__(kIoThreads) void devio_emit_f16(EmitArgs a) { emit_body<Half, kEpt16>(a); }
+__global__ __launch_bounds__(kIoThreads) void devio_emit_bf16(EmitArgs a) { emit_body<BHalf, kEpt16>(a); }
 
 // Levels of an emission (or of an offline result): per stream s and channel c the REPET_LEVEL_FIELDS float64 values of
 // include/repet_hip.h -- sums of squares and largest magnitudes of the three signals emit_sample forms, the live samples and
@@ -688,7 +753,8 @@ int element_size(int dtype) {
     switch (dtype) {
         case REPET_F64: return 8;
         case REPET_F32: return 4;
-        default: return 2;
+        case REPET_I16: case REPET_F16: case REPET_BF16: return 2;
+        default: return 0;                                        // not a dtype
     }
 }
 
@@ -837,9 +903,19 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
     if (dtype == REPET_F64) {
         const dim3 grid((unsigned)ceil_div(ceil_div(count, 2), kIoThreads));
         devio_egress_f64<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<double*>(dst));
-    } else {
+    } else if (dtype == REPET_F32) {
         const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
         devio_egress_f32<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<float*>(dst));
+    } else {
+        // a dense 16-bit destination takes one store of kEpt16 elements per lane: aligned for that, or element by element
+        const dim3 grid((unsigned)ceil_div(ceil_div(count, kEpt16), kIoThreads));
+        const int dense = is_dense(dst, g, n_streams, 2 * kEpt16) ? 1 : 0;
+        switch (dtype) {
+            case REPET_I16: devio_egress_i16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<int16_t*>(dst)); break;
+            case REPET_F16: devio_egress_f16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<Half*>(dst)); break;
+            case REPET_BF16: devio_egress_bf16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<BHalf*>(dst)); break;
+            default: return hipErrorInvalidValue;
+        }
     }
     return hipGetLastError();
 }
@@ -890,12 +966,21 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
     }
     a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts;
+    // (the vector store of a dense destination: 16 bytes for F64 / F32, kEpt16 elements for the 16-bit types)
+    const int vec_bytes = dtype == REPET_F64 || dtype == REPET_F32 ? 16 : 2 * kEpt16;
     for (int k = 0; k < n_dsts; ++k) {
         const IoGeo g{count, n, ch, dsts[k].strides[0], dsts[k].strides[1], dsts[k].strides[2]};
-        a.out[k] = EmitOut{dsts[k].p, g.s_clip, g.s_sample, g.s_channel, dsts[k].which, is_dense(dsts[k].p, g, n_streams, 16) ? 1 : 0};
+        a.out[k] = EmitOut{dsts[k].p, g.s_clip, g.s_sample, g.s_channel, dsts[k].which, is_dense(dsts[k].p, g, n_streams, vec_bytes) ? 1 : 0};
     }
-    if (dtype == REPET_F64) devio_emit_f64<<<dim3((unsigned)ceil_div(ceil_div(count, 2), kIoThreads)), kIoThreads, 0, s>>>(a);
-    else devio_emit_f32<<<dim3((unsigned)ceil_div(ceil_div(count, 4), kIoThreads)), kIoThreads, 0, s>>>(a);
+    const dim3 grid16((unsigned)ceil_div(ceil_div(count, kEpt16), kIoThreads));
+    switch (dtype) {
+        case REPET_F64: devio_emit_f64<<<dim3((unsigned)ceil_div(ceil_div(count, 2), kIoThreads)), kIoThreads, 0, s>>>(a); break;
+        case REPET_F32: devio_emit_f32<<<dim3((unsigned)ceil_div(ceil_div(count, 4), kIoThreads)), kIoThreads, 0, s>>>(a); break;
+        case REPET_I16: devio_emit_i16<<<grid16, kIoThreads, 0, s>>>(a); break;
+        case REPET_F16: devio_emit_f16<<<grid16, kIoThreads, 0, s>>>(a); break;
+        case REPET_BF16: devio_emit_bf16<<<grid16, kIoThreads, 0, s>>>(a); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
@@ -948,6 +1033,13 @@ int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(p0), b0 = reinterpret_cast<uintptr_t>(p1);
     if (a0 < b0 + (uintptr_t)last(st1) && b0 < a0 + (uintptr_t)last(st0))
         return fail(REPET_ERR_BAD_ARG, "the two destinations overlap (their address ranges must not intersect)");
+    return REPET_OK;
+}
+
+int dtype_bytes(int dtype) { return element_size(dtype); }
+
+int check_emit_dtype(int dtype) {
+    if (!element_size(dtype)) return fail(REPET_ERR_BAD_ARG, "the result is float64, float32, int16, float16 or bfloat16");
     return REPET_OK;
 }
 
@@ -1054,6 +1146,8 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     return REPET_OK;
 }
 
+int repet_emit_dtype_supported(int dtype) { return element_size(dtype) ? 1 : 0; }
+
 int repet_ctx_set_online_start(repet_ctx* c, int32_t start_frames) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (start_frames < 0) return fail(REPET_ERR_BAD_ARG, "start_frames must be >= 0 (0: buffer_frames, the reference)");
@@ -1080,7 +1174,7 @@ int repet_ctx_set_background_gain(repet_ctx* c, float gain) {
 int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const int64_t strides[3], void* signal_stream) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
-    if (dtype != REPET_F32 && dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_emit_dtype(dtype));
     RP_TRY(check_strides(strides));
     RP_TRY(check_no_overlap(strides, c->n_clips, c->n_samples, c->n_channels));
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;
@@ -1101,16 +1195,7 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
                                    c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels, dtype, &d, 1,
                                    c->stream, c->result_gain ? &gain : nullptr));
     } else if (count > 0) {
-        IoGeo g{count, c->n_samples, c->n_channels, strides[0], strides[1], strides[2]};
-        const float* in = c->out.as<float>();
-        if (dtype == REPET_F64) {
-            const dim3 grid((unsigned)ceil_div(ceil_div(count, 2), kIoThreads));
-            devio_egress_f64<<<grid, kIoThreads, 0, c->stream>>>(in, g, is_dense(dst, g, c->n_clips, 16) ? 1 : 0, static_cast<double*>(dst));
-        } else {
-            const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
-            devio_egress_f32<<<grid, kIoThreads, 0, c->stream>>>(in, g, is_dense(dst, g, c->n_clips, 16) ? 1 : 0, static_cast<float*>(dst));
-        }
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_stream_egress(c->out.as<float>(), c->n_clips, c->n_samples, c->n_channels, dst, dtype, strides, c->stream));
     }
     // the caller's stream continues behind the egress
     HIP_TRY(hipEventRecord(c->io_done, c->stream));

@@ -274,7 +274,7 @@ float background_gain_factor(float gain);
 // the streaming handle's per-push data movement (devio.hip), n_streams streams at per-stream element strides:
 //   append   chunk [S][n][C] (strided, any device dtype) -> hi / lo at s * dst_stream + dst_off (fp32 + fp32 remainder)
 //   copies   up to kRowCopyParts parts of `blocks` runs of `len` floats per stream (src null: zeros), one launch
-//   egress   fp32 [S][n][C] -> strided F32 / F64 destination
+//   egress   fp32 [S][n][C] -> strided F64 / F32 / I16 / F16 / BF16 destination
 //            a part with row_len > 0 covers frame rows of row_len floats, the first of them frame `frame0`: of stream b only
 //            the rows of frames before slot_start[b] are written (the rows of a slot whose own stream has not begun)
 //   reset    the named slots' own stream begins at frame `value` (kSlotIdle: never): slot_start[slot] = value and up to
@@ -326,6 +326,9 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
 hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s);
 hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int32_t n_slots, hipStream_t s);
 hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s);
+// bytes of an element of a REPET_* dtype (0: not a dtype), and the refusal of a destination dtype the emission does not write
+int dtype_bytes(int dtype);
+int check_emit_dtype(int dtype);
 int check_disjoint(const void* p0, const int64_t* st0, const void* p1, const int64_t* st1, int elem_bytes, int32_t n_clips, int64_t n,
                    int32_t ch);
 constexpr int kRankMinList = 24;     // shortest list bound for which the column sort is worth its time

@@ -1196,7 +1196,7 @@ int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int6
     repet_ctx* c = nullptr;
     RP_TRY(thread_ctx(device, &c));
     RP_TRY(check_params(p));
-    if (out_dtype != REPET_F32 && out_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_emit_dtype(out_dtype));
     c->strict = !(p->flags & REPET_FLAG_REFUSE_NONFINITE);
     RP_TRY(repet_ctx_upload_device_strided(c, src, dtype, n_clips, n, ch, in_strides, stream));
     RP_TRY(repet_ctx_execute_async(c, algo, p));

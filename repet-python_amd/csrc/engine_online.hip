@@ -474,7 +474,7 @@ int online_check_also_host(const repet_online* o, int64_t n_emit, const double* 
 }
 
 int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int dst_dtype, const int64_t dst_strides[3], int streams = 0) {
-    if (dst_dtype != REPET_F32 && dst_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_emit_dtype(dst_dtype));
     RP_TRY(check_strides(dst_strides));
     RP_TRY(check_no_overlap(dst_strides, streams > 0 ? streams : o->S, n_emit, o->C));
     if (n_emit > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
@@ -485,7 +485,7 @@ int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int
         if (o->also.dtype != dst_dtype) return fail(REPET_ERR_BAD_ARG, "online: the two outputs of one call have one dtype");
         RP_TRY(check_strides(st));
         RP_TRY(check_no_overlap(st, S, n_emit, o->C));
-        RP_TRY(check_disjoint(dst, dst_strides, o->also.dst, st, dst_dtype == REPET_F64 ? 8 : 4, S, n_emit, o->C));
+        RP_TRY(check_disjoint(dst, dst_strides, o->also.dst, st, dtype_bytes(dst_dtype), S, n_emit, o->C));
     }
     return REPET_OK;
 }
@@ -749,7 +749,7 @@ int repet_online_also_emit(repet_online* o, int which, void* dst, int dtype, con
     if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
     o->also.which = -1;
     RP_TRY(check_which(which));
-    if (dtype != REPET_F32 && dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_emit_dtype(dtype));
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     o->also.dst = dst; o->also.dtype = dtype;
     for (int k = 0; k < 3; ++k) o->also.strides[k] = strides ? strides[k] : 0;
@@ -786,7 +786,7 @@ int repet_online_last_emission_device(repet_online* o, int which, void* dst, int
     *n_written = 0;
     RP_TRY(check_which(which));
     if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, "online: the last emission is stale (a push, finish, restart or release came after it)");
-    if (dst_dtype != REPET_F32 && dst_dtype != REPET_F64) return fail(REPET_ERR_BAD_ARG, "the result is float32 or float64");
+    RP_TRY(check_emit_dtype(dst_dtype));
     RP_TRY(check_strides(dst_strides));
     const int64_t strides[3] = {o->em.slot < 0 ? dst_strides[0] : 0, dst_strides[1], dst_strides[2]};
     RP_TRY(check_no_overlap(strides, o->em.S, o->em.n, o->C));

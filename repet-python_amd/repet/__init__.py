@@ -120,7 +120,7 @@ def release_workspaces():
 
 
 def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
-                     levels=False):
+                     levels=False, dtype=None):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
@@ -134,6 +134,7 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     x, shape = layout[0], layout[2]
     result_shape = shape if x.dim() == 3 else shape[1:]
     outs = _native.out_pair(out) if which == "both" else (out,)
+    _native.emit_dtype(dtype, outs)
     for o in outs:
         if o is None:
             continue
@@ -141,7 +142,7 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
             raise ValueError(f"out must be a tensor on {x.device}")
         if tuple(o.shape) != result_shape:
             raise ValueError(f"out has shape {tuple(o.shape)}, the result {result_shape}")
-        _native.result_tensor_code(o)
+        _native.emit_tensor_code(o)
     ctx = _native.tensor_context(x.device.index)
     ctx.set_strict_reference(strict_reference)
     stream = torch.cuda.current_stream(x.device)
@@ -149,14 +150,14 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     ctx.execute_async(algo, params)
     record = None
     if background_gain is None:
-        results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+        results = tuple(ctx.download_tensor(o, stream, name, dtype) for o, name in zip(outs, names))
         if levels:
             record = ctx.result_levels(stream=stream)
     else:
         # on this thread's cached context for this call alone: later calls are the plain foreground again, whatever happens here
         try:
             ctx.set_background_gain(background_gain)
-            results = tuple(ctx.download_tensor(o, stream, name) for o, name in zip(outs, names))
+            results = tuple(ctx.download_tensor(o, stream, name, dtype) for o, name in zip(outs, names))
             if levels:
                 record = ctx.result_levels(stream=stream)
         finally:
@@ -205,12 +206,19 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False):
+def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
-    clips one after another). Returns a float64 tensor on the tensor's device -- or fills ``out``, a float32 / float64 tensor
-    of the same shape with any strides, and returns it. Every clip's result is what the one-clip call returns, bit for bit;
-    the work is ordered on the device's current stream with no host wait (see ``_separate_tensor``).
+    clips one after another). Returns a float64 tensor on the tensor's device -- one of ``dtype``, where given -- or fills
+    ``out``, a float64 / float32 / int16 / float16 / bfloat16 tensor of the same shape with any strides, and returns it. Every
+    clip's result is what the one-clip call returns, bit for bit; the work is ordered on the device's current stream with no
+    host wait (see ``_separate_tensor``).
+
+    A destination dtype is the inverse of the same source dtype: a cast of the float64 value the egress forms, never a rescale,
+    rounded once. float16 / bfloat16: the nearest value, ties to even, straight from float64 (``result.to(torch.bfloat16)`` of
+    a float64 result rounds twice), inf beyond the largest finite value. int16: rounded to nearest, ties to even, saturated to
+    [-32768, 32767], NaN 0 -- int16 PCM in, int16 PCM out in the same units; a +-1.0 float signal written as int16 is 0 / +-1.
+    ``dtype`` beside an ``out`` of another dtype, and a pair of two dtypes, are a ValueError before anything runs.
 
     ``which``: "background" (default), "foreground" -- ``audio_signal - background`` written by the egress itself, in float64
     from the samples as the engine holds them (exact for float32 / float16 / bfloat16 / int16 tensors; 48 bits of a float64
@@ -238,7 +246,7 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
-                            background_gain=background_gain, levels=bool(levels))
+                            background_gain=background_gain, levels=bool(levels), dtype=dtype)
 
 
 def online(sampling_frequency, number_channels, start_length=None):
@@ -276,8 +284,13 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     streaming handle on the device of :func:`set_device`, pushed in lockstep. ``push(chunk, out=None)`` takes a chunk
     ``(number_streams, n, number_channels)`` -- a host array, or a ROCm tensor (the dtypes :func:`separate` takes, any strides)
     -- and returns the ``(number_streams, n_emit, number_channels)`` background samples that became final: a float64 array
-    for a host chunk; for a tensor a float64 tensor on its device, or ``out`` (float32 / float64, any strides) filled, ordered
-    on the current stream with no host wait. ``finish(out=None)`` returns the rest, ``close()`` frees the device state. Each
+    for a host chunk; for a tensor a float64 tensor on its device (``dtype=``: one of that torch dtype), or ``out`` (float64 /
+    float32 / int16 / float16 / bfloat16, any strides) filled, ordered on the current stream with no host wait. A destination
+    dtype is the inverse of the same source dtype -- a cast of the float64 value of the emission, never a rescale, rounded once
+    to nearest, ties to even, by the launch that writes it (int16 saturates, NaN 0; the 16-bit floats go to inf beyond their
+    largest finite value): int16 hops in, int16 hops out, at the launches a float32 ``out`` costs. ``finish``,
+    ``finish_stream`` and ``last_emission`` take ``dtype=`` likewise; with a host chunk, or beside an ``out`` of another dtype,
+    it is a ValueError. ``last_levels`` measures the float64 values before that store, whatever the dtype. ``finish(out=None)`` returns the rest, ``close()`` frees the device state. Each
     stream's concatenated output equals ``simonline`` of its concatenated input, bit for bit. ``max_push_samples`` sizes the
     device buffers at open (pushes up to that size then never grow them); the module parameters are snapshotted now.
 

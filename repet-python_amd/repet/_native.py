@@ -234,6 +234,7 @@ _SIGNATURES = {
     "repet_online_last_levels": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_last_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_ctx_result_levels_device": (C.c_int, [_P, _P, _P]),
+    "repet_emit_dtype_supported": (C.c_int, [C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -357,6 +358,30 @@ def result_tensor_code(out):
     if code is None:
         raise ValueError("out must be a float32 or float64 tensor")
     return code
+
+
+def emit_tensor_code(out):
+    """The dtype code of a destination tensor of the device-side egress (a live handle's ``out=``, ``download_tensor``,
+    ``repet.separate``): float64, float32, int16, float16 or bfloat16 -- each the inverse of the same source dtype, a cast of
+    the float64 value the engine holds and never a rescale. ValueError for anything else."""
+    code = _TENSOR_CODES.get(str(out.dtype))
+    if code is None:
+        raise ValueError("out must be a float64, float32, int16, float16 or bfloat16 tensor")
+    return code
+
+
+def emit_dtype(dtype, outs=()):
+    """``dtype=`` of a device-path call: the torch dtype of a fresh result -- ``dtype``, or float64 for None. ValueError, before
+    anything runs, for a dtype the egress does not write and for an ``out`` tensor (None entries skipped) of another dtype."""
+    import torch
+    if dtype is None:
+        return torch.float64
+    if not isinstance(dtype, torch.dtype) or str(dtype) not in _TENSOR_CODES:
+        raise ValueError(f"dtype must be torch.float64, float32, int16, float16 or bfloat16, not {dtype!r}")
+    for o in outs:
+        if o is not None and is_tensor(o) and o.dtype != dtype:
+            raise ValueError(f"dtype is {dtype}, out is {o.dtype}")
+    return dtype
 
 
 def _strides(strides):
@@ -509,20 +534,23 @@ class Context:
         self.shape = shape[1:] if x.dim() == 2 else shape
         return x
 
-    def download_tensor(self, out=None, stream=None, which="background"):
-        """The result of the last run into ``out`` (a float32 or float64 tensor of the resident shape, any non-negative
-        strides whose elements do not overlap) or a fresh float64 tensor, written on the engine's stream behind what
-        ``stream`` (default: the current stream of this context's device) has enqueued so far; ``stream`` then waits for it.
-        No host wait. ``which``: "background", "foreground" (resident input - background, from the samples and, after a
-        float64 upload, their remainders) or "mixture"."""
+    def download_tensor(self, out=None, stream=None, which="background", dtype=None):
+        """The result of the last run into ``out`` (a float64, float32, int16, float16 or bfloat16 tensor of the resident
+        shape, any non-negative strides whose elements do not overlap) or a fresh tensor of ``dtype`` (None: float64), written
+        on the engine's stream behind what ``stream`` (default: the current stream of this context's device) has enqueued so
+        far; ``stream`` then waits for it. No host wait. ``which``: "background", "foreground" (resident input - background,
+        from the samples and, after a float64 upload, their remainders) or "mixture". A 16-bit destination takes the float64
+        value rounded once, to nearest, ties to even -- a cast, never a rescale (int16 saturates, NaN is 0); ``dtype`` beside an
+        ``out`` of another dtype is a ValueError."""
         import torch
         codes = which_codes(which)
         if len(codes) != 1:
             raise ValueError("download_tensor writes one signal (repet.separate pairs two calls for \"both\")")
         code = codes[0]
         device = torch.device("cuda", self._device)
+        dtype = emit_dtype(dtype, (out,))
         if out is None:
-            out = torch.empty(self.shape, dtype=torch.float64, device=device)
+            out = torch.empty(self.shape, dtype=dtype, device=device)
         elif not is_device_tensor(out) or out.device != device:
             raise ValueError(f"out must be a tensor on {device}")
         if tuple(out.shape) != tuple(self.shape):
@@ -534,7 +562,7 @@ class Context:
             strides = (out.shape[0] * out.shape[1],) + strides
         if stream is None:
             stream = torch.cuda.current_stream(device)
-        out_code = result_tensor_code(out)
+        out_code = emit_tensor_code(out)
         check(lib().repet_ctx_select_result(self._h, code))
         try:
             check(lib().repet_ctx_download_device_strided(self._h, C.c_void_p(out.data_ptr() or None), out_code,
@@ -1072,20 +1100,22 @@ class OnlineStreams:
         if shape[2] != self._channels:
             raise ValueError(f"chunk has {shape[2]} channels, the streams {self._channels}")
 
-    def _device_outs(self, out, n_emit, codes, shape=None):
-        """The destination tensor(s) of a device call: (tensors, dtype code, list of strides); a pair for "both"."""
+    def _device_outs(self, out, n_emit, codes, shape=None, dtype=None):
+        """The destination tensor(s) of a device call: (tensors, dtype code, list of strides); a pair for "both". Fresh ones
+        are of ``dtype`` (None: float64), which an ``out`` given beside it must have."""
         outs = [out] if len(codes) == 1 else list(out_pair(out))
-        checked = [self._device_out(o, n_emit, shape) for o in outs]
+        dtype = emit_dtype(dtype, outs)
+        checked = [self._device_out(o, n_emit, shape, dtype) for o in outs]
         if len({c[1] for c in checked}) != 1:
             raise ValueError("the two tensors of out have one dtype")
         return [c[0] for c in checked], checked[0][1], [c[2] for c in checked]
 
-    def _device_out(self, out, n_emit, shape=None):
+    def _device_out(self, out, n_emit, shape=None, dtype=None):
         import torch
         device = torch.device("cuda", self._device)
         shape = shape or (self._streams, n_emit, self._channels)
         if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=device)
+            out = torch.empty(shape, dtype=dtype or torch.float64, device=device)
         else:
             if not is_device_tensor(out) or out.device != device:
                 raise ValueError(f"out must be a tensor on {device}")
@@ -1093,16 +1123,19 @@ class OnlineStreams:
                 raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
             if any(st < 0 for st in out.stride()):
                 raise ValueError("out has negative strides")
-        return out, result_tensor_code(out), tuple(int(st) for st in out.stride())
+        return out, emit_tensor_code(out), tuple(int(st) for st in out.stride())
 
-    def push(self, chunk, out=None, which="background"):
+    def push(self, chunk, out=None, which="background", dtype=None):
         """Feed ``(S, n, C)`` more samples; returns the ``(S, n_emit, C)`` samples that became final: their background, or
-        the signal ``which`` names (a pair of arrays / tensors for "both")."""
+        the signal ``which`` names (a pair of arrays / tensors for "both"). Device chunks: ``out`` (float64, float32, int16,
+        float16 or bfloat16) is filled, or a fresh tensor of ``dtype`` (None: float64) returned; see ``repet.online_streams``."""
         codes = which_codes(which)
         if is_device_tensor(chunk):
-            return self._push_device(chunk, out, codes)
+            return self._push_device(chunk, out, codes, dtype)
         if out is not None:
             raise ValueError("out is for device chunks (a host chunk returns a new array)")
+        if dtype is not None:
+            raise ValueError("dtype is for device chunks (a host chunk returns a float64 array)")
         if is_tensor(chunk):
             chunk = chunk.numpy()
         a, code = as_input(chunk)
@@ -1119,13 +1152,15 @@ class OnlineStreams:
         self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
 
-    def last_emission(self, which="foreground", out=None):
+    def last_emission(self, which="foreground", out=None, dtype=None):
         """Another signal ("background", "foreground", "mixture") of exactly the samples the last ``push`` / ``finish`` /
-        ``finish_stream`` emitted: a float64 array, or a tensor on the device (``out``, or a fresh float64 one) when ``out`` is
-        given or the last push was a device chunk. ValueError once a push, finish, restart or release has followed."""
+        ``finish_stream`` emitted: a float64 array, or a tensor on the device (``out``, or a fresh one of ``dtype``, None:
+        float64) when ``out`` is given or the last push was a device chunk. ValueError once a push, finish, restart or release
+        has followed, and for ``dtype`` where the result is a host array."""
         codes = which_codes(which)
         if len(codes) != 1:
             raise ValueError("last_emission returns one signal")
+        self._check_dtype(dtype, out)
         n = C.c_int64()
         # (a call without a destination only asks: its refusal tells a stale emission from one that needs room)
         rc = lib().repet_online_last_emission(self._handle(), codes[0], None, 1 << 62, C.byref(n))
@@ -1134,7 +1169,7 @@ class OnlineStreams:
         shape = self._emitted_shape
         if out is not None or self._last_on_device:
             import torch
-            (out,), out_code, (strides,) = self._device_outs(out, shape[1], codes, shape)
+            (out,), out_code, (strides,) = self._device_outs(out, shape[1], codes, shape, dtype)
             stream = torch.cuda.current_stream(out.device)
             check(lib().repet_online_last_emission_device(self._handle(), codes[0], C.c_void_p(out.data_ptr() or None), out_code,
                                                           _strides(strides), _stream_handle(stream), C.byref(n)))
@@ -1161,7 +1196,12 @@ class OnlineStreams:
         check(lib().repet_online_last_levels(self._handle(), ptr(result), result.size, C.byref(n)))
         return result
 
-    def _push_device(self, x, out, codes):
+    def _check_dtype(self, dtype, out):
+        """``dtype=`` of a call whose result goes to the host unless ``out`` is given or the last push was a device chunk."""
+        if dtype is not None and out is None and not self._last_on_device:
+            raise ValueError("dtype is for device results (after host chunks the result is a float64 array)")
+
+    def _push_device(self, x, out, codes, dtype=None):
         import torch
         if x.device.index != self._device:
             raise ValueError(f"tensor is on {x.device}, the streams on device {self._device}")
@@ -1170,7 +1210,7 @@ class OnlineStreams:
         self._check_shape(tuple(x.shape))
         x, code, shape, strides = tensor_layout(x, batched=True)
         n = shape[1]
-        outs, out_code, out_strides = self._device_outs(out, self.emit_count(n), codes)
+        outs, out_code, out_strides = self._device_outs(out, self.emit_count(n), codes, dtype=dtype)
         out = outs[0] if len(outs) == 1 else tuple(outs)
         stream = torch.cuda.current_stream(x.device)
         written = C.c_int64()
@@ -1271,19 +1311,21 @@ class OnlineStreams:
         check(lib().repet_online_stream_emit_count(self._handle(), self._slot(slot), C.byref(n)))
         return n.value
 
-    def finish_stream(self, slot, out=None, which="background"):
+    def finish_stream(self, slot, out=None, which="background", dtype=None):
         """End the stream of one slot where the handle stands: its ``(n_rest, C)`` tail, as ``finish`` returns for all (a
         tensor on the device when ``out`` is given or the last push was a device chunk; the signal ``which`` names, a pair
         for "both"). The other slots and the handle's counters are untouched and the slot is idle afterwards. ValueError for
-        an idle slot, or for a stream shorter than the buffer (the slot then stays as it was)."""
+        an idle slot, or for a stream shorter than the buffer (the slot then stays as it was). ``dtype``: as ``push``'s, for a
+        result on the device."""
         codes = which_codes(which)
+        self._check_dtype(dtype, out)
         slot = self._slot(slot)
         n_emit = self.stream_emit_count(slot)
         written = C.c_int64()
         shape = (n_emit, self._channels)
         if out is not None or self._last_on_device:
             import torch
-            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, shape)
+            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, shape, dtype)
             stream = torch.cuda.current_stream(outs[0].device)
             _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides((0,) + out_strides[-1]))
             check(lib().repet_online_finish_stream_device(self._handle(), slot, C.c_void_p(outs[0].data_ptr() or None),
@@ -1299,17 +1341,18 @@ class OnlineStreams:
         self._tail_emitted = True
         return results[0] if len(results) == 1 else tuple(results)
 
-    def finish(self, out=None, which="background"):
+    def finish(self, out=None, which="background", dtype=None):
         """End every stream: the remaining samples, ``(S, n_rest, C)`` -- a float64 tensor on the device when ``out`` is given
         or the last push was a device chunk, a NumPy array otherwise; the signal ``which`` names, a pair for "both". ValueError
         if the handle has seen fewer samples than the buffer holds. Every live slot ends with its own length; idle slots
-        return zeros."""
+        return zeros. ``dtype``: as ``push``'s, for a result on the device."""
         codes = which_codes(which)
+        self._check_dtype(dtype, out)
         n_emit = self.emit_count(0, finishing=True)
         written = C.c_int64()
         if out is not None or self._last_on_device:
             import torch
-            outs, out_code, out_strides = self._device_outs(out, n_emit, codes)
+            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, dtype=dtype)
             stream = torch.cuda.current_stream(outs[0].device)
             _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
             check(lib().repet_online_finish_device(self._handle(), C.c_void_p(outs[0].data_ptr() or None), out_code,

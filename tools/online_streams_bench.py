@@ -54,13 +54,20 @@ def stats(lat_s, n, fs):
             "audio_ms_per_push": round(1e3 * n / fs, 2), "pushes_timed": len(lat)}
 
 
-def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None):
+def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None,
+               out_dtype=None):
     import ctypes
     import torch
     from repet import _native
     S, N, ch = xs.shape
     hop = repet.derive_params(fs).step_length
     n = hops * hop
+    # --out-dtype: the hop-sized device pushes fill out= tensors of that torch dtype, allocated once (None: every push returns
+    # a fresh float64 tensor, as ever)
+    as_dtype = {}
+    if out_dtype and device:
+        outs = [torch.empty((S, n, ch), dtype=getattr(torch, out_dtype), device="cuda:0") for _ in range(2 if which == "both" else 1)]
+        as_dtype = {"out": tuple(outs) if which == "both" else outs[0]}
     src = torch.tensor(xs, device="cuda:0") if device else xs
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info(0)[0]
@@ -74,7 +81,7 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
         h.push(src[:, pos:pos + fs // 2], which=which)
         pos += fs // 2
     for _ in range(3):                                         # the per-push workspaces take their size
-        h.push(src[:, pos:pos + n], which=which)
+        h.push(src[:, pos:pos + n], which=which, **as_dtype)
         pos += n
     torch.cuda.synchronize()
     held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
@@ -87,7 +94,7 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
         if gain is not None and gain_every > 0 and k % gain_every == 0:
             h.set_background_gain((gain + 0.01 * (k + 1)) % 1.0)
         t0 = time.perf_counter()
-        h.push(src[:, pos:pos + n], which=which)
+        h.push(src[:, pos:pos + n], which=which, **as_dtype)
         if levels == "device":
             h.last_levels(out=record_dev)
         elif levels == "host":
@@ -301,6 +308,8 @@ def main():
                     help="with --background-gain: set a new gain before every K-th timed push")
     ap.add_argument("--levels", choices=["host", "device"], default=None,
                     help="a levels call after every timed push of the one-handle cases, inside the clock (see above)")
+    ap.add_argument("--out-dtype", choices=["float64", "float32", "int16", "float16", "bfloat16"], default=None,
+                    help="the hop-sized one-handle device pushes fill out= tensors of this dtype (default: fresh float64 results)")
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
@@ -334,6 +343,8 @@ def main():
         result["gain_change_every"] = args.gain_change_every
     if args.levels is not None:
         result["levels"] = args.levels
+    if args.out_dtype is not None:
+        result["out_dtype"] = args.out_dtype
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
@@ -341,7 +352,7 @@ def main():
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
                 case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
-                                       args.gain_change_every, args.levels)
+                                       args.gain_change_every, args.levels, args.out_dtype)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
                                                             gain=args.background_gain, gain_every=args.gain_change_every,
