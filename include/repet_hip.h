@@ -685,6 +685,38 @@ int repet_set_run_background_gain(int device, float gain);
  *                   REPET_ERR_BAD_ARG for a context with no clip. More than 1024 channels: REPET_ERR_LIMIT (all three). */
 int repet_online_last_levels(repet_online* h, double* out, int64_t capacity_doubles, int64_t* n_written);
 int repet_online_last_levels_device(repet_online* h, void* dst, void* signal_stream);
+
+/* (still ABI 4: additions only -- look the symbols up to detect them) A stream that SITS OUT PUSHES. Pushes stay (S, n, C) in and
+ * (S, n_emit, C) out, but a slot may be HELD: for as long as it is, time does not pass for its stream (silence suppression, a
+ * lost or late packet, a caller whose clock lags). With P = samples per slot pushed so far and H the hop:
+ * hold_streams    : the named live slots are held from the handle's sample P on. While a slot is held its share of every
+ *                   pushed chunk is ignored (NaN and infinities included), its share of every emitted signal (background,
+ *                   foreground, mixture, both outputs of one call, every destination dtype) is zero, last_levels counts
+ *                   nothing for it (LIVE = 0), and nothing it holds changes: its rows of the similarity buffer, its last masked
+ *                   spectrum, its held samples and their remainders stay as they are while the other slots' slide.
+ * resume_streams  : the named held slots go on from the handle's sample P as if the pushes in between had not been made.
+ * The guarantee: per slot, the output pieces of the pushes during which the slot was not held, concatenated in order and
+ * followed by its finish_stream / finish tail, equal repet.simonline of the concatenated input pieces of those same pushes,
+ * bit for bit -- whatever the other slots do and whatever the held chunks carried. The output runs one hop behind the input,
+ * so the hop that belongs to the last input before a hold comes out of the first push after the resume; nothing is emitted
+ * twice or dropped. The slot's first frame moves along with the handle (a held push of k hops adds k), so the stream's own
+ * frame numbers, its circular positions and what start_frames counts are what they were.
+ * Rules: hold and resume only where P % H == 0 (REPET_ERR_BAD_ARG otherwise, nothing changes: restart_streams' rule). While at
+ * least one slot is held, a push of n % H != 0 samples is refused with REPET_ERR_BAD_ARG before anything is enqueued, so the
+ * handle stays on the hop grid for as long as a hold lasts. An idle slot cannot be held and a slot out of range is refused
+ * (REPET_ERR_BAD_ARG, nothing changes); holding a held slot and resuming a slot that is not held do nothing. restart_streams,
+ * release_streams, import_stream and finish_stream on a held slot do what they always do and end the hold; finish ends held
+ * slots like the others, each with its own length. export_stream of a held slot returns the stream as it stands (header and
+ * payload unchanged, version 1): imported anywhere it goes on bit for bit. hold and resume make last_emission / last_levels
+ * stale, as restart does. A background gain set for a held slot counts as covered by the emitting calls made meanwhile, as
+ * for an idle slot: the fade elapses unheard and the new gain is in force at the resume.
+ * stream_held     : *held = 1 where `slot` is held, 0 otherwise; answered on the host with no device work.
+ * hold / resume enqueue one small launch per 256 slots named, with no host wait. A handle with no slot held enqueues per push
+ * what it always did; a push with held slots enqueues the same number of launches (another slide kernel, and the background
+ * alone goes through the kernel that emits the other signals). */
+int repet_online_hold_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
+int repet_online_resume_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
+int repet_online_stream_held(repet_online* h, int32_t slot, int32_t* held);
 int repet_ctx_result_levels_device(repet_ctx* ctx, void* dst, void* signal_stream);
 
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,

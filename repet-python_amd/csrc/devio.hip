@@ -663,6 +663,54 @@ __global__ __launch_bounds__(kIoThreads) void online_row_copies(RowCopyArgs a) {
     }
 }
 
+// The slide of a push during which slots are HELD (repet_online_hold_streams): the row copies above, except that a stream whose
+// table entry is kSlotHeld takes element i of a run from `held_delta` floats further on in its source (<= 0: its content stays
+// where it is while the others' moves down) for i >= zero_below, and zero below it -- the source is never read there, so the
+// offset may point in front of the stream's share (the runs in front of a held slot's content while the handle's history
+// grows). Slots of four floats as above; plain vector stores.
+struct SlideDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream, held_delta, zero_below; int32_t src_vec, dst_vec, held_vec; };
+struct SlideArgs { SlideDev part[repet_eng::kRowCopyParts]; int32_t n_streams; const int64_t* slot_start; };
+
+__global__ __launch_bounds__(kIoThreads) void online_slide_held(SlideArgs a) {
+    const SlideDev p = a.part[blockIdx.z];
+    const int64_t slots = p.slots_per_block * p.blocks;
+    for (int64_t b = blockIdx.y; b < a.n_streams; b += gridDim.y) {
+        const bool held = a.slot_start[b] == repet_eng::kSlotHeld;
+        const int64_t zb = held ? p.zero_below : 0;
+        const int64_t base = b * p.src_stream + (held ? p.held_delta : 0);
+        const bool vec = held ? p.held_vec != 0 : p.src_vec != 0;
+        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+            const int64_t blk = q / p.slots_per_block;
+            const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+            if (i0 >= p.len) continue;
+            float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
+            const int64_t so = base + blk * p.src_block + i0;
+            if (i0 + 4 <= p.len && p.dst_vec) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (i0 >= zb) {
+                    if (vec) v = *reinterpret_cast<const float4*>(p.src + so);
+                    else v = make_float4(p.src[so], p.src[so + 1], p.src[so + 2], p.src[so + 3]);
+                } else if (i0 + 4 > zb) {                         // the slot the boundary cuts
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = i0 + k >= zb ? p.src[so + k] : 0.f;
+                    v = make_float4(e[0], e[1], e[2], e[3]);
+                }
+                *reinterpret_cast<float4*>(d) = v;
+            } else {
+                const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
+                for (int64_t k = 0; k < m; ++k) d[k] = i0 + k >= zb ? p.src[so + k] : 0.f;
+            }
+        }
+    }
+}
+
+// Hold / resume: table[slot[i]] = value[i] (kSlotHeld, or the slot's own first frame again). One workgroup.
+struct SlotSetArgs { int64_t* table; int32_t n; unsigned short slot[repet_eng::kSlotResetIds]; int64_t value[repet_eng::kSlotResetIds]; };
+__global__ __launch_bounds__(kIoThreads) void online_slot_set(SlotSetArgs g) {
+    for (int32_t i = threadIdx.x; i < g.n; i += kIoThreads) g.table[g.slot[i]] = g.value[i];
+}
+
 // Slot reset (restart / release of slots of the streaming handle): workgroups (x, slot of the list, part) write the part's
 // runs of zeros into that slot's share of the buffers, and one thread per slot its new first frame.
 struct ZeroPartDev { float* dst; int64_t len, slots_per_block, blocks, dst_block, dst_stream; int32_t vec; };
@@ -823,6 +871,51 @@ hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_stream
     }
     online_row_copies<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
+}
+
+hipError_t launch_slide_held(const RowCopy* parts, const HeldShift* shifts, int n_parts, int32_t n_streams, hipStream_t s,
+                             const int64_t* slot_start) {
+    if (n_parts <= 0 || n_parts > kRowCopyParts || n_streams <= 0 || !slot_start || !shifts) return hipErrorInvalidValue;
+    SlideArgs a{};
+    a.n_streams = n_streams;
+    a.slot_start = slot_start;
+    int64_t most = 1;
+    auto aligned = [](const float* p, int64_t b1, int64_t b2) {
+        return !(reinterpret_cast<uintptr_t>(p) & 15) && !(b1 & 3) && !(b2 & 3);
+    };
+    for (int k = 0; k < kRowCopyParts; ++k) {
+        SlideDev& d = a.part[k];
+        d = SlideDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;      // an empty part: no slots
+        const RowCopy& p = parts[k];
+        const HeldShift& h = shifts[k];
+        if (!p.src || !p.dst || p.row_len != 0 || h.delta > 0 || h.zero_below < 0) return hipErrorInvalidValue;
+        d.src = p.src; d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
+        d.src_block = p.src_block; d.dst_block = p.dst_block; d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
+        d.held_delta = h.delta; d.zero_below = std::min(h.zero_below, p.len);
+        d.dst_vec = aligned(p.dst, p.dst_block, p.dst_stream) ? 1 : 0;
+        d.src_vec = aligned(p.src, p.src_block, p.src_stream) ? 1 : 0;
+        d.held_vec = d.src_vec && !(h.delta & 3) ? 1 : 0;
+        most = std::max(most, d.slots_per_block * d.blocks);
+    }
+    online_slide_held<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// (the slots of one call are distinct: two threads never write one entry)
+hipError_t launch_slot_set(int64_t* slot_start, const int32_t* slots, const int64_t* values, int32_t n_slots, hipStream_t s) {
+    if (n_slots <= 0) return hipSuccess;
+    if (!slot_start || !slots || !values) return hipErrorInvalidValue;
+    SlotSetArgs g{};
+    g.table = slot_start;
+    for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
+        g.n = std::min<int32_t>(kSlotResetIds, n_slots - first);
+        for (int32_t k = 0; k < g.n; ++k) { g.slot[k] = (unsigned short)slots[first + k]; g.value[k] = values[first + k]; }
+        online_slot_set<<<1, kIoThreads, 0, s>>>(g);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* slots, int32_t n_slots, const ZeroPart* parts,

@@ -286,6 +286,16 @@ constexpr int kSlotResetIds = 256;
 constexpr int64_t kSlotIdle = (int64_t)1 << 60;
 hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* slots, int32_t n_slots, const ZeroPart* parts,
                              int n_parts, hipStream_t s);
+//   hold     a HELD slot (repet_online_hold_streams) reads kSlotHeld in the table: past kSlotIdle, so every kernel that is given
+//            the table treats it as idle, and the slide can tell the two apart. set: slot_start[slots[k]] = values[k] (kSlotHeld,
+//            or the slot's own first frame at the resume), one launch per kSlotResetIds slots. slide: launch_row_copies with
+//            copying parts only, where a held stream's element i of a run comes from shifts[part].delta (<= 0) floats further
+//            on in the source for i >= zero_below and is zero below it (the source is not read there); one launch
+constexpr int64_t kSlotHeld = kSlotIdle + 1;
+struct HeldShift { int64_t delta, zero_below; };
+hipError_t launch_slot_set(int64_t* slot_start, const int32_t* slots, const int64_t* values, int32_t n_slots, hipStream_t s);
+hipError_t launch_slide_held(const RowCopy* parts, const HeldShift* shifts, int n_parts, int32_t n_streams, hipStream_t s,
+                             const int64_t* slot_start);
 //   export   ONE slot's share of the handle's buffers gathered into a dense payload, one launch: up to kRowCopyParts parts of
 //            `blocks` runs of `len` floats; element i of a run is src[src_off + blk * src_block + i] for i >= zero_below and
 //            zero below it (a run right-aligned on what the source holds: src_off may be negative, src null with zero_below = len)

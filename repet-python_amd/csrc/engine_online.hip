@@ -16,6 +16,8 @@ using namespace repet_eng;
 // later than the handle's (repet_online_restart_streams), end earlier (repet_online_finish_stream) or be absent
 // (repet_online_release_streams). All of that is one number per slot, the frame at which its stream began, which the peak
 // picking, the mask and the row zeroing behind the STFT read on the device; the launch shapes are the handle's.
+// A slot may also sit out pushes (repet_online_hold_streams): held, it reads as idle on the device while its share of the buffers
+// stays where it is (launch_slide_held) and its first frame moves along with the handle on the host.
 // =====================================================================================================
 struct repet_online {
     repet_ctx* ctx = nullptr;       // stream, tables, tile cache, scratch buffers
@@ -29,6 +31,12 @@ struct repet_online {
     DevBuf slot_start;
     bool slots_on = false;
     int64_t latest_start = 0, n_idle = 0;
+    // Held slots (repet_online_hold_streams): time does not pass for them. start[s] stays the slot's TRUE first frame and moves
+    // along with the handle -- a held push of k hops adds k, on the host alone -- while the device table reads kSlotHeld for the
+    // length of the hold: every kernel that is given the table takes the slot for idle, the slide (launch_slide_held) leaves
+    // its share of the buffers where it is, and the resume writes start[s] back. One table, and no launch for the bump.
+    std::vector<unsigned char> held;
+    int64_t n_held = 0;
     int C = 0, W = 0, H = 0, F = 0, FS = 0, B = 0, Hh = 0, LP = 0;
     // start_frames (repet_online_set_start_frames; B: the reference): a stream's frames M-1 .. B-2 are separated on its buffer as
     // far as it has filled (peaks.h: row_columns). The handle's, for every slot and restart; the launches are the same for any M.
@@ -180,12 +188,16 @@ int online_ensure_pending(repet_online* o, int64_t n) {
 // fixed sequence of launches, whatever S and C.
 // slot >= 0 (finish_stream): the same sequence on that slot alone (a batch of one at the slot's offsets), with no slide and
 // no counter touched: the handle goes on as if the call had not been made.
-int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1) {
+// n_app: the samples per stream this push appended. While slots are held the slide has to know: their share of the pending
+// buffers ends n_app samples before the others' does, and their first frames move on by n_app / H.
+int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1, int64_t n_app = 0) {
     repet_ctx* c = o->ctx;
     o->em = repet_online::Emission{true, o->pcur, slot < 0 ? o->S : 1, slot, o->pend_hist, std::max<int64_t>(n_emit, 0), o->emitted};
     o->tail_valid = false;
     o->em.g0 = o->em.g1 = o->gcur;
-    if (n_new <= 0 && n_emit <= 0) return REPET_OK;
+    // (a held push that completes no frame -- a handle younger than a window -- still slides the samples: the held slots' stay)
+    const bool held_push = slot < 0 && o->n_held > 0 && n_app > 0;
+    if (n_new <= 0 && n_emit <= 0 && !held_push) return REPET_OK;
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, o->W, &tb));
     RP_TRY(online_ensure_windows(o, n_new));
@@ -217,7 +229,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         const int64_t Tpad = round_up(Tw, kTile);
         // (same launch) the new rows of frames before a slot's own first frame -- the frame that straddles a restart, every
         // frame of an idle slot -- hold nothing of that slot's stream: zero in Vn, V and X, whatever the chunk carried
-        const bool early = starts && (o->n_idle > 0 || o->latest_start > o->frames_done);
+        const bool early = starts && (o->n_idle > 0 || o->n_held > 0 || o->latest_start > o->frames_done);
         const int64_t hv = o->hist_valid * o->FS, nn = n_new * o->FS;
         const RowCopy zero[4] = {
             {nullptr, Vnb + Tw * o->FS, (Tpad - Tw) * o->FS, 1, 0, 0, 0, vns},
@@ -286,7 +298,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         if (all) { std::fill(o->gain_dirty.begin(), o->gain_dirty.end(), 0); o->n_dirty = 0; }
         else { o->gain_dirty[(size_t)slot] = 0; o->n_dirty -= 1; }
     }
-    if (n_new > 0 && all) {
+    if ((n_new > 0 || held_push) && all) {
         // slide, one launch for every stream and channel: the last min(Hh, Tw) rows of V and Vn and the last masked spectrum
         // (overlap-add tail of the next hop) become the history of the other window; the samples of the window's frames
         // (h2 hops of history) and the unconsumed ones move to the front of the other pending buffer
@@ -298,20 +310,48 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         const int64_t keep = std::min<int64_t>(h2 * (int64_t)o->H, o->pend_hist + consumed);
         const int64_t from = o->pend_hist + consumed - keep;
         const int64_t FS = o->FS;
+        const int64_t rows = n_new > 0 ? 1 : 0;                 // (no new frame: the windows stay, only the samples move)
         const RowCopy parts[kRowCopyParts] = {
-            {o->Vn[o->cur].as<float>() + src * FS, o->Vn[nxt].as<float>() + dst * FS, h2 * FS, 1, 0, 0, vns, vns},
-            {o->V[o->cur].as<float>() + src * FS, o->V[nxt].as<float>() + dst * FS, h2 * FS, o->C, plane, plane, spec, spec},
-            {o->X[o->cur].as<float>() + 2 * (r0 + Tw - 1) * FS, o->X[nxt].as<float>() + 2 * (o->Hh - 1) * FS, 2 * FS, o->C,
+            {o->Vn[o->cur].as<float>() + src * FS, o->Vn[nxt].as<float>() + dst * FS, rows * h2 * FS, 1, 0, 0, vns, vns},
+            {o->V[o->cur].as<float>() + src * FS, o->V[nxt].as<float>() + dst * FS, rows * h2 * FS, o->C, plane, plane, spec, spec},
+            {o->X[o->cur].as<float>() + 2 * (r0 + Tw - 1) * FS, o->X[nxt].as<float>() + 2 * (o->Hh - 1) * FS, rows * 2 * FS, o->C,
              2 * plane, 2 * plane, 2 * spec, 2 * spec},
             {o->pend[o->pcur].as<float>() + from * o->C, o->pend[o->pcur ^ 1].as<float>(), (keep + left) * o->C, 1, 0, 0, pst, pst},
             {o->pend_lo[o->pcur].as<float>() + from * o->C, o->pend_lo[o->pcur ^ 1].as<float>(), (keep + left) * o->C, 1, 0, 0, pst, pst}};
-        HIP_TRY(launch_row_copies(parts, kRowCopyParts, S, c->stream));
-        o->cur = nxt;
-        o->hist_valid = h2;
+        if (o->n_held > 0) {
+            // A held slot's share stays as it is, right-aligned like everybody's: its history rows [Hh - hist_valid, Hh) of the
+            // current window become the same rows of the other one, the h2 - hist_valid rows in front of them (a history that
+            // still grows) zero; its held samples [0, pend_hist + pend_count - n_app) -- what it held before this push's chunk
+            // was appended behind them -- end where the others' end, behind `shift` zeros. Relative to the parts' sources:
+            //   rows     (src - dst) = n_new rows back: reads rows [Hh - hist_valid, Hh) of the current window
+            //   spectrum row r0 + Tw - 1 -> row Hh - 1, n_new rows back (nothing to keep while the handle has no history)
+            //   samples  from + shift = n_app samples back: reads [0, pend_hist + pend_count - n_app) of the stream's share
+            // and never in front of a share: below zero_below the source is not read.
+            const int64_t grow = h2 - o->hist_valid, before = o->pend_count - n_app;
+            const int64_t shift = keep + left - o->pend_hist - before;
+            if (grow < 0 || before < 0 || shift < 0 || from + shift != n_app)
+                return fail(REPET_ERR_LIMIT, "online: a held stream does not fit the slide");
+            const HeldShift shifts[kRowCopyParts] = {{-n_new * FS, grow * FS}, {-n_new * FS, grow * FS},
+                                                     {-2 * n_new * FS, o->hist_valid > 0 ? 0 : 2 * FS},
+                                                     {-n_app * o->C, shift * o->C}, {-n_app * o->C, shift * o->C}};
+            HIP_TRY(launch_slide_held(parts, shifts, kRowCopyParts, S, c->stream, o->slot_start.as<int64_t>()));
+        } else {
+            HIP_TRY(launch_row_copies(parts, kRowCopyParts, S, c->stream));
+        }
+        if (n_new > 0) {
+            o->cur = nxt;
+            o->hist_valid = h2;
+            o->frames_done += n_new;
+        }
         o->pcur ^= 1;
         o->pend_hist = keep;
         o->pend_count = left;
-        o->frames_done += n_new;
+        if (held_push) {
+            // time did not pass for the held slots: their first frames move on with the handle
+            const int64_t hops = n_app / o->H;
+            for (size_t s = 0; s < o->held.size(); ++s)
+                if (o->held[s]) { o->start[s] += hops; o->latest_start = std::max(o->latest_start, o->start[s]); }
+        }
     }
     if (all) o->emitted += n_emit;
     return REPET_OK;
@@ -357,7 +397,8 @@ int online_emit(repet_online* o, const EmitDst* dsts, int n_dsts, int dtype) {
     const repet_online::Emission& em = o->em;
     if (!em.valid) return fail(REPET_ERR_BAD_ARG, "online: no emission to return");
     if ((int64_t)em.S * em.n * o->C <= 0 || n_dsts <= 0) return REPET_OK;
-    if (n_dsts == 1 && dsts[0].which == REPET_OUT_BACKGROUND) {
+    // (a held slot's last masked spectrum still rings into the first hop of a push: its background is zeroed with the table, below)
+    if (n_dsts == 1 && dsts[0].which == REPET_OUT_BACKGROUND && !(o->n_held > 0 && em.slot < 0)) {
         HIP_TRY(launch_stream_egress(o->outf.as<float>(), em.S, em.n, o->C, dsts[0].p, dtype, dsts[0].strides, c->stream));
         return REPET_OK;
     }
@@ -527,6 +568,9 @@ int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t
         int64_t& st = o->start[(size_t)slots[k]];
         o->n_idle += (first_frame == kSlotIdle ? 1 : 0) - (st == kSlotIdle ? 1 : 0);
         st = first_frame;
+        unsigned char& hd = o->held[(size_t)slots[k]];            // (the launch wrote the table: a hold ends here)
+        o->n_held -= hd;
+        hd = 0;
     }
     if (first_frame != kSlotIdle) o->latest_start = std::max(o->latest_start, first_frame);
     o->slots_on = true;
@@ -723,9 +767,41 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     int64_t& st = o->start[(size_t)slot];
     if (st == kSlotIdle) o->n_idle -= 1;
     st = first;
+    o->n_held -= o->held[(size_t)slot];                         // (the launch wrote the table: a hold ends here)
+    o->held[(size_t)slot] = 0;
     o->latest_start = std::max(o->latest_start, first);
     o->slots_on = true;
     return REPET_OK;
+}
+
+// Hold (on = true) or resume the named slots: one small launch writes kSlotHeld, or the slots' own first frames again, into the
+// device table. Slots that are there already are skipped; with none left nothing is enqueued and nothing changes. Enqueues only.
+int online_hold_slots(repet_online* o, const int32_t* slots, int32_t n, bool on) {
+    repet_ctx* c = o->ctx;
+    std::vector<int32_t> ids;
+    std::vector<int64_t> values;
+    for (int32_t k = 0; k < n; ++k) {
+        unsigned char& hd = o->held[(size_t)slots[k]];
+        if ((hd != 0) == on) continue;
+        hd = on ? 1 : 0;
+        o->n_held += on ? 1 : -1;
+        ids.push_back(slots[k]);
+        values.push_back(on ? kSlotHeld : o->start[(size_t)slots[k]]);
+    }
+    if (ids.empty()) return REPET_OK;
+    o->em.valid = false; o->tail_valid = false;
+    o->slots_on = true;
+    HIP_TRY(launch_slot_set(o->slot_start.as<int64_t>(), ids.data(), values.data(), (int32_t)ids.size(), c->stream));
+    return REPET_OK;
+}
+
+// finish and finish_stream end the holds of the slots they end
+int online_resume_all(repet_online* o) {
+    if (o->n_held == 0) return REPET_OK;
+    std::vector<int32_t> ids;
+    for (int32_t s = 0; s < o->S; ++s)
+        if (o->held[(size_t)s]) ids.push_back(s);
+    return online_hold_slots(o, ids.data(), (int32_t)ids.size(), false);
 }
 
 }  // namespace repet_eng
@@ -918,6 +994,32 @@ int repet_online_release_streams(repet_online* o, const int32_t* slots, int32_t 
     return online_reset_slots(o, slots, n, kSlotIdle);
 }
 
+static const char* const kHoldGrid = "online: a stream can only be held or resumed on a hop boundary (samples pushed % step_length == 0)";
+static const char* const kHeldPush = "online: while a stream is held a push is a whole number of hops (n % step_length == 0)";
+
+int repet_online_hold_streams(repet_online* o, const int32_t* slots, int32_t n) {
+    RP_TRY(online_check_slots(o, slots, n));
+    if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, kHoldGrid);
+    for (int32_t k = 0; k < n; ++k)
+        if (o->start[(size_t)slots[k]] == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
+    DeviceGuard guard(o->ctx->device);
+    return online_hold_slots(o, slots, n, true);
+}
+
+int repet_online_resume_streams(repet_online* o, const int32_t* slots, int32_t n) {
+    RP_TRY(online_check_slots(o, slots, n));
+    if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, kHoldGrid);
+    DeviceGuard guard(o->ctx->device);
+    return online_hold_slots(o, slots, n, false);
+}
+
+int repet_online_stream_held(repet_online* o, int32_t slot, int32_t* held) {
+    if (!o || !held) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    *held = o->held[(size_t)slot] ? 1 : 0;
+    return REPET_OK;
+}
+
 int repet_online_stream_emit_count(repet_online* o, int32_t slot, int64_t* n_emit) {
     int64_t n_new = 0;
     return online_plan_slot(o, slot, &n_new, n_emit);
@@ -933,6 +1035,7 @@ int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64
     RP_TRY(online_check_also_host(o, n_emit, out, 1));
     DeviceGuard guard(o->ctx->device);
     o->slots_on = true;
+    RP_TRY(online_hold_slots(o, &slot, 1, false));              // a held slot ends as it stands
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_host_result(o, n_emit, out, 1));
     bool kept = false;
@@ -956,6 +1059,7 @@ int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, 
     DeviceGuard guard(c->device);
     o->slots_on = true;
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_hold_slots(o, &slot, 1, false));              // a held slot ends as it stands
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
     bool kept = false;
@@ -1052,6 +1156,7 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
     o->FS = (int)round_up(o->F, kFreqAlign); o->B = p->buffer_frames; o->M = o->B; o->Hh = o->B - 1; o->LP = (int)round_up(o->B, 64);
     o->max_push = max_push_samples;
     o->start.assign((size_t)n_streams, 0);
+    o->held.assign((size_t)n_streams, 0);
     {   // every slot's stream begins with the handle's until a restart or release says otherwise
         DeviceGuard guard(o->ctx->device);
         hipError_t e = o->slot_start.ensure((size_t)n_streams * sizeof(int64_t));
@@ -1107,6 +1212,7 @@ int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int
     if (!o || !n_written || (n > 0 && !audio)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    if (o->n_held > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     *n_written = 0;
@@ -1126,7 +1232,7 @@ int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int
         const int64_t dense[3] = {n * o->C, o->C, 1};
         RP_TRY(online_append(o, o->staging.p, dtype, n, dense));
     }
-    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_process(o, n_new, n_emit, -1, n));
     RP_TRY(online_host_result(o, n_emit, out));
     *n_written = n_emit;
     return REPET_OK;
@@ -1144,6 +1250,7 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
     if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    if (o->n_held > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
     RP_TRY(check_strides(src_strides));
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
@@ -1153,7 +1260,7 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
     DeviceGuard guard(c->device);
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
     RP_TRY(online_append(o, src, dtype, n, src_strides));
-    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(online_process(o, n_new, n_emit, -1, n));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
     *n_written = n_emit;
     return REPET_OK;
@@ -1169,6 +1276,7 @@ int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, 
     RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
     RP_TRY(online_check_also_host(o, n_emit, out));
+    RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
     RP_TRY(online_process(o, n_new, n_emit));
     RP_TRY(online_host_result(o, n_emit, out));
     *n_written = n_emit;
@@ -1191,6 +1299,7 @@ int repet_online_finish_device(repet_online* o, void* dst, int dst_dtype, const 
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
     RP_TRY(online_process(o, n_new, n_emit));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
     *n_written = n_emit;

@@ -356,6 +356,24 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     on which nothing was pushed holds no sample yet, the state one hop that was never emitted: the first push after such
     an import emits that hop, which is a hop of zeros in front of every other slot's own output.)
 
+    A stream can sit out pushes -- silence suppression, a lost or late packet, a caller whose clock lags: ``hold(slots)`` holds
+    live slots from the handle's current sample on and ``resume(slots)`` lets them go on (``held(slot)`` tells). While a slot
+    is held, time does not pass for its stream: its share of every chunk is ignored, NaN and inf included; its share of every
+    emitted signal -- background, foreground, mixture, both of "both", every dtype -- is zero; ``last_levels`` counts nothing
+    for it; and its similarity buffer, its overlap-add tail and its held samples stay as they are while the other slots'
+    slide. Per slot, the output pieces of the pushes during which it was not held, in order, then its ``finish_stream`` /
+    ``finish`` tail, equal ``simonline`` of the input pieces of those same pushes, bit for bit, whatever the other slots do
+    and whatever the held chunks carried. The output runs one hop behind the input, so the hop that belongs to the last
+    input before a hold comes out of the first push after the resume; nothing is emitted twice or dropped, and
+    ``stream_samples(slot)`` counts only what the stream itself was fed. Both calls need ``samples_pushed`` on the hop grid,
+    and while any slot is held a push must be a whole number of hops (ValueError before anything runs, nothing changes).
+    ValueError for an idle slot or a slot out of range; holding a held slot or resuming one that is not held does nothing.
+    ``restart``, ``release``, ``import_stream`` and ``finish_stream`` on a held slot do what they always do and end the hold;
+    ``finish`` ends held slots like the others; ``export_stream`` of a held slot returns the stream as it stands. Both make
+    ``last_emission`` / ``last_levels`` stale, as ``restart`` does. A gain set during a hold is in force, its fade elapsed
+    unheard, at the resume. One small launch each, no host wait; a handle with no slot held pushes at the launches it always
+    cost, and so does a push with held slots (``repet.online``, one stream, needs neither: not pushing is its hold).
+
     ``start_length`` (seconds; None: ``buffer_length``, the reference) lets every slot separate before its 10-s buffer has
     filled, from its own frame ``start_frames - 1`` on (see :func:`online`; the ``start_frames`` property), after every
     ``restart`` too: each life then equals the one-stream handle's output with the same ``start_length``, a stream of

@@ -235,6 +235,9 @@ _SIGNATURES = {
     "repet_online_last_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_ctx_result_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_emit_dtype_supported": (C.c_int, [C.c_int]),
+    "repet_online_hold_streams": (C.c_int, [_P, _P, C.c_int32]),
+    "repet_online_resume_streams": (C.c_int, [_P, _P, C.c_int32]),
+    "repet_online_stream_held": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1050,7 +1053,11 @@ class OnlineStreams:
     ``which`` of ``push`` / ``finish`` / ``finish_stream`` selects the signal of the emitted samples: "background" (default),
     "foreground" (input - background), "mixture" (the input, aligned with the emission) or "both": the pair (background,
     foreground) from one pass, with ``out=`` a pair of tensors. ``last_emission(which)`` returns another signal of the samples
-    the last of these calls emitted."""
+    the last of these calls emitted.
+
+    ``hold(slots)`` lets live slots sit out the pushes that follow and ``resume(slots)`` lets them go on: a held slot ignores
+    its share of the chunks, emits zeros and keeps all it holds, so its stream goes on bit for bit as if those pushes had not
+    been made (``repet.online_streams``)."""
 
     def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0, start_frames=None):
         self._h = C.c_void_p()
@@ -1069,6 +1076,7 @@ class OnlineStreams:
         self._emitted_shape = (self._streams, 0, self._channels)
         self._tail_emitted = False                    # the last emitting call was a finish_stream: one slot's record
         self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
+        self._held = set()                            # slots that sit out the pushes: their beginnings move along with them
 
     @property
     def shape(self):
@@ -1146,11 +1154,16 @@ class OnlineStreams:
         written = C.c_int64()
         _select_output(self._handle(), codes, ptr(results[-1]))
         check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(results[0]), n_emit, C.byref(written)))
-        self._pushed += n
+        self._count_push(n)
         self._last_on_device = False
         self._emitted_shape = results[0].shape
         self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
+
+    def _count_push(self, n):
+        self._pushed += n
+        for s in self._held:                          # time does not pass for a held slot
+            self._begun[s] += n
 
     def last_emission(self, which="foreground", out=None, dtype=None):
         """Another signal ("background", "foreground", "mixture") of exactly the samples the last ``push`` / ``finish`` /
@@ -1222,7 +1235,7 @@ class OnlineStreams:
         # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
         # recorded on it, the caching allocator hands its block out again only once the ingest has read it
         x.record_stream(stream)
-        self._pushed += n
+        self._count_push(n)
         self._last_on_device = True
         self._tail_emitted = False
         return out
@@ -1233,7 +1246,8 @@ class OnlineStreams:
         return self._pushed
 
     def stream_samples(self, slot):
-        """Samples of the stream that lives in ``slot`` so far (None: the slot is idle)."""
+        """Samples of the stream that lives in ``slot`` so far (None: the slot is idle): what the stream itself was fed, without
+        the pushes it sat out while it was held."""
         begun = self._begun[self._slot(slot)]
         return None if begun is None else self._pushed - begun
 
@@ -1272,6 +1286,30 @@ class OnlineStreams:
         check(lib().repet_online_restart_streams(self._handle(), arr, len(slots)))
         for s in slots:
             self._begun[s] = self._pushed
+            self._held.discard(s)
+
+    def hold(self, slots):
+        """The named live slots sit out the pushes that follow: their share of every chunk is ignored (NaN included), their
+        share of everything emitted is zero, and all they hold stays as it is. Only where ``samples_pushed`` is a multiple of
+        the hop, and while a slot is held every push is a whole number of hops (ValueError otherwise, nothing changes).
+        ValueError for an idle slot; a slot that is held already stays held. ``last_emission`` becomes stale. No host wait."""
+        slots, arr = self._slot_list(slots)
+        check(lib().repet_online_hold_streams(self._handle(), arr, len(slots)))
+        self._held.update(slots)
+
+    def resume(self, slots):
+        """The named held slots go on from here as if the pushes since their ``hold`` had not been made; a slot that is not
+        held is left alone. Only where ``samples_pushed`` is a multiple of the hop. ``last_emission`` becomes stale. No host
+        wait."""
+        slots, arr = self._slot_list(slots)
+        check(lib().repet_online_resume_streams(self._handle(), arr, len(slots)))
+        self._held.difference_update(slots)
+
+    def held(self, slot):
+        """True while ``slot`` is held."""
+        out = C.c_int32()
+        check(lib().repet_online_stream_held(self._handle(), self._slot(slot), C.byref(out)))
+        return bool(out.value)
 
     def release(self, slots):
         """The named slots become idle without output: they ignore their share of the chunks and emit zeros."""
@@ -1279,6 +1317,7 @@ class OnlineStreams:
         check(lib().repet_online_release_streams(self._handle(), arr, len(slots)))
         for s in slots:
             self._begun[s] = None
+            self._held.discard(s)
 
     @property
     def stream_state_nbytes(self):
@@ -1304,6 +1343,7 @@ class OnlineStreams:
         slot = self._slot(slot)
         fields = _import_state(self._handle(), slot, state, self._device)
         self._begun[slot] = self._pushed - fields["length_samples"]
+        self._held.discard(slot)
 
     def stream_emit_count(self, slot):
         """Samples ``finish_stream(slot)`` will return. ValueError for an idle slot or a stream shorter than the buffer."""
@@ -1332,12 +1372,14 @@ class OnlineStreams:
                                                           out_code, (C.c_int64 * 2)(*out_strides[0]), _stream_handle(stream),
                                                           C.byref(written)))
             self._begun[slot] = None
+            self._held.discard(slot)
             self._tail_emitted = True
             return outs[0] if len(outs) == 1 else tuple(outs)
         results = [np.empty(shape, dtype=np.float64) for _ in codes]
         _select_output(self._handle(), codes, ptr(results[-1]))
         check(lib().repet_online_finish_stream(self._handle(), slot, ptr(results[0]), n_emit, C.byref(written)))
         self._begun[slot] = None
+        self._held.discard(slot)
         self._tail_emitted = True
         return results[0] if len(results) == 1 else tuple(results)
 
@@ -1359,10 +1401,12 @@ class OnlineStreams:
                                                    _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
             self._emitted_shape = tuple(outs[0].shape)
             self._tail_emitted = False
+            self._held.clear()
             return outs[0] if len(outs) == 1 else tuple(outs)
         results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
         _select_output(self._handle(), codes, ptr(results[-1]))
         check(lib().repet_online_finish_streams(self._handle(), ptr(results[0]), n_emit, C.byref(written)))
+        self._held.clear()
         self._emitted_shape = results[0].shape
         self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)

@@ -19,6 +19,11 @@ In the same run, what a caller without these calls would do to keep a stream's b
 hops, here as one device push into a restarted one-slot handle (the cheapest form: on the S-slot handle the replay would be
 pushed in lockstep through every slot).
 
+``--hold K``: instead, slots that sit out pushes. One handle of S slots past its warm-up, device chunks of one hop into a
+preallocated ``out``, each push timed with a synchronize: first on the handle as it is (no ``hold`` was ever called), then, four
+times over, ``hold`` of K slots spread over the handle, pushes with them held, ``resume``, pushes with nobody held; ``hold`` and
+``resume`` are each timed as one call plus a synchronize.
+
 ``--start-length SECONDS``: the one-handle cases on handles opened with ``start_length`` (separation from that age on, before
 the 10-s buffer has filled). The streams are then pushed only half a second past the start length, so the timed pushes are
 those of YOUNG frames, each decided on the frames heard so far; keep ``--timed`` x hops inside the buffer's first 10 s.
@@ -287,8 +292,62 @@ def migrate_one_handle(xs, fs, timed, warm_s):
             "replay_buffer_one_slot_ms_median": ms(replay), "replay_hops": B, "calls_timed": len(export)}
 
 
+def hold_one_handle(xs, fs, n_held, timed, warm_s):
+    import torch
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    src = torch.tensor(xs, device="cuda:0")
+    h = repet.online_streams(fs, ch, S, max_push_samples=hop)
+    pos = 0
+    while pos < warm_s * fs // hop * hop:
+        n = min(fs // 2 // hop * hop, warm_s * fs // hop * hop - pos)
+        h.push(src[:, pos:pos + n])
+        pos += n
+    out = torch.empty((S, hop, ch), dtype=torch.float64, device="cuda:0")
+    for _ in range(3):
+        h.push(src[:, pos:pos + hop], out=out)
+        pos += hop
+    torch.cuda.synchronize()
+
+    def pushes(count):
+        nonlocal pos
+        lat = []
+        while len(lat) < count and pos + hop <= N:
+            t0 = time.perf_counter()
+            h.push(src[:, pos:pos + hop], out=out)
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t0)
+            pos += hop
+        return lat
+
+    def call(fn, slots):
+        t0 = time.perf_counter()
+        fn(slots)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    never = pushes(timed)                                      # no hold call was ever made on this handle
+    slots = list(range(0, S, max(1, S // n_held)))[:n_held]    # (spread over the handle)
+    h.hold(slots)
+    pushes(3)                                                  # (the held slide has run once before the clock starts)
+    h.resume(slots)
+    held, hold, resume, after = [], [], [], []
+    for _ in range(4):
+        hold.append(call(h.hold, slots))
+        held += pushes(timed // 4)
+        resume.append(call(h.resume, slots))
+        after += pushes(timed // 4)
+    h.close()
+    ms = lambda v: round(float(np.median(np.array(v) * 1e3)), 3) if v else None
+    return {"hop_ms": round(1e3 * hop / fs, 2), "slots_held": len(slots), "push_ms_median_no_hold_call": ms(never),
+            "push_ms_p95_no_hold_call": round(float(np.percentile(np.array(never) * 1e3, 95)), 3),
+            "push_ms_median_slots_held": ms(held), "push_ms_median_after_resume": ms(after),
+            "hold_ms_median": ms(hold), "resume_ms_median": ms(resume), "pushes_timed": len(never)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--hold", type=int, default=0, metavar="K", help="the hold leg: pushes of one hop with K of the slots held")
     ap.add_argument("--migrate", type=int, default=0, help="1: the migrate leg (export_stream / import_stream per call)")
     ap.add_argument("--streams", default="1,8,64,256")
     ap.add_argument("--hops", default="1,4")
@@ -313,6 +372,14 @@ def main():
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
+    if args.hold > 0:
+        hop = repet.derive_params(fs).step_length
+        result = {"fs": fs, "channels": ch, "cases": []}
+        for S in streams:
+            xs = stream_signals(S, warm_s + 1 + (3 * args.timed + 16) * hop / fs, fs, ch)
+            result["cases"].append(dict({"streams": S}, **hold_one_handle(xs, fs, min(args.hold, S), args.timed, warm_s)))
+        print(json.dumps(result, indent=1))
+        return
     if args.migrate > 0:
         hop = repet.derive_params(fs).step_length
         result = {"fs": fs, "channels": ch, "cases": []}
