@@ -686,6 +686,53 @@ int repet_set_run_background_gain(int device, float gain);
 int repet_online_last_levels(repet_online* h, double* out, int64_t capacity_doubles, int64_t* n_written);
 int repet_online_last_levels_device(repet_online* h, void* dst, void* signal_stream);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) The SPECTRA of the frames the last push completed, whole
+ * or in bands: what a push decides is a time-frequency decision, and for every new frame of every slot the handle still holds
+ * the mixture magnitudes and the masked spectrum until the next push writes there. For a frame j of a stream, channel c and bin
+ * f in [0, F), F = window_length / 2 + 1, these are the reference's own quantities (repet.py:834-898), in fp32:
+ *   REPET_OUT_MIXTURE     |audio_stft[f, j]|, as the forward kernel stored it, bit for bit
+ *   REPET_OUT_BACKGROUND  mask[f] * mixture: the magnitude of the masked spectrum, by the device function the forward kernel
+ *                         forms the mixture with -- so background == mixture to the bit wherever the mask is 1 (the high-pass
+ *                         bins 1 .. cutoff_bins)
+ *   REPET_OUT_FOREGROUND  mixture - background, and 0 where a rounding makes that negative; NaN where either is NaN
+ * The frames covered are the n_frames the last push / finish completed: handle frames [first, first + n_frames), frame k
+ * beginning at the caller's pushed sample k * step_length (first is counted in the caller's pushes, also on a handle whose
+ * epoch an import of an older stream has moved). Per slot: a frame before the slot's own first frame -- the frame that straddles
+ * a restart, every frame of an idle or held slot -- is ZERO in all three signals, whatever the chunk carried, NaN included; a
+ * warm-up frame (the slot's own frame < start_frames - 1) has the mixture as it is, background 0 and foreground == mixture, as
+ * in the time domain; finish's zero-padded last frame is a frame like any other.
+ * Computed ON DEMAND from a small host record of the push: a push that nobody asks about enqueues what it always did. The record
+ * is valid after a push or finish and STALE after the next push, finish, finish_stream, restart, release, import, hold or resume
+ * (REPET_ERR_BAD_ARG): the frames of a finish_stream tail are not served. A push that completed no frame has n_frames = 0, and
+ * the calls below then write nothing and launch nothing.
+ * repet_online_last_frame_range          : first and n_frames, from the host record: no device work.
+ * repet_online_last_frames               : host form, `which` as dense fp32 out[S][n_frames][C][F] through the pinned buffer
+ *                   (one launch, one copy, one wait). out == NULL (or a capacity too small) only asks: REPET_ERR_BAD_ARG with
+ *                   *n_written = the floats needed.
+ * repet_online_last_frames_device        : the same values at `dst` on the handle's device, element (s, j, c, f) at
+ *                   dst_strides[0] * s + [1] * j + [2] * c + [3] * f floats (non-negative; the elements must not overlap),
+ *                   ordered behind `signal_stream` by events as last_emission_device is; one launch, no host wait.
+ * repet_online_last_band_energies        : the same values reduced to bands: edges[0 .. n_bands] ascending (equal neighbours: an
+ *                   empty band, 0) with 0 <= edges[k] <= F and 1 <= n_bands <= REPET_MAX_BANDS; band k is the float64 sum of
+ *                   (double)m * (double)m over bins [edges[k], edges[k + 1]) of the fp32 value m above. Dense float64
+ *                   out[S][n_frames][C][n_bands]; out == NULL or a capacity too small only asks, as above.
+ * repet_online_last_band_energies_device : the same at `dst` (dense float64) on the handle's device, ordered as above.
+ *                   The edges travel in the kernel's arguments: no copy, no host wait. One launch, which reads the handle's
+ *                   rows itself (the full frames need not be written first). DETERMINISTIC: a lane adds its own bins in bin
+ *                   order, a wave folds by __shfl_xor, no floating-point atomics -- two calls on one push, the host and the
+ *                   device form, return identical bits. NaN and inf propagate as plain IEEE sums.
+ * Errors, before anything is enqueued and with nothing changed: REPET_ERR_BAD_ARG for an unknown `which`, edges that are null,
+ * descending or outside [0, F], n_bands < 1, a null destination or overlapping strides in the device forms, or a stale record;
+ * REPET_ERR_LIMIT for more than REPET_MAX_BANDS bands. */
+#define REPET_MAX_BANDS 128
+int repet_online_last_frame_range(repet_online* h, int64_t* first_frame, int64_t* n_frames);
+int repet_online_last_frames(repet_online* h, int which, float* out, int64_t capacity_floats, int64_t* n_written);
+int repet_online_last_frames_device(repet_online* h, int which, void* dst, const int64_t dst_strides[4], void* signal_stream);
+int repet_online_last_band_energies(repet_online* h, int which, const int32_t* edges, int32_t n_bands,
+                                    double* out, int64_t capacity_doubles, int64_t* n_written);
+int repet_online_last_band_energies_device(repet_online* h, int which, const int32_t* edges, int32_t n_bands,
+                                           void* dst, void* signal_stream);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) A stream that SITS OUT PUSHES. Pushes stay (S, n, C) in and
  * (S, n_emit, C) out, but a slot may be HELD: for as long as it is, time does not pass for its stream (silence suppression, a
  * lost or late packet, a caller whose clock lags). With P = samples per slot pushed so far and H the hop:

@@ -336,6 +336,18 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
 hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s);
 hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int32_t n_slots, hipStream_t s);
 hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s);
+//   frames   (frames.hip) the spectra of the frames a push completed, read from the window it wrote: V / X at the first of the
+//            n_frames rows of slot 0's plane 0 (`plane` / `spec` elements between channel planes / slots), handle frame frame0
+//            in that row, `warm` = start_frames - 1, slot_start nullable (every slot's stream is the handle's). frames: fp32
+//            `which` of every (slot, frame, channel, bin < F) into dst at element strides [4]; bands: the float64 sums of
+//            their squares over bins [edges[k], edges[k + 1]), dense [n_streams][n_frames][C][n_bands], the edges in the
+//            kernel arguments. One launch each, none for n_frames == 0; hipErrorInvalidValue for edges out of order or range
+struct FrameArgs {
+    const float* V; const float2* X; int64_t plane, spec; int32_t FS, F, C, which; int64_t n_frames, frame0, warm;
+    const int64_t* slot_start;
+};
+hipError_t launch_online_frames(const FrameArgs& a, int32_t n_streams, float* dst, const int64_t strides[4], hipStream_t s);
+hipError_t launch_online_bands(const FrameArgs& a, int32_t n_streams, const int32_t* edges, int32_t n_bands, double* dst, hipStream_t s);
 // bytes of an element of a REPET_* dtype (0: not a dtype), and the refusal of a destination dtype the emission does not write
 int dtype_bytes(int dtype);
 int check_emit_dtype(int dtype);

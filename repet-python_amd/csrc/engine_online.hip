@@ -83,6 +83,12 @@ struct repet_online {
     DevBuf levels;
     bool levels_on = false, tail_valid = false;
     double* tail_levels() const { return levels.as<double>() + (int64_t)S * C * REPET_LEVEL_FIELDS; }
+    // Frames (repet_online_last_frames* / last_band_energies*): where the spectra of the frames the last push or finish completed
+    // lie. After the push's slide flipped `cur` they are rows [row0, row0 + n) of every slot's planes of X[win] / V[win], the
+    // window that was current DURING the push; the first of them is handle frame `first`. Nothing writes that window before
+    // the next push. Host record only: a handle that is never asked runs nothing for it. Every call that changes the slot
+    // table ends its validity with the emission's, so the table at query time is the table of the push.
+    struct Frames { bool valid = false; int win = 0, S = 0; int64_t row0 = 0, n = 0, first = 0; } fr;
     std::vector<float> gain;
     std::vector<unsigned char> gain_dirty;
     int64_t n_dirty = 0;
@@ -195,6 +201,8 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
     o->em = repet_online::Emission{true, o->pcur, slot < 0 ? o->S : 1, slot, o->pend_hist, std::max<int64_t>(n_emit, 0), o->emitted};
     o->tail_valid = false;
     o->em.g0 = o->em.g1 = o->gcur;
+    // (the new frames' rows follow the history in the current window; a finish_stream tail's frames are not served)
+    o->fr = repet_online::Frames{slot < 0, o->cur, o->S, o->Hh, std::max<int64_t>(n_new, 0), o->frames_done};
     // (a held push that completes no frame -- a handle younger than a window -- still slides the samples: the held slots' stay)
     const bool held_push = slot < 0 && o->n_held > 0 && n_app > 0;
     if (n_new <= 0 && n_emit <= 0 && !held_push) return REPET_OK;
@@ -380,7 +388,7 @@ int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new
 // the chunk's samples (already where `src` says, device memory) appended to every stream's pending buffer
 int online_append(repet_online* o, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
     if (n <= 0) return REPET_OK;
-    o->em.valid = false; o->tail_valid = false;
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
     RP_TRY(online_ensure_pending(o, n));
     hipError_t e = launch_stream_append(src, dtype, o->S, n, o->C, strides, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
                                         o->pend_stride(), (o->pend_hist + o->pend_count) * o->C, o->ctx->stream);
@@ -549,7 +557,7 @@ int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
 // spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
 int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t first_frame) {
     repet_ctx* c = o->ctx;
-    o->em.valid = false; o->tail_valid = false;
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
     if (n <= 0) return REPET_OK;
     const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), held = (o->pend_hist + o->pend_count) * o->C;
     ZeroPart parts[kRowCopyParts] = {};
@@ -747,7 +755,7 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     repet_ctx* c = o->ctx;
     const StateLayout l = state_layout(o);
     const int64_t delta = std::max<int64_t>(0, l.m + h.hist_rows - o->total_in / o->H);
-    o->em.valid = false; o->tail_valid = false;
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
     RP_TRY(online_ensure_windows(o, std::max<int64_t>(o->max_push / o->H + 1, o->W / o->H + 1)));
     RP_TRY(online_ensure_pending(o, delta * o->H));
     if (delta > 0) RP_TRY(online_shift_epoch(o, delta));
@@ -789,7 +797,7 @@ int online_hold_slots(repet_online* o, const int32_t* slots, int32_t n, bool on)
         values.push_back(on ? kSlotHeld : o->start[(size_t)slots[k]]);
     }
     if (ids.empty()) return REPET_OK;
-    o->em.valid = false; o->tail_valid = false;
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
     o->slots_on = true;
     HIP_TRY(launch_slot_set(o->slot_start.as<int64_t>(), ids.data(), values.data(), (int32_t)ids.size(), c->stream));
     return REPET_OK;
@@ -919,6 +927,149 @@ int repet_online_last_levels_device(repet_online* o, void* dst, void* signal_str
         HIP_TRY(hipMemcpyAsync(dst, o->tail_levels(), (size_t)o->C * REPET_LEVEL_FIELDS * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     else
         RP_TRY(online_levels(o, static_cast<double*>(dst)));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+static const char* const kStaleFrames =
+    "online: the last frames are stale (a push, finish, finish_stream, restart, release, import, hold or resume came after them)";
+
+// what the frame kernels read of the last push (o->fr), from the host record alone
+static int online_frame_args(const repet_online* o, int which, FrameArgs* a) {
+    const repet_online::Frames& fr = o->fr;
+    *a = FrameArgs{};
+    if (fr.n <= 0) return REPET_OK;
+    if (fr.row0 < 0 || fr.row0 + fr.n > o->rows_cap || fr.S != o->S) return fail(REPET_ERR_LIMIT, "online: the last frames are not in the window");
+    const int64_t at = fr.row0 * o->FS;
+    a->V = o->V[fr.win].as<float>() + at; a->X = o->X[fr.win].as<float2>() + at;
+    a->plane = o->plane(); a->spec = o->spec_stride(); a->FS = o->FS; a->F = o->F; a->C = o->C; a->which = which;
+    a->n_frames = fr.n; a->frame0 = fr.first; a->warm = o->M - 1;
+    a->slot_start = o->slots_on ? o->slot_start.as<int64_t>() : nullptr;
+    return REPET_OK;
+}
+
+static int check_band_edges(const repet_online* o, const int32_t* edges, int32_t n_bands) {
+    if (n_bands > REPET_MAX_BANDS) return fail(REPET_ERR_LIMIT, "online: at most REPET_MAX_BANDS (128) bands");
+    if (n_bands < 1 || !edges) return fail(REPET_ERR_BAD_ARG, "online: at least one band and its edges");
+    for (int32_t k = 0; k <= n_bands; ++k)
+        if (edges[k] < 0 || edges[k] > o->F || (k > 0 && edges[k] < edges[k - 1]))
+            return fail(REPET_ERR_BAD_ARG, "online: band edges are ascending bins in [0, window_length / 2 + 1]");
+    return REPET_OK;
+}
+
+// a destination [S][n][C][F] at element strides: non-negative, and no two elements at one address (check_no_overlap's rule)
+static int check_frame_strides(const int64_t* strides, const int64_t size[4]) {
+    if (!strides) return fail(REPET_ERR_BAD_ARG, "strides is null");
+    int order[4] = {0, 1, 2, 3};
+    for (int k = 0; k < 4; ++k)
+        if (strides[k] < 0) return fail(REPET_ERR_BAD_ARG, "negative stride (make the tensor contiguous first)");
+    std::sort(order, order + 4, [&](int a, int b) { return strides[a] < strides[b]; });
+    int64_t span = 0;
+    for (int k : order) {
+        if (size[k] <= 1) continue;
+        if (strides[k] <= span) return fail(REPET_ERR_BAD_ARG, "the destination's elements overlap (an expanded or aliasing view)");
+        span += strides[k] * (size[k] - 1);
+    }
+    return REPET_OK;
+}
+
+int repet_online_last_frame_range(repet_online* o, int64_t* first_frame, int64_t* n_frames) {
+    if (!o || !first_frame || !n_frames) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
+    *first_frame = o->fr.first - o->epoch;
+    *n_frames = o->fr.n;
+    return REPET_OK;
+}
+
+// the host forms: the result dense in out64, one copy into the pinned buffer, one wait
+static int online_frames_to_host(repet_online* o, void* out, size_t bytes) {
+    repet_ctx* c = o->ctx;
+    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, bytes));
+    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(out, o->host_out, bytes);
+    return REPET_OK;
+}
+
+int repet_online_last_frames(repet_online* o, int which, float* out, int64_t capacity_floats, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    RP_TRY(check_which(which));
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
+    const int64_t count = (int64_t)o->S * o->fr.n * o->C * o->F;
+    if (count == 0) return REPET_OK;
+    *n_written = count;
+    if (!out || capacity_floats < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    *n_written = 0;
+    FrameArgs a;
+    RP_TRY(online_frame_args(o, which, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    HIP_TRY(o->out64.ensure((size_t)count * sizeof(float)));
+    const int64_t dense[4] = {o->fr.n * o->C * o->F, (int64_t)o->C * o->F, o->F, 1};
+    HIP_TRY(launch_online_frames(a, o->S, o->out64.as<float>(), dense, c->stream));
+    RP_TRY(online_frames_to_host(o, out, (size_t)count * sizeof(float)));
+    *n_written = count;
+    return REPET_OK;
+}
+
+int repet_online_last_frames_device(repet_online* o, int which, void* dst, const int64_t dst_strides[4], void* signal_stream) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    RP_TRY(check_which(which));
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
+    const int64_t size[4] = {o->S, o->fr.n, o->C, o->F};
+    RP_TRY(check_frame_strides(dst_strides, size));
+    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    if (o->fr.n <= 0) return REPET_OK;
+    FrameArgs a;
+    RP_TRY(online_frame_args(o, which, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    HIP_TRY(launch_online_frames(a, o->S, static_cast<float*>(dst), dst_strides, c->stream));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+int repet_online_last_band_energies(repet_online* o, int which, const int32_t* edges, int32_t n_bands, double* out,
+                                    int64_t capacity_doubles, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    RP_TRY(check_which(which));
+    RP_TRY(check_band_edges(o, edges, n_bands));
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
+    const int64_t count = (int64_t)o->S * o->fr.n * o->C * n_bands;
+    if (count == 0) return REPET_OK;
+    *n_written = count;
+    if (!out || capacity_doubles < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    *n_written = 0;
+    FrameArgs a;
+    RP_TRY(online_frame_args(o, which, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
+    HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, o->out64.as<double>(), c->stream));
+    RP_TRY(online_frames_to_host(o, out, (size_t)count * sizeof(double)));
+    *n_written = count;
+    return REPET_OK;
+}
+
+int repet_online_last_band_energies_device(repet_online* o, int which, const int32_t* edges, int32_t n_bands, void* dst,
+                                           void* signal_stream) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    RP_TRY(check_which(which));
+    RP_TRY(check_band_edges(o, edges, n_bands));
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
+    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    if (o->fr.n <= 0) return REPET_OK;
+    FrameArgs a;
+    RP_TRY(online_frame_args(o, which, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, static_cast<double*>(dst), c->stream));
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
     return REPET_OK;

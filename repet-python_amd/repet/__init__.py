@@ -266,6 +266,10 @@ def online(sampling_frequency, number_channels, start_length=None):
     ``set_background_gain(gain)`` keeps ``gain`` (in [0, 1]) of the background in the foreground, ``x - float32(1 - gain) *
     background``, fading to it over at most one hop; ``background_gain()`` reads it back: see :func:`online_streams`.
 
+    ``last_frames(which="foreground", bands=None, out=None)`` returns the spectra of the frames the last ``push`` / ``finish``
+    completed (``last_frame_range`` tells which), float32 magnitudes ``(T, number_channels, window_length / 2 + 1)`` or, with
+    ``bands``, float64 band energies ``(T, number_channels, n_bands)``: see :func:`online_streams`.
+
     ``start_length`` (seconds; None: ``buffer_length``, the reference): separate before the buffer has filled. The reference
     writes nothing until its buffer holds ``buffer_length`` (10 s) of frames; with ``start_frames = min(buffer_frames, max(1,
     round(start_length * fs / step_length)))`` (the ``start_frames`` property) a stream's frame ``j >= start_frames - 1`` is
@@ -341,6 +345,21 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     slot's samples, on a handle that ``last_levels`` has been called on before; ValueError otherwise, and once a push,
     finish, restart or release has followed.
 
+    ``last_frames(which="foreground", bands=None, out=None)`` hands out what a push decided in the time-frequency plane, for the
+    ``T`` frames the last ``push`` / ``finish`` completed (``last_frame_range`` is ``(first, T)``; frame ``k`` begins at pushed
+    sample ``k * step_length``): the float32 magnitudes ``(number_streams, T, number_channels, window_length / 2 + 1)`` of the
+    mixture (``|STFT|``, as the handle stored it), the background (the magnitude of the masked spectrum: equal to the mixture
+    bit for bit on the high-pass bins ``1 .. cutoff_bins``) or the foreground (mixture - background, never negative) -- what a
+    recogniser or a VAD would otherwise re-STFT the foreground for. With ``bands`` (``n_bands + 1`` ascending bin edges, at
+    most 128 bands, e.g. :func:`band_edges`) the result is the float64 energy per band, ``(number_streams, T,
+    number_channels, n_bands)``: a spectrum display or a per-band meter, summed on the device in a fixed order (identical bits
+    from repeated calls). A NumPy array, or a tensor on the device (``out``, any strides for the frames, or a fresh one) when
+    ``out`` is a tensor or the last push was a device chunk, then with no host wait. Idle and held slots and the frame that
+    straddles a ``restart`` are zero, whatever the chunk carried; a warm-up frame has background 0 and foreground = mixture.
+    One launch on demand: a push that nobody asks about costs what it always cost. ValueError once a push, finish,
+    finish_stream, restart, release, import, hold or resume has followed (the frames of a ``finish_stream`` tail are not
+    served). ``repet.online`` has the same calls without the stream axis.
+
     A stream can move between handles: ``export_stream(slot, device=False)`` returns a snapshot of the slot's state as a
     :class:`StreamState` -- ``header``, a small ``bytes`` value the host knows at once, and ``payload``, a ``numpy.uint8``
     array or (``device=True``, no host wait) a ``torch.uint8`` tensor on the handle's device, ``stream_state_nbytes`` bytes
@@ -385,6 +404,29 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     params = derive_params(sampling_frequency)
     return _native.OnlineStreams(params, number_channels, number_streams, _device, max_push_samples or 0,
                                  _native.start_frames_for(params, sampling_frequency, start_length))
+
+
+def band_edges(sampling_frequency, number_bands, f_min=0.0, f_max=None):
+    """Bin edges for ``last_frames(bands=...)`` of a live handle at ``sampling_frequency``: ``number_bands + 1`` ascending
+    integers from ``round(f_min * W / fs)`` to ``round(f_max * W / fs) + 1`` (``W`` the window length; ``f_max`` None: ``fs /
+    2``, so that the defaults cover every bin), equally spaced on the mel scale ``2595 * log10(1 + f / 700)``, rounded to bins
+    and forced non-decreasing (at low frequencies neighbouring edges may coincide: an empty band, energy 0). A convenience,
+    nothing more: any ascending edges will do."""
+    fs = float(sampling_frequency)
+    n = int(number_bands)
+    if n < 1:
+        raise ValueError("at least one band")
+    f_max = fs / 2 if f_max is None else float(f_max)
+    f_min = float(f_min)
+    if not 0 <= f_min <= f_max <= fs / 2:
+        raise ValueError("0 <= f_min <= f_max <= sampling_frequency / 2")
+    w = _window_length(sampling_frequency)
+    lo, hi = int(round(f_min * w / fs)), int(round(f_max * w / fs)) + 1
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
+    f = 700.0 * (10.0 ** (np.linspace(mel(lo * fs / w), mel(hi * fs / w), n + 1) / 2595.0) - 1.0)
+    edges = np.clip(np.round(f * w / fs).astype(np.int64), lo, hi)
+    edges[0], edges[-1] = lo, hi
+    return [int(e) for e in np.maximum.accumulate(edges)]
 
 
 def run_batch(algo, audio_signals, sampling_frequency, n_devices=1, transport="host", device=None, depth=None):

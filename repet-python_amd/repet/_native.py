@@ -238,6 +238,11 @@ _SIGNATURES = {
     "repet_online_hold_streams": (C.c_int, [_P, _P, C.c_int32]),
     "repet_online_resume_streams": (C.c_int, [_P, _P, C.c_int32]),
     "repet_online_stream_held": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
+    "repet_online_last_frame_range": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "repet_online_last_frames": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_last_frames_device": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "repet_online_last_band_energies": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_last_band_energies_device": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -948,6 +953,92 @@ def _import_state(handle, slot, state, device):
     return fields
 
 
+def _frame_range(handle):
+    first, count = C.c_int64(), C.c_int64()
+    check(lib().repet_online_last_frame_range(handle, C.byref(first), C.byref(count)))
+    return first.value, count.value
+
+
+def band_edge_array(bands):
+    """``bands=`` of ``last_frames`` as the int32 array the library takes: ``n_bands + 1`` integers. ValueError for anything
+    else; their order and range are the library's to check."""
+    try:
+        edges = np.asarray(bands)
+        if edges.ndim != 1 or edges.size < 2 or edges.dtype.kind not in "iu":
+            raise ValueError
+        wide = edges.astype(np.int64)
+        if (np.abs(wide) > 2 ** 31 - 1).any():
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("bands is a sequence of n_bands + 1 integer bin edges") from None
+    return np.ascontiguousarray(wide.astype(np.int32))
+
+
+def _ask_frames(handle, code, edges):
+    """An empty result (a push that completed no frame): the library still refuses a bad ``which`` or ``bands`` and a stale
+    record, and launches nothing."""
+    n = C.c_int64()
+    if edges is None:
+        check(lib().repet_online_last_frames(handle, code, None, 0, C.byref(n)))
+    else:
+        check(lib().repet_online_last_band_energies(handle, code, ptr(edges), edges.size - 1, None, 0, C.byref(n)))
+
+
+def _last_frames(handle, device, lead, bins, which, bands, out, on_device):
+    """``last_frames`` of a live handle whose result has the leading dimensions ``lead`` -- (S,) or () -- before (T, C, F) or
+    (T, C, n_bands): see ``OnlineStreams.last_frames``. ``lead`` plus the channel count come as ``(lead, C)``."""
+    lead, channels = lead
+    codes = which_codes(which)
+    if len(codes) != 1:
+        raise ValueError("last_frames returns one signal")
+    edges = None if bands is None else band_edge_array(bands)
+    _, count = _frame_range(handle)
+    last = bins if edges is None else edges.size - 1
+    shape = tuple(lead) + (count, channels, last)
+    np_dtype = np.float32 if edges is None else np.float64
+    if out is not None and not is_tensor(out):
+        if not isinstance(out, np.ndarray) or out.dtype != np_dtype or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {np.dtype(np_dtype).name} array of shape {shape}, or a tensor on the device")
+    if is_tensor(out) or (out is None and on_device):
+        import torch
+        dev = torch.device("cuda", device)
+        t_dtype = torch.float32 if edges is None else torch.float64
+        if out is None:
+            out = torch.empty(shape, dtype=t_dtype, device=dev)
+        else:
+            if not is_device_tensor(out) or out.device != dev:
+                raise ValueError(f"out must be a tensor on {dev}")
+            if out.dtype != t_dtype:
+                raise ValueError(f"the result is {t_dtype}, out is {out.dtype}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
+            if any(st < 0 for st in out.stride()):
+                raise ValueError("out has negative strides")
+            if edges is not None and not out.is_contiguous():
+                raise ValueError("out must be dense (contiguous)")
+        stream = torch.cuda.current_stream(dev)
+        if not out.numel():
+            _ask_frames(handle, codes[0], edges)
+        elif edges is not None:
+            check(lib().repet_online_last_band_energies_device(handle, codes[0], ptr(edges), edges.size - 1, C.c_void_p(out.data_ptr()),
+                                                               _stream_handle(stream)))
+        else:
+            strides = tuple(int(st) for st in out.stride())
+            strides = (0,) * (4 - len(strides)) + strides
+            check(lib().repet_online_last_frames_device(handle, codes[0], C.c_void_p(out.data_ptr()), (C.c_int64 * 4)(*strides),
+                                                        _stream_handle(stream)))
+        return out
+    result = np.empty(shape, dtype=np_dtype) if out is None else out
+    n = C.c_int64()
+    if not result.size:
+        _ask_frames(handle, codes[0], edges)
+    elif edges is not None:
+        check(lib().repet_online_last_band_energies(handle, codes[0], ptr(edges), edges.size - 1, ptr(result), result.size, C.byref(n)))
+    else:
+        check(lib().repet_online_last_frames(handle, codes[0], ptr(result), result.size, C.byref(n)))
+    return result
+
+
 class OnlineSeparator:
     """Streaming online REPET-SIM: ``push(chunk)`` returns the background samples that became final,
     ``finish()`` the rest; the concatenation equals ``repet.simonline`` of the whole signal. ``which`` ("background",
@@ -958,6 +1049,7 @@ class OnlineSeparator:
         self._h = C.c_void_p()
         self._channels = int(n_channels)
         self._window = int(params.window_length)
+        self._bins = self._window // 2 + 1
         self._device = int(device)
         if lib().repet_device_count() < 1:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
@@ -1005,6 +1097,19 @@ class OnlineSeparator:
         n = C.c_int64()
         check(lib().repet_online_last_levels(self._h, ptr(result), result.size, C.byref(n)))
         return result
+
+    @property
+    def last_frame_range(self):
+        """``(first, count)``: the frames the last ``push`` / ``finish`` completed; frame ``k`` begins at pushed sample ``k *
+        step_length``. ValueError once another call has followed; see ``repet.online_streams``."""
+        return _frame_range(self._h)
+
+    def last_frames(self, which="foreground", bands=None, out=None):
+        """The spectra of the frames the last ``push`` / ``finish`` completed: float32 ``(T, C, F)`` magnitudes of ``which``
+        ("background", "foreground", "mixture"), or with ``bands`` (``n_bands + 1`` ascending bin edges) their float64 band
+        energies ``(T, C, n_bands)``. A NumPy array, or ``out`` (an array of that shape, or a tensor on the device: no host
+        wait). See ``repet.online_streams``. ValueError once another call has followed."""
+        return _last_frames(self._h, self._device, ((), self._channels), self._bins, which, bands, out, False)
 
     def set_background_gain(self, gain):
         """Keep ``gain`` (in [0, 1]) of the background in the foreground from the next emission on, see ``repet.online``."""
@@ -1063,6 +1168,7 @@ class OnlineStreams:
         self._h = C.c_void_p()
         self._channels = int(n_channels)
         self._streams = int(n_streams)
+        self._bins = int(params.window_length) // 2 + 1
         self._device = int(device)
         self._last_on_device = False
         if self._streams < 1 or self._channels < 1:
@@ -1208,6 +1314,25 @@ class OnlineStreams:
         n = C.c_int64()
         check(lib().repet_online_last_levels(self._handle(), ptr(result), result.size, C.byref(n)))
         return result
+
+    @property
+    def last_frame_range(self):
+        """``(first, count)``: the frames the last ``push`` / ``finish`` completed, handle frames ``[first, first + count)``;
+        frame ``k`` begins at pushed sample ``k * step_length``. From the host's record, no device work. ValueError once a
+        push, finish, finish_stream, restart, release, import, hold or resume has followed."""
+        return _frame_range(self._handle())
+
+    def last_frames(self, which="foreground", bands=None, out=None):
+        """The spectra of the ``T`` frames the last ``push`` / ``finish`` completed (``last_frame_range``): float32 ``(S, T, C,
+        F)`` magnitudes of ``which`` ("background", "foreground", "mixture"), ``F = window_length / 2 + 1``; with ``bands``
+        (a sequence of ``n_bands + 1`` ascending bin edges in [0, F], at most 128 bands, see ``repet.band_edges``) the float64
+        sums of their squares per band, ``(S, T, C, n_bands)``. A NumPy array (``out``: a C-contiguous array of that shape and
+        dtype), or a tensor on the handle's device -- ``out``, with any non-overlapping strides for the frames and dense for
+        the bands, or a fresh one -- when ``out`` is a tensor or the last push was a device chunk: then with no host wait.
+        One launch on demand; see ``repet.online_streams``. ValueError for a wrong ``which``, ``bands`` or ``out`` (before
+        anything runs) and once a push, finish, finish_stream, restart, release, import, hold or resume has followed."""
+        return _last_frames(self._handle(), self._device, ((self._streams,), self._channels), self._bins, which, bands, out,
+                            self._last_on_device)
 
     def _check_dtype(self, dtype, out):
         """``dtype=`` of a call whose result goes to the host unless ``out`` is given or the last push was a device chunk."""

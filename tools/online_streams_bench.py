@@ -34,7 +34,11 @@ one of the steady state with gains set. ``--gain-change-every K`` (with it): a n
 
 ``--levels host|device``: the one-handle cases with a levels call after every timed push, inside the clock: ``device`` is
 ``last_levels()`` into a preallocated tensor on the device (no host wait of its own), ``host`` the C ABI's host form (one copy
-through the pinned buffer and one wait), whatever the chunks are."""
+through the pinned buffer and one wait), whatever the chunks are.
+
+``--frames frames|bands``: the one-handle cases with a ``last_frames`` call after every timed push, inside the clock, into a
+preallocated tensor on the device (no host wait of its own): ``frames`` the foreground magnitudes ``(S, T, C, F)``, ``bands`` the
+foreground's energies in the 32 bands of ``repet.band_edges(fs, 32)``."""
 import argparse
 import json
 import sys
@@ -60,7 +64,7 @@ def stats(lat_s, n, fs):
 
 
 def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None,
-               out_dtype=None):
+               out_dtype=None, frames=None):
     import ctypes
     import torch
     from repet import _native
@@ -92,6 +96,10 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
     held = free0 - torch.cuda.mem_get_info(0)[0]            # the handle's device memory (and the results torch keeps cached)
     record_dev = torch.empty((S, ch, len(repet.LEVELS)), dtype=torch.float64, device="cuda:0") if levels == "device" else None
     record_host, written = np.empty((S, ch, len(repet.LEVELS))), ctypes.c_int64()
+    edges = repet.band_edges(fs, 32) if frames == "bands" else None
+    if frames:
+        last = 32 if frames == "bands" else repet.derive_params(fs).window_length // 2 + 1
+        spectra = torch.empty((S, hops, ch, last), dtype=torch.float64 if frames == "bands" else torch.float32, device="cuda:0")
     lat = []
     for k in range(timed):
         if pos + n > N:
@@ -105,6 +113,8 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
         elif levels == "host":
             _native.check(_native.lib().repet_online_last_levels(h._handle(), _native.ptr(record_host), record_host.size,
                                                                  ctypes.byref(written)))
+        if frames:
+            h.last_frames("foreground", bands=edges, out=spectra)
         if device:
             torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
@@ -367,6 +377,8 @@ def main():
                     help="with --background-gain: set a new gain before every K-th timed push")
     ap.add_argument("--levels", choices=["host", "device"], default=None,
                     help="a levels call after every timed push of the one-handle cases, inside the clock (see above)")
+    ap.add_argument("--frames", choices=["frames", "bands"], default=None,
+                    help="a last_frames call after every timed push of the one-handle cases, inside the clock (see above)")
     ap.add_argument("--out-dtype", choices=["float64", "float32", "int16", "float16", "bfloat16"], default=None,
                     help="the hop-sized one-handle device pushes fill out= tensors of this dtype (default: fresh float64 results)")
     args = ap.parse_args()
@@ -412,6 +424,8 @@ def main():
         result["levels"] = args.levels
     if args.out_dtype is not None:
         result["out_dtype"] = args.out_dtype
+    if args.frames is not None:
+        result["frames"] = args.frames
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
@@ -419,7 +433,7 @@ def main():
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
                 case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
-                                       args.gain_change_every, args.levels, args.out_dtype)
+                                       args.gain_change_every, args.levels, args.out_dtype, args.frames)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
                                                             gain=args.background_gain, gain_every=args.gain_change_every,
