@@ -644,6 +644,40 @@ int repet_online_background_gain(repet_online* h, int32_t slot, float* gain_out)
 int repet_ctx_set_background_gain(repet_ctx* ctx, float gain);
 int repet_set_run_background_gain(int device, float gain);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) A share of the background kept BAND BY BAND, on the live
+ * handles. Every slot has a table g[k], k < F = window_length / 2 + 1, every entry in [0, 1], all zero by default. With
+ *     a[k] = (float)(1.0 - (double)g[k])
+ * the SHAPED background of a slot is the handle's overlap-add inverse STFT with the masked spectrum Y_j of frame j taken as
+ * a_j[k] * Y_j[k] (one fp32 rounding per product, bin N - k with bin k's factor; the same window sum and trimming), and the
+ * foreground is fma(-a_s, shaped_bg, x) in float64, a_s the slot's scalar gain above with its fade: the two gains multiply.
+ * The background, the mixture, last_frames in all three signals, the MIX / BG / LIVE / NONFINITE level fields, every counter
+ * and the exported state do not change by a bit; FG_ENERGY / FG_PEAK measure the shaped foreground; idle and held slots and the
+ * samples before a slot's stream began stay zero. g = 1 on every bin returns the input for finite input.
+ * WHICH TABLE A FRAME GETS: frame j of a slot is shaped, once and whole, with the table the slot had when the push or finish
+ * that completed frame j was enqueued. A frame overlap-adds into two hops, so a change cross-fades through the analysis window
+ * over one frame; the frame carried over from the call before keeps the table it was completed under. A set on a held slot
+ * applies to the frames completed after its resume. A frame that arrives with import_stream is shaped with the importing
+ * slot's table. The table is the SLOT's: it survives restart_streams, release_streams, finish_stream and import_stream, and it
+ * is not part of an exported state.
+ * repet_online_set_background_band_gains : the tables of slots[k], k < n_slots (slots == NULL: every slot, n_slots ignored),
+ *                   replaced whole. edges: n_bands + 1 ascending bins in [0, F], 1 <= n_bands <= F; band b is the bins
+ *                   [edges[b], edges[b + 1]) and takes gains[r * n_bands + b], bins outside every band take 0. edges == NULL:
+ *                   one gain per bin, n_bands == F. gains_rows is 1 (row r = 0 for every slot named) or the number of slots
+ *                   named (r = k; a slot named twice takes the last row). REPET_ERR_BAD_ARG, before anything is enqueued and
+ *                   with nothing changed, for a gain that is NaN or outside [0, 1], bad edges, a slot out of range or a wrong
+ *                   size; REPET_ERR_LIMIT on a handle whose window_length exceeds 4096. At any time, on or off the hop grid:
+ *                   one small launch, no host wait, and the last emission stays valid (it was shaped already).
+ *                   COST: a handle on which no table was ever set enqueues what it always did. While any slot's table -- as
+ *                   set, or as still in force for a frame -- is not all zero, every emitting call enqueues one inverse-STFT
+ *                   launch more, and each of the first two frame-completing calls after a set one small launch that brings
+ *                   the tables up to date. Two frame-completing pushes after every table was cleared the handle is back to
+ *                   what it enqueued before.
+ * repet_online_background_band_gains     : the F gains last set for `slot` (zeros before any set) into out (capacity >= F
+ *                   floats), from the host's copy: no device work. */
+int repet_online_set_background_band_gains(repet_online* h, const int32_t* slots, int32_t n_slots, const int32_t* edges, int32_t n_bands,
+                                           const float* gains, int32_t gains_rows);
+int repet_online_background_band_gains(repet_online* h, int32_t slot, float* out, int32_t capacity);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) LEVELS of what a live handle or a tensor call emitted:
  * how loud the input, the background and the foreground of every slot were, whether anything repeating was found, whether a
  * stream clips or carries NaN -- reduced on the device, so that a server need not pull three signals to the host per hop. For

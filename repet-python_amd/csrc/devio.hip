@@ -276,6 +276,7 @@ struct EmitArgs {
     int32_t n_channels, n_out;
     EmitOut out[2];
     const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
+    const float* bg_fg;             // (nullable) the background the FOREGROUND is formed from, laid out like bg: a live handle's shaped one
 };
 
 // The per-sample arithmetic of an emission, shared by the kernels that write it (emit_body) and that measure it (devio_levels):
@@ -287,12 +288,13 @@ __device__ inline double emit_gain_at(double at, double ac, int64_t j1, int64_t 
 
 // the three float64 signals of one sample: h + l (or h, infinite), the fp32 background widened, x - bg or fma(-ak, bg, x); a
 // sample that is not live is zero in all three by a select
-__device__ inline void emit_sample(float h, float l, float b, bool live, bool gain, double ak, double& mix, double& bgv, double& fgv) {
+// (bf: the background the foreground takes, b itself but for a live handle's shaped foreground)
+__device__ inline void emit_sample(float h, float l, float b, float bf, bool live, bool gain, double ak, double& mix, double& bgv, double& fgv) {
     // (an infinite float64 sample narrows to an infinite hi and a NaN remainder: the sample is hi. So it is with a zero
     // remainder, which adds nothing and must not: -0 + +0 is +0, and the mixture of a negative zero is a negative zero)
     const double x = (fabsf(h) <= 3.402823466e38f || h != h) && l != 0.f ? (double)h + (double)l : (double)h;
     mix = live ? x : 0.0;
-    const double f = gain ? fma(-ak, (double)b, x) : x - (double)b;
+    const double f = gain ? fma(-ak, (double)bf, x) : x - (double)bf;
     fgv = live ? f : 0.0;
     bgv = live ? (double)b : 0.0;
 }
@@ -310,6 +312,18 @@ __device__ inline void emit_body(const EmitArgs& a) {
     } else {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) b[k] = k < m ? a.bg[i0 + k] : 0.f;
+    }
+    float bf[EPT];
+    if (a.bg_fg) {
+        if (m == EPT) {
+            load_run<EPT>(a.bg_fg + i0, bf);
+        } else {
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) bf[k] = k < m ? a.bg_fg[i0 + k] : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) bf[k] = b[k];
     }
     const float* ph = a.hi + s0 * a.in_stream + r0;
     const bool one_stream = m == EPT && r0 + EPT <= a.per;
@@ -365,7 +379,7 @@ __device__ inline void emit_body(const EmitArgs& a) {
     }
     double bgv[EPT], fgv[EPT], mix[EPT];
 #pragma unroll
-    for (int k = 0; k < EPT; ++k) emit_sample(h[k], l[k], b[k], live[k], a.gain != 0, a.gain ? ak[k] : 0.0, mix[k], bgv[k], fgv[k]);
+    for (int k = 0; k < EPT; ++k) emit_sample(h[k], l[k], b[k], bf[k], live[k], a.gain != 0, a.gain ? ak[k] : 0.0, mix[k], bgv[k], fgv[k]);
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         if (d >= a.n_out) break;
@@ -420,6 +434,7 @@ struct LevelArgs {
     int32_t n_channels, n_chunks, tile;
     const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
     double* dst; double* partial;
+    const float* bg_fg;             // as in EmitArgs
 };
 
 template <int F> __device__ inline double level_fold(double x, double y) {
@@ -510,7 +525,7 @@ __global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
             if (r0 >= e1) break;
             int m = a.tile - 4 * t < 4 ? a.tile - 4 * t : 4;
             if (e1 - r0 < m) m = (int)(e1 - r0);
-            float b[4], h[4], l[4];
+            float b[4], h[4], l[4], bf[4];
             const float* pb = bg_s + r0;
             const float* ph = hi_s + r0;
             if (m == 4 && !((reinterpret_cast<uintptr_t>(pb) | reinterpret_cast<uintptr_t>(ph)) & 15)) {
@@ -535,6 +550,18 @@ __global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
                     }
                 }
             }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bf[k] = b[k];
+            if (a.bg_fg) {                                        // (laid out like bg: aligned together)
+                const float* pf = a.bg_fg + s * a.per + r0;
+                if (m == 4 && !(reinterpret_cast<uintptr_t>(pf) & 15)) {
+                    const float4 vf = *reinterpret_cast<const float4*>(pf);
+                    bf[0] = vf.x; bf[1] = vf.y; bf[2] = vf.z; bf[3] = vf.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) bf[k] = k < m ? pf[k] : 0.f;
+                }
+            }
             int64_t j = r0 / C;                                   // sample of the run's first element, and its channel
             int c = (int)(r0 - j * C);
 #pragma unroll
@@ -542,7 +569,7 @@ __global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
                 const bool live = k < m && any_live && j >= live_from;
                 const double ak = a.gain == kGainTables ? emit_gain_at(at, ac, j + 1, a.ramp) : at;
                 double mix, bgv, fgv;
-                emit_sample(h[k], l[k], b[k], live, a.gain != 0, ak, mix, bgv, fgv);
+                emit_sample(h[k], l[k], b[k], bf[k], live, a.gain != 0, ak, mix, bgv, fgv);
                 energy[0][k] += mix * mix; energy[1][k] += bgv * bgv; energy[2][k] += fgv * fgv;
                 peak[0][k] = fmax(peak[0][k], fabs(mix)); peak[1][k] = fmax(peak[1][k], fabs(bgv)); peak[2][k] = fmax(peak[2][k], fabs(fgv));
                 n_live[k] += live ? 1u : 0u;
@@ -797,6 +824,45 @@ __global__ __launch_bounds__(kIoThreads) void online_gain_commit(const float* tg
     for (int32_t i = threadIdx.x; i < n; i += kIoThreads) cur_new[i] = slot < 0 || i == slot ? tgt[i] : cur_old[i];
 }
 
+// Band gains of the streaming handle (engine.h: bands). expand: workgroup (x, named slot i) writes bins of the slot's pending
+// row; the band of a bin by bisection over the ascending edges (up to F + 1 of them). Everything it reads of the job lies
+// inside band_job_words() words; everything it writes inside the slot's three rows.
+struct BandExpandArgs { float* tab; const int32_t* job; int32_t FS, F, n, n_bands, rows, init; };
+__global__ __launch_bounds__(kIoThreads) void online_band_expand(BandExpandArgs a) {
+    const int32_t i = blockIdx.y;
+    const int32_t* slot = a.job;
+    const int32_t* row = slot + a.n;
+    const int32_t* edges = row + a.n;
+    const float* gains = reinterpret_cast<const float*>(edges + a.n_bands + 1);
+    const int32_t r = row[i];
+    float* base = a.tab + (int64_t)slot[i] * repet_eng::kBandRows * a.FS;
+    for (int32_t k = blockIdx.x * kIoThreads + threadIdx.x; k < a.FS; k += gridDim.x * kIoThreads) {
+        float g = 0.f;
+        if (r >= 0 && r < a.rows && k < a.F && k >= edges[0] && k < edges[a.n_bands]) {
+            int32_t lo = 0, hi = a.n_bands;                       // edges[lo] <= k < edges[hi]
+            while (hi - lo > 1) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (edges[mid] <= k) lo = mid; else hi = mid;
+            }
+            g = gains[(int64_t)r * a.n_bands + lo];
+        }
+        base[repet_eng::kBandPending * a.FS + k] = (float)(1.0 - (double)g);
+        if (a.init) { base[repet_eng::kBandCarried * a.FS + k] = 1.f; base[repet_eng::kBandNew * a.FS + k] = 1.f; }
+    }
+}
+
+// commit / settle: workgroup (x, slot). A thread moves its own bins only, so the rows of a slot need no order between threads.
+__global__ __launch_bounds__(kIoThreads) void online_band_commit(float* tab, int32_t FS, int32_t slot, int32_t mode, const int64_t* slot_start) {
+    const int32_t s = slot < 0 ? (int32_t)blockIdx.y : slot;
+    if (slot < 0 && slot_start && slot_start[s] == repet_eng::kSlotHeld) return;
+    float* base = tab + (int64_t)s * repet_eng::kBandRows * FS;
+    for (int32_t k = blockIdx.x * kIoThreads + threadIdx.x; k < FS; k += gridDim.x * kIoThreads) {
+        const float p = base[repet_eng::kBandPending * FS + k], n = base[repet_eng::kBandNew * FS + k];
+        base[repet_eng::kBandCarried * FS + k] = mode == repet_eng::kBandSettle ? p : n;
+        if (mode != repet_eng::kBandCarry) base[repet_eng::kBandNew * FS + k] = p;
+    }
+}
+
 int element_size(int dtype) {
     switch (dtype) {
         case REPET_F64: return 8;
@@ -1043,9 +1109,28 @@ hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur
     return hipGetLastError();
 }
 
+int64_t band_job_words(int32_t n, int32_t n_bands, int32_t rows) { return 2 * (int64_t)n + n_bands + 1 + (int64_t)rows * n_bands; }
+
+hipError_t launch_band_expand(float* tab, int32_t FS, int32_t F, const int32_t* job, int32_t n, int32_t n_bands, int32_t rows, bool init,
+                              hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!tab || !job || FS < F || F < 1 || n > 65535 || n_bands < 1 || n_bands > F || rows < 1) return hipErrorInvalidValue;
+    const BandExpandArgs a{tab, job, FS, F, n, n_bands, rows, init ? 1 : 0};
+    online_band_expand<<<dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)n), kIoThreads, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_band_commit(float* tab, int32_t FS, int32_t n_slots, int32_t slot, int mode, const int64_t* slot_start, hipStream_t s) {
+    if (n_slots <= 0) return hipSuccess;
+    if (!tab || FS < 1 || n_slots > 65535 || slot >= n_slots || mode < kBandCommit || mode > kBandCarry) return hipErrorInvalidValue;
+    online_band_commit<<<dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)(slot < 0 ? n_slots : 1)), kIoThreads, 0, s>>>(
+        tab, FS, slot, mode, slot_start);
+    return hipGetLastError();
+}
+
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s, const EmitGain* gain) {
+                              int n_dsts, hipStream_t s, const EmitGain* gain, const float* bg_fg) {
     const int64_t count = (int64_t)n_streams * n * ch;
     if (count <= 0 || n_dsts <= 0) return hipSuccess;
     if (n_dsts > 2 || !bg || !hi) return hipErrorInvalidValue;
@@ -1057,7 +1142,7 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
             a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
         }
     }
-    a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
+    a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts;
     // (the vector store of a dense destination: 16 bytes for F64 / F32, kEpt16 elements for the 16-bit types)
     const int vec_bytes = dtype == REPET_F64 || dtype == REPET_F32 ? 16 : 2 * kEpt16;
@@ -1091,7 +1176,7 @@ int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch) {
 
 hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                                 int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
-                                hipStream_t s, const EmitGain* gain) {
+                                hipStream_t s, const EmitGain* gain, const float* bg_fg) {
     if (n_streams <= 0 || ch <= 0) return hipSuccess;
     if (!dst) return hipErrorInvalidValue;
     const int64_t count = (int64_t)n_streams * n * ch;
@@ -1108,7 +1193,7 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
             a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
         }
     }
-    a.bg = bg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
+    a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_chunks = (int32_t)chunks;
     a.dst = dst; a.partial = partials;
     devio_levels<<<dim3((unsigned)chunks, (unsigned)n_streams), kIoThreads, 0, s>>>(a);

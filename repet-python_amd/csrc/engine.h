@@ -315,11 +315,13 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
 //            gain (nullable: the foreground is x - bg as ever): the foreground is x - a * bg, with a the scalar (offline) or
 //            per stream from fp32 tables [n_streams]: a_tgt[s] from sample `ramp` - 1 of the emission on, a linear fade from
 //            a_cur[s] before it (ramp 0: a_tgt everywhere)
+//            bg_fg (nullable, laid out like bg): the background the FOREGROUND is formed from where it is not bg itself -- the
+//            shaped one of a live handle with band gains; the background and the mixture never read it
 struct EmitDst { void* p = nullptr; int which = -1; int64_t strides[3] = {0, 0, 0}; };
 struct EmitGain { const float* a_cur = nullptr; const float* a_tgt = nullptr; int64_t ramp = 0; float a = 1.f; bool scalar = false; };
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s, const EmitGain* gain = nullptr);
+                              int n_dsts, hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr);
 //   levels   the REPET_LEVEL_FIELDS float64 values per stream and channel of the emission the same arguments describe to
 //            launch_stream_emit (include/repet_hip.h: energies, peaks, live and non-finite samples), dense [n_streams][ch][8]
 //            into dst: one launch over (chunk of kLevelChunk samples, stream), and for more than one chunk a second small one
@@ -329,13 +331,30 @@ constexpr int64_t kLevelChunk = REPET_LEVEL_CHUNK;
 int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch);
 hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                                 int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
-                                hipStream_t s, const EmitGain* gain = nullptr);
+                                hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr);
 //   gains    the background gains of the streaming handle, fp32 [S] tables of a = (float)(1 - gain). fill: n entries = a.
 //            set: tgt[slots[k]] = a[k], one launch per kSlotResetIds slots named. commit: cur_new[s] = tgt[s] for the slots an
 //            emission covers (slot < 0: all), cur_old[s] for the others; one launch
 hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s);
 hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int32_t n_slots, hipStream_t s);
 hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s);
+//   bands    the band gains of the streaming handle (repet_online_set_background_band_gains): per slot three rows of FS fp32
+//            factors a[k] = (float)(1 - (double)g[k]), tab[slot][kBandCarried | kBandNew | kBandPending][FS] -- the table of the
+//            frame carried over from the last push, of the frames a push completes, and of the last set.
+//            expand: the pending row of the n named slots from band gains. `job` is memory the DEVICE reads (the caller's to
+//            keep until the launch has run), int32 / fp32 words: slot[n] | row[n] (the row of `gains` the slot takes; < 0: every
+//            g = 0) | edges[n_bands + 1] | gains[rows][n_bands]; bin k takes the gain of the band [edges[b], edges[b + 1]) that
+//            holds it, 0 outside all of them and for the pad bins. init: the other two rows of the named slots are written 1
+//            (a handle's first set names every slot: the tables begin there). One launch.
+//            commit, for every slot (slot < 0) that is not held in slot_start (nullable) or for the one slot named, one launch:
+//            kBandCommit carried = new, new = pending (a call that completes frames); kBandCarry carried = new (one that only
+//            inverts the carried frame); kBandSettle carried = new = pending (a stream that moves into the slot).
+constexpr int kBandCarried = 0, kBandNew = 1, kBandPending = 2, kBandRows = 3;
+constexpr int kBandCommit = 0, kBandSettle = 1, kBandCarry = 2;
+int64_t band_job_words(int32_t n, int32_t n_bands, int32_t rows);
+hipError_t launch_band_expand(float* tab, int32_t FS, int32_t F, const int32_t* job, int32_t n, int32_t n_bands, int32_t rows, bool init,
+                              hipStream_t s);
+hipError_t launch_band_commit(float* tab, int32_t FS, int32_t n_slots, int32_t slot, int mode, const int64_t* slot_start, hipStream_t s);
 //   frames   (frames.hip) the spectra of the frames a push completed, read from the window it wrote: V / X at the first of the
 //            n_frames rows of slot 0's plane 0 (`plane` / `spec` elements between channel planes / slots), handle frame frame0
 //            in that row, `warm` = start_frames - 1, slot_start nullable (every slot's stream is the handle's). frames: fp32

@@ -66,8 +66,9 @@ struct repet_online {
     // share). Nothing writes that buffer before the next push's slide; restart / release and the next append end its validity.
     int out_which = REPET_OUT_BACKGROUND;
     struct Also { int which = -1; void* dst = nullptr; int dtype = REPET_F64; int64_t strides[3] = {0, 0, 0}; } also;
-    // (g0, g1, ramp: the gain tables of that emission, see below -- a fade from table g0 to table g1 over its first `ramp` samples)
-    struct Emission { bool valid = false; int buf = 0, S = 0, slot = -1; int64_t off = 0, n = 0, pos0 = 0; int g0 = 0, g1 = 0; int64_t ramp = 0; } em;
+    // (g0, g1, ramp: the gain tables of that emission, see below -- a fade from table g0 to table g1 over its first `ramp` samples;
+    // shaped: its foreground is formed from the shaped background in `outs`, see the band gains below)
+    struct Emission { bool valid = false; int buf = 0, S = 0, slot = -1; int64_t off = 0, n = 0, pos0 = 0; int g0 = 0, g1 = 0; int64_t ramp = 0; bool shaped = false; } em;
     // Background gains (repet_online_set_background_gain): the foreground of slot s is x - a[s] * bg, a = (float)(1 - gain). The
     // gain is the SLOT's: no restart, release, finish_stream or import touches it. gain[s] is the host mirror of what was set;
     // gain_tab holds three fp32 tables [S] on the device, all 1 at open: the target (written by a set, entry for entry, with no
@@ -97,6 +98,33 @@ struct repet_online {
     bool gains_on = false;
     float* gain_target() const { return gain_tab.as<float>(); }
     float* gain_current(int k) const { return gain_tab.as<float>() + (int64_t)(1 + k) * S; }
+    // Band gains (repet_online_set_background_band_gains): the foreground of slot s takes a SHAPED background, the overlap-add
+    // inverse of a[k] * Y_j[k] with a = (float)(1 - g) per bin, in place of the plain one. The inverse is linear and a frame is
+    // shaped once and whole, with the table its slot had when the call that completed it was enqueued; a frame rings into two
+    // hops, so the frame carried over from the call before needs the table IT was completed under. band_tab holds three rows of
+    // FS factors per slot (engine.h: bands): carried, new, pending. A set writes the pending row (one launch, the gains read from a
+    // pinned job buffer: no copy, no wait) and marks the slot; every call that inverts first brings the rows of its slots up to
+    // date where a mark says so (one launch: carried = new, and where it completes frames new = pending), which is twice after
+    // a set -- the second time for the carried row alone -- and never again. Held slots keep rows and marks until they resume.
+    // band_stale[s]: bit 0 new != pending, bit 1 carried != new. band_nd[s]: bits 0 / 1 / 2 the pending / new / carried row is not
+    // all ones. While any slot has a bit of band_nd the emitting calls run the inverse a second time, with the rows, into `outs`
+    // beside outf, and em.shaped says that the foreground of that emission reads it. The tables belong to the slots (no
+    // restart, release, finish_stream or import touches them; an import settles its slot: all three rows = pending) and exist
+    // from the first set on (bands_on): until then nothing here costs a launch.
+    DevBuf band_tab, outs;
+    bool bands_on = false;
+    std::vector<std::vector<float>> band_gain;          // g as last set, per slot (empty: all zero)
+    std::vector<unsigned char> band_stale, band_nd;
+    int64_t n_band_stale = 0, n_band_nd = 0;            // slots with a bit of either
+    static constexpr int kBandJobs = 4;
+    struct BandJob { void* p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; } band_job[kBandJobs];
+    int band_job_next = 0;
+    float* band_rows(int64_t slot) const { return band_tab.as<float>() + slot * kBandRows * FS; }
+    void band_mark(size_t s, unsigned char stale, unsigned char nd) {
+        n_band_stale += (stale != 0) - (band_stale[s] != 0);
+        n_band_nd += (nd != 0) - (band_nd[s] != 0);
+        band_stale[s] = stale; band_nd[s] = nd;
+    }
 
     int64_t plane() const { return (rows_cap + kPadRows) * FS; }        // elements between channel planes of X and V
     int64_t spec_stride() const { return (int64_t)C * plane(); }      // ... between streams in X and V
@@ -294,6 +322,37 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         hipError_t e = launch_istft_ola(a, c->stream);
         if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
         HIP_TRY(e);
+        if (o->bands_on) {
+            // band gains: the rows of the slots this call inverts, brought up to date where a set (or the call before) left a mark
+            const int mode = n_new > 0 ? kBandCommit : kBandCarry;
+            const unsigned char due = n_new > 0 ? 3 : 2;
+            auto step = [&](size_t s) {
+                const unsigned char st = o->band_stale[s], nd = o->band_nd[s];
+                const unsigned char carried = (nd & 2) ? 4 : 0;                      // carried = new
+                if (n_new > 0) o->band_mark(s, (st & 1) ? 2 : 0, (unsigned char)((nd & 1) | ((nd & 1) ? 2 : 0) | carried));
+                else o->band_mark(s, st & 1, (unsigned char)((nd & 3) | carried));
+            };
+            if (all && o->n_band_stale > 0) {
+                bool any = false;
+                for (size_t s = 0; s < (size_t)o->S; ++s)
+                    if (!o->held[s] && (o->band_stale[s] & due)) { any = true; step(s); }
+                if (any) HIP_TRY(launch_band_commit(o->band_tab.as<float>(), o->FS, o->S, -1, mode, o->slots_on ? o->slot_start.as<int64_t>() : nullptr, c->stream));
+            } else if (!all && (o->band_stale[(size_t)slot] & due)) {
+                step((size_t)slot);
+                HIP_TRY(launch_band_commit(o->band_tab.as<float>(), o->FS, o->S, slot, mode, nullptr, c->stream));
+            }
+        }
+        if (o->n_band_nd > 0) {
+            // some slot's rows are not all ones: the same inverse once more, every bin times its slot's factor as it is fetched,
+            // into the buffer the foreground of this emission reads (a slot whose rows are all ones gets the plain bits)
+            HIP_TRY(o->outs.ensure((size_t)S * n_emit * o->C * sizeof(float)));
+            a.out = o->outs.as<float>();
+            a.G = o->band_rows(sb); a.G_batch_stride = (int64_t)kBandRows * o->FS; a.G_split = o->hist_valid;
+            e = launch_istft_ola(a, c->stream);
+            if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
+            HIP_TRY(e);
+            o->em.shaped = true;
+        }
     }
     if (n_emit > 0 && o->gains_on && (all ? o->n_dirty > 0 : o->gain_dirty[(size_t)slot] != 0)) {
         // a gain was set since these slots last emitted: this emission fades to it, and it is in force afterwards
@@ -416,7 +475,7 @@ int online_emit(repet_online* o, const EmitDst* dsts, int n_dsts, int dtype) {
     if (o->gains_on) { gain.a_cur = o->gain_current(em.g0) + sb; gain.a_tgt = o->gain_current(em.g1) + sb; gain.ramp = em.ramp; }
     HIP_TRY(launch_stream_emit(o->outf.as<float>(), o->pend[em.buf].as<float>() + at, o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
                                o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dtype, dsts,
-                               n_dsts, c->stream, o->gains_on ? &gain : nullptr));
+                               n_dsts, c->stream, o->gains_on ? &gain : nullptr, em.shaped ? o->outs.as<float>() : nullptr));
     return REPET_OK;
 }
 
@@ -437,7 +496,8 @@ static int online_levels(repet_online* o, double* dst) {
     const hipError_t e = launch_stream_levels(o->outf.as<float>(), empty ? nullptr : o->pend[em.buf].as<float>() + at,
                                               empty ? nullptr : o->pend_lo[em.buf].as<float>() + at, o->pend_stride(),
                                               o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr, em.pos0, o->H, em.S, em.n, o->C, dst,
-                                              partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream, o->gains_on ? &gain : nullptr);
+                                              partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream, o->gains_on ? &gain : nullptr,
+                                              em.shaped ? o->outs.as<float>() : nullptr);
     if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
     HIP_TRY(e);
     return REPET_OK;
@@ -777,6 +837,11 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     st = first;
     o->n_held -= o->held[(size_t)slot];                         // (the launch wrote the table: a hold ends here)
     o->held[(size_t)slot] = 0;
+    if (o->bands_on && o->band_stale[(size_t)slot]) {
+        // band gains: the frame that comes with the stream is shaped with the table the slot has now
+        HIP_TRY(launch_band_commit(o->band_tab.as<float>(), o->FS, o->S, slot, kBandSettle, nullptr, c->stream));
+        o->band_mark((size_t)slot, 0, (o->band_nd[(size_t)slot] & 1) ? 7 : 0);
+    }
     o->latest_start = std::max(o->latest_start, first);
     o->slots_on = true;
     return REPET_OK;
@@ -1118,6 +1183,78 @@ int repet_online_background_gain(repet_online* o, int32_t slot, float* gain_out)
     return REPET_OK;
 }
 
+int repet_online_set_background_band_gains(repet_online* o, const int32_t* slots, int32_t n_slots, const int32_t* edges, int32_t n_bands,
+                                           const float* gains, int32_t gains_rows) {
+    if (!o || !gains) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
+    const int32_t n = slots ? n_slots : o->S;
+    if (gains_rows != 1 && gains_rows != n) return fail(REPET_ERR_BAD_ARG, "online: one row of band gains, or one per slot named");
+    if (edges) {
+        if (n_bands < 1 || n_bands > o->F) return fail(REPET_ERR_BAD_ARG, "online: between one band and one per bin");
+        for (int32_t k = 0; k <= n_bands; ++k)
+            if (edges[k] < 0 || edges[k] > o->F || (k > 0 && edges[k] < edges[k - 1]))
+                return fail(REPET_ERR_BAD_ARG, "online: band edges are ascending bins in [0, window_length / 2 + 1]");
+    } else if (n_bands != o->F) {
+        return fail(REPET_ERR_BAD_ARG, "online: without edges there is one gain per bin (window_length / 2 + 1 of them)");
+    }
+    for (int32_t k = 0; k < n; ++k)
+        if (slots && (slots[k] < 0 || slots[k] >= o->S)) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    for (int64_t k = 0; k < (int64_t)gains_rows * n_bands; ++k)
+        if (!(gains[k] >= 0.f && gains[k] <= 1.f)) return fail(REPET_ERR_BAD_ARG, "online: a band gain lies in [0, 1]");
+    if (o->W > 4096) return fail(REPET_ERR_LIMIT, "online: band gains need a window_length of at most 4096");
+    if (n == 0) return REPET_OK;
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    // a slot named twice takes the last row given for it: the launch gets every slot once. The first set names every slot
+    // (row -1: g = 0), and its launch writes the tables' beginning
+    const bool init = !o->bands_on;
+    std::vector<int32_t> row_of((size_t)o->S, -1);
+    for (int32_t k = 0; k < n; ++k) row_of[(size_t)(slots ? slots[k] : k)] = gains_rows == 1 ? 0 : k;
+    std::vector<int32_t> ids;
+    for (int32_t s = 0; s < o->S; ++s)
+        if (init || row_of[(size_t)s] >= 0) ids.push_back(s);
+    const int32_t m = (int32_t)ids.size();
+    if (init) HIP_TRY(o->band_tab.ensure((size_t)o->S * kBandRows * o->FS * sizeof(float)));
+    repet_online::BandJob& job = o->band_job[o->band_job_next];
+    if (job.busy) HIP_TRY(hipEventSynchronize(job.done));       // (the launch of kBandJobs sets ago: long over)
+    job.busy = false;
+    RP_TRY(ensure_pinned(job.p, job.cap, (size_t)band_job_words(m, n_bands, gains_rows) * 4));
+    if (!job.done) HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming));
+    int32_t* w = static_cast<int32_t*>(job.p);
+    for (int32_t i = 0; i < m; ++i) { w[i] = ids[(size_t)i]; w[m + i] = row_of[(size_t)ids[(size_t)i]]; }
+    for (int32_t k = 0; k <= n_bands; ++k) w[2 * m + k] = edges ? edges[k] : k;
+    std::memcpy(w + 2 * m + n_bands + 1, gains, (size_t)gains_rows * n_bands * sizeof(float));
+    HIP_TRY(launch_band_expand(o->band_tab.as<float>(), o->FS, o->F, w, m, n_bands, gains_rows, init, c->stream));
+    HIP_TRY(hipEventRecord(job.done, c->stream));
+    job.busy = true;
+    o->band_job_next = (o->band_job_next + 1) % repet_online::kBandJobs;
+    o->bands_on = true;
+    for (int32_t s = 0; s < o->S; ++s) {
+        const int32_t r = row_of[(size_t)s];
+        if (r < 0) continue;
+        std::vector<float>& g = o->band_gain[(size_t)s];
+        g.assign((size_t)o->F, 0.f);
+        bool any = false;
+        for (int32_t b = 0; b < n_bands; ++b) {
+            const float v = gains[(int64_t)r * n_bands + b];
+            const int32_t k0 = edges ? edges[b] : b, k1 = edges ? edges[b + 1] : b + 1;
+            for (int32_t k = k0; k < k1; ++k) g[(size_t)k] = v;
+            any = any || (v != 0.f && k1 > k0);
+        }
+        o->band_mark((size_t)s, o->band_stale[(size_t)s] | 1, (unsigned char)((o->band_nd[(size_t)s] & 6) | (any ? 1 : 0)));
+    }
+    return REPET_OK;
+}
+
+int repet_online_background_band_gains(repet_online* o, int32_t slot, float* out, int32_t capacity) {
+    if (!o || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    if (capacity < o->F) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (window_length / 2 + 1 values)");
+    const std::vector<float>& g = o->band_gain[(size_t)slot];
+    for (int32_t k = 0; k < o->F; ++k) out[k] = g.empty() ? 0.f : g[(size_t)k];
+    return REPET_OK;
+}
+
 int repet_online_set_start_frames(repet_online* o, int32_t start_frames) {
     if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->total_in != 0 || o->epoch != 0 || o->finished) return fail(REPET_ERR_BAD_ARG, "online: start_frames can only be set before the first push");
@@ -1308,6 +1445,9 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
     o->max_push = max_push_samples;
     o->start.assign((size_t)n_streams, 0);
     o->held.assign((size_t)n_streams, 0);
+    o->band_gain.assign((size_t)n_streams, std::vector<float>());
+    o->band_stale.assign((size_t)n_streams, 0);
+    o->band_nd.assign((size_t)n_streams, 0);
     {   // every slot's stream begins with the handle's until a restart or release says otherwise
         DeviceGuard guard(o->ctx->device);
         hipError_t e = o->slot_start.ensure((size_t)n_streams * sizeof(int64_t));
@@ -1342,6 +1482,12 @@ int repet_online_close(repet_online* o) {
         DeviceGuard guard(o->ctx->device);
         (void)hipStreamSynchronize(o->ctx->stream);
         for (int k = 0; k < 2; ++k) { o->X[k].release(); o->V[k].release(); o->Vn[k].release(); o->pend[k].release(); o->pend_lo[k].release(); }
+        o->band_tab.release(); o->outs.release();
+        for (auto& j : o->band_job) {
+            free_pinned(j.p, j.cap);
+            if (j.done) (void)hipEventDestroy(j.done);
+            j.done = nullptr;
+        }
         o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release(); o->levels.release();
         free_pinned(o->host_in, o->host_in_cap);
         free_pinned(o->host_out, o->host_out_cap);

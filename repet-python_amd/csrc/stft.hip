@@ -790,7 +790,8 @@ struct __attribute__((packed, aligned(4))) Float4U { float x, y, z, w; };    // 
 
 // accumulate_weighted: 0 = store, 1 = out += w y, 2 = out = w y (a class of segments that tiles its span and is the first
 // to write there: no read of the cleared buffer)
-template <int W, bool MASKED>
+// MASKED: 0 no mask, 1 a mask plane M, 3 factor rows G (one per batch slot and row class, every channel's: fetched as M is)
+template <int W, int MASKED>
 __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <= 2048 ? REPET_ISTFT_MIN_WAVES : 1, 8))) void istft_ola_kernel(IstftOlaArgs a, int run) {
     constexpr int N = W / 2;          // complex points per frame = samples per hop (H = W/2)
     constexpr int HP = N / 2;         // float2 per half frame
@@ -811,7 +812,8 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
     if (a.n_batch > 0) {
         const int j = a.batch_first + (int)blockIdx.y * a.batch_step;
         a.Y += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
-        if (MASKED) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
+        if (MASKED == 1) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
+        if (MASKED == 3) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
         a.out_offset += (int64_t)j * a.batch_out_stride;
         a.fade_in = j > 0 ? a.overlap : 0;
         a.fade_out = a.overlap;
@@ -846,7 +848,8 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
         for (int c = 0; c < C; ++c) {
             const float2* z = buf0;
             if (have) {
-                fetch_spectrum<W, MASKED>(spec, a.Y + c * a.chan_stride + t * a.FS, MASKED ? a.M + c * a.chan_stride + t * a.FS : nullptr);
+                fetch_spectrum<W, MASKED != 0>(spec, a.Y + c * a.chan_stride + t * a.FS,
+                                               MASKED == 1 ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr);
                 repack_spectrum<W>(spec, tables, buf0);
                 __syncthreads();
                 z = fft_lds_regs<N, true>(buf0, buf1, tables.ft);
@@ -1368,7 +1371,9 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s, int path, Fft
     // the same for a mask PLANE at the longest window: istft_ola_kernel<8192, masked> does not exist (no registers to spare,
     // ensure_spectra keeps the mask in X there), and the plain kernel would ignore the plane
     if (a.M && a.W > 4096) return hipErrorInvalidValue;
-    const bool wave_takes = a.out_channels == 0 && a.W <= 4096 && a.n_channels <= 4 && a.n_channels != 3;
+    // factor rows: the block kernel's (and the register kernel's above); never beside a mask plane, and not at the longest window
+    if (a.G && (a.M || a.W > 4096)) return hipErrorInvalidValue;
+    const bool wave_takes = a.out_channels == 0 && a.W <= 4096 && a.n_channels <= 4 && a.n_channels != 3 && !a.G;
     if (path == kFftPathWave && !wave_takes) return hipErrorInvalidValue;
     if ((path == kFftPathWave || (path == kFftPathAuto && use_wave_kernels())) && wave_takes) {
         const int C = a.n_channels;
@@ -1415,9 +1420,11 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s, int path, Fft
             report(info, name, kFftPathBlock, run, slots, ceil_div(hops, run) * batches, hops);
         };
         if constexpr (Wc <= 4096) {
-            if (a.M) go(&istft_ola_kernel<Wc, true>, "istft_ola_kernel<masked>"); else go(&istft_ola_kernel<Wc, false>, "istft_ola_kernel<plain>");
+            if (a.M) go(&istft_ola_kernel<Wc, 1>, "istft_ola_kernel<masked>");
+            else if (a.G) go(&istft_ola_kernel<Wc, 3>, "istft_ola_kernel<shaped>");
+            else go(&istft_ola_kernel<Wc, 0>, "istft_ola_kernel<plain>");
         } else {
-            go(&istft_ola_kernel<Wc, false>, "istft_ola_kernel<plain>");       // the engine keeps the mask in X for the longest window (registers)
+            go(&istft_ola_kernel<Wc, 0>, "istft_ola_kernel<plain>");       // the engine keeps the mask in X for the longest window (registers)
         }
     });
 }

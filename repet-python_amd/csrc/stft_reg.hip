@@ -463,7 +463,8 @@ __global__ __launch_bounds__(64 * kFwdWaves) void stft_reg_kernel(StftArgs a, in
 constexpr int kInvWaves = 12;
 constexpr int kInvLdsFloat2 = kInvWaves * kExPitch + kTwFloat2 + kRegN + 2 * 8 * 64;    // + split twiddles [N] + carry [2][8][64]
 
-template <int C, int MASKED>      // C = 1, 2; MASKED: 0 no mask, 1 a mask plane M, 2 magnitudes + repeating-segment model
+template <int C, int MASKED>      // C = 1, 2; MASKED: 0 no mask, 1 a mask plane M, 2 magnitudes + repeating-segment model,
+                                  // 3 factor rows G (one per batch slot and row class, every channel's: fetched and applied as M is)
 __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaArgs a, int rounds) {
     constexpr int N = kRegN;          // samples per hop = complex FFT length
     extern __shared__ __attribute__((aligned(16))) float2 inv_lds[];
@@ -478,6 +479,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
         const int j = a.batch_first + (int)blockIdx.y * a.batch_step;
         a.Y += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
         if (MASKED == 1) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
+        if (MASKED == 3) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
         if (MASKED == 2) {
             const int local = a.batch_local0 + (int)blockIdx.y * a.batch_step;
             a.model += (int64_t)local * a.model_batch_stride;
@@ -532,7 +534,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
             float2 v[16];
             if (have) {
                 const float2* Y = a.Y + c * a.chan_stride + t * a.FS;
-                const float* Mr = MASKED == 1 ? a.M + c * a.chan_stride + t * a.FS : nullptr;
+                const float* Mr = MASKED == 1 ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr;
                 // MASKED == 2: the model row of this frame's position inside its period (wave-uniform)
                 const float* Wr = MASKED == 2 ? a.model + c * a.model_chan_stride + (t % period) * a.FS : nullptr;
                 // merge the half spectrum back into the packed transform: Z[k] = E + i conj(W_2048^k) D, E = (A + B) / 2,
@@ -546,11 +548,11 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
                 // itself, Z[N/2] = conj(A). All loads of a transform are issued before the first is consumed.
                 const int partner = (64 - lane) & 63;
                 float2 xk[8], xc[8], x512;
-                float mk[MASKED == 1 ? 8 : 1], mc[MASKED == 1 ? 8 : 1], m512 = 1.f;
+                float mk[(MASKED & 1) ? 8 : 1], mc[(MASKED & 1) ? 8 : 1], m512 = 1.f;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { xk[j] = Y[64 * j + lane]; xc[j] = Y[N - (64 * j + lane)]; }
                 x512 = Y[N / 2];                                              // (every lane the same address: one request)
-                if constexpr (MASKED == 1) {
+                if constexpr ((MASKED & 1) != 0) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { mk[j] = Mr[64 * j + lane]; mc[j] = Mr[N - (64 * j + lane)]; }
                     m512 = Mr[N / 2];
@@ -573,7 +575,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
                         a_ = make_float2(mul_rounded(a_.x, mk2), mul_rounded(a_.y, mk2));
                         b_ = make_float2(mul_rounded(b_.x, mc2), mul_rounded(b_.y, mc2));
                         __builtin_amdgcn_sched_barrier(0);                     // two divisions' temporaries at a time, not sixteen
-                    } else if constexpr (MASKED == 1) {
+                    } else if constexpr ((MASKED & 1) != 0) {
                         a_ = make_float2(mul_rounded(a_.x, mk[j]), mul_rounded(a_.y, mk[j]));
                         b_ = make_float2(mul_rounded(b_.x, mc[j]), mul_rounded(b_.y, mc[j]));
                     }
@@ -776,12 +778,12 @@ hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t
         (void)ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)dyn);
         hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)batches), dim3(64 * kInvWaves), dyn, s, a, rounds);
     };
-    const int mode = a.model ? 2 : a.M ? 1 : 0;
-    if (a.n_channels == 2) { if (mode == 2) go(&istft_ola_reg_kernel<2, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<2, 1>); else go(&istft_ola_reg_kernel<2, 0>); }
-    else { if (mode == 2) go(&istft_ola_reg_kernel<1, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<1, 1>); else go(&istft_ola_reg_kernel<1, 0>); }
+    const int mode = a.model ? 2 : a.M ? 1 : a.G ? 3 : 0;
+    if (a.n_channels == 2) { if (mode == 3) go(&istft_ola_reg_kernel<2, 3>); else if (mode == 2) go(&istft_ola_reg_kernel<2, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<2, 1>); else go(&istft_ola_reg_kernel<2, 0>); }
+    else { if (mode == 3) go(&istft_ola_reg_kernel<1, 3>); else if (mode == 2) go(&istft_ola_reg_kernel<1, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<1, 1>); else go(&istft_ola_reg_kernel<1, 0>); }
     if (info) {
-        static const char* const names[2][3] = {{"istft_ola_reg_kernel<1, 0>", "istft_ola_reg_kernel<1, 1>", "istft_ola_reg_kernel<1, 2>"},
-                                                {"istft_ola_reg_kernel<2, 0>", "istft_ola_reg_kernel<2, 1>", "istft_ola_reg_kernel<2, 2>"}};
+        static const char* const names[2][4] = {{"istft_ola_reg_kernel<1, 0>", "istft_ola_reg_kernel<1, 1>", "istft_ola_reg_kernel<1, 2>", "istft_ola_reg_kernel<1, 3>"},
+                                                {"istft_ola_reg_kernel<2, 0>", "istft_ola_reg_kernel<2, 1>", "istft_ola_reg_kernel<2, 2>", "istft_ola_reg_kernel<2, 3>"}};
         info->kernel = names[a.n_channels == 2][mode];
         info->family = kFftPathReg; info->run = kInvWaves * rounds - 1; info->rounds = rounds; info->slots = cus;
         info->workgroups = (int64_t)blocks * batches; info->units = hops; info->launches += 1;

@@ -265,6 +265,8 @@ def online(sampling_frequency, number_channels, start_length=None):
 
     ``set_background_gain(gain)`` keeps ``gain`` (in [0, 1]) of the background in the foreground, ``x - float32(1 - gain) *
     background``, fading to it over at most one hop; ``background_gain()`` reads it back: see :func:`online_streams`.
+    ``set_background_band_gains(gains, edges=None)``, ``background_band_gains()`` and ``clear_background_band_gains()`` keep a
+    share of the background band by band, as :func:`online_streams` describes (here without ``slots``).
 
     ``last_frames(which="foreground", bands=None, out=None)`` returns the spectra of the frames the last ``push`` / ``finish``
     completed (``last_frame_range`` tells which), float32 magnitudes ``(T, number_channels, window_length / 2 + 1)`` or, with
@@ -329,6 +331,21 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     on. The gain is the slot's, not the stream's -- ``restart``, ``release``, ``finish_stream`` and ``import_stream`` leave it,
     and an exported state does not carry it --; ``background_gain(slot)`` reads it back. No host wait; a push in steady state
     costs the launches it always cost. ValueError for a value outside [0, 1] (NaN included) or a slot out of range.
+
+    ``set_background_band_gains(gains, edges=None, slots=None)`` keeps a share of the background BAND BY BAND: ``gains`` in [0, 1],
+    ``(n_bands,)`` for all named slots or ``(len(slots), n_bands)``, one per band of ``edges`` (``n_bands + 1`` ascending bin
+    edges in ``[0, window_length / 2 + 1]``; ``repet.band_edges`` fits) or, with ``edges=None``, one per bin; a set replaces the
+    slot's whole table and bins outside the edges get 0. The masked spectrum of every frame is multiplied by ``a[k] = float32(1
+    - g[k])`` where the inverse STFT fetches it, into a second, shaped background, and the foreground is ``x - a_s *
+    shaped_background`` with ``a_s`` the scalar gain above: the two multiply. The background, the mixture, ``last_frames``, the
+    mixture's and background's levels and an exported state do not change by a bit; 1 on every bin returns the input. A frame is
+    shaped, whole, with the table its slot had when the push (or finish) that completed it was made, so a change cross-fades
+    through the analysis window over one frame, and the frame carried over from the push before keeps its own table; a set on
+    a held slot applies from the frames after its ``resume``; a frame that arrives with ``import_stream`` takes the importing
+    slot's table. The table is the slot's, like the scalar gain. ``background_band_gains(slot)`` returns the float32 ``(F,)``
+    table last set (a host copy), ``clear_background_band_gains(slots=None)`` sets zeros. A set may come at any time: one
+    small launch, no host wait, ``last_emission`` stays valid. A handle that never set a table costs what it always cost; while
+    one is set a push enqueues one inverse-STFT launch more. Window lengths up to 4096 (sampling rates below about 100 kHz).
 
     ``last_levels(out=None)`` tells what the handle just did to every slot without pulling a signal to the host: for the
     samples the last ``push`` / ``finish`` emitted, per stream and channel the eight float64 values ``repet.LEVELS`` names --

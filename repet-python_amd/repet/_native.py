@@ -84,6 +84,44 @@ def background_gains(gain, count=None):
     return np.ascontiguousarray(g)
 
 
+def band_gain_rows(gains, edges, bins, count=None):
+    """``gains`` / ``edges`` of ``set_background_band_gains`` as what the library takes: ``(edges, g)`` with ``edges`` None (one
+    gain per bin, ``bins`` of them) or the int32 array of ``band_edge_array`` with at most ``bins`` bands, and ``g`` float32
+    ``(rows, n_bands)`` with ``rows`` 1, or ``count`` where one row per named slot was given. ValueError, before any device is
+    touched, for a value that is NaN, infinite or outside [0, 1] (checked on the float32 value the library takes), edges that
+    are not ascending bins in [0, bins], or a wrong size."""
+    if edges is not None:
+        edges = band_edge_array(edges)
+        if edges.size - 1 > bins or (edges < 0).any() or (edges > bins).any() or (np.diff(edges) < 0).any():
+            raise ValueError(f"edges are at most {bins} bands: ascending bin edges in [0, {bins}]")
+    n_bands = bins if edges is None else edges.size - 1
+    try:
+        g = np.asarray(gains, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"band gains must be numbers in [0, 1], not {gains!r}") from None
+    if g.ndim == 1:
+        g = g.reshape(1, -1)
+    if g.ndim != 2 or g.shape[1] != n_bands or (g.shape[0] != 1 and g.shape[0] != count):
+        what = f"({n_bands},)" + ("" if count is None else f" or ({count}, {n_bands})")
+        raise ValueError(f"band gains of shape {np.shape(gains)}: {what} is expected")
+    if not np.all((g >= 0) & (g <= 1)):
+        raise ValueError("band gains must lie in [0, 1] (NaN and infinities are refused)")
+    return edges, np.ascontiguousarray(g)
+
+
+def _set_band_gains(handle_of, slots, n_slots, gains, edges, bins, count):
+    """(the arguments are checked before the handle is looked at: ``handle_of`` returns it)"""
+    edges, g = band_gain_rows(gains, edges, bins, count)
+    check(lib().repet_online_set_background_band_gains(handle_of(), slots, n_slots, None if edges is None else ptr(edges), g.shape[1],
+                                                       ptr(g), g.shape[0]))
+
+
+def _get_band_gains(handle, slot, bins):
+    out = np.zeros(bins, dtype=np.float32)
+    check(lib().repet_online_background_band_gains(handle, slot, ptr(out), bins))
+    return out
+
+
 class Params(C.Structure):
     _fields_ = [("window_length", C.c_int32), ("step_length", C.c_int32), ("period_lo", C.c_int32),
                 ("period_hi", C.c_int32), ("cutoff_bins", C.c_int32), ("filter_order", C.c_int32),
@@ -229,6 +267,8 @@ _SIGNATURES = {
     "repet_select_run_result": (C.c_int, [C.c_int, C.c_int]),
     "repet_online_set_background_gain": (C.c_int, [_P, _P, C.c_int32, _P]),
     "repet_online_background_gain": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float)]),
+    "repet_online_set_background_band_gains": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32]),
+    "repet_online_background_band_gains": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "repet_ctx_set_background_gain": (C.c_int, [_P, C.c_float]),
     "repet_set_run_background_gain": (C.c_int, [C.c_int, C.c_float]),
     "repet_online_last_levels": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
@@ -1122,6 +1162,19 @@ class OnlineSeparator:
         check(lib().repet_online_background_gain(self._h, 0, C.byref(out)))
         return out.value
 
+    def set_background_band_gains(self, gains, edges=None):
+        """Keep a share of the background in the foreground band by band: ``gains`` in [0, 1], one per band of ``edges``
+        (``n_bands + 1`` ascending bin edges) or, without ``edges``, one per bin. See ``repet.online_streams``."""
+        _set_band_gains(lambda: self._h, None, 0, gains, edges, self._bins, None)
+
+    def background_band_gains(self):
+        """The per-bin gains last set, float32 ``(F,)`` (zeros: the plain foreground). A host copy: no device work."""
+        return _get_band_gains(self._h, 0, self._bins)
+
+    def clear_background_band_gains(self):
+        """Back to the plain foreground: every bin's gain 0."""
+        _set_band_gains(lambda: self._h, None, 0, np.zeros(self._bins, dtype=np.float32), None, self._bins, None)
+
     def export_stream(self):
         """A snapshot of the stream's state (a ``StreamState`` with a host payload); the stream goes on untouched. ValueError
         unless the samples pushed so far are a multiple of the hop."""
@@ -1403,6 +1456,29 @@ class OnlineStreams:
         out = C.c_float()
         check(lib().repet_online_background_gain(self._handle(), self._slot(slot), C.byref(out)))
         return out.value
+
+    def set_background_band_gains(self, gains, edges=None, slots=None):
+        """Keep a share of the background in the foreground of the named slots (None: every slot) band by band. ``gains`` in
+        [0, 1]: ``(n_bands,)`` for all named slots or ``(len(slots), n_bands)``; ``edges``: ``n_bands + 1`` ascending bin edges
+        in [0, F] (``repet.band_edges`` fits), or None for one gain per bin. A set replaces the slot's whole table; bins outside
+        the edges get 0. Frames completed from the next push on are shaped with it; see ``repet.online_streams``. At most one
+        small launch, no host wait. ValueError, with nothing changed, for a value outside [0, 1] (NaN included), bad edges, a
+        wrong size or a slot out of range."""
+        if slots is None:
+            _set_band_gains(self._handle, None, 0, gains, edges, self._bins, self._streams)
+            return
+        slots, arr = self._slot_list(slots)
+        _set_band_gains(self._handle, arr, len(slots), gains, edges, self._bins, len(slots))
+
+    def background_band_gains(self, slot):
+        """The per-bin gains last set for ``slot``, float32 ``(F,)`` (zeros: the plain foreground). A host copy: no device
+        work, no wait."""
+        slot = self._slot(slot)
+        return _get_band_gains(self._handle(), slot, self._bins)
+
+    def clear_background_band_gains(self, slots=None):
+        """Back to the plain foreground for the named slots (None: every slot): every bin's gain 0."""
+        self.set_background_band_gains(np.zeros(self._bins, dtype=np.float32), None, slots)
 
     def restart(self, slots):
         """Begin a new stream in every named slot: its sample 0 is the handle's sample ``samples_pushed``, which must be a

@@ -38,7 +38,12 @@ through the pinned buffer and one wait), whatever the chunks are.
 
 ``--frames frames|bands``: the one-handle cases with a ``last_frames`` call after every timed push, inside the clock, into a
 preallocated tensor on the device (no host wait of its own): ``frames`` the foreground magnitudes ``(S, T, C, F)``, ``bands`` the
-foreground's energies in the 32 bands of ``repet.band_edges(fs, 32)``."""
+foreground's energies in the 32 bands of ``repet.band_edges(fs, 32)``.
+
+``--band-gains N``: the one-handle cases with ``set_background_band_gains`` of N mel bands (``repet.band_edges(fs, N)``) with
+distinct gains made right after the open, so every timed push carries the second, shaped inverse STFT (use it with ``--which
+foreground`` or ``both``). ``--band-gains-change-every K`` (with it): the bands are set again, with the gains rotated, before
+every K-th timed push (outside the clock), so those pushes also bring the tables up to date."""
 import argparse
 import json
 import sys
@@ -64,7 +69,7 @@ def stats(lat_s, n, fs):
 
 
 def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None,
-               out_dtype=None, frames=None):
+               out_dtype=None, frames=None, band_gains=0, band_every=0):
     import ctypes
     import torch
     from repet import _native
@@ -83,6 +88,10 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
     h = repet.online_streams(fs, ch, S, max_push_samples=n, start_length=start_length)
     if gain is not None:
         h.set_background_gain(gain)
+    if band_gains > 0:
+        band_edges = repet.band_edges(fs, band_gains)
+        band_values = (np.arange(band_gains) + 1.0) / (band_gains + 1.0)
+        h.set_background_band_gains(band_values, band_edges)
     if start_length is not None:
         warm_s = start_length + 0.5                            # past the start length, far from a full buffer
     pos = 0
@@ -106,6 +115,8 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
             break
         if gain is not None and gain_every > 0 and k % gain_every == 0:
             h.set_background_gain((gain + 0.01 * (k + 1)) % 1.0)
+        if band_gains > 0 and band_every > 0 and k % band_every == 0:
+            h.set_background_band_gains(np.roll(band_values, k + 1), band_edges)
         t0 = time.perf_counter()
         h.push(src[:, pos:pos + n], which=which, **as_dtype)
         if levels == "device":
@@ -379,6 +390,10 @@ def main():
                     help="a levels call after every timed push of the one-handle cases, inside the clock (see above)")
     ap.add_argument("--frames", choices=["frames", "bands"], default=None,
                     help="a last_frames call after every timed push of the one-handle cases, inside the clock (see above)")
+    ap.add_argument("--band-gains", type=int, default=0, metavar="N",
+                    help="set_background_band_gains of N mel bands with distinct gains after the open (one-handle cases)")
+    ap.add_argument("--band-gains-change-every", type=int, default=0, metavar="K",
+                    help="with --band-gains: set the bands again before every K-th timed push")
     ap.add_argument("--out-dtype", choices=["float64", "float32", "int16", "float16", "bfloat16"], default=None,
                     help="the hop-sized one-handle device pushes fill out= tensors of this dtype (default: fresh float64 results)")
     args = ap.parse_args()
@@ -426,6 +441,9 @@ def main():
         result["out_dtype"] = args.out_dtype
     if args.frames is not None:
         result["frames"] = args.frames
+    if args.band_gains > 0:
+        result["band_gains"] = args.band_gains
+        result["band_gains_change_every"] = args.band_gains_change_every
     for S in streams:
         xs = stream_signals(S, seconds, fs, ch)
         for hops in hops_list:
@@ -433,7 +451,8 @@ def main():
             for which in args.which.split(","):
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
                 case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
-                                       args.gain_change_every, args.levels, args.out_dtype, args.frames)
+                                       args.gain_change_every, args.levels, args.out_dtype, args.frames, args.band_gains,
+                                       args.band_gains_change_every)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
                                                             gain=args.background_gain, gain_every=args.gain_change_every,
