@@ -678,6 +678,43 @@ int repet_online_set_background_band_gains(repet_online* h, const int32_t* slots
                                            const float* gains, int32_t gains_rows);
 int repet_online_background_band_gains(repet_online* h, int32_t slot, float* out, int32_t capacity);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) The same share of the background BAND BY BAND for the
+ * TENSOR calls: a context (and the per-thread context of repet_run_device) keeps one table per clip for the whole clip -- the
+ * statement above without the frame rule. With a[k] = (float)(1.0 - (double)g[k]) the SHAPED background of a clip is the
+ * variant's own inverse STFT with the masked spectrum Y_j[k] = fl(m_j[k] * X_j[k]) taken as fl(a[k] * Y_j[k]) (two fp32
+ * roundings per component, the first the plain path's; bin N - k with bin k's factor; the same overlap-add, window sum,
+ * trimming and centring, and for `extended` the same triangular cross-fade of the segments), and the foreground is
+ * fma(-a_s, shaped_bg, x) in float64, a_s from repet_ctx_set_background_gain: the two gains multiply. The background, the
+ * mixture, the MIX / BG / LIVE / NONFINITE level fields, repet_ctx_download, repet_ctx_download_foreground,
+ * repet_ctx_result_wav, repet_ctx_spectrogram, the similar-frame lists and the periods do not change by a bit; FG_ENERGY /
+ * FG_PEAK measure the shaped foreground; g = 1 on every bin returns the input for finite input. A table that is all zero is
+ * no table: the run enqueues the plain path and its foreground is the plain one bit for bit.
+ * WHICH TABLE A RUN GETS: the one in force when repet_ctx_execute(_async) is enqueued. A set or clear afterwards changes the
+ * next run; the result already made keeps its shaped background -- for repet_ctx_download_device_strided with
+ * REPET_OUT_FOREGROUND and repet_ctx_result_levels_device, in all five destination dtypes -- until the next execute or upload.
+ * COST: under a table every inverse-STFT launch of the variant is followed by one more, with the factor rows beside the mask
+ * plane, the repeating-segment model or the masked-in-place spectrum the first one read, into a second result buffer that
+ * exists only once a table was set. A context on which none was set enqueues what it always did.
+ * repet_ctx_set_background_band_gains : edges and gains as for repet_online_set_background_band_gains, F from window_length.
+ *                   gains_rows is 1, or the number of clips of the next upload (row b for clip b). gains == NULL or
+ *                   n_bands == 0 clears. REPET_ERR_BAD_ARG, with nothing changed, for a gain that is NaN or outside [0, 1],
+ *                   bad edges, a window_length that is no power of two in [64, 8192] or a wrong size; REPET_ERR_LIMIT for a
+ *                   window_length above 4096 (its inverse kernel has no masked form). The factor rows are copied on the
+ *                   context's stream, behind the runs enqueued so far, and the call waits for that copy.
+ *                   An execute is refused with REPET_ERR_BAD_ARG before anything is enqueued when params->window_length is
+ *                   not the table's, or gains_rows is neither 1 nor the number of resident clips;
+ *                   repet_ctx_execute_extended_range(_async) is refused while a table that is not all zero is set (the
+ *                   shards of a multi-GPU `extended` do not take one).
+ * repet_ctx_background_band_gains     : the F gains of `clip` (any clip where one row was given) into out (capacity >= F
+ *                   floats), from the host's copy: no device work. REPET_ERR_BAD_ARG when no table is set.
+ * repet_set_run_background_band_gains : the same set or clear for the calling thread's repet_run_device context of `device`,
+ *                   with the lifetime repet_set_run_background_gain has. */
+int repet_ctx_set_background_band_gains(repet_ctx* ctx, int32_t window_length, const int32_t* edges, int32_t n_bands,
+                                        const float* gains, int32_t gains_rows);
+int repet_ctx_background_band_gains(repet_ctx* ctx, int32_t clip, float* out, int32_t capacity);
+int repet_set_run_background_band_gains(int device, int32_t window_length, const int32_t* edges, int32_t n_bands,
+                                        const float* gains, int32_t gains_rows);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) LEVELS of what a live handle or a tensor call emitted:
  * how loud the input, the background and the foreground of every slot were, whether anything repeating was found, whether a
  * stream clips or carries NaN -- reduced on the device, so that a server need not pull three signals to the host per hop. For

@@ -174,10 +174,11 @@ struct IstftOlaArgs {
     // channel groups (launch_istft_ola splits a clip with more channels than one workgroup's LDS holds): this launch writes
     // channels [out_chan0, out_chan0 + n_channels) of an output interleaved over out_channels (0: n_channels, from 0)
     int32_t out_channels, out_chan0;
-    // (nullable, the live handles' shaped foreground; never with M or model) per-bin factors of the spectrum Y, the same for
+    // (nullable, the shaped foreground of a live handle or a tensor call) per-bin factors of the spectrum Y, the same for
     // every channel: batch slot b reads two rows of FS floats at G + b * G_batch_stride, the first for the frames t < G_split
     // (the frame carried over from the call before), the second for the others. Applied where the spectrum is fetched, with
-    // the access widths and the rounded products of the mask plane M. W <= 4096.
+    // the access widths and the rounded products of the mask plane M. W <= 4096. Beside M (block and register kernels) or
+    // beside a model (register kernel) the factor multiplies the already rounded masked value: a second rounded product.
     const float* G; int64_t G_batch_stride, G_split;
 };
 hipError_t launch_istft_ola(const IstftOlaArgs& a, hipStream_t s);

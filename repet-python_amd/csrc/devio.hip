@@ -1321,6 +1321,7 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     c->input_unscanned = true;
     c->n_samples = n; c->n_channels = ch; c->n_clips = n_clips; c->clip_base = 0;
     c->win_total = 0; c->win_offset = 0;
+    c->result_shaped = false;
     return REPET_OK;
 }
 
@@ -1371,7 +1372,7 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
         gain.scalar = true; gain.a = c->result_a;
         HIP_TRY(launch_stream_emit(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
                                    c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels, dtype, &d, 1,
-                                   c->stream, c->result_gain ? &gain : nullptr));
+                                   c->stream, c->result_gain ? &gain : nullptr, c->shaped_bg()));
     } else if (count > 0) {
         HIP_TRY(launch_stream_egress(c->out.as<float>(), c->n_clips, c->n_samples, c->n_channels, dst, dtype, strides, c->stream));
     }
@@ -1400,7 +1401,7 @@ int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream)
     const hipError_t e = launch_stream_levels(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
                                               c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels,
                                               static_cast<double*>(dst), partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream,
-                                              c->result_gain ? &gain : nullptr);
+                                              c->result_gain ? &gain : nullptr, c->shaped_bg());
     if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
     HIP_TRY(e);
     HIP_TRY(hipEventRecord(c->io_done, c->stream));

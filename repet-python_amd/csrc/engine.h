@@ -120,7 +120,17 @@ struct repet_ctx {
     int result_which = REPET_OUT_BACKGROUND;   // what repet_ctx_download_device_strided writes (repet_ctx_select_result)
     // repet_ctx_set_background_gain: the foreground it writes is x - result_a * bg, result_a = (float)(1 - gain); off: x - bg as ever
     float result_a = 1.f; bool result_gain = false;
-    int online_start = 0;         // simonline: start_frames of this context (repet_ctx_set_online_start; 0: buffer_frames, the reference)
+    // repet_ctx_set_background_band_gains: a table g[row][k < F] (host copy band_g; band_rows 0: never set or cleared) and
+    // its factors a = (float)(1 - (double)g) on the device, band_tab[row][FS] (written on the context's stream where the
+    // table is set, so behind every run enqueued before). A run enqueued while a table with a gain other than 0 is set
+    // (band_any) is `run_shaped`: behind every inverse STFT of the pipeline a second one, with the factor rows beside whatever
+    // mask form the first took, writes the SHAPED background into out_fg. result_shaped: out_fg belongs to the resident
+    // result -- the foreground and its levels are formed from it (bg_fg of the emission kernels) until the next execute or upload.
+    std::vector<float> band_g; int32_t band_W = 0, band_rows = 0; bool band_any = false;
+    DevBuf band_tab, out_fg;
+    bool run_shaped = false, result_shaped = false;
+    const float* shaped_bg() const { return result_shaped ? static_cast<const float*>(out_fg.p) : nullptr; }
+    int online_start = 0;        // simonline: start_frames of this context (repet_ctx_set_online_start; 0: buffer_frames, the reference)
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
     DevBuf X, V, Vn, P, S, band, beat, idx, cnt, periods, win_periods, frames, tmp_a, tmp_b, tmp_c;
@@ -264,6 +274,12 @@ MaskArgs mask_args(repet_ctx* c, const Geo& g, int cutoff);
 void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr);
 int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
               bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr = nullptr);
+// the shaped background of a run under band gains (engine.hip, beside run_istft): the checks and the buffer before anything is
+// enqueued, the twin of an inverse STFT just enqueued, its timing mark, the twin of a clear of `out` (values, not samples)
+int begin_shaped(repet_ctx* c, const repet_params* p);
+int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain);
+void mark_shaped(repet_ctx* c, double bytes);
+int clear_shaped(repet_ctx* c, int64_t first_value, int64_t n_values);
 // device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events
 int check_strides(const int64_t* strides);
 int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch);

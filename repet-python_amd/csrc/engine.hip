@@ -428,6 +428,52 @@ int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_
     if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
     HIP_TRY(e);
     mark(c, "istft_ola", (mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n_out * g.C, 0);      // (a model: a third of a plane at most)
+    RP_TRY(launch_istft_shaped(c, a));
+    mark_shaped(c, (mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n_out * g.C);
+    return REPET_OK;
+}
+
+// The shaped twin of an inverse STFT the pipeline has just enqueued (repet_ctx::run_shaped; nothing otherwise): the same
+// arguments -- mask plane, model or masked-in-place spectrum, batch, cross-fade, channel groups -- with the table's factor rows
+// beside them, into out_fg instead of out. One row for every frame (G_split beyond any frame). A batch of CLIPS (no
+// cross-fade) takes a row per clip where the table has one; the segments of `extended` and the clips a batch context works
+// through one by one take the row of their clip.
+int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain) {
+    if (!c->run_shaped) return REPET_OK;
+    IstftOlaArgs a = plain;
+    const bool clips = a.n_batch > 0 && a.accumulate_weighted == 0;
+    const int64_t row = (!clips && c->band_rows > 1 && c->n_samples > 0 && c->clip_base > 0) ? c->clip_base / c->n_samples : 0;
+    if (row >= c->band_rows || (clips && c->band_rows > 1 && a.n_batch > c->band_rows)) return fail(REPET_ERR_BAD_ARG, "band gains: fewer rows than clips");
+    a.out = c->out_fg.as<float>();
+    a.G = c->band_tab.as<float>() + row * a.FS;
+    a.G_batch_stride = clips && c->band_rows > 1 ? a.FS : 0;
+    a.G_split = INT64_MAX;
+    const hipError_t e = launch_istft_ola(a, c->stream);
+    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
+    HIP_TRY(e);
+    return REPET_OK;
+}
+
+void mark_shaped(repet_ctx* c, double bytes) {
+    if (c->run_shaped) mark(c, "istft_ola_shaped", bytes, 0);
+}
+
+// a clear of `out` the pipeline enqueues (extended), repeated for the shaped background
+int clear_shaped(repet_ctx* c, int64_t first_value, int64_t n_values) {
+    if (!c->run_shaped || n_values <= 0) return REPET_OK;
+    HIP_TRY(hipMemsetAsync(c->out_fg.as<float>() + first_value, 0, (size_t)n_values * sizeof(float), c->stream));
+    return REPET_OK;
+}
+
+// what an execute does about the table before it enqueues anything
+int begin_shaped(repet_ctx* c, const repet_params* p) {
+    c->run_shaped = false;
+    if (!c->band_any) return REPET_OK;               // never set, cleared, or all zero: the plain path
+    if (p->window_length != c->band_W) return fail(REPET_ERR_BAD_ARG, "band gains were set for another window_length than this run's");
+    if (c->band_rows != 1 && c->band_rows != c->n_clips) return fail(REPET_ERR_BAD_ARG, "band gains: one row, or one per resident clip");
+    const int64_t count = c->n_samples * c->n_channels * c->n_clips;
+    HIP_TRY(c->out_fg.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
+    c->run_shaped = true;
     return REPET_OK;
 }
 
@@ -595,6 +641,7 @@ int repet_ctx_destroy(repet_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->aux) {
         c->aux->audio.release(); c->aux->out.release();           // borrowed: just forgotten
+        c->aux->out_fg.release(); c->aux->band_tab.release();
         repet_ctx_destroy(c->aux);
         c->aux = nullptr;
         for (hipEvent_t e : {c->aux_start, c->aux_main_done, c->aux_done}) if (e) (void)hipEventDestroy(e);
@@ -604,7 +651,7 @@ int repet_ctx_destroy(repet_ctx* c) {
                       &c->refine_stats, &c->R, &c->Vs, &c->rank_codes, &c->code_planes, &c->median_codes, &c->tiles_big,
                       &c->audio_lo, &c->redo_list, &c->redo_flag, &c->u64, &c->u64_gen, &c->exact_scratch,
                       &c->lite_list, &c->lite_flag, &c->lite_records, &c->frame_list, &c->frame_flag,
-                      &c->seg, &c->nonfinite_word, &c->levels_ws,
+                      &c->seg, &c->nonfinite_word, &c->levels_ws, &c->band_tab, &c->out_fg,
                       &c->idx, &c->cnt, &c->periods, &c->win_periods, &c->frames, &c->tmp_a, &c->tmp_b, &c->tmp_c})
         b->release();
     for (auto& kv : c->tile_lists) kv.second.buf.release();
@@ -714,6 +761,7 @@ int repet_ctx_upload_batch(repet_ctx* c, const void* audio, int dtype, int64_t n
     c->n_clips = n_clips;
     c->clip_base = 0;
     c->win_total = 0; c->win_offset = 0;
+    c->result_shaped = false;
     return REPET_OK;
 }
 
@@ -745,6 +793,7 @@ int repet_ctx_upload_device_split(repet_ctx* c, const float* dev_audio, const fl
     c->ring.lo_in_flight = false;              // (the stream waited for it above and is idle now)
     c->n_samples = n; c->n_channels = ch; c->n_clips = n_clips; c->clip_base = 0;
     c->win_total = 0; c->win_offset = 0;
+    c->result_shaped = false;
     return REPET_OK;
 }
 
@@ -871,12 +920,15 @@ int repet_ctx_execute(repet_ctx* c, int algo, const repet_params* p, repet_timin
     RP_TRY(check_params(p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     DeviceGuard guard(c->device);
+    RP_TRY(begin_shaped(c, p));
     begin_timing(c, timing);
     c->last_algo = algo;
     c->last_n_periods = 0;
     c->last_idx_rows = 0;
     c->last_idx_batch = 1;
     int rc = run_algo(c, algo, p);
+    c->result_shaped = rc == REPET_OK && c->run_shaped;
+    c->run_shaped = false;
     hipError_t e = hipStreamSynchronize(c->stream);
     if (rc == REPET_OK && e != hipSuccess) rc = fail(REPET_ERR_HIP, std::string("execute: ") + hipGetErrorString(e));
     if (rc == REPET_OK) end_timing(c);
@@ -889,6 +941,7 @@ int repet_ctx_execute_async(repet_ctx* c, int algo, const repet_params* p) {
     RP_TRY(check_params(p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     DeviceGuard guard(c->device);
+    RP_TRY(begin_shaped(c, p));
     c->timing = nullptr;
     const bool timed = c->series_on && c->series_steps < c->series_cap;
     if (timed) {
@@ -900,6 +953,8 @@ int repet_ctx_execute_async(repet_ctx* c, int algo, const repet_params* p) {
     c->last_idx_rows = 0;
     c->last_idx_batch = 1;
     const int rc = run_algo(c, algo, p);
+    c->result_shaped = rc == REPET_OK && c->run_shaped;
+    c->run_shaped = false;
     if (timed && c->timing) {
         c->series_marks = c->n_marks;
         c->series_steps++;
@@ -971,7 +1026,9 @@ int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
     if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
+    if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
     DeviceGuard guard(c->device);
+    c->result_shaped = false;
     begin_timing(c, timing);
     c->last_algo = REPET_EXTENDED;
     c->last_n_periods = 0;
@@ -989,7 +1046,9 @@ int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, 
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
     if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
+    if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
     DeviceGuard guard(c->device);
+    c->result_shaped = false;
     c->timing = nullptr;
     c->last_algo = REPET_EXTENDED;
     c->last_n_periods = 0;
@@ -1029,6 +1088,7 @@ int repet_ctx_upload_wav(repet_ctx* c, const void* file_bytes, int64_t n_bytes, 
     c->input_unscanned = w.format != 1;
     c->n_samples = w.n_samples; c->n_channels = w.n_channels; c->n_clips = 1; c->clip_base = 0;
     c->win_total = 0; c->win_offset = 0;
+    c->result_shaped = false;
     c->last_fs = w.sampling_frequency;
     return REPET_OK;
 }
@@ -1182,6 +1242,71 @@ int repet_select_run_result(int device, int which) {
     repet_ctx* c = nullptr;
     RP_TRY(thread_ctx(device, &c));
     return repet_ctx_select_result(c, which);
+}
+
+int repet_ctx_set_background_band_gains(repet_ctx* c, int32_t window_length, const int32_t* edges, int32_t n_bands, const float* gains,
+                                        int32_t gains_rows) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (!gains || n_bands == 0) {                       // clear: the next run takes the plain path
+        c->band_g.clear(); c->band_W = 0; c->band_rows = 0; c->band_any = false;
+        return REPET_OK;
+    }
+    if (window_length < 64 || window_length > 8192 || (window_length & (window_length - 1)))
+        return fail(REPET_ERR_BAD_ARG, "band gains: window_length must be a power of two in [64, 8192]");
+    const int32_t F = window_length / 2 + 1;
+    if (gains_rows < 1) return fail(REPET_ERR_BAD_ARG, "band gains: one row, or one per clip of the next upload");
+    if (edges) {
+        if (n_bands < 1 || n_bands > F) return fail(REPET_ERR_BAD_ARG, "band gains: between one band and one per bin");
+        for (int32_t k = 0; k <= n_bands; ++k)
+            if (edges[k] < 0 || edges[k] > F || (k > 0 && edges[k] < edges[k - 1]))
+                return fail(REPET_ERR_BAD_ARG, "band gains: band edges are ascending bins in [0, window_length / 2 + 1]");
+    } else if (n_bands != F) {
+        return fail(REPET_ERR_BAD_ARG, "band gains: without edges there is one gain per bin (window_length / 2 + 1 of them)");
+    }
+    for (int64_t k = 0; k < (int64_t)gains_rows * n_bands; ++k)
+        if (!(gains[k] >= 0.f && gains[k] <= 1.f)) return fail(REPET_ERR_BAD_ARG, "band gains: a band gain lies in [0, 1]");
+    if (window_length > 4096) return fail(REPET_ERR_LIMIT, "band gains need a window_length of at most 4096");
+    // per bin on the host: the copy that is read back, and the factors a = (float)(1 - (double)g) the inverse STFT multiplies
+    // by (pad bins: 1; never fetched)
+    const int32_t FS = (int32_t)round_up(F, kFreqAlign);
+    std::vector<float> g((size_t)gains_rows * F, 0.f), a((size_t)gains_rows * FS, 1.f);
+    bool any = false;
+    for (int32_t r = 0; r < gains_rows; ++r)
+        for (int32_t b = 0; b < n_bands; ++b) {
+            const float v = gains[(int64_t)r * n_bands + b];
+            const int32_t k0 = edges ? edges[b] : b, k1 = edges ? edges[b + 1] : b + 1;
+            for (int32_t k = k0; k < k1; ++k) g[(size_t)r * F + k] = v;
+            any = any || (v != 0.f && k1 > k0);
+        }
+    for (int32_t r = 0; r < gains_rows; ++r)
+        for (int32_t k = 0; k < F; ++k) a[(size_t)r * FS + k] = (float)(1.0 - (double)g[(size_t)r * F + k]);
+    DeviceGuard guard(c->device);
+    // on the context's stream: behind every run enqueued so far, which keeps the table it was enqueued under. The call waits
+    // for the copy (a few KB), so the host rows may go when it returns.
+    HIP_TRY(c->band_tab.ensure(a.size() * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(c->band_tab.p, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->band_g.swap(g); c->band_W = window_length; c->band_rows = gains_rows; c->band_any = any;
+    return REPET_OK;
+}
+
+int repet_ctx_background_band_gains(repet_ctx* c, int32_t clip, float* out, int32_t capacity) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (!out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->band_rows == 0) return fail(REPET_ERR_BAD_ARG, "band gains: no table is set on this context");
+    if (clip < 0 || (c->band_rows > 1 && clip >= c->band_rows)) return fail(REPET_ERR_BAD_ARG, "band gains: clip out of range");
+    const int32_t F = c->band_W / 2 + 1;
+    if (capacity < F) return fail(REPET_ERR_BAD_ARG, "band gains: output capacity too small (window_length / 2 + 1 values)");
+    const float* g = c->band_g.data() + (size_t)(c->band_rows > 1 ? clip : 0) * F;
+    for (int32_t k = 0; k < F; ++k) out[k] = g[k];
+    return REPET_OK;
+}
+
+int repet_set_run_background_band_gains(int device, int32_t window_length, const int32_t* edges, int32_t n_bands, const float* gains,
+                                        int32_t gains_rows) {
+    repet_ctx* c = nullptr;
+    RP_TRY(thread_ctx(device, &c));
+    return repet_ctx_set_background_band_gains(c, window_length, edges, n_bands, gains, gains_rows);
 }
 
 int repet_set_run_background_gain(int device, float gain) {

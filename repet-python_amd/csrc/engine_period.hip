@@ -95,10 +95,13 @@ int run_original(repet_ctx* c, const repet_params* p, int64_t offset, int64_t n,
         if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
         HIP_TRY(e);
         mark(c, "istft_ola", B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C), 0);
+        RP_TRY(launch_istft_shaped(c, a));
+        mark_shaped(c, B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C));
     } else {
         // segments that overlap in the output must not be accumulated concurrently: one launch per residue
         // class modulo ceil(n / hop) (2 for the default 10 s / 5 s), each class writes disjoint samples
         const int classes = hop > 0 ? (int)ceil_div(n, hop) : 1;
+        std::vector<IstftOlaArgs> twins;                          // (band gains: the same launches again, behind the mark)
         for (int k = 0; k < classes && k < B; ++k) {
             IstftOlaArgs a{};
             a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.W = g.W;
@@ -115,8 +118,11 @@ int run_original(repet_ctx* c, const repet_params* p, int64_t offset, int64_t n,
             hipError_t e = launch_istft_ola(a, c->stream);
             if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
             HIP_TRY(e);
+            if (c->run_shaped) twins.push_back(a);
         }
         mark(c, "istft_ola", B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C), 0);
+        for (const IstftOlaArgs& a : twins) RP_TRY(launch_istft_shaped(c, a));
+        mark_shaped(c, B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C));
     }
     c->last_T = T;
     return REPET_OK;
@@ -179,6 +185,7 @@ int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64
         if (n_seg == 1) return exec_original(c, p);
         if (!c->win_skip_clear)
             HIP_TRY(hipMemsetAsync(c->out.as<float>() + c->clip_base * c->n_channels, 0, (size_t)N * c->n_channels * sizeof(float), c->stream));
+        if (!c->win_skip_clear) RP_TRY(clear_shaped(c, c->clip_base * c->n_channels, N * c->n_channels));
         return REPET_OK;
     }
     const int64_t O = L - Hs;
@@ -202,6 +209,9 @@ int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64
         float* o = c->out.as<float>() + c->clip_base * c->n_channels;
         if (s0 > 0) HIP_TRY(hipMemsetAsync(o, 0, (size_t)s0 * c->n_channels * sizeof(float), c->stream));
         if (s1 < N) HIP_TRY(hipMemsetAsync(o + s1 * c->n_channels, 0, (size_t)(N - s1) * c->n_channels * sizeof(float), c->stream));
+        // (the shaped twins take the kernels the plain launches take, so they store where those store)
+        if (s0 > 0) RP_TRY(clear_shaped(c, c->clip_base * c->n_channels, s0 * c->n_channels));
+        if (s1 < N) RP_TRY(clear_shaped(c, (c->clip_base + s1) * c->n_channels, (N - s1) * c->n_channels));
     }
     // the equal-length segments go through every stage as ONE batch -- in bounded batches, so that the workspaces of an
     // hours-long recording stay at a few GB (a segment's spectra are about 15 MB at 44.1 kHz stereo)
@@ -233,6 +243,9 @@ int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64
         repet_ctx* x = c->aux;
         x->audio.borrow(c->audio.p, c->audio.cap);
         x->out.borrow(c->out.p, c->out.cap);
+        // band gains: the last segment's twin goes into the same shaped background, with the clip's row of the same table
+        x->run_shaped = c->run_shaped; x->band_rows = c->band_rows;
+        x->out_fg.borrow(c->out_fg.p, c->out_fg.cap); x->band_tab.borrow(c->band_tab.p, c->band_tab.cap);
         x->n_samples = c->n_samples; x->n_channels = c->n_channels; x->n_clips = 1; x->clip_base = c->clip_base;
         x->timing = nullptr;
         x->strict = c->strict; x->input_not_finite = c->input_not_finite; x->input_unscanned = c->input_unscanned;
@@ -256,6 +269,7 @@ int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64
         const int rc = run_original(x, p, last * Hs, N - last * Hs, 1, 0, c->periods.as<int32_t>() + uniform, true, (int)last, (int)count, O);
         x->pre_synthesis = nullptr;
         x->stream = aux_stream;
+        x->run_shaped = false;
         if (rc != REPET_OK) { (void)hipStreamSynchronize(aux_stream); (void)hipStreamSynchronize(c->stream); return rc; }
         mark(c, "last_segment", 0, 0);
     } else {

@@ -743,8 +743,10 @@ __device__ __forceinline__ void inverse_tables(InverseTables<W>& t, const float2
 template <int W>
 struct SpectrumRegs { float2 xk[(W / 2 + kFftThreads - 1) / kFftThreads], xc[(W / 2 + kFftThreads - 1) / kFftThreads]; };
 
-template <int W, bool MASKED>
-__device__ __forceinline__ void fetch_spectrum(SpectrumRegs<W>& r, const float2* __restrict__ Y, const float* __restrict__ M) {
+// BESIDE: factor rows G next to the mask plane (a tensor call's shaped background): a second rounded product, on the masked value
+template <int W, bool MASKED, bool BESIDE = false>
+__device__ __forceinline__ void fetch_spectrum(SpectrumRegs<W>& r, const float2* __restrict__ Y, const float* __restrict__ M,
+                                               const float* __restrict__ G = nullptr) {
     constexpr int N = W / 2;
 #pragma unroll
     for (int i = 0; i < (N + kFftThreads - 1) / kFftThreads; ++i) {
@@ -757,6 +759,11 @@ __device__ __forceinline__ void fetch_spectrum(SpectrumRegs<W>& r, const float2*
                 // ones in the last bit, and the stream from the offline result)
                 xk = make_float2(mul_rounded(xk.x, mk), mul_rounded(xk.y, mk));
                 xc = make_float2(mul_rounded(xc.x, mc), mul_rounded(xc.y, mc));
+                if constexpr (BESIDE) {
+                    const float gk = G[k], gc = G[N - k];
+                    xk = make_float2(mul_rounded(xk.x, gk), mul_rounded(xk.y, gk));
+                    xc = make_float2(mul_rounded(xc.x, gc), mul_rounded(xc.y, gc));
+                }
             }
             r.xk[i] = xk; r.xc[i] = xc;
         }
@@ -790,7 +797,8 @@ struct __attribute__((packed, aligned(4))) Float4U { float x, y, z, w; };    // 
 
 // accumulate_weighted: 0 = store, 1 = out += w y, 2 = out = w y (a class of segments that tiles its span and is the first
 // to write there: no read of the cleared buffer)
-// MASKED: 0 no mask, 1 a mask plane M, 3 factor rows G (one per batch slot and row class, every channel's: fetched as M is)
+// MASKED: 0 no mask, 1 a mask plane M, 3 factor rows G (one per batch slot and row class, every channel's: fetched as M is),
+// 5 the plane with factor rows beside it
 template <int W, int MASKED>
 __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <= 2048 ? REPET_ISTFT_MIN_WAVES : 1, 8))) void istft_ola_kernel(IstftOlaArgs a, int run) {
     constexpr int N = W / 2;          // complex points per frame = samples per hop (H = W/2)
@@ -812,8 +820,8 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
     if (a.n_batch > 0) {
         const int j = a.batch_first + (int)blockIdx.y * a.batch_step;
         a.Y += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
-        if (MASKED == 1) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
-        if (MASKED == 3) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
+        if (MASKED == 1 || MASKED == 5) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
+        if (MASKED == 3 || MASKED == 5) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
         a.out_offset += (int64_t)j * a.batch_out_stride;
         a.fade_in = j > 0 ? a.overlap : 0;
         a.fade_out = a.overlap;
@@ -848,8 +856,9 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
         for (int c = 0; c < C; ++c) {
             const float2* z = buf0;
             if (have) {
-                fetch_spectrum<W, MASKED != 0>(spec, a.Y + c * a.chan_stride + t * a.FS,
-                                               MASKED == 1 ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr);
+                fetch_spectrum<W, MASKED != 0, MASKED == 5>(spec, a.Y + c * a.chan_stride + t * a.FS,
+                                                            (MASKED == 1 || MASKED == 5) ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr,
+                                                            MASKED == 5 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr);
                 repack_spectrum<W>(spec, tables, buf0);
                 __syncthreads();
                 z = fft_lds_regs<N, true>(buf0, buf1, tables.ft);
@@ -1371,8 +1380,8 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s, int path, Fft
     // the same for a mask PLANE at the longest window: istft_ola_kernel<8192, masked> does not exist (no registers to spare,
     // ensure_spectra keeps the mask in X there), and the plain kernel would ignore the plane
     if (a.M && a.W > 4096) return hipErrorInvalidValue;
-    // factor rows: the block kernel's (and the register kernel's above); never beside a mask plane, and not at the longest window
-    if (a.G && (a.M || a.W > 4096)) return hipErrorInvalidValue;
+    // factor rows: the block kernel's (and the register kernel's above), alone or beside a mask plane; not at the longest window
+    if (a.G && a.W > 4096) return hipErrorInvalidValue;
     const bool wave_takes = a.out_channels == 0 && a.W <= 4096 && a.n_channels <= 4 && a.n_channels != 3 && !a.G;
     if (path == kFftPathWave && !wave_takes) return hipErrorInvalidValue;
     if ((path == kFftPathWave || (path == kFftPathAuto && use_wave_kernels())) && wave_takes) {
@@ -1420,7 +1429,8 @@ hipError_t launch_istft_ola(const IstftOlaArgs& a0, hipStream_t s, int path, Fft
             report(info, name, kFftPathBlock, run, slots, ceil_div(hops, run) * batches, hops);
         };
         if constexpr (Wc <= 4096) {
-            if (a.M) go(&istft_ola_kernel<Wc, 1>, "istft_ola_kernel<masked>");
+            if (a.M && a.G) go(&istft_ola_kernel<Wc, 5>, "istft_ola_kernel<masked, shaped>");
+            else if (a.M) go(&istft_ola_kernel<Wc, 1>, "istft_ola_kernel<masked>");
             else if (a.G) go(&istft_ola_kernel<Wc, 3>, "istft_ola_kernel<shaped>");
             else go(&istft_ola_kernel<Wc, 0>, "istft_ola_kernel<plain>");
         } else {

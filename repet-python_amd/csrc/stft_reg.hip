@@ -464,7 +464,9 @@ constexpr int kInvWaves = 12;
 constexpr int kInvLdsFloat2 = kInvWaves * kExPitch + kTwFloat2 + kRegN + 2 * 8 * 64;    // + split twiddles [N] + carry [2][8][64]
 
 template <int C, int MASKED>      // C = 1, 2; MASKED: 0 no mask, 1 a mask plane M, 2 magnitudes + repeating-segment model,
-                                  // 3 factor rows G (one per batch slot and row class, every channel's: fetched and applied as M is)
+                                  // 3 factor rows G (one per batch slot and row class, every channel's: fetched and applied as M is),
+                                  // 5 / 6 the plane / the model with factor rows BESIDE it (a tensor call's shaped background): the
+                                  // factor multiplies the already rounded masked value, a second rounded product
 __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaArgs a, int rounds) {
     constexpr int N = kRegN;          // samples per hop = complex FFT length
     extern __shared__ __attribute__((aligned(16))) float2 inv_lds[];
@@ -478,9 +480,9 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
     if (a.n_batch > 0) {
         const int j = a.batch_first + (int)blockIdx.y * a.batch_step;
         a.Y += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
-        if (MASKED == 1) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
-        if (MASKED == 3) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
-        if (MASKED == 2) {
+        if (MASKED == 1 || MASKED == 5) a.M += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.batch_spec_stride;
+        if (MASKED == 3 || MASKED == 5 || MASKED == 6) a.G += (int64_t)(a.batch_local0 + (int)blockIdx.y * a.batch_step) * a.G_batch_stride;
+        if (MASKED == 2 || MASKED == 6) {
             const int local = a.batch_local0 + (int)blockIdx.y * a.batch_step;
             a.model += (int64_t)local * a.model_batch_stride;
             a.periods += local;
@@ -501,7 +503,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
     const RegTwiddles tw{tw_lds, tw_lds + 16 * 64};
     __syncthreads();
 
-    const int period = MASKED == 2 ? __builtin_amdgcn_readfirstlane(a.periods[0]) : 1;
+    const int period = (MASKED == 2 || MASKED == 6) ? __builtin_amdgcn_readfirstlane(a.periods[0]) : 1;
     const int hops_per_wg = kInvWaves * rounds - 1;
     const int64_t h0 = a.first_hop + (int64_t)blockIdx.x * hops_per_wg;
     const int64_t h_last = (h0 + hops_per_wg - 1 < a.last_hop) ? h0 + hops_per_wg - 1 : a.last_hop;
@@ -534,9 +536,12 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
             float2 v[16];
             if (have) {
                 const float2* Y = a.Y + c * a.chan_stride + t * a.FS;
-                const float* Mr = MASKED == 1 ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr;
+                const float* Mr = (MASKED == 1 || MASKED == 5) ? a.M + c * a.chan_stride + t * a.FS : MASKED == 3 ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr;
+                // MASKED == 5 / 6: the factor row beside the plane / the model, fetched pair by pair where it is applied (the row is
+                // the same for every frame and channel of a clip, 4 KB that stay in the cache: sixteen more live registers would not fit)
+                const float* Gr = (MASKED == 5 || MASKED == 6) ? a.G + (t < a.G_split ? 0 : a.FS) : nullptr;
                 // MASKED == 2: the model row of this frame's position inside its period (wave-uniform)
-                const float* Wr = MASKED == 2 ? a.model + c * a.model_chan_stride + (t % period) * a.FS : nullptr;
+                const float* Wr = (MASKED == 2 || MASKED == 6) ? a.model + c * a.model_chan_stride + (t % period) * a.FS : nullptr;
                 // merge the half spectrum back into the packed transform: Z[k] = E + i conj(W_2048^k) D, E = (A + B) / 2,
                 // D = (A - B) / 2, A = X[k], B = conj X[N-k] (both masked first). Round 6: in PAIRS, as the forward kernel splits --
                 // Z[N-k] = conj(E) + i conj(conj(W^k) D) comes out of the same E and D, so a lane takes its slots s < 8 only:
@@ -557,8 +562,8 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
                     for (int j = 0; j < 8; ++j) { mk[j] = Mr[64 * j + lane]; mc[j] = Mr[N - (64 * j + lane)]; }
                     m512 = Mr[N / 2];
                 }
-                float wk[MASKED == 2 ? 8 : 1], wc[MASKED == 2 ? 8 : 1];          // MASKED == 2: the model at the lane's sixteen bins
-                if constexpr (MASKED == 2) {
+                float wk[(MASKED == 2 || MASKED == 6) ? 8 : 1], wc[(MASKED == 2 || MASKED == 6) ? 8 : 1];          // MASKED == 2: the model at the lane's sixteen bins
+                if constexpr (MASKED == 2 || MASKED == 6) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { wk[j] = Wr[64 * j + lane]; wc[j] = Wr[N - (64 * j + lane)]; }
                     m512 = soft_mask(magnitude(x512), Wr[N / 2], N / 2, a.cutoff);
@@ -568,16 +573,27 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
                 for (int j = 0; j < 8; ++j) {
                     const int k = 64 * j + lane;
                     float2 a_ = xk[j], b_ = xc[j];
-                    if constexpr (MASKED == 2) {
+                    if constexpr (MASKED == 2 || MASKED == 6) {
                         // the pair's masks where they are used: |X| with the forward kernel's own roundings (magnitude(): V is not
                         // read at all); the model values die here (all sixteen masks first cost a register spill)
                         const float mk2 = soft_mask(magnitude(a_), wk[j], k, a.cutoff), mc2 = soft_mask(magnitude(b_), wc[j], N - k, a.cutoff);
                         a_ = make_float2(mul_rounded(a_.x, mk2), mul_rounded(a_.y, mk2));
                         b_ = make_float2(mul_rounded(b_.x, mc2), mul_rounded(b_.y, mc2));
+                        if constexpr (MASKED == 6) {
+                            const float gk = Gr[k], gc = Gr[N - k];
+                            a_ = make_float2(mul_rounded(a_.x, gk), mul_rounded(a_.y, gk));
+                            b_ = make_float2(mul_rounded(b_.x, gc), mul_rounded(b_.y, gc));
+                        }
                         __builtin_amdgcn_sched_barrier(0);                     // two divisions' temporaries at a time, not sixteen
                     } else if constexpr ((MASKED & 1) != 0) {
                         a_ = make_float2(mul_rounded(a_.x, mk[j]), mul_rounded(a_.y, mk[j]));
                         b_ = make_float2(mul_rounded(b_.x, mc[j]), mul_rounded(b_.y, mc[j]));
+                        if constexpr (MASKED == 5) {
+                            const float gk = Gr[k], gc = Gr[N - k];
+                            a_ = make_float2(mul_rounded(a_.x, gk), mul_rounded(a_.y, gk));
+                            b_ = make_float2(mul_rounded(b_.x, gc), mul_rounded(b_.y, gc));
+                            __builtin_amdgcn_sched_barrier(0);                 // one pair's factors at a time (registers)
+                        }
                     }
                     const float ex_ = a_.x + b_.x, ey_ = a_.y - b_.y;         // A + B   (B = conj X[N-k])
                     const float dx_ = a_.x - b_.x, dy_ = a_.y + b_.y;         // A - B
@@ -589,6 +605,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void istft_ola_reg_kernel(IstftOlaA
                 }
                 float2 z512 = x512;
                 if constexpr (MASKED != 0) z512 = make_float2(mul_rounded(x512.x, m512), mul_rounded(x512.y, m512));
+                if constexpr (MASKED == 5 || MASKED == 6) { const float g512 = Gr[N / 2]; z512 = make_float2(mul_rounded(z512.x, g512), mul_rounded(z512.y, g512)); }
                 z512.y = -z512.y;                                              // Z[N/2] = conj(A)
                 // slots 15 .. 8: from the mirror lane's pairs 0 .. 7 (lane 0: its own pairs 1 .. 7 are its slots 15 .. 9, slot 8 is bin N/2)
 #pragma unroll
@@ -778,12 +795,15 @@ hipError_t launch_istft_ola_reg(const IstftOlaArgs& a, int64_t hops, hipStream_t
         (void)ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)dyn);
         hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)batches), dim3(64 * kInvWaves), dyn, s, a, rounds);
     };
-    const int mode = a.model ? 2 : a.M ? 1 : a.G ? 3 : 0;
-    if (a.n_channels == 2) { if (mode == 3) go(&istft_ola_reg_kernel<2, 3>); else if (mode == 2) go(&istft_ola_reg_kernel<2, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<2, 1>); else go(&istft_ola_reg_kernel<2, 0>); }
+    const int mode = a.model ? (a.G ? 6 : 2) : a.M ? (a.G ? 5 : 1) : a.G ? 3 : 0;
+    if (mode >= 5) {
+        if (a.n_channels == 2) { if (mode == 6) go(&istft_ola_reg_kernel<2, 6>); else go(&istft_ola_reg_kernel<2, 5>); }
+        else { if (mode == 6) go(&istft_ola_reg_kernel<1, 6>); else go(&istft_ola_reg_kernel<1, 5>); }
+    } else if (a.n_channels == 2) { if (mode == 3) go(&istft_ola_reg_kernel<2, 3>); else if (mode == 2) go(&istft_ola_reg_kernel<2, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<2, 1>); else go(&istft_ola_reg_kernel<2, 0>); }
     else { if (mode == 3) go(&istft_ola_reg_kernel<1, 3>); else if (mode == 2) go(&istft_ola_reg_kernel<1, 2>); else if (mode == 1) go(&istft_ola_reg_kernel<1, 1>); else go(&istft_ola_reg_kernel<1, 0>); }
     if (info) {
-        static const char* const names[2][4] = {{"istft_ola_reg_kernel<1, 0>", "istft_ola_reg_kernel<1, 1>", "istft_ola_reg_kernel<1, 2>", "istft_ola_reg_kernel<1, 3>"},
-                                                {"istft_ola_reg_kernel<2, 0>", "istft_ola_reg_kernel<2, 1>", "istft_ola_reg_kernel<2, 2>", "istft_ola_reg_kernel<2, 3>"}};
+        static const char* const names[2][7] = {{"istft_ola_reg_kernel<1, 0>", "istft_ola_reg_kernel<1, 1>", "istft_ola_reg_kernel<1, 2>", "istft_ola_reg_kernel<1, 3>", "", "istft_ola_reg_kernel<1, 5>", "istft_ola_reg_kernel<1, 6>"},
+                                                {"istft_ola_reg_kernel<2, 0>", "istft_ola_reg_kernel<2, 1>", "istft_ola_reg_kernel<2, 2>", "istft_ola_reg_kernel<2, 3>", "", "istft_ola_reg_kernel<2, 5>", "istft_ola_reg_kernel<2, 6>"}};
         info->kernel = names[a.n_channels == 2][mode];
         info->family = kFftPathReg; info->run = kInvWaves * rounds - 1; info->rounds = rounds; info->slots = cus;
         info->workgroups = (int64_t)blocks * batches; info->units = hops; info->launches += 1;

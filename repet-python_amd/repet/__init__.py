@@ -120,12 +120,12 @@ def release_workspaces():
 
 
 def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
-                     levels=False, dtype=None):
+                     levels=False, dtype=None, band_gains=None):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
     has checked, or None. ``levels``: also the level record of the result (one reduction launch more, two for a long clip), under
-    the same gain."""
+    the same gain. ``band_gains``: ``(edges, g)`` that ``separate`` has checked with ``band_gain_rows``, or None."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
@@ -147,21 +147,23 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     ctx.set_strict_reference(strict_reference)
     stream = torch.cuda.current_stream(x.device)
     ctx.upload_layout(*layout, stream=stream)
-    ctx.execute_async(algo, params)
     record = None
-    if background_gain is None:
+    # gains: on this thread's cached context for this call alone -- later calls are the plain foreground again, whatever
+    # happens here. The band table shapes the run it is set in front of; the scalar gain acts in the egress.
+    try:
+        if band_gains is not None:
+            ctx.set_background_band_gains(band_gains[1], band_gains[0], window_length=params.window_length)
+        ctx.execute_async(algo, params)
+        if background_gain is not None:
+            ctx.set_background_gain(background_gain)
         results = tuple(ctx.download_tensor(o, stream, name, dtype) for o, name in zip(outs, names))
         if levels:
             record = ctx.result_levels(stream=stream)
-    else:
-        # on this thread's cached context for this call alone: later calls are the plain foreground again, whatever happens here
-        try:
-            ctx.set_background_gain(background_gain)
-            results = tuple(ctx.download_tensor(o, stream, name, dtype) for o, name in zip(outs, names))
-            if levels:
-                record = ctx.result_levels(stream=stream)
-        finally:
+    finally:
+        if background_gain is not None:
             ctx.set_background_gain(0.0)
+        if band_gains is not None:
+            ctx.clear_background_band_gains()
     results = results if which == "both" else results[0]
     return (results, record) if levels else results
 
@@ -206,7 +208,8 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None):
+def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
+             background_band_gains=None, band_edges=None):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
     clips one after another). Returns a float64 tensor on the tensor's device -- one of ``dtype``, where given -- or fills
@@ -231,6 +234,17 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     background: ``10 ** (-12 / 20)``; 0 is the plain foreground, 1 the input). For this call alone. ValueError for a value
     outside [0, 1] (NaN included) or with another ``which``.
 
+    ``background_band_gains`` (with ``which="foreground"`` or ``"both"`` only): keep a share of the background BAND BY BAND.
+    ``(n_bands,)`` gains in [0, 1], or ``(B, n_bands)`` for a batch (one row per clip); ``band_edges`` the ``n_bands + 1``
+    ascending bin edges in ``[0, window_length / 2 + 1]`` (:func:`band_edges` fits) or None for one gain per bin. The foreground
+    is formed from a SHAPED background: the variant's own inverse STFT of the masked spectrum with bin ``k`` multiplied by
+    ``float32(1 - g[k])`` (a second inverse launch behind each plain one), so a gain of 1 over the bass bins gives the bass the
+    high-pass rule hands to the background back to the foreground. The returned background, the mixture and their levels keep
+    their bits; ``background_gain`` multiplies on top; ``levels=True`` measures the shaped foreground; all zeros is the plain
+    call bit for bit. For this call alone. ValueError, before the library is touched, for gains outside [0, 1] (NaN included),
+    bad edges, a wrong size or another ``which``; windows above 4096 samples (sampling frequencies above 102.4 kHz) are refused
+    by the library.
+
     ``levels=True`` returns ``(result, levels)``: the level record of the call (``repet.LEVELS``: per channel the sums of squares
     and the largest magnitudes of mixture, background and foreground, the samples and those whose mixture is not finite), a
     float64 tensor ``(C, 8)`` -- ``(B, C, 8)`` for a batch -- on the tensor's device, reduced there from the float64 values the
@@ -243,10 +257,19 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
         if which not in ("foreground", "both"):
             raise ValueError('background_gain changes the foreground: it goes with which="foreground" or "both"')
         background_gain = float(_native.background_gains(background_gain)[0])
+    band_gains = None
+    if background_band_gains is not None:
+        if which not in ("foreground", "both"):
+            raise ValueError('background_band_gains change the foreground: they go with which="foreground" or "both"')
+        shape = tuple(getattr(audio_signal, "shape", ()))
+        band_gains = _native.band_gain_rows(background_band_gains, band_edges, derive_params(sampling_frequency).window_length // 2 + 1,
+                                            int(shape[0]) if len(shape) == 3 else None)
+    elif band_edges is not None:
+        raise ValueError("band_edges go with background_band_gains")
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
-                            background_gain=background_gain, levels=bool(levels), dtype=dtype)
+                            background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains)
 
 
 def online(sampling_frequency, number_channels, start_length=None):

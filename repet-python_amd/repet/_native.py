@@ -109,6 +109,12 @@ def band_gain_rows(gains, edges, bins, count=None):
     return edges, np.ascontiguousarray(g)
 
 
+def g_rows(gains):
+    """The number of rows a two-dimensional ``gains`` has (None for anything else: ``band_gain_rows`` then expects one row)."""
+    shape = np.shape(gains) if not hasattr(gains, "shape") else tuple(gains.shape)
+    return int(shape[0]) if len(shape) == 2 else None
+
+
 def _set_band_gains(handle_of, slots, n_slots, gains, edges, bins, count):
     """(the arguments are checked before the handle is looked at: ``handle_of`` returns it)"""
     edges, g = band_gain_rows(gains, edges, bins, count)
@@ -271,6 +277,9 @@ _SIGNATURES = {
     "repet_online_background_band_gains": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "repet_ctx_set_background_gain": (C.c_int, [_P, C.c_float]),
     "repet_set_run_background_gain": (C.c_int, [C.c_int, C.c_float]),
+    "repet_ctx_set_background_band_gains": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32]),
+    "repet_ctx_background_band_gains": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "repet_set_run_background_band_gains": (C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, _P, C.c_int32]),
     "repet_online_last_levels": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_last_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_ctx_result_levels_device": (C.c_int, [_P, _P, _P]),
@@ -639,6 +648,39 @@ class Context:
         ``x - float32(1 - gain) * background``. 0, the default, is the plain foreground. ValueError outside [0, 1]."""
         g = background_gains(gain)
         check(lib().repet_ctx_set_background_gain(self._h, float(g[0])))
+
+    def set_background_band_gains(self, gains, edges=None, window_length=None):
+        """Keep a share of the background BAND BY BAND in the foreground of the runs enqueued from now on: ``gains`` in [0, 1],
+        ``(n_bands,)`` or one row per clip of the batch that will be resident, ``(B, n_bands)``; ``edges`` the ``n_bands + 1``
+        ascending bin edges in ``[0, window_length / 2 + 1]`` (``repet.band_edges`` fits) or None for one gain per bin.
+        ``window_length`` is the one of the runs to come (``derive_params(fs).window_length``), at most 4096. The foreground is
+        ``x - float32(1 - background_gain) * shaped``, where ``shaped`` is the variant's inverse STFT of the masked spectrum with
+        bin ``k`` multiplied by ``float32(1 - g[k])``; background, mixture and everything else keep their bits. The table in
+        force when ``execute`` / ``execute_async`` is enqueued shapes that run's result, whatever is set afterwards. ValueError,
+        before the library is touched, for gains outside [0, 1] (NaN included), bad edges or a wrong size."""
+        if window_length is None:
+            raise ValueError("window_length of the runs the table is for (derive_params(fs).window_length)")
+        w = int(window_length)
+        if w < 64 or w > 8192 or w & (w - 1):
+            raise ValueError("window_length must be a power of two in [64, 8192]")
+        bins = w // 2 + 1
+        edges, g = band_gain_rows(gains, edges, bins, g_rows(gains))
+        check(lib().repet_ctx_set_background_band_gains(self._h, w, None if edges is None else ptr(edges), g.shape[1], ptr(g), g.shape[0]))
+        self._band_bins = bins
+
+    def background_band_gains(self, clip=0):
+        """The float32 ``(F,)`` table in force for ``clip`` (a host copy); None when no table is set."""
+        bins = getattr(self, "_band_bins", None)
+        if bins is None:
+            return None
+        out = np.zeros(bins, dtype=np.float32)
+        check(lib().repet_ctx_background_band_gains(self._h, int(clip), ptr(out), bins))
+        return out
+
+    def clear_background_band_gains(self):
+        """No table: the runs enqueued from now on take the plain path."""
+        check(lib().repet_ctx_set_background_band_gains(self._h, 0, None, 0, None, 0))
+        self._band_bins = None
 
     def torch_stream(self):
         """The context's stream as a ``torch.cuda.ExternalStream`` (cached)."""

@@ -2,7 +2,11 @@
 clip), beside the NumPy drop-in call and the device step (timing series of a resident context) measured in the same run.
 Host clock around call + torch.cuda.synchronize(); medians over --reps calls after a warm-up. One JSON line per row.
 --kernels: only a few tensor calls of each dtype (for a `rocprofv3 --kernel-trace --stats` run of the ingest / egress
-kernels, devio_ingest_* and devio_egress_*)."""
+kernels, devio_ingest_* and devio_egress_*).
+--which foreground [--bands N]: only repet.separate("sim", tensor, which="foreground") on the float64 and the float32 tensor,
+without a table or with N band gains (repet.band_edges(fs, N), gains from 0.1 to 0.9), and the device stages of the same run on
+a resident context (the inverse STFT and, under a table, its shaped twin side by side). --calls K with --which: K calls and
+nothing else (for a kernel trace of exactly those calls)."""
 import argparse
 import json
 import os
@@ -32,16 +36,52 @@ def median_ms(fn, reps):
     return float(np.median(ts) * 1e3), float(np.min(ts) * 1e3)
 
 
+def probe_which(args, fs, x64, x32):
+    kw = {}
+    if args.bands:
+        kw = {"background_band_gains": np.round(np.linspace(0.1, 0.9, args.bands) * 32) / 32,
+              "band_edges": repet.band_edges(fs, args.bands)}
+    label = f"{args.which}, {args.bands} bands" if args.bands else f"{args.which}, no table"
+    if args.calls:
+        for _ in range(args.calls):
+            repet.separate("sim", x64, fs, which=args.which, **kw)
+        torch.cuda.synchronize()
+        print(json.dumps({"calls": args.calls, "what": label}))
+        return
+    for name, t in (("f64", x64), ("f32", x32)):
+        med, best = median_ms(lambda: repet.separate("sim", t, fs, which=args.which, **kw), args.reps)
+        print(json.dumps({"row": f"tensor_{name}_ms", "what": label, "median_ms": round(med, 4), "min_ms": round(best, 4)}))
+    p = repet.derive_params(fs)
+    ctx = repet.Context(0)
+    ctx.upload_tensor(x64)
+    if args.bands:
+        ctx.set_background_band_gains(kw["background_band_gains"], kw["band_edges"], window_length=p.window_length)
+    ctx.execute("sim", p)
+    ctx.timing_series_begin(args.reps)
+    for _ in range(args.reps):
+        ctx.execute_async("sim", p)
+    series = ctx.timing_series_end()
+    ctx.close()
+    stages = {st["name"]: round(st["ms"], 4) for st in series["stages"] if st["name"].startswith("istft")}
+    print(json.dumps({"row": "device_step_ms", "what": label, "mean_ms": round(series["total_ms"], 4), "stages": stages}))
+    print(json.dumps({"clip": f"{args.seconds:g} s {fs} Hz stereo", "reps": args.reps, "device": torch.cuda.get_device_name(0)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=180.0)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--which", default=None)
+    ap.add_argument("--bands", type=int, default=0)
+    ap.add_argument("--calls", type=int, default=0)
     args = ap.parse_args()
     fs = 44100
     x = synth(args.seconds, fs, 2, 0)
     x64 = torch.from_numpy(x).cuda()
     x32 = x64.float()
+    if args.which:
+        return probe_which(args, fs, x64, x32)
     if args.kernels:
         for t in (x64, x32):
             for _ in range(5):
