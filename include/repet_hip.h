@@ -804,6 +804,42 @@ int repet_online_last_band_energies(repet_online* h, int which, const int32_t* e
 int repet_online_last_band_energies_device(repet_online* h, int which, const int32_t* edges, int32_t n_bands,
                                            void* dst, void* signal_stream);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) The SIMILAR FRAMES the last push matched: for every frame
+ * a live handle decides which earlier frames of the stream's buffer it resembles, and the frame's mask is the median over exactly
+ * those (repet.py:855-866: the similarity vector of the frame against the buffer, its peaks, the list). For the n_frames frames
+ * the last push / finish completed (repet_online_last_frame_range) and every slot, with K = repet_online_match_capacity:
+ *   count       int32 [S][n_frames]     the length of the frame's list (repet.py:861-866), the frame itself included when it
+ *                                       is in its own list -- its similarity with itself is 1, so it is unless an exact copy of
+ *                                       it lies within similarity_distance
+ *   age         int32 [S][n_frames][K]  entry k < count: how many of the stream's OWN frames back the similar frame lies, 0 the
+ *                                       frame itself, 1 the frame before; strictly ascending (the order is by age, not by
+ *                                       similarity, and not the engine's own); -1 for k >= count
+ *   similarity  fp32  [S][n_frames][K]  the cosine similarity of the pair (repet.py:855-858), exactly the fp32 entry of the
+ *                                       handle's similarity band that the peak picking read; 0 for k >= count
+ * Own frames: a frame that passed while the slot was held does not exist for the slot, an imported stream's ages go on from
+ * the exporting handle's, and under start_frames a stream's frame j holds min(buffer_frames, j + 1) frames, so age <= j.
+ * A row has NO LIST -- count 0, every age -1, every similarity 0, whatever the chunk carried, NaN included -- for an idle or
+ * held slot, the frame that straddles a restart, every warm-up frame (the slot's own frame < start_frames - 1) and a frame
+ * whose similarity vector is NaN (a NaN sample in the frame: the reference's list is empty too).
+ * Computed ON DEMAND from the host record of the push and what its peak picking left on the device: a push that nobody asks
+ * about enqueues what it always did. Valid where repet_online_last_frames is: after a push or finish, STALE after the next
+ * push, finish, finish_stream, restart, release, import, hold or resume (REPET_ERR_BAD_ARG); the frames of a finish_stream tail
+ * are not served. A push that completed no frame has n_frames = 0: nothing is written and nothing launched.
+ * repet_online_match_capacity       : K = min(similarity_number, ceil(buffer_frames / (similarity_distance_frames + 1))), the
+ *                   most entries a list can have (repet.py:1294-1340: peaks at least similarity_distance apart, the
+ *                   similarity_number largest kept). From the handle's parameters: no device work.
+ * repet_online_last_matches         : host form, the three arrays dense as above through the pinned buffer (one launch, one
+ *                   copy, one wait); *n_rows = S * n_frames. All three outputs NULL only asks for *n_rows (REPET_OK); one of
+ *                   them NULL or capacity_rows < S * n_frames is REPET_ERR_BAD_ARG with *n_rows set.
+ * repet_online_last_matches_device  : the same three dense arrays on the handle's device, ordered behind `signal_stream` by
+ *                   events as last_emission_device is; one launch, no host wait. A null destination is REPET_ERR_BAD_ARG.
+ * DETERMINISTIC: an entry's place is the number of entries of its list with a smaller age, counted inside one wavefront; no
+ * atomics. Two calls on one push, the host and the device form, return identical bits. Asking changes nothing else. */
+int repet_online_match_capacity(repet_online* h, int32_t* capacity);
+int repet_online_last_matches(repet_online* h, int32_t* count_out, int32_t* age_out, float* similarity_out, int64_t capacity_rows,
+                              int64_t* n_rows);
+int repet_online_last_matches_device(repet_online* h, void* count_dst, void* age_dst, void* similarity_dst, void* signal_stream);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) A stream that SITS OUT PUSHES. Pushes stay (S, n, C) in and
  * (S, n_emit, C) out, but a slot may be HELD: for as long as it is, time does not pass for its stream (silence suppression, a
  * lost or late packet, a caller whose clock lags). With P = samples per slot pushed so far and H the hop:

@@ -383,6 +383,19 @@ struct FrameArgs {
 };
 hipError_t launch_online_frames(const FrameArgs& a, int32_t n_streams, float* dst, const int64_t strides[4], hipStream_t s);
 hipError_t launch_online_bands(const FrameArgs& a, int32_t n_streams, const int32_t* edges, int32_t n_bands, double* dst, hipStream_t s);
+//   matches  (matches.hip) the similar-frame lists of the frames a push completed, read from what its peak picking left: list
+//            row r of slot s at idx + s * idx_stride + r * idx_pitch (cnt likewise), for record frame n_frames - n_active + r;
+//            the entries are window rows, record frame 0 being row `hist`; band: the similarities, LP lags per row, in the
+//            look-back layout (band[j][l] = sim(j, j - l)) or the diagonal one (band[t][l] = sim(t, t + l)). Per (slot, frame):
+//            count, and K ages (ascending, -1 behind the list) and similarities (0 behind it), dense [n_streams][n_frames](K).
+//            A row of an idle or held slot, before the slot's own frame `warm`, or of a push that picked no peaks (n_active
+//            == 0: idx, cnt and band are not read) is empty. One launch, none for n_frames == 0
+struct MatchArgs {
+    const int32_t* idx; const int32_t* cnt; const float* band; int64_t idx_stride, cnt_stride, band_stride;
+    int32_t idx_pitch, LP, K, lookback; int64_t n_frames, n_active, hist, frame0, warm;
+    const int64_t* slot_start;
+};
+hipError_t launch_online_matches(const MatchArgs& a, int32_t n_streams, int32_t* count, int32_t* age, float* similarity, hipStream_t s);
 // bytes of an element of a REPET_* dtype (0: not a dtype), and the refusal of a destination dtype the emission does not write
 int dtype_bytes(int dtype);
 int check_emit_dtype(int dtype);

@@ -90,6 +90,14 @@ struct repet_online {
     // the next push. Host record only: a handle that is never asked runs nothing for it. Every call that changes the slot
     // table ends its validity with the emission's, so the table at query time is the table of the push.
     struct Frames { bool valid = false; int win = 0, S = 0; int64_t row0 = 0, n = 0, first = 0; } fr;
+    // Matches (repet_online_last_matches*): where the similar-frame lists of those frames lie. The push left them in the context's
+    // idx / cnt (list row r belongs to record frame n - n_active + r; idx_pitch entries per row, the slots n_active rows apart)
+    // as rows of the window counted from its first valid row, where record frame 0 is row `hist`; the similarities the peak
+    // picking read are still in `band` (band_stride floats per slot), in the look-back layout or the diagonal one. Nothing
+    // between a push and the next call that ends the record's validity writes any of the three: the levels, frames, gain and
+    // band-gain launches have buffers of their own, and finish_stream, which runs the peak picking again, ends the validity.
+    // n_active == 0: the push picked no peaks (every frame a warm-up frame) and the buffers are not read.
+    struct Matches { int64_t n_active = 0, hist = 0, band_stride = 0; int idx_pitch = 0; bool lookback = false; } mt;
     std::vector<float> gain;
     std::vector<unsigned char> gain_dirty;
     int64_t n_dirty = 0;
@@ -231,6 +239,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
     o->em.g0 = o->em.g1 = o->gcur;
     // (the new frames' rows follow the history in the current window; a finish_stream tail's frames are not served)
     o->fr = repet_online::Frames{slot < 0, o->cur, o->S, o->Hh, std::max<int64_t>(n_new, 0), o->frames_done};
+    o->mt = repet_online::Matches{};
     // (a held push that completes no frame -- a handle younger than a window -- still slides the samples: the held slots' stay)
     const bool held_push = slot < 0 && o->n_held > 0 && n_app > 0;
     if (n_new <= 0 && n_emit <= 0 && !held_push) return REPET_OK;
@@ -300,6 +309,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
                                   o->p.sim_distance_frames, K, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), first_global, rf,
                                   batch, pend, pend_lo,
                                   o->pend_hist + o->pend_count, pst, o->pend_hist - o->hist_valid * (int64_t)o->H, Tpad, S));
+            o->mt = repet_online::Matches{n_active, o->hist_valid, band_stride, KP, c->band_lookback};
         }
         MaskArgs m{};
         m.V = Vb; m.chan_stride = plane; m.n_channels = o->C; m.T = Tw; m.F = o->F; m.FS = o->FS; m.X = Xb; m.mask = nullptr;
@@ -1135,6 +1145,90 @@ int repet_online_last_band_energies_device(repet_online* o, int which, const int
     DeviceGuard guard(c->device);
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
     HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, static_cast<double*>(dst), c->stream));
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+static const char* const kStaleMatches =
+    "online: the last matches are stale (a push, finish, finish_stream, restart, release, import, hold or resume came after them)";
+
+static int online_max_peaks(const repet_online* o) {
+    return (int)std::min<int64_t>(o->p.sim_number, ceil_div(o->B, o->p.sim_distance_frames + 1));
+}
+
+// what the match kernel reads of the last push (o->fr, o->mt), from the host record alone
+static int online_match_args(const repet_online* o, MatchArgs* a) {
+    const repet_online::Frames& fr = o->fr;
+    const repet_online::Matches& mt = o->mt;
+    repet_ctx* c = o->ctx;
+    *a = MatchArgs{};
+    if (fr.n <= 0) return REPET_OK;
+    a->K = online_max_peaks(o); a->n_frames = fr.n; a->frame0 = fr.first; a->warm = o->M - 1;
+    a->slot_start = o->slots_on ? o->slot_start.as<int64_t>() : nullptr;
+    if (mt.n_active <= 0) return REPET_OK;
+    const int64_t rows = round_up(mt.hist + fr.n, kTile);
+    if (fr.S != o->S || mt.n_active > fr.n || mt.idx_pitch < a->K || mt.band_stride < rows * o->LP ||
+        c->idx.cap < (size_t)o->S * mt.n_active * mt.idx_pitch * sizeof(int32_t) || c->cnt.cap < (size_t)o->S * mt.n_active * sizeof(int32_t) ||
+        o->band.cap < (size_t)o->S * mt.band_stride * sizeof(float))
+        return fail(REPET_ERR_LIMIT, "online: the last matches are not in the workspaces");
+    a->idx = c->idx.as<int32_t>(); a->cnt = c->cnt.as<int32_t>(); a->band = o->band.as<float>();
+    a->idx_stride = mt.n_active * mt.idx_pitch; a->cnt_stride = mt.n_active; a->band_stride = mt.band_stride;
+    a->idx_pitch = mt.idx_pitch; a->LP = o->LP; a->lookback = mt.lookback ? 1 : 0;
+    a->n_active = mt.n_active; a->hist = mt.hist;
+    return REPET_OK;
+}
+
+int repet_online_match_capacity(repet_online* o, int32_t* capacity) {
+    if (!o || !capacity) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *capacity = online_max_peaks(o);
+    return REPET_OK;
+}
+
+int repet_online_last_matches(repet_online* o, int32_t* count_out, int32_t* age_out, float* similarity_out, int64_t capacity_rows,
+                              int64_t* n_rows) {
+    if (!o || !n_rows) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_rows = 0;
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleMatches);
+    const int64_t rows = (int64_t)o->S * o->fr.n, K = online_max_peaks(o);
+    *n_rows = rows;
+    if (rows == 0 || (!count_out && !age_out && !similarity_out)) return REPET_OK;
+    if (!count_out || !age_out || !similarity_out || capacity_rows < rows) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    *n_rows = 0;
+    MatchArgs a;
+    RP_TRY(online_match_args(o, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    // count | age | similarity, one after the other: one copy
+    const size_t words = (size_t)rows * (1 + 2 * K);
+    HIP_TRY(o->out64.ensure(words * 4));
+    int32_t* cnt = o->out64.as<int32_t>();
+    int32_t* age = cnt + rows;
+    float* sim = reinterpret_cast<float*>(age + rows * K);
+    HIP_TRY(launch_online_matches(a, o->S, cnt, age, sim, c->stream));
+    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, words * 4));
+    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int32_t* got = static_cast<const int32_t*>(o->host_out);
+    std::memcpy(count_out, got, (size_t)rows * 4);
+    std::memcpy(age_out, got + rows, (size_t)rows * K * 4);
+    std::memcpy(similarity_out, got + rows + rows * K, (size_t)rows * K * 4);
+    *n_rows = rows;
+    return REPET_OK;
+}
+
+int repet_online_last_matches_device(repet_online* o, void* count_dst, void* age_dst, void* similarity_dst, void* signal_stream) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleMatches);
+    if (!count_dst || !age_dst || !similarity_dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    if (o->fr.n <= 0) return REPET_OK;
+    MatchArgs a;
+    RP_TRY(online_match_args(o, &a));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    HIP_TRY(launch_online_matches(a, o->S, static_cast<int32_t*>(count_dst), static_cast<int32_t*>(age_dst),
+                                  static_cast<float*>(similarity_dst), c->stream));
     HIP_TRY(hipEventRecord(c->io_done, c->stream));
     HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
     return REPET_OK;

@@ -24,6 +24,7 @@ from ._native import Context  # noqa: F401  (device-resident API used by bench.p
 from ._native import OnlineSeparator as _OnlineSeparator
 from ._native import StreamState  # noqa: F401  (what export_stream returns and import_stream takes)
 from ._native import LEVELS  # noqa: F401  (the eight fields of a level record, in index order)
+from ._native import Matches  # noqa: F401  (what last_matches of a live handle returns: count, age, similarity)
 
 # ---- public parameters (repet.py:42-63) ----------------------------------------------------------------
 cutoff_frequency = 100
@@ -295,6 +296,9 @@ def online(sampling_frequency, number_channels, start_length=None):
     completed (``last_frame_range`` tells which), float32 magnitudes ``(T, number_channels, window_length / 2 + 1)`` or, with
     ``bands``, float64 band energies ``(T, number_channels, n_bands)``: see :func:`online_streams`.
 
+    ``last_matches(out=None)`` returns the similar frames those frames matched, ``Matches(count, age, similarity)`` of shapes
+    ``(T,)``, ``(T, match_capacity)`` and ``(T, match_capacity)``: see :func:`online_streams`.
+
     ``start_length`` (seconds; None: ``buffer_length``, the reference): separate before the buffer has filled. The reference
     writes nothing until its buffer holds ``buffer_length`` (10 s) of frames; with ``start_frames = min(buffer_frames, max(1,
     round(start_length * fs / step_length)))`` (the ``start_frames`` property) a stream's frame ``j >= start_frames - 1`` is
@@ -399,6 +403,20 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     One launch on demand: a push that nobody asks about costs what it always cost. ValueError once a push, finish,
     finish_stream, restart, release, import, hold or resume has followed (the frames of a ``finish_stream`` tail are not
     served). ``repet.online`` has the same calls without the stream axis.
+
+    ``last_matches(out=None)`` reports the decision behind those spectra: which earlier frames of its stream's buffer each of
+    the ``T`` frames resembles -- the frames its mask is the median of. A :class:`Matches` ``(count, age, similarity)``:
+    ``count`` int32 ``(number_streams, T)``, the length of the frame's list (the frame itself included: its similarity with
+    itself is 1); ``age`` int32 ``(number_streams, T, K)``, how many of the stream's own frames back each similar frame lies
+    (0 the frame itself, 1 the frame before), strictly ascending, ``-1`` behind the list; ``similarity`` float32 of the same
+    shape, the cosine similarity of the pair as the handle's peak picking read it, 0 behind the list. ``K`` is
+    ``match_capacity``, ``min(similarity_number, ceil(buffer_frames / (similarity_distance_frames + 1)))``. Own frames are the
+    stream's: a frame that passed while the slot was held does not exist for it, and an imported stream's ages go on from the
+    exporting handle's. Idle and held slots, the frame that straddles a ``restart``, warm-up frames and a frame with a NaN
+    sample have ``count`` 0. How many matches there are, how far apart and how alike says whether anything repeats: hold
+    music shows as evenly spaced ages, a stationary noise does not. NumPy arrays, or tensors on the device, with no host wait,
+    when ``out`` is a triple of dense tensors of these dtypes and shapes or the last push was a device chunk. One launch on
+    demand, valid exactly where ``last_frames`` is; ``repet.online`` has the same without the stream axis.
 
     A stream can move between handles: ``export_stream(slot, device=False)`` returns a snapshot of the slot's state as a
     :class:`StreamState` -- ``header``, a small ``bytes`` value the host knows at once, and ``payload``, a ``numpy.uint8``

@@ -1,5 +1,6 @@
 """ctypes binding of librepet_hip.so (include/repet_hip.h). No CPU fallback: if the library or a GPU
 is missing the calls raise, loudly."""
+import collections
 import ctypes as C
 import os
 import struct
@@ -33,6 +34,10 @@ LEVELS = ("mixture_energy", "background_energy", "foreground_energy", "mixture_p
           "live_samples", "nonfinite_samples")
 LEVEL_FIELDS = len(LEVELS)
 LEVEL_CHUNK = 4096             # REPET_LEVEL_CHUNK: samples of one stream per workgroup of the reduction
+
+# what last_matches of a live handle returns: per frame the length of its similar-frame list, and per entry how many of the
+# stream's own frames back it lies (ascending; -1 behind the list) and its cosine similarity (0 behind the list)
+Matches = collections.namedtuple("Matches", ["count", "age", "similarity"])
 
 
 def levels_out(out, shape, device):
@@ -292,6 +297,9 @@ _SIGNATURES = {
     "repet_online_last_frames_device": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "repet_online_last_band_energies": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_last_band_energies_device": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P]),
+    "repet_online_match_capacity": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "repet_online_last_matches": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "repet_online_last_matches_device": (C.c_int, [_P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1121,6 +1129,60 @@ def _last_frames(handle, device, lead, bins, which, bands, out, on_device):
     return result
 
 
+def _match_capacity(handle):
+    k = C.c_int32()
+    check(lib().repet_online_match_capacity(handle, C.byref(k)))
+    return k.value
+
+
+def match_outs(out, shapes, device):
+    """``out=`` of ``last_matches`` against the three shapes of the result: a triple of dense tensors on cuda:``device``, int32,
+    int32 and float32. ValueError otherwise, before anything runs."""
+    import torch
+    dev = torch.device("cuda", device)
+    try:
+        outs = tuple(out)
+    except TypeError:
+        outs = ()
+    if len(outs) != 3:
+        raise ValueError("out is a triple of tensors (count, age, similarity)")
+    for name, t, shape, dtype in zip(Matches._fields, outs, shapes, (torch.int32, torch.int32, torch.float32)):
+        if not is_device_tensor(t) or t.device != dev:
+            raise ValueError(f"out: {name} must be a tensor on {dev}")
+        if t.dtype != dtype:
+            raise ValueError(f"out: {name} is {dtype}, not {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out: {name} has shape {tuple(t.shape)}, the result {shape}")
+        if not t.is_contiguous():
+            raise ValueError(f"out: {name} must be dense (contiguous)")
+    return outs
+
+
+def _last_matches(handle, device, lead, out, on_device):
+    """``last_matches`` of a live handle whose result has the leading dimensions ``lead`` -- (S,) or () -- before (T,) and
+    (T, K): see ``OnlineStreams.last_matches``."""
+    _, count = _frame_range(handle)
+    k = _match_capacity(handle)
+    shapes = (tuple(lead) + (count,), tuple(lead) + (count, k), tuple(lead) + (count, k))
+    if out is not None or on_device:
+        import torch
+        dev = torch.device("cuda", device)
+        if out is None:
+            outs = tuple(torch.empty(shape, dtype=dtype, device=dev)
+                         for shape, dtype in zip(shapes, (torch.int32, torch.int32, torch.float32)))
+        else:
+            outs = match_outs(out, shapes, device)
+        if outs[0].numel():
+            check(lib().repet_online_last_matches_device(handle, *(C.c_void_p(t.data_ptr()) for t in outs),
+                                                         _stream_handle(torch.cuda.current_stream(dev))))
+        return Matches(*outs)
+    outs = tuple(np.empty(shape, dtype=dtype) for shape, dtype in zip(shapes, (np.int32, np.int32, np.float32)))
+    n = C.c_int64()
+    if outs[0].size:
+        check(lib().repet_online_last_matches(handle, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), outs[0].size, C.byref(n)))
+    return Matches(*outs)
+
+
 class OnlineSeparator:
     """Streaming online REPET-SIM: ``push(chunk)`` returns the background samples that became final,
     ``finish()`` the rest; the concatenation equals ``repet.simonline`` of the whole signal. ``which`` ("background",
@@ -1192,6 +1254,17 @@ class OnlineSeparator:
         energies ``(T, C, n_bands)``. A NumPy array, or ``out`` (an array of that shape, or a tensor on the device: no host
         wait). See ``repet.online_streams``. ValueError once another call has followed."""
         return _last_frames(self._h, self._device, ((), self._channels), self._bins, which, bands, out, False)
+
+    @property
+    def match_capacity(self):
+        """``K``: the most similar frames a frame can have, the last axis of ``last_matches``; see ``repet.online_streams``."""
+        return _match_capacity(self._h)
+
+    def last_matches(self, out=None):
+        """The similar frames the frames of the last ``push`` / ``finish`` matched: ``repet.Matches(count, age, similarity)``,
+        int32 ``(T,)``, int32 ``(T, K)`` and float32 ``(T, K)`` NumPy arrays, or ``out`` (a triple of dense tensors on the device:
+        no host wait). See ``repet.online_streams``. ValueError once another call has followed."""
+        return _last_matches(self._h, self._device, (), out, False)
 
     def set_background_gain(self, gain):
         """Keep ``gain`` (in [0, 1]) of the background in the foreground from the next emission on, see ``repet.online``."""
@@ -1428,6 +1501,24 @@ class OnlineStreams:
         anything runs) and once a push, finish, finish_stream, restart, release, import, hold or resume has followed."""
         return _last_frames(self._handle(), self._device, ((self._streams,), self._channels), self._bins, which, bands, out,
                             self._last_on_device)
+
+    @property
+    def match_capacity(self):
+        """``K = min(similarity_number, ceil(buffer_frames / (similarity_distance_frames + 1)))``: the most similar frames a
+        frame can have, the last axis of ``last_matches``. From the handle's parameters, no device work."""
+        return _match_capacity(self._handle())
+
+    def last_matches(self, out=None):
+        """The similar frames that the ``T`` frames of the last ``push`` / ``finish`` (``last_frame_range``) matched, as the
+        handle used them for the mask: ``repet.Matches(count, age, similarity)`` -- ``count`` int32 ``(S, T)``, the length of a
+        frame's list; ``age`` int32 ``(S, T, K)``, how many of the stream's own frames back each similar frame lies, 0 the frame
+        itself, strictly ascending, -1 behind the list; ``similarity`` float32 ``(S, T, K)``, the cosine similarity of the pair
+        as the peak picking read it, 0 behind the list. ``K`` is ``match_capacity``. NumPy arrays, or tensors on the handle's
+        device with no host wait when ``out`` is a triple of dense tensors of those dtypes and shapes (which is filled and
+        returned) or the last push was a device chunk. One launch on demand; see ``repet.online_streams``. ValueError for a
+        wrong ``out`` (before anything runs) and once a push, finish, finish_stream, restart, release, import, hold or resume
+        has followed."""
+        return _last_matches(self._handle(), self._device, (self._streams,), out, self._last_on_device)
 
     def _check_dtype(self, dtype, out):
         """``dtype=`` of a call whose result goes to the host unless ``out`` is given or the last push was a device chunk."""

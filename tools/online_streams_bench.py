@@ -40,6 +40,9 @@ through the pinned buffer and one wait), whatever the chunks are.
 preallocated tensor on the device (no host wait of its own): ``frames`` the foreground magnitudes ``(S, T, C, F)``, ``bands`` the
 foreground's energies in the 32 bands of ``repet.band_edges(fs, 32)``.
 
+``--matches``: the one-handle cases with a ``last_matches`` call after every timed push, inside the clock, into three
+preallocated tensors on the device (no host wait of its own).
+
 ``--band-gains N``: the one-handle cases with ``set_background_band_gains`` of N mel bands (``repet.band_edges(fs, N)``) with
 distinct gains made right after the open, so every timed push carries the second, shaped inverse STFT (use it with ``--which
 foreground`` or ``both``). ``--band-gains-change-every K`` (with it): the bands are set again, with the gains rotated, before
@@ -69,7 +72,7 @@ def stats(lat_s, n, fs):
 
 
 def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_length=None, gain=None, gain_every=0, levels=None,
-               out_dtype=None, frames=None, band_gains=0, band_every=0):
+               out_dtype=None, frames=None, band_gains=0, band_every=0, matches=False):
     import ctypes
     import torch
     from repet import _native
@@ -109,6 +112,10 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
     if frames:
         last = 32 if frames == "bands" else repet.derive_params(fs).window_length // 2 + 1
         spectra = torch.empty((S, hops, ch, last), dtype=torch.float64 if frames == "bands" else torch.float32, device="cuda:0")
+    if matches:
+        cap = h.match_capacity
+        lists = (torch.empty((S, hops), dtype=torch.int32, device="cuda:0"), torch.empty((S, hops, cap), dtype=torch.int32, device="cuda:0"),
+                 torch.empty((S, hops, cap), dtype=torch.float32, device="cuda:0"))
     lat = []
     for k in range(timed):
         if pos + n > N:
@@ -126,6 +133,8 @@ def one_handle(xs, fs, hops, device, timed, warm_s, which="background", start_le
                                                                  ctypes.byref(written)))
         if frames:
             h.last_frames("foreground", bands=edges, out=spectra)
+        if matches:
+            h.last_matches(out=lists)
         if device:
             torch.cuda.synchronize()
         lat.append(time.perf_counter() - t0)
@@ -390,6 +399,8 @@ def main():
                     help="a levels call after every timed push of the one-handle cases, inside the clock (see above)")
     ap.add_argument("--frames", choices=["frames", "bands"], default=None,
                     help="a last_frames call after every timed push of the one-handle cases, inside the clock (see above)")
+    ap.add_argument("--matches", action="store_true",
+                    help="a last_matches call after every timed push of the one-handle cases, inside the clock (see above)")
     ap.add_argument("--band-gains", type=int, default=0, metavar="N",
                     help="set_background_band_gains of N mel bands with distinct gains after the open (one-handle cases)")
     ap.add_argument("--band-gains-change-every", type=int, default=0, metavar="K",
@@ -441,6 +452,8 @@ def main():
         result["out_dtype"] = args.out_dtype
     if args.frames is not None:
         result["frames"] = args.frames
+    if args.matches:
+        result["matches"] = True
     if args.band_gains > 0:
         result["band_gains"] = args.band_gains
         result["band_gains_change_every"] = args.band_gains_change_every
@@ -452,7 +465,7 @@ def main():
                 key = "one_handle_device_chunks" + ("" if which == "background" else "_" + which)
                 case[key] = one_handle(xs, fs, hops, True, args.timed, warm_s, which, args.start_length, args.background_gain,
                                        args.gain_change_every, args.levels, args.out_dtype, args.frames, args.band_gains,
-                                       args.band_gains_change_every)
+                                       args.band_gains_change_every, args.matches)
             if args.only == "all":
                 case["one_handle_host_chunks"] = one_handle(xs, fs, hops, False, args.timed, warm_s, start_length=args.start_length,
                                                             gain=args.background_gain, gain_every=args.gain_change_every,
