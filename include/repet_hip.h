@@ -871,6 +871,62 @@ int repet_online_last_matches_device(repet_online* h, void* count_dst, void* age
 int repet_online_hold_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
 int repet_online_resume_streams(repet_online* h, const int32_t* slots, int32_t n_slots);
 int repet_online_stream_held(repet_online* h, int32_t slot, int32_t* held);
+
+/* (ABI 4) Per-slot inboxes: the slots of a handle of open_streams fed at their own pace. A push is in lockstep -- one chunk
+ * [S][n][C] with one n -- while packets arrive per stream in sizes that never match the hop, late, in bursts or not at all.
+ * With the inboxes the handle does the re-blocking itself. With H the hop, P the samples per slot pushed so far:
+ * enable_feed     : every slot gets a FIFO of capacity_samples (>= H) samples per channel in device memory, held as the pending
+ *                   buffers hold samples (fp32, and the fp32 remainder of float64 sources): S * capacity * C * 8 bytes. Once
+ *                   per handle, at any age with P % H == 0. A handle that never calls it allocates nothing and enqueues what
+ *                   it always did.
+ * feed            : appends to the inboxes of the n_slots named slots: row i of the host array [n_slots][n][C] (REPET_F32 /
+ *                   REPET_F64 / REPET_I16) brings its first counts[i] samples (counts null: all n) to slot slots[i]. What lies
+ *                   behind counts[i] in a row is never read, NaN included; non-finite samples are let through as in a push.
+ *                   All or nothing: REPET_ERR_BAD_ARG before anything is enqueued or changed for a slot out of range or named
+ *                   twice, an idle slot, a count outside [0, n], a slot whose queued + count would exceed the capacity, and a
+ *                   handle without inboxes or finished. A slot the caller holds may be fed: its queue grows. One staging copy
+ *                   and one launch per 256 slots named; the values that later reach the pending buffers are bit for bit what
+ *                   a push of them would have written.
+ * feed_device     : the same from device memory (any ingest dtype, element strides [3] of [n_slots][n][C]): ordered behind
+ *                   wait_stream, and signal_stream is made to wait for the copy, so the caller may overwrite the packet. No
+ *                   host wait.
+ * queued          : slot >= 0: *queued = the samples in that slot's inbox; slot < 0: queued[S], every slot's. Host counters.
+ * pad_feed        : feeds each named slot (null: every live slot) (-queued) % H zeros, so that its queue ends on the hop grid,
+ *                   and writes the pad counts to pads[n_slots] (pads[S] where slots is null). After the ticks that drain the
+ *                   queue, the slot's finish_stream tail without its last `pad` samples is the stream's true tail. Refusals
+ *                   as feed's.
+ * clear_feed      : empties the inboxes of the named slots (null: of all). Host counters alone.
+ * tick            : a lockstep push of hops * H samples whose chunk the handle assembles: requires P % H == 0. The READY slots
+ *                   are the live slots that the caller does not hold and whose inbox has at least hops * H samples. Nobody
+ *                   ready: nothing is enqueued, *n_written = 0, consumed[] all 0, and the handle, its last emission and its
+ *                   records stay as they were. Otherwise every live slot the caller does not hold and that is not ready is
+ *                   STARVED -- held for this push by the mechanism of hold_streams, the table written only for slots whose
+ *                   state differs from the tick before -- each ready slot's oldest hops * H samples leave its inbox for the
+ *                   pending buffers (one launch per 256 slots in the place of the push's append), and the push runs as ever:
+ *                   out, the selected output, also_emit, last_emission, last_levels, last_frames and last_matches are the
+ *                   push's, and a starved slot reads everywhere as a held one (zeros, LIVE = 0). consumed (nullable, [S]):
+ *                   1 for the slots that took part. All decisions come from host counters; nothing is read back.
+ * tick_device     : the same into a device destination, as push_device.
+ * The guarantee is hold_streams', with starved ticks in the place of held pushes: per slot, the output pieces of the ticks
+ * that consumed it, in order, followed by its finish_stream / finish tail, equal repet.simonline of the samples it consumed,
+ * bit for bit, whatever the other slots did and in whatever packets the samples arrived.
+ * With the rest of the handle: restart_streams, release_streams and import_stream empty the inboxes of their slots;
+ * finish_stream, finish and stream_emit_count are refused (REPET_ERR_BAD_ARG, the message names clear_feed and pad_feed) while a
+ * slot they end has queued samples; a plain push is refused while any inbox holds samples and otherwise first resumes the
+ * starved slots (one launch) and is the push it always was; stream_held reports the caller's holds only, and resume_streams of
+ * a starved slot leaves it held on the device until a tick finds it ready; export_stream returns the stream as consumed (the
+ * queue is not part of the state, version 1). */
+int repet_online_enable_feed(repet_online* h, int64_t capacity_samples);
+int repet_online_feed(repet_online* h, const int32_t* slots, const int64_t* counts, int32_t n_slots, const void* audio, int dtype,
+                      int64_t n);
+int repet_online_feed_device(repet_online* h, const int32_t* slots, const int64_t* counts, int32_t n_slots, const void* src, int dtype,
+                             int64_t n, const int64_t src_strides[3], void* wait_stream, void* signal_stream);
+int repet_online_queued(repet_online* h, int32_t slot, int64_t* queued);
+int repet_online_pad_feed(repet_online* h, const int32_t* slots, int32_t n_slots, int64_t* pads);
+int repet_online_clear_feed(repet_online* h, const int32_t* slots, int32_t n_slots);
+int repet_online_tick(repet_online* h, int64_t hops, double* out, int64_t capacity, uint8_t* consumed, int64_t* n_written);
+int repet_online_tick_device(repet_online* h, int64_t hops, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                             uint8_t* consumed, int64_t* n_written);
 int repet_ctx_result_levels_device(repet_ctx* ctx, void* dst, void* signal_stream);
 
 /* (ABI 4) Self-test of the host conversions a staged upload / download runs (float64 -> fp32 samples + fp32 remainders,

@@ -738,6 +738,122 @@ __global__ __launch_bounds__(kIoThreads) void online_slot_set(SlotSetArgs g) {
     for (int32_t i = threadIdx.x; i < g.n; i += kIoThreads) g.table[g.slot[i]] = g.value[i];
 }
 
+// ---- per-slot inboxes (repet_online_enable_feed): slot b owns a ring of ring_len = capacity * C floats per plane (hi, and lo
+// for the fp32 remainders of float64 sources) at b * ring_stride; queued sample p of it lies at float (p * C) % ring_len. The
+// host mirrors every read and write position and hands them over in the kernel arguments (the SlotSetArgs pattern: no copy
+// to the device and no wait); both kernels wrap inside. Slots of four floats aligned on the side that is stored to, as above.
+//
+// Feed: row r of the source [rows][n][C] (strided, any ingest dtype; IoGeo's clip = row) brings its first count[r] samples to
+// the ring of slot[r], from float wpos[r] on. What lies behind count[r] in a row is never read. The conversions are append's.
+struct FeedArgs {
+    float* hi; float* lo; int64_t ring_stride, ring_len; int32_t row0, n_rows;
+    unsigned short slot[repet_eng::kSlotResetIds]; int32_t count[repet_eng::kSlotResetIds]; int32_t wpos[repet_eng::kSlotResetIds];
+};
+
+template <typename T>
+__device__ inline void feed_body(const T* __restrict__ src, IoGeo g, const FeedArgs& a) {
+    const int64_t per = g.n_samples * g.n_channels;
+    bool unused = false;
+    for (int32_t r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
+        const int64_t len = (int64_t)a.count[r] * g.n_channels, w0 = a.wpos[r], head = w0 & 3;
+        const int64_t slots = (head + len + 3) >> 2, row = (int64_t)(a.row0 + r) * per;
+        float* hi_b = a.hi + a.slot[r] * a.ring_stride;
+        float* lo_b = a.lo + a.slot[r] * a.ring_stride;
+        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+            const int64_t j0 = q * 4 - head;                      // row element of the slot's first position
+            int64_t d0 = w0 + j0;
+            if (d0 >= a.ring_len) d0 -= a.ring_len;
+            if (j0 >= 0 && j0 + 4 <= len && d0 + 4 <= a.ring_len && !(d0 & 3)) {
+                float h[4], l[4];
+                Walker w(g, row + j0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    split1<T>(src + w.off, h[k], l[k], unused, false);
+                    if (k < 3) w.next(g);
+                }
+                *reinterpret_cast<float4*>(hi_b + d0) = make_float4(h[0], h[1], h[2], h[3]);
+                *reinterpret_cast<float4*>(lo_b + d0) = make_float4(l[0], l[1], l[2], l[3]);
+            } else {                                              // first / last slot of a row, and the one the wrap cuts
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t j = j0 + k;
+                    if (j < 0 || j >= len) continue;
+                    int64_t d = w0 + j;
+                    if (d >= a.ring_len) d -= a.ring_len;
+                    Walker w(g, row + j);
+                    float h, l;
+                    split1<T>(src + w.off, h, l, unused, false);
+                    hi_b[d] = h;
+                    lo_b[d] = l;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void online_feed_f64(const double* src, IoGeo g, FeedArgs a) { feed_body<double>(src, g, a); }
+__global__ __launch_bounds__(kIoThreads) void online_feed_f32(const float* src, IoGeo g, FeedArgs a) { feed_body<float>(src, g, a); }
+__global__ __launch_bounds__(kIoThreads) void online_feed_i16(const int16_t* src, IoGeo g, FeedArgs a) { feed_body<int16_t>(src, g, a); }
+__global__ __launch_bounds__(kIoThreads) void online_feed_f16(const Half* src, IoGeo g, FeedArgs a) { feed_body<Half>(src, g, a); }
+__global__ __launch_bounds__(kIoThreads) void online_feed_bf16(const BHalf* src, IoGeo g, FeedArgs a) { feed_body<BHalf>(src, g, a); }
+
+// Take (the append of a tick): `len` floats of both planes from float rpos[i] of slot first + i's ring go to its share of the
+// pending buffers at dst_off, where online_append_* would have written them. A slot whose table entry is idle or held -- the
+// caller's holds and the starved slots of this tick -- is skipped: nothing of its ring is read and nothing of its share written.
+struct TakeArgs {
+    const float* hi; const float* lo; int64_t ring_stride, ring_len; float* dst_hi; float* dst_lo; int64_t dst_stream, dst_off, len;
+    const int64_t* slot_start; int32_t first, n_slots; int32_t rpos[repet_eng::kSlotResetIds];
+};
+
+__device__ inline void take4(const float* __restrict__ ring, int64_t s0, int64_t ring_len, float (&v)[4]) {
+    if (s0 + 4 <= ring_len) {
+        if (!(s0 & 3)) {
+            const float4 x = *reinterpret_cast<const float4*>(ring + s0);
+            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = ring[s0 + k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = ring[s0 + k < ring_len ? s0 + k : s0 + k - ring_len];
+    }
+}
+
+__global__ __launch_bounds__(kIoThreads) void online_take(TakeArgs a) {
+    const int64_t head = a.dst_off & 3;
+    const int64_t slots = (head + a.len + 3) >> 2;
+    for (int32_t i = blockIdx.y; i < a.n_slots; i += gridDim.y) {
+        const int64_t b = a.first + i;
+        if (a.slot_start[b] >= repet_eng::kSlotIdle) continue;
+        const float* sh = a.hi + b * a.ring_stride;
+        const float* sl = a.lo + b * a.ring_stride;
+        float* dh = a.dst_hi + b * a.dst_stream + a.dst_off - head;
+        float* dl = a.dst_lo + b * a.dst_stream + a.dst_off - head;
+        const int64_t r0 = a.rpos[i];
+        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
+            const int64_t j0 = q * 4 - head;
+            if (j0 >= 0 && j0 + 4 <= a.len) {
+                int64_t s0 = r0 + j0;
+                if (s0 >= a.ring_len) s0 -= a.ring_len;
+                float h[4], l[4];
+                take4(sh, s0, a.ring_len, h);
+                take4(sl, s0, a.ring_len, l);
+                *reinterpret_cast<float4*>(dh + q * 4) = make_float4(h[0], h[1], h[2], h[3]);
+                *reinterpret_cast<float4*>(dl + q * 4) = make_float4(l[0], l[1], l[2], l[3]);
+            } else {
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t j = j0 + k;
+                    if (j < 0 || j >= a.len) continue;
+                    int64_t s = r0 + j;
+                    if (s >= a.ring_len) s -= a.ring_len;
+                    dh[q * 4 + k] = sh[s];
+                    dl[q * 4 + k] = sl[s];
+                }
+            }
+        }
+    }
+}
+
 // Slot reset (restart / release of slots of the streaming handle): workgroups (x, slot of the list, part) write the part's
 // runs of zeros into that slot's share of the buffers, and one thread per slot its new first frame.
 struct ZeroPartDev { float* dst; int64_t len, slots_per_block, blocks, dst_block, dst_stream; int32_t vec; };
@@ -978,6 +1094,70 @@ hipError_t launch_slot_set(int64_t* slot_start, const int32_t* slots, const int6
         g.n = std::min<int32_t>(kSlotResetIds, n_slots - first);
         for (int32_t k = 0; k < g.n; ++k) { g.slot[k] = (unsigned short)slots[first + k]; g.value[k] = values[first + k]; }
         online_slot_set<<<1, kIoThreads, 0, s>>>(g);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// (the rows of one call name distinct slots and every run fits its ring: two threads never write one float)
+hipError_t launch_feed(const void* src, int dtype, int64_t n, int32_t ch, const int64_t src_strides[3], const int32_t* slots,
+                       const int64_t* counts, const int64_t* wpos, int32_t n_rows, float* hi, float* lo, int64_t ring_stride,
+                       int64_t ring_len, hipStream_t s) {
+    if (n_rows <= 0 || n <= 0) return hipSuccess;
+    if (!src || !slots || !counts || !wpos || !hi || !lo || ring_len <= 0 || ring_len > INT32_MAX || ring_stride < ring_len ||
+        (ring_stride & 3) || (reinterpret_cast<uintptr_t>(hi) & 15) || (reinterpret_cast<uintptr_t>(lo) & 15))
+        return hipErrorInvalidValue;
+    const IoGeo g{n * ch * n_rows, n, ch, src_strides[0], src_strides[1], src_strides[2]};
+    FeedArgs a{};
+    a.hi = hi; a.lo = lo; a.ring_stride = ring_stride; a.ring_len = ring_len;
+    for (int32_t first = 0; first < n_rows; first += kSlotResetIds) {
+        a.row0 = first;
+        a.n_rows = std::min<int32_t>(kSlotResetIds, n_rows - first);
+        int64_t most = 0;
+        for (int32_t k = 0; k < a.n_rows; ++k) {
+            const int64_t cnt = counts[first + k], w = wpos[first + k];
+            if (cnt < 0 || cnt > n || cnt * ch > ring_len || w < 0 || w >= ring_len || slots[first + k] < 0 || slots[first + k] > 65535)
+                return hipErrorInvalidValue;
+            a.slot[k] = (unsigned short)slots[first + k]; a.count[k] = (int32_t)cnt; a.wpos[k] = (int32_t)w;
+            most = std::max(most, cnt);
+        }
+        if (most == 0) continue;
+        const dim3 grid = stream_grid(ceil_div(3 + most * ch, 4), a.n_rows, 1);
+        switch (dtype) {
+            case REPET_F64: online_feed_f64<<<grid, kIoThreads, 0, s>>>(static_cast<const double*>(src), g, a); break;
+            case REPET_F32: online_feed_f32<<<grid, kIoThreads, 0, s>>>(static_cast<const float*>(src), g, a); break;
+            case REPET_I16: online_feed_i16<<<grid, kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, a); break;
+            case REPET_F16: online_feed_f16<<<grid, kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, a); break;
+            case REPET_BF16: online_feed_bf16<<<grid, kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, a); break;
+            default: return hipErrorInvalidValue;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_take(const float* hi, const float* lo, int64_t ring_stride, int64_t ring_len, const int64_t* rpos, int32_t n_slots,
+                       int64_t len, float* dst_hi, float* dst_lo, int64_t dst_stream, int64_t dst_off, const int64_t* slot_start,
+                       hipStream_t s) {
+    if (n_slots <= 0 || len <= 0) return hipSuccess;
+    if (!hi || !lo || !rpos || !dst_hi || !dst_lo || !slot_start || ring_len <= 0 || ring_len > INT32_MAX || len > ring_len ||
+        ring_stride < ring_len || (ring_stride & 3) || (dst_stream & 3) || dst_off < 0 || dst_off + len > dst_stream ||
+        (reinterpret_cast<uintptr_t>(hi) & 15) || (reinterpret_cast<uintptr_t>(lo) & 15) || (reinterpret_cast<uintptr_t>(dst_hi) & 15) ||
+        (reinterpret_cast<uintptr_t>(dst_lo) & 15))
+        return hipErrorInvalidValue;
+    TakeArgs a{};
+    a.hi = hi; a.lo = lo; a.ring_stride = ring_stride; a.ring_len = ring_len; a.dst_hi = dst_hi; a.dst_lo = dst_lo;
+    a.dst_stream = dst_stream; a.dst_off = dst_off; a.len = len; a.slot_start = slot_start;
+    for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
+        a.first = first;
+        a.n_slots = std::min<int32_t>(kSlotResetIds, n_slots - first);
+        for (int32_t k = 0; k < a.n_slots; ++k) {
+            if (rpos[first + k] < 0 || rpos[first + k] >= ring_len) return hipErrorInvalidValue;
+            a.rpos[k] = (int32_t)rpos[first + k];
+        }
+        online_take<<<stream_grid(ceil_div((dst_off & 3) + len, 4), a.n_slots, 1), kIoThreads, 0, s>>>(a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -312,6 +312,17 @@ struct HeldShift { int64_t delta, zero_below; };
 hipError_t launch_slot_set(int64_t* slot_start, const int32_t* slots, const int64_t* values, int32_t n_slots, hipStream_t s);
 hipError_t launch_slide_held(const RowCopy* parts, const HeldShift* shifts, int n_parts, int32_t n_streams, hipStream_t s,
                              const int64_t* slot_start);
+//   feed     the per-slot inboxes (repet_online_enable_feed): slot b's ring of ring_len floats per plane at b * ring_stride of hi /
+//            lo. feed: row r of the source [n_rows][n][C] (strided, any ingest dtype) brings its first counts[r] samples to the
+//            ring of slots[r] from float wpos[r] on, converted as append converts. take: `len` floats of both planes from float
+//            rpos[b] of every slot's ring to dst_hi / dst_lo at b * dst_stream + dst_off, except for the slots that read idle
+//            or held in the table. Positions travel in the kernel arguments; both wrap; one launch per kSlotResetIds slots
+hipError_t launch_feed(const void* src, int dtype, int64_t n, int32_t ch, const int64_t src_strides[3], const int32_t* slots,
+                       const int64_t* counts, const int64_t* wpos, int32_t n_rows, float* hi, float* lo, int64_t ring_stride,
+                       int64_t ring_len, hipStream_t s);
+hipError_t launch_take(const float* hi, const float* lo, int64_t ring_stride, int64_t ring_len, const int64_t* rpos, int32_t n_slots,
+                       int64_t len, float* dst_hi, float* dst_lo, int64_t dst_stream, int64_t dst_off, const int64_t* slot_start,
+                       hipStream_t s);
 //   export   ONE slot's share of the handle's buffers gathered into a dense payload, one launch: up to kRowCopyParts parts of
 //            `blocks` runs of `len` floats; element i of a run is src[src_off + blk * src_block + i] for i >= zero_below and
 //            zero below it (a run right-aligned on what the source holds: src_off may be negative, src null with zero_below = len)

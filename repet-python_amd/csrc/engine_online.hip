@@ -37,6 +37,20 @@ struct repet_online {
     // its share of the buffers where it is, and the resume writes start[s] back. One table, and no launch for the bump.
     std::vector<unsigned char> held;
     int64_t n_held = 0;
+    // Inboxes (repet_online_enable_feed): every slot owns a ring of feed_cap samples per channel in `ring` (the hi plane of every
+    // slot, then the lo plane; slot s at s * ring_stride floats of either), filled by repet_online_feed* at the slot's own pace
+    // and emptied one lockstep chunk at a time by repet_online_tick*, which is a push whose chunk the handle takes from the
+    // rings itself. q_count[s] / q_read[s]: the queued samples and the sample position of the oldest, host mirrors of what the
+    // launches enqueued so far: the handle's stream orders the ring's reads and writes, and no call reads anything back. A live
+    // slot that a tick finds short is STARVED: held for that push by the mechanism above. `held` stays what the device table
+    // says -- held by either -- while caller_held / starved say by whom, so the table changes only where their OR does.
+    // feed_cap == 0 (no enable_feed): none of this exists and every call enqueues what it always did.
+    DevBuf ring;
+    int64_t feed_cap = 0, ring_stride = 0;
+    std::vector<int64_t> q_count, q_read;
+    std::vector<unsigned char> caller_held, starved;
+    float* ring_hi() const { return ring.as<float>(); }
+    float* ring_lo() const { return ring.as<float>() + (int64_t)S * ring_stride; }
     int C = 0, W = 0, H = 0, F = 0, FS = 0, B = 0, Hh = 0, LP = 0;
     // start_frames (repet_online_set_start_frames; B: the reference): a stream's frames M-1 .. B-2 are separated on its buffer as
     // far as it has filled (peaks.h: row_columns). The handle's, for every slot and restart; the launches are the same for any M.
@@ -622,6 +636,13 @@ int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
     return REPET_OK;
 }
 
+// a launch has just written the slot's table entry (restart, release, import): nobody holds it any more, and its inbox is empty
+static void online_forget_slot(repet_online* o, int32_t slot) {
+    o->caller_held[(size_t)slot] = 0;
+    o->starved[(size_t)slot] = 0;
+    if (o->feed_cap > 0) { o->q_count[(size_t)slot] = 0; o->q_read[(size_t)slot] = 0; }
+}
+
 // restart (first_frame = the handle's next frame) or release (kSlotIdle) of the named slots: one launch writes their first
 // frame on the device and clears what the slots hold of an earlier stream -- the history rows of Vn and V, the last masked
 // spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
@@ -649,6 +670,7 @@ int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t
         unsigned char& hd = o->held[(size_t)slots[k]];            // (the launch wrote the table: a hold ends here)
         o->n_held -= hd;
         hd = 0;
+        online_forget_slot(o, slots[k]);
     }
     if (first_frame != kSlotIdle) o->latest_start = std::max(o->latest_start, first_frame);
     o->slots_on = true;
@@ -663,6 +685,11 @@ int online_check_slots(const repet_online* o, const int32_t* slots, int32_t n) {
     return REPET_OK;
 }
 
+static const char* const kQueuedEnd =
+    "online: the stream still has queued samples (repet_online_pad_feed and the ticks that drain them, or repet_online_clear_feed, come first)";
+static const char* const kQueuedPush =
+    "online: a push while an inbox holds samples (repet_online_tick consumes them, repet_online_clear_feed drops them)";
+
 // what finish_stream of `slot` writes: the frames still to process and the samples of the tail. The slot's stream is the
 // handle's samples [start * H, total_in): it ends where the handle stands, so both numbers are those of the handle's own
 // finish; only the length that must cover the buffer is the slot's
@@ -671,6 +698,7 @@ int online_plan_slot(const repet_online* o, int32_t slot, int64_t* n_new, int64_
     RP_TRY(online_check_slots(o, &slot, 1));
     const int64_t st = o->start[(size_t)slot];
     if (st == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
+    if (o->feed_cap > 0 && o->q_count[(size_t)slot] > 0) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
     const int64_t N = o->total_in - st * (int64_t)o->H;
     if (N < (int64_t)(o->M - 2) * o->H + o->W)
         return fail(REPET_ERR_TOO_SHORT, "operands could not be broadcast together (signal shorter than the buffer)");
@@ -847,6 +875,7 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     st = first;
     o->n_held -= o->held[(size_t)slot];                         // (the launch wrote the table: a hold ends here)
     o->held[(size_t)slot] = 0;
+    online_forget_slot(o, slot);
     if (o->bands_on && o->band_stale[(size_t)slot]) {
         // band gains: the frame that comes with the stream is shaped with the table the slot has now
         HIP_TRY(launch_band_commit(o->band_tab.as<float>(), o->FS, o->S, slot, kBandSettle, nullptr, c->stream));
@@ -857,19 +886,22 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     return REPET_OK;
 }
 
-// Hold (on = true) or resume the named slots: one small launch writes kSlotHeld, or the slots' own first frames again, into the
-// device table. Slots that are there already are skipped; with none left nothing is enqueued and nothing changes. Enqueues only.
-int online_hold_slots(repet_online* o, const int32_t* slots, int32_t n, bool on) {
+// The device table follows the flags of the named slots: a slot is held on the device while the caller holds it (caller_held) or
+// a tick found its inbox short (starved). One small launch writes kSlotHeld, or the slots' own first frames again, for the slots
+// whose state changes; with none nothing is enqueued and nothing changes. Enqueues only.
+static int online_sync_holds(repet_online* o, const int32_t* slots, int32_t n) {
     repet_ctx* c = o->ctx;
     std::vector<int32_t> ids;
     std::vector<int64_t> values;
     for (int32_t k = 0; k < n; ++k) {
-        unsigned char& hd = o->held[(size_t)slots[k]];
-        if ((hd != 0) == on) continue;
-        hd = on ? 1 : 0;
-        o->n_held += on ? 1 : -1;
+        const size_t s = (size_t)slots[k];
+        const bool want = o->caller_held[s] || o->starved[s];
+        unsigned char& hd = o->held[s];
+        if ((hd != 0) == want) continue;
+        hd = want ? 1 : 0;
+        o->n_held += want ? 1 : -1;
         ids.push_back(slots[k]);
-        values.push_back(on ? kSlotHeld : o->start[(size_t)slots[k]]);
+        values.push_back(want ? kSlotHeld : o->start[s]);
     }
     if (ids.empty()) return REPET_OK;
     o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
@@ -878,13 +910,133 @@ int online_hold_slots(repet_online* o, const int32_t* slots, int32_t n, bool on)
     return REPET_OK;
 }
 
+// Hold (on = true) or resume the named slots for the caller. Slots that are there already are skipped, and so is the resume of
+// a starved slot, which stays held on the device until a tick finds it ready. end_starved: the call ends that too (finish and
+// finish_stream, which end the slots as they stand).
+int online_hold_slots(repet_online* o, const int32_t* slots, int32_t n, bool on, bool end_starved = false) {
+    for (int32_t k = 0; k < n; ++k) {
+        o->caller_held[(size_t)slots[k]] = on ? 1 : 0;
+        if (end_starved) o->starved[(size_t)slots[k]] = 0;
+    }
+    return online_sync_holds(o, slots, n);
+}
+
 // finish and finish_stream end the holds of the slots they end
 int online_resume_all(repet_online* o) {
     if (o->n_held == 0) return REPET_OK;
     std::vector<int32_t> ids;
     for (int32_t s = 0; s < o->S; ++s)
         if (o->held[(size_t)s]) ids.push_back(s);
-    return online_hold_slots(o, ids.data(), (int32_t)ids.size(), false);
+    return online_hold_slots(o, ids.data(), (int32_t)ids.size(), false, true);
+}
+
+// ---- per-slot inboxes: repet_online_enable_feed / feed / tick ----------------------------------------------------------------
+static const char* const kNoFeed = "online: the handle has no inboxes (repet_online_enable_feed comes first)";
+
+static int online_check_feed(const repet_online* o) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->feed_cap <= 0) return fail(REPET_ERR_BAD_ARG, kNoFeed);
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    return REPET_OK;
+}
+
+// whether any inbox holds samples (never on a handle without inboxes)
+static bool online_any_queued(const repet_online* o) {
+    if (o->feed_cap <= 0) return false;
+    for (int64_t q : o->q_count)
+        if (q > 0) return true;
+    return false;
+}
+
+// the slots the caller holds: what the whole-hop rule of a push counts (starved slots are resumed by the push itself)
+static int64_t online_caller_holds(const repet_online* o) {
+    if (o->feed_cap <= 0) return o->n_held;
+    int64_t n = 0;
+    for (unsigned char h : o->caller_held) n += h;
+    return n;
+}
+
+// a plain push after ticks: nobody is starved any more (one launch per 256 slots that were, none where no slot is)
+static int online_end_starving(repet_online* o) {
+    if (o->feed_cap <= 0) return REPET_OK;
+    std::vector<int32_t> ids;
+    for (int32_t s = 0; s < o->S; ++s)
+        if (o->starved[(size_t)s]) { o->starved[(size_t)s] = 0; ids.push_back(s); }
+    return online_sync_holds(o, ids.data(), (int32_t)ids.size());
+}
+
+// the checked rows of a feed: slot ids, counts and the ring positions they are written from; then the host counters move
+struct FeedPlan { std::vector<int32_t> slots; std::vector<int64_t> counts, wpos; };
+
+static int online_feed_plan(const repet_online* o, const int32_t* slots, const int64_t* counts, int32_t n_slots, int64_t n, FeedPlan* plan) {
+    RP_TRY(online_check_feed(o));
+    if (n_slots < 0 || n < 0 || (n_slots > 0 && !slots)) return fail(REPET_ERR_BAD_ARG, "bad size");
+    std::vector<unsigned char> seen((size_t)o->S, 0);
+    for (int32_t k = 0; k < n_slots; ++k) {
+        const int32_t s = slots[k];
+        if (s < 0 || s >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        if (seen[(size_t)s]) return fail(REPET_ERR_BAD_ARG, "online: a slot is named twice in one feed");
+        seen[(size_t)s] = 1;
+        if (o->start[(size_t)s] == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
+        const int64_t cnt = counts ? counts[k] : n;
+        if (cnt < 0 || cnt > n) return fail(REPET_ERR_BAD_ARG, "online: a count of a feed lies in [0, n]");
+        if (o->q_count[(size_t)s] + cnt > o->feed_cap) return fail(REPET_ERR_BAD_ARG, "online: the inbox of a slot would overflow (its capacity is enable_feed's)");
+        plan->slots.push_back(s);
+        plan->counts.push_back(cnt);
+        plan->wpos.push_back(((o->q_read[(size_t)s] + o->q_count[(size_t)s]) % o->feed_cap) * o->C);
+    }
+    return REPET_OK;
+}
+
+static int online_feed_launch(repet_online* o, const FeedPlan& plan, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
+    HIP_TRY(launch_feed(src, dtype, n, o->C, strides, plan.slots.data(), plan.counts.data(), plan.wpos.data(), (int32_t)plan.slots.size(),
+                        o->ring_hi(), o->ring_lo(), o->ring_stride, o->feed_cap * o->C, o->ctx->stream));
+    for (size_t k = 0; k < plan.slots.size(); ++k) o->q_count[(size_t)plan.slots[k]] += plan.counts[k];
+    return REPET_OK;
+}
+
+// A tick's plan, from the host counters alone: who is ready (live, not held by the caller, hops * H samples queued), and what the
+// push of hops * H samples completes and emits. Nobody ready: *n_ready = 0 and the tick is not made.
+static int online_tick_plan(const repet_online* o, int64_t hops, std::vector<unsigned char>* ready, int64_t* n_ready, int64_t* n,
+                            int64_t* n_new, int64_t* n_emit) {
+    RP_TRY(online_check_feed(o));
+    if (hops < 1 || hops > INT32_MAX) return fail(REPET_ERR_BAD_ARG, "online: a tick is at least one hop");
+    if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, "online: a tick is only made on a hop boundary (samples pushed % step_length == 0)");
+    *n = hops * (int64_t)o->H;
+    ready->assign((size_t)o->S, 0);
+    *n_ready = 0;
+    for (size_t s = 0; s < (size_t)o->S; ++s)
+        if (o->start[s] != kSlotIdle && !o->caller_held[s] && o->q_count[s] >= *n) { (*ready)[s] = 1; *n_ready += 1; }
+    return online_plan(o, *n, false, n_new, n_emit);
+}
+
+// The tick's chunk: the slots that are short are starved and those that were and are ready again resumed (the table changes only
+// where a slot's state does: a slot the caller holds keeps its flag until it is looked at again), then the ready slots' oldest
+// n samples go from their rings to where a push's append would have put them, and leave the queues.
+static int online_tick_take(repet_online* o, const std::vector<unsigned char>& ready, int64_t n) {
+    repet_ctx* c = o->ctx;
+    std::vector<int32_t> changed;
+    for (int32_t s = 0; s < o->S; ++s) {
+        const size_t k = (size_t)s;
+        if (o->start[k] == kSlotIdle || o->caller_held[k]) continue;
+        const unsigned char want = ready[k] ? 0 : 1;
+        if (o->starved[k] == want) continue;
+        o->starved[k] = want;
+        changed.push_back(s);
+    }
+    RP_TRY(online_sync_holds(o, changed.data(), (int32_t)changed.size()));
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    RP_TRY(online_ensure_pending(o, n));
+    std::vector<int64_t> rpos((size_t)o->S);
+    for (size_t s = 0; s < (size_t)o->S; ++s) rpos[s] = o->q_read[s] * o->C;
+    HIP_TRY(launch_take(o->ring_hi(), o->ring_lo(), o->ring_stride, o->feed_cap * o->C, rpos.data(), o->S, n * o->C,
+                        o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(), o->pend_stride(),
+                        (o->pend_hist + o->pend_count) * o->C, o->slot_start.as<int64_t>(), c->stream));
+    o->pend_count += n;
+    o->total_in += n;
+    for (size_t s = 0; s < (size_t)o->S; ++s)
+        if (ready[s]) { o->q_count[s] -= n; o->q_read[s] = (o->q_read[s] + n) % o->feed_cap; }
+    return REPET_OK;
 }
 
 }  // namespace repet_eng
@@ -1398,7 +1550,167 @@ int repet_online_resume_streams(repet_online* o, const int32_t* slots, int32_t n
 int repet_online_stream_held(repet_online* o, int32_t slot, int32_t* held) {
     if (!o || !held) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
-    *held = o->held[(size_t)slot] ? 1 : 0;
+    *held = o->caller_held[(size_t)slot] ? 1 : 0;
+    return REPET_OK;
+}
+
+int repet_online_enable_feed(repet_online* o, int64_t capacity_samples) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    if (o->feed_cap > 0) return fail(REPET_ERR_BAD_ARG, "online: the handle has its inboxes already (enable_feed is made once)");
+    if (capacity_samples < o->H) return fail(REPET_ERR_BAD_ARG, "online: an inbox holds at least one hop (capacity_samples >= step_length)");
+    if (capacity_samples * (int64_t)o->C > INT32_MAX) return fail(REPET_ERR_LIMIT, "online: an inbox holds fewer than 2^31 values");
+    if (o->total_in % o->H) return fail(REPET_ERR_BAD_ARG, "online: the inboxes can only be enabled on a hop boundary (samples pushed % step_length == 0)");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    const int64_t stride = round_up(capacity_samples * o->C, 4);
+    HIP_TRY(o->ring.ensure((size_t)2 * o->S * stride * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(o->ring.p, 0, (size_t)2 * o->S * stride * sizeof(float), c->stream));
+    RP_TRY(ensure_io_events(c));
+    o->ring_stride = stride;
+    o->q_count.assign((size_t)o->S, 0);
+    o->q_read.assign((size_t)o->S, 0);
+    o->feed_cap = capacity_samples;
+    return REPET_OK;
+}
+
+int repet_online_feed(repet_online* o, const int32_t* slots, const int64_t* counts, int32_t n_slots, const void* audio, int dtype, int64_t n) {
+    FeedPlan plan;
+    RP_TRY(online_feed_plan(o, slots, counts, n_slots, n, &plan));
+    if (dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    if (n_slots == 0 || n == 0) return REPET_OK;
+    if (!audio) return fail(REPET_ERR_BAD_ARG, "null argument");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    // the rows [n_slots][n][C] through the pinned buffer into the staging buffer, then into the rings on the device
+    const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
+    const size_t bytes = (size_t)n_slots * n * o->C * esz;
+    HIP_TRY(hipStreamSynchronize(c->stream));          // a device call may still be running; the pinned buffer is free
+    RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
+    HIP_TRY(o->staging.ensure(bytes));
+    std::memcpy(o->host_in, audio, bytes);
+    HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    const int64_t dense[3] = {n * o->C, o->C, 1};
+    return online_feed_launch(o, plan, o->staging.p, dtype, n, dense);
+}
+
+int repet_online_feed_device(repet_online* o, const int32_t* slots, const int64_t* counts, int32_t n_slots, const void* src, int dtype,
+                             int64_t n, const int64_t src_strides[3], void* wait_stream, void* signal_stream) {
+    FeedPlan plan;
+    RP_TRY(online_feed_plan(o, slots, counts, n_slots, n, &plan));
+    if (dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    RP_TRY(check_strides(src_strides));
+    if (n_slots == 0 || n == 0) return REPET_OK;
+    if (!src) return fail(REPET_ERR_BAD_ARG, "null argument");
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_feed_launch(o, plan, src, dtype, n, src_strides));
+    // the caller's stream continues behind the copy: the packet may be overwritten once that stream gets there
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
+int repet_online_queued(repet_online* o, int32_t slot, int64_t* queued) {
+    if (!o || !queued) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->feed_cap <= 0) return fail(REPET_ERR_BAD_ARG, kNoFeed);
+    if (slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    if (slot >= 0) { *queued = o->q_count[(size_t)slot]; return REPET_OK; }
+    for (size_t s = 0; s < (size_t)o->S; ++s) queued[s] = o->q_count[s];
+    return REPET_OK;
+}
+
+int repet_online_pad_feed(repet_online* o, const int32_t* slots, int32_t n_slots, int64_t* pads) {
+    RP_TRY(online_check_feed(o));
+    if (!pads || (slots && n_slots < 0)) return fail(REPET_ERR_BAD_ARG, "null argument");
+    // every live slot where none is named (an idle one pads nothing); named, an idle slot is refused as feed refuses it
+    std::vector<int32_t> ids;
+    if (slots) ids.assign(slots, slots + n_slots);
+    else for (int32_t s = 0; s < o->S; ++s) if (o->start[(size_t)s] != kSlotIdle) ids.push_back(s);
+    std::vector<int64_t> counts;
+    for (int32_t s : ids) {
+        if (s < 0 || s >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        counts.push_back((o->H - o->q_count[(size_t)s] % o->H) % o->H);
+    }
+    FeedPlan plan;
+    RP_TRY(online_feed_plan(o, ids.data(), counts.data(), (int32_t)ids.size(), o->H, &plan));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    bool any = false;
+    for (int64_t cnt : counts) any = any || cnt > 0;
+    if (any) {
+        // one hop of zeros that every row reads (row stride 0)
+        const size_t bytes = (size_t)o->H * o->C * sizeof(float);
+        HIP_TRY(o->staging.ensure(bytes));
+        HIP_TRY(hipMemsetAsync(o->staging.p, 0, bytes, c->stream));
+        const int64_t strides[3] = {0, o->C, 1};
+        RP_TRY(online_feed_launch(o, plan, o->staging.p, REPET_F32, o->H, strides));
+    }
+    if (slots) for (size_t k = 0; k < ids.size(); ++k) pads[k] = counts[k];
+    else {
+        for (int32_t s = 0; s < o->S; ++s) pads[s] = 0;
+        for (size_t k = 0; k < ids.size(); ++k) pads[(size_t)ids[k]] = counts[k];
+    }
+    return REPET_OK;
+}
+
+int repet_online_clear_feed(repet_online* o, const int32_t* slots, int32_t n_slots) {
+    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->feed_cap <= 0) return fail(REPET_ERR_BAD_ARG, kNoFeed);
+    if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
+    for (int32_t k = 0; slots && k < n_slots; ++k)
+        if (slots[k] < 0 || slots[k] >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    // host counters alone: the launches that filled the rings stay where they are in the stream, and what they wrote is
+    // overwritten by the feeds that follow before any take reads it
+    if (!slots) { std::fill(o->q_count.begin(), o->q_count.end(), 0); std::fill(o->q_read.begin(), o->q_read.end(), 0); }
+    else for (int32_t k = 0; k < n_slots; ++k) { o->q_count[(size_t)slots[k]] = 0; o->q_read[(size_t)slots[k]] = 0; }
+    return REPET_OK;
+}
+
+static void tick_consumed(const repet_online* o, const std::vector<unsigned char>* ready, uint8_t* consumed) {
+    if (!consumed) return;
+    for (size_t s = 0; s < (size_t)o->S; ++s) consumed[s] = ready ? (*ready)[s] : 0;
+}
+
+int repet_online_tick(repet_online* o, int64_t hops, double* out, int64_t capacity, uint8_t* consumed, int64_t* n_written) {
+    AlsoScope also(o);
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    std::vector<unsigned char> ready;
+    int64_t n_ready = 0, n = 0, n_new = 0, n_emit = 0;
+    RP_TRY(online_tick_plan(o, hops, &ready, &n_ready, &n, &n_new, &n_emit));
+    if (n_ready == 0) { tick_consumed(o, nullptr, consumed); return REPET_OK; }
+    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs hops * step_length)");
+    RP_TRY(online_check_also_host(o, n_emit, out));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_tick_take(o, ready, n));
+    RP_TRY(online_process(o, n_new, n_emit, -1, n));
+    RP_TRY(online_host_result(o, n_emit, out));
+    tick_consumed(o, &ready, consumed);
+    *n_written = n_emit;
+    return REPET_OK;
+}
+
+int repet_online_tick_device(repet_online* o, int64_t hops, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
+                             uint8_t* consumed, int64_t* n_written) {
+    AlsoScope also(o);
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    std::vector<unsigned char> ready;
+    int64_t n_ready = 0, n = 0, n_new = 0, n_emit = 0;
+    RP_TRY(online_tick_plan(o, hops, &ready, &n_ready, &n, &n_new, &n_emit));
+    if (n_ready == 0) { tick_consumed(o, nullptr, consumed); return REPET_OK; }
+    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
+    repet_ctx* c = o->ctx;
+    DeviceGuard guard(c->device);
+    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_tick_take(o, ready, n));
+    RP_TRY(online_process(o, n_new, n_emit, -1, n));
+    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
+    tick_consumed(o, &ready, consumed);
+    *n_written = n_emit;
     return REPET_OK;
 }
 
@@ -1417,7 +1729,7 @@ int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64
     RP_TRY(online_check_also_host(o, n_emit, out, 1));
     DeviceGuard guard(o->ctx->device);
     o->slots_on = true;
-    RP_TRY(online_hold_slots(o, &slot, 1, false));              // a held slot ends as it stands
+    RP_TRY(online_hold_slots(o, &slot, 1, false, true));        // a held slot ends as it stands
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_host_result(o, n_emit, out, 1));
     bool kept = false;
@@ -1441,7 +1753,7 @@ int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, 
     DeviceGuard guard(c->device);
     o->slots_on = true;
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
-    RP_TRY(online_hold_slots(o, &slot, 1, false));              // a held slot ends as it stands
+    RP_TRY(online_hold_slots(o, &slot, 1, false, true));        // a held slot ends as it stands
     RP_TRY(online_process(o, n_new, n_emit, slot));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
     bool kept = false;
@@ -1539,6 +1851,8 @@ int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels,
     o->max_push = max_push_samples;
     o->start.assign((size_t)n_streams, 0);
     o->held.assign((size_t)n_streams, 0);
+    o->caller_held.assign((size_t)n_streams, 0);
+    o->starved.assign((size_t)n_streams, 0);
     o->band_gain.assign((size_t)n_streams, std::vector<float>());
     o->band_stale.assign((size_t)n_streams, 0);
     o->band_nd.assign((size_t)n_streams, 0);
@@ -1582,7 +1896,7 @@ int repet_online_close(repet_online* o) {
             if (j.done) (void)hipEventDestroy(j.done);
             j.done = nullptr;
         }
-        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release(); o->levels.release();
+        o->band.release(); o->outf.release(); o->out64.release(); o->staging.release(); o->slot_start.release(); o->gain_tab.release(); o->levels.release(); o->ring.release();
         free_pinned(o->host_in, o->host_in_cap);
         free_pinned(o->host_out, o->host_out_cap);
     }
@@ -1603,7 +1917,8 @@ int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int
     if (!o || !n_written || (n > 0 && !audio)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
-    if (o->n_held > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedPush);
+    if (online_caller_holds(o) > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     *n_written = 0;
@@ -1611,6 +1926,7 @@ int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int
     RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs n_samples + window_length)");
     RP_TRY(online_check_also_host(o, n_emit, out));
+    RP_TRY(online_end_starving(o));                             // (after ticks: the slots they starved take part again)
     if (n > 0) {
         // the chunk [S][n][C] through the pinned buffer into the staging buffer, then appended to every stream on the device
         const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
@@ -1641,7 +1957,8 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
     if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
     if (n < 0 || dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
-    if (o->n_held > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedPush);
+    if (online_caller_holds(o) > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
     RP_TRY(check_strides(src_strides));
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
@@ -1650,6 +1967,7 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
     RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(online_end_starving(o));                             // (after ticks: the slots they starved take part again)
     RP_TRY(online_append(o, src, dtype, n, src_strides));
     RP_TRY(online_process(o, n_new, n_emit, -1, n));
     RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
@@ -1665,6 +1983,7 @@ int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, 
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
     RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
     if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
     RP_TRY(online_check_also_host(o, n_emit, out));
     RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
@@ -1686,6 +2005,7 @@ int repet_online_finish_device(repet_online* o, void* dst, int dst_dtype, const 
     *n_written = 0;
     int64_t n_new = 0, n_emit = 0;
     RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
     RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);

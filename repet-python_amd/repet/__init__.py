@@ -451,6 +451,28 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     unheard, at the resume. One small launch each, no host wait; a handle with no slot held pushes at the launches it always
     cost, and so does a push with held slots (``repet.online``, one stream, needs neither: not pushing is its hold).
 
+    Slots can be fed at their own pace -- packets of 10, 20 or 30 ms that never match the hop, with jitter, bursts and gaps.
+    ``enable_feed(capacity_samples)`` (once, on the hop grid; ``feed_capacity``) gives every slot an inbox of that many samples
+    per channel in device memory (``S * capacity * C * 8`` bytes), held as the handle holds samples, so that what reaches the
+    stream is bit for bit what a push of the same values would have written. ``feed(slots, chunk, counts=None)`` appends to
+    the inboxes of live slots: one slot takes ``(n, C)``, several ``(len(slots), n, C)`` with an optional ``counts[i] <= n``
+    per row, behind which nothing is read; host arrays or ROCm tensors of any ingest dtype and stride, all or nothing
+    (ValueError, nothing changed, for a slot out of range, named twice or idle, a bad count, an overflow, a handle without
+    inboxes or finished), no host wait on the device path, and the packet may be overwritten afterwards. ``tick(hops=1)`` is
+    the lockstep push of ``hops`` hops that the handle assembles itself: the live slots that are not held and have that much
+    queued (``queued(slot=None)``) are consumed, oldest samples first; the other live slots that are not held are *starved*,
+    which is ``hold`` for the length of that push, written to the device only when a slot's state changes. So the guarantee
+    is ``hold``'s: per slot, the pieces of the ticks that consumed it, then its tail, equal ``simonline`` of the samples it
+    consumed, bit for bit, in whatever packets they came and whatever the others did. ``tick`` returns what ``push``
+    returns (``out``, ``which``, ``dtype``; a tensor when ``out`` is one or the last ``feed`` was a device tensor), or None,
+    with nothing run and every record as it was, when nobody is ready; ``last_consumed`` is the bool ``(S,)`` of who took
+    part. ``pad_feed(slots=None)`` zero-pads queues to the hop grid and returns the pad counts: after the ticks that drain
+    the queue ``finish_stream(slot)[:-pad]`` is a stream's true tail. ``clear_feed(slots=None)`` empties inboxes, and so do
+    ``restart``, ``release`` and ``import_stream`` for their slots; ``finish_stream`` / ``finish`` refuse while a slot they end
+    has queued samples; a plain ``push`` is refused while any inbox holds samples and otherwise resumes the starved slots
+    first; ``held`` reports the caller's holds only; ``export_stream`` returns the stream as consumed; ``stream_samples``
+    counts consumed samples (``repet.online``, one stream, needs none of this: its ``push`` takes any ``n``).
+
     ``start_length`` (seconds; None: ``buffer_length``, the reference) lets every slot separate before its 10-s buffer has
     filled, from its own frame ``start_frames - 1`` on (see :func:`online`; the ``start_frames`` property), after every
     ``restart`` too: each life then equals the one-stream handle's output with the same ``start_length``, a stream of

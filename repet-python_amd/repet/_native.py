@@ -300,6 +300,14 @@ _SIGNATURES = {
     "repet_online_match_capacity": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "repet_online_last_matches": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "repet_online_last_matches_device": (C.c_int, [_P, _P, _P, _P, _P]),
+    "repet_online_enable_feed": (C.c_int, [_P, C.c_int64]),
+    "repet_online_feed": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int, C.c_int64]),
+    "repet_online_feed_device": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int, C.c_int64, _P, _P, _P]),
+    "repet_online_queued": (C.c_int, [_P, C.c_int32, _P]),
+    "repet_online_pad_feed": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "repet_online_clear_feed": (C.c_int, [_P, _P, C.c_int32]),
+    "repet_online_tick": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    "repet_online_tick_device": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int64)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1330,7 +1338,11 @@ class OnlineStreams:
 
     ``hold(slots)`` lets live slots sit out the pushes that follow and ``resume(slots)`` lets them go on: a held slot ignores
     its share of the chunks, emits zeros and keeps all it holds, so its stream goes on bit for bit as if those pushes had not
-    been made (``repet.online_streams``)."""
+    been made (``repet.online_streams``).
+
+    ``enable_feed(capacity_samples)`` gives every slot an inbox: ``feed(slots, chunk, counts=None)`` then takes packets of any
+    size per slot and ``tick(hops=1)`` is the push, made of the slots that have ``hops`` hops queued while the others sit it
+    out as held slots do (``queued``, ``pad_feed``, ``clear_feed``, ``last_consumed``; see ``repet.online_streams``)."""
 
     def __init__(self, params, n_channels, n_streams, device=0, max_push_samples=0, start_frames=None):
         self._h = C.c_void_p()
@@ -1351,6 +1363,10 @@ class OnlineStreams:
         self._tail_emitted = False                    # the last emitting call was a finish_stream: one slot's record
         self._begun = [0] * self._streams             # handle sample at which each slot's stream began (None: idle)
         self._held = set()                            # slots that sit out the pushes: their beginnings move along with them
+        self._hop = int(params.step_length)
+        self._feed_cap = 0                            # samples per channel of every slot's inbox (enable_feed)
+        self._feed_on_device = False                  # the last feed was a device tensor: ticks return tensors
+        self._consumed = np.zeros(self._streams, dtype=bool)
 
     @property
     def shape(self):
@@ -1644,6 +1660,140 @@ class OnlineStreams:
         out = C.c_int32()
         check(lib().repet_online_stream_held(self._handle(), self._slot(slot), C.byref(out)))
         return bool(out.value)
+
+    def enable_feed(self, capacity_samples):
+        """Give every slot an inbox of ``capacity_samples`` (at least one hop) samples per channel in device memory, ``S *
+        capacity * C * 8`` bytes in all: from here on ``feed`` fills the slots at their own pace and ``tick`` is the push. Once
+        per handle, where ``samples_pushed`` is a multiple of the hop (ValueError otherwise, nothing changes)."""
+        check(lib().repet_online_enable_feed(self._handle(), int(capacity_samples)))
+        self._feed_cap = int(capacity_samples)
+
+    @property
+    def feed_capacity(self):
+        """Samples per channel every slot's inbox holds (0: ``enable_feed`` has not been called)."""
+        return self._feed_cap
+
+    def feed(self, slots, chunk, counts=None):
+        """Append samples to the inboxes of live slots. One slot (an int) takes ``(n, C)``; several take ``(len(slots), n, C)``
+        and optionally ``counts``, one per slot with ``counts[i] <= n``: row ``i`` brings its first ``counts[i]`` samples and
+        the rest of the row is never read. Host arrays (float32 / float64 / int16) or ROCm tensors (those and float16 /
+        bfloat16, any strides); a device packet is copied on the current stream's order with no host wait and may be
+        overwritten afterwards. All or nothing: ValueError, with nothing enqueued or changed, for a slot out of range, named
+        twice or idle, a count outside ``[0, n]``, an inbox that would overflow, and a handle without inboxes or finished. A
+        held slot may be fed."""
+        single = np.isscalar(slots)
+        slots, arr = self._slot_list(slots)
+        on_device = is_device_tensor(chunk)
+        if on_device:
+            if chunk.device.index != self._device:
+                raise ValueError(f"tensor is on {chunk.device}, the streams on device {self._device}")
+            x = chunk
+        else:
+            x, code = as_input(chunk.numpy() if is_tensor(chunk) else chunk)
+        if single:
+            if len(x.shape) != 2:
+                raise ValueError("a packet for one slot is (number_samples, number_channels)")
+            x = x.unsqueeze(0) if on_device else x[None]
+        if len(x.shape) != 3 or x.shape[0] != len(slots) or x.shape[2] != self._channels:
+            raise ValueError(f"packets for {len(slots)} slots are ({len(slots)}, number_samples, {self._channels})")
+        n = int(x.shape[1])
+        cnt = None
+        if counts is not None:
+            counts = [int(k) for k in ([counts] if np.isscalar(counts) else counts)]
+            if len(counts) != len(slots):
+                raise ValueError("one count per slot named")
+            cnt = (C.c_int64 * max(len(counts), 1))(*counts)
+        if on_device:
+            import torch
+            x, code, shape, strides = tensor_layout(x, batched=True)
+            stream = torch.cuda.current_stream(x.device)
+            check(lib().repet_online_feed_device(self._handle(), arr, cnt, len(slots), C.c_void_p(x.data_ptr() or None), code, n,
+                                                 _strides(strides), _stream_handle(stream), _stream_handle(stream)))
+            x.record_stream(stream)
+        else:
+            check(lib().repet_online_feed(self._handle(), arr, cnt, len(slots), ptr(x), code, n))
+        self._feed_on_device = on_device
+
+    def queued(self, slot=None):
+        """Samples waiting in the inbox of ``slot``, or of every slot as an int64 ``(S,)`` array. Host counters: no device work."""
+        if slot is not None:
+            out = C.c_int64()
+            check(lib().repet_online_queued(self._handle(), self._slot(slot), C.byref(out)))
+            return out.value
+        out = np.zeros(self._streams, dtype=np.int64)
+        check(lib().repet_online_queued(self._handle(), -1, ptr(out)))
+        return out
+
+    def pad_feed(self, slots=None):
+        """Feed each named slot (None: every live slot) ``(-queued) % step_length`` zeros, so that its queue ends on the hop
+        grid, and return the pad counts (an int for one slot, an int64 array otherwise; ``(S,)`` for None). For a stream that
+        ends with a sub-hop remainder: after the ticks that drain the queue, ``finish_stream(slot)[:-pad]`` is its true tail."""
+        if slots is None:
+            pads = np.zeros(self._streams, dtype=np.int64)
+            check(lib().repet_online_pad_feed(self._handle(), None, 0, ptr(pads)))
+            return pads
+        single = np.isscalar(slots)
+        slots, arr = self._slot_list(slots)
+        pads = np.zeros(max(len(slots), 1), dtype=np.int64)
+        check(lib().repet_online_pad_feed(self._handle(), arr, len(slots), ptr(pads)))
+        return int(pads[0]) if single else pads[:len(slots)]
+
+    def clear_feed(self, slots=None):
+        """Empty the inboxes of the named slots (None: of all): what was queued is dropped. No device work."""
+        if slots is None:
+            check(lib().repet_online_clear_feed(self._handle(), None, 0))
+            return
+        slots, arr = self._slot_list(slots)
+        check(lib().repet_online_clear_feed(self._handle(), arr, len(slots)))
+
+    def tick(self, hops=1, out=None, which="background", dtype=None):
+        """The lockstep push of ``hops * step_length`` samples whose chunk the handle assembles from the inboxes. Every live
+        slot that is not held and has that many samples queued is *ready* and its oldest samples are consumed; every other
+        live slot that is not held is *starved*: held for this push, so it emits zeros and its stream goes on bit for bit
+        later. Returns what ``push`` returns (``out``, ``which``, ``dtype`` as there): a tensor when ``out`` is a tensor or the
+        last ``feed`` was a device tensor, else NumPy. With nobody ready nothing runs, None is returned and the handle, its
+        last emission and its records stay as they were. ``last_consumed`` says who took part. ValueError unless
+        ``samples_pushed`` is a multiple of the hop. No host wait on the device path; nothing is read back."""
+        codes = which_codes(which)
+        on_device = out is not None or self._feed_on_device
+        if dtype is not None and not on_device:
+            raise ValueError("dtype is for device results (after host packets the result is a float64 array)")
+        if self._feed_cap <= 0:
+            raise ValueError("the handle has no inboxes: enable_feed comes first")
+        hops = int(hops)
+        if hops < 1:
+            raise ValueError("a tick is at least one hop")
+        n = hops * self._hop
+        n_emit = self.emit_count(n)
+        consumed = np.zeros(self._streams, dtype=np.uint8)
+        written = C.c_int64()
+        if on_device:
+            import torch
+            results, out_code, out_strides = self._device_outs(out, n_emit, codes, dtype=dtype)
+            stream = torch.cuda.current_stream(results[0].device)
+            _select_output(self._handle(), codes, C.c_void_p(results[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
+            check(lib().repet_online_tick_device(self._handle(), hops, C.c_void_p(results[0].data_ptr() or None), out_code,
+                                                 _strides(out_strides[0]), _stream_handle(stream), ptr(consumed), C.byref(written)))
+        else:
+            results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
+            _select_output(self._handle(), codes, ptr(results[-1]))
+            check(lib().repet_online_tick(self._handle(), hops, ptr(results[0]), n_emit, ptr(consumed), C.byref(written)))
+        self._consumed = consumed.astype(bool)
+        if not self._consumed.any():
+            return None
+        self._pushed += n
+        for s in range(self._streams):                # time does not pass for a slot that sat the tick out
+            if self._begun[s] is not None and not self._consumed[s]:
+                self._begun[s] += n
+        self._last_on_device = on_device
+        self._emitted_shape = tuple(results[0].shape)
+        self._tail_emitted = False
+        return results[0] if len(results) == 1 else tuple(results)
+
+    @property
+    def last_consumed(self):
+        """bool ``(S,)``: the slots whose samples the last ``tick`` consumed (all False where nobody was ready)."""
+        return self._consumed.copy()
 
     def release(self, slots):
         """The named slots become idle without output: they ignore their share of the chunks and emit zeros."""

@@ -24,6 +24,12 @@ preallocated ``out``, each push timed with a synchronize: first on the handle as
 times over, ``hold`` of K slots spread over the handle, pushes with them held, ``resume``, pushes with nobody held; ``hold`` and
 ``resume`` are each timed as one call plus a synchronize.
 
+``--feed 1``: instead, slots fed at their own pace. One handle of S slots past its warm-up, device chunks into a preallocated
+``out``, every call timed with a synchronize: plain pushes of one hop before ``enable_feed`` was ever called; then, on the handle
+with inboxes of four hops, ``feed`` of one hop to all slots and ``tick`` (each timed alone) alternating with plain pushes; then
+packets of 882 samples (20 ms) per slot at staggered phases, one ``feed`` of all packets plus one ``tick`` per packet time, with
+the share of slots each tick consumed.
+
 ``--start-length SECONDS``: the one-handle cases on handles opened with ``start_length`` (separation from that age on, before
 the 10-s buffer has filled). The streams are then pushed only half a second past the start length, so the timed pushes are
 those of YOUNG frames, each decided on the frames heard so far; keep ``--timed`` x hops inside the buffer's first 10 s.
@@ -375,8 +381,86 @@ def hold_one_handle(xs, fs, n_held, timed, warm_s):
             "hold_ms_median": ms(hold), "resume_ms_median": ms(resume), "pushes_timed": len(never)}
 
 
+def feed_one_handle(xs, fs, timed, warm_s, packet=882):
+    import torch
+    S, N, ch = xs.shape
+    hop = repet.derive_params(fs).step_length
+    src = torch.tensor(xs, device="cuda:0")
+    h = repet.online_streams(fs, ch, S, max_push_samples=hop)
+    pos = 0
+    while pos < warm_s * fs // hop * hop:
+        n = min(fs // 2 // hop * hop, warm_s * fs // hop * hop - pos)
+        h.push(src[:, pos:pos + n])
+        pos += n
+    out = torch.empty((S, hop, ch), dtype=torch.float64, device="cuda:0")
+    for _ in range(3):
+        h.push(src[:, pos:pos + hop], out=out)
+        pos += hop
+    torch.cuda.synchronize()
+    slots = list(range(S))
+    clock = lambda t0: (torch.cuda.synchronize(), time.perf_counter() - t0)[1]
+    before = []                                                # plain pushes before enable_feed was ever called
+    for _ in range(timed):
+        t0 = time.perf_counter()
+        h.push(src[:, pos:pos + hop], out=out)
+        before.append(clock(t0))
+        pos += hop
+    h.enable_feed(4 * hop)
+    plain, feed, tick, both = [], [], [], []
+    for k in range(2 * timed + 6):
+        chunk = src[:, pos:pos + hop]
+        pos += hop
+        if k % 2:                                              # plain pushes between the ticks, on the handle with inboxes
+            t0 = time.perf_counter()
+            h.push(chunk, out=out)
+            plain.append(clock(t0))
+            continue
+        t0 = time.perf_counter()
+        h.feed(slots, chunk)
+        t1 = clock(t0)
+        t2 = time.perf_counter()
+        h.tick(out=out)
+        t3 = clock(t2)
+        if k >= 6:                                             # (the take and feed kernels have run before the clock starts)
+            feed.append(t1), tick.append(t3), both.append(t1 + t3)
+    # packets that never match the hop: every slot gets `packet` samples per packet time, at a phase of its own
+    for s in range(S):
+        lead = (s * 131) % hop
+        if lead:
+            h.feed(s, src[s, pos:pos + lead])
+    cursor = [pos + (s * 131) % hop for s in range(S)]
+    ragged, share, writes = [], [], 0
+    staged = torch.empty((S, packet, ch), dtype=torch.float64, device="cuda:0")
+    for k in range(timed + 3):
+        if max(cursor) + packet > N:
+            break
+        for s in range(S):
+            staged[s] = src[s, cursor[s]:cursor[s] + packet]
+            cursor[s] += packet
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.feed(slots, staged)
+        h.tick(out=out)
+        t1 = clock(t0)
+        if k >= 3:
+            ragged.append(t1)
+            share.append(float(h.last_consumed.mean()))
+    h.close()
+    ms = lambda v: round(float(np.median(np.array(v) * 1e3)), 3) if v else None
+    p95 = lambda v: round(float(np.percentile(np.array(v) * 1e3, 95)), 3) if v else None
+    return {"hop_ms": round(1e3 * hop / fs, 2), "inbox_hops": 4,
+            "push_ms_median_no_enable_feed": ms(before), "push_ms_p95_no_enable_feed": p95(before),
+            "push_ms_median_with_inboxes": ms(plain),
+            "feed_ms_median": ms(feed), "feed_ms_p95": p95(feed), "tick_ms_median": ms(tick), "tick_ms_p95": p95(tick),
+            "feed_plus_tick_ms_median": ms(both),
+            "packet_samples": packet, "ragged_feed_plus_tick_ms_median": ms(ragged), "ragged_feed_plus_tick_ms_p95": p95(ragged),
+            "ragged_share_of_slots_consumed": round(float(np.mean(share)), 3) if share else None,
+            "calls_timed": len(both), "ragged_ticks_timed": len(ragged)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--feed", type=int, default=0, help="1: the feed leg (feed / tick of slots fed at their own pace)")
     ap.add_argument("--hold", type=int, default=0, metavar="K", help="the hold leg: pushes of one hop with K of the slots held")
     ap.add_argument("--migrate", type=int, default=0, help="1: the migrate leg (export_stream / import_stream per call)")
     ap.add_argument("--streams", default="1,8,64,256")
@@ -410,6 +494,14 @@ def main():
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
+    if args.feed > 0:
+        hop = repet.derive_params(fs).step_length
+        result = {"fs": fs, "channels": ch, "cases": []}
+        for S in streams:
+            xs = stream_signals(S, warm_s + 1 + (4 * args.timed + 24) * hop / fs, fs, ch)
+            result["cases"].append(dict({"streams": S}, **feed_one_handle(xs, fs, args.timed, warm_s)))
+        print(json.dumps(result, indent=1))
+        return
     if args.hold > 0:
         hop = repet.derive_params(fs).step_length
         result = {"fs": fs, "channels": ch, "cases": []}
