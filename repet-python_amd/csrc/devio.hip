@@ -1437,6 +1437,24 @@ int ensure_io_events(repet_ctx* c) {
     return REPET_OK;
 }
 
+int wait_caller(repet_ctx* c, void* wait_stream, void* signal_stream) {
+    const hipStream_t wait = static_cast<hipStream_t>(wait_stream), signal = static_cast<hipStream_t>(signal_stream);
+    RP_TRY(ensure_io_events(c));
+    HIP_TRY(hipEventRecord(c->io_wait, wait));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    if (signal != wait) {
+        HIP_TRY(hipEventRecord(c->io_wait, signal));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    }
+    return REPET_OK;
+}
+
+int signal_caller(repet_ctx* c, void* signal_stream) {
+    HIP_TRY(hipEventRecord(c->io_done, c->stream));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    return REPET_OK;
+}
+
 }  // namespace repet_eng
 
 extern "C" {
@@ -1453,10 +1471,8 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     HIP_TRY(c->audio.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
     HIP_TRY(c->out.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
     if (dtype == REPET_F64) HIP_TRY(c->audio_lo.ensure(std::max<size_t>((size_t)count * sizeof(float), 256)));
-    RP_TRY(ensure_io_events(c));
     // the producer of `src` is the caller's stream: the context's stream starts the ingest behind what it has enqueued so far
-    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(wait_stream)));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    RP_TRY(wait_caller(c, wait_stream, wait_stream));
     // a float64 host upload of this context may still have its remainder plane on the way into audio_lo (copy stream): the
     // ingest must land after it, not under it. (lo_in_flight stays set: the host has not seen the copy finish, and the ring's
     // remainder buffer must not be refilled before it has -- StagingRing waits for lo_done then.)
@@ -1539,11 +1555,9 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;
     if (count > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null argument");
     DeviceGuard guard(c->device);
-    RP_TRY(ensure_io_events(c));
     // the destination belongs to the caller's stream: what that stream has enqueued up to now (a pending reader of a block the
     // caching allocator has just handed out again, the caller's own writes to `dst`) comes before the egress writes it
-    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(signal_stream)));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     if (count > 0 && c->result_which != REPET_OUT_BACKGROUND) {
         // foreground / mixture: the resident samples and, where a float64 upload left them, their remainders beside the result
         if (c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
@@ -1557,9 +1571,7 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
         HIP_TRY(launch_stream_egress(c->out.as<float>(), c->n_clips, c->n_samples, c->n_channels, dst, dtype, strides, c->stream));
     }
     // the caller's stream continues behind the egress
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream) {
@@ -1567,10 +1579,8 @@ int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream)
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
     DeviceGuard guard(c->device);
-    RP_TRY(ensure_io_events(c));
     // the destination belongs to the caller's stream, as in repet_ctx_download_device_strided
-    HIP_TRY(hipEventRecord(c->io_wait, static_cast<hipStream_t>(signal_stream)));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;
     if (count > 0 && c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
     const int64_t partials = stream_levels_partials(c->n_clips, c->n_samples, c->n_channels);
@@ -1584,9 +1594,7 @@ int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream)
                                               c->result_gain ? &gain : nullptr, c->shaped_bg());
     if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
     HIP_TRY(e);
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   engine_sim.hip     sim, simonline, the peak picking's refinement plumbing
 //   engine_batch.hip   repet_run_batch over several devices, the RCCL transport
 //   engine_stages.hip  stage-level exports and the accessors of a run's integer intermediates
-//   engine_online.hip  the streaming handle
+//   engine_online.hip  the streaming handle: one body per emitting call, host and device forms alike
 #pragma once
 #include "../../include/repet_hip.h"
 #include "common.h"
@@ -280,10 +280,14 @@ int begin_shaped(repet_ctx* c, const repet_params* p);
 int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain);
 void mark_shaped(repet_ctx* c, double bytes);
 int clear_shaped(repet_ctx* c, int64_t first_value, int64_t n_values);
-// device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events
+// device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events and the two waits made of them
 int check_strides(const int64_t* strides);
 int check_no_overlap(const int64_t* strides, int32_t n_clips, int64_t n, int32_t ch);
 int ensure_io_events(repet_ctx* c);
+// the context's stream behind what the caller's stream(s) have enqueued so far (the producer of a source, earlier users of a
+// destination; the same stream twice is recorded and waited for once), and the caller's stream behind what the context's has
+int wait_caller(repet_ctx* c, void* wait_stream, void* signal_stream);
+int signal_caller(repet_ctx* c, void* signal_stream);
 // a background gain g in [0, 1] (BAD_ARG otherwise, NaN included) and what the egress multiplies the background by: (float)(1 - g)
 int check_background_gain(float gain);
 float background_gain_factor(float gain);

@@ -18,6 +18,9 @@ using namespace repet_eng;
 // picking, the mask and the row zeroing behind the STFT read on the device; the launch shapes are the handle's.
 // A slot may also sit out pushes (repet_online_hold_streams): held, it reads as idle on the device while its share of the buffers
 // stays where it is (launch_slide_held) and its first frame moves along with the handle on the host.
+// Every emitting call (push, tick, finish, finish_stream) has one body, online_*_impl; its host and device entry points differ in
+// the Sink they build. The waits on the caller's streams are the context's (engine.h: wait_caller / signal_caller), the pinned
+// round trips of the host forms online_download / online_upload.
 // =====================================================================================================
 struct repet_online {
     repet_ctx* ctx = nullptr;       // stream, tables, tile cache, scratch buffers
@@ -167,6 +170,39 @@ static int ensure_pinned(void*& p, size_t& cap, size_t bytes) {
     const size_t want = std::max<size_t>((bytes + 4095) & ~size_t(4095), 4096);
     HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
     cap = want;
+    return REPET_OK;
+}
+
+// The pinned round trips of the host forms, once each. Down: `bytes` of device memory into the pinned buffer, one copy and one
+// wait; the caller copies on from o->host_out (several scatter one block into two or three arrays).
+static int online_download(repet_online* o, const void* dev, size_t bytes) {
+    repet_ctx* c = o->ctx;
+    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, bytes));
+    HIP_TRY(hipMemcpyAsync(o->host_out, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return REPET_OK;
+}
+
+// Up: `bytes` of the caller's memory through the pinned buffer on their way into o->staging.
+static int online_upload(repet_online* o, const void* host, size_t bytes) {
+    repet_ctx* c = o->ctx;
+    HIP_TRY(hipStreamSynchronize(c->stream));          // a device call may still be running; the pinned buffer is free
+    RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
+    HIP_TRY(o->staging.ensure(bytes));
+    std::memcpy(o->host_in, host, bytes);
+    HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    return REPET_OK;
+}
+
+// The records of the last emitting call (its emission, a finish_stream tail's levels, its frames and with them its matches) end
+// with every call that appends samples (push, tick) or changes the slot table (restart, release, finish_stream, import, hold,
+// resume): what the records point at is about to be overwritten, or the table at query time would not be the call's.
+static void online_invalidate_records(repet_online* o) {
+    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+}
+
+static int check_slot(const repet_online* o, int32_t slot) {
+    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
     return REPET_OK;
 }
 
@@ -471,7 +507,7 @@ int online_plan(const repet_online* o, int64_t n, bool finishing, int64_t* n_new
 // the chunk's samples (already where `src` says, device memory) appended to every stream's pending buffer
 int online_append(repet_online* o, const void* src, int dtype, int64_t n, const int64_t strides[3]) {
     if (n <= 0) return REPET_OK;
-    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    online_invalidate_records(o);
     RP_TRY(online_ensure_pending(o, n));
     hipError_t e = launch_stream_append(src, dtype, o->S, n, o->C, strides, o->pend[o->pcur].as<float>(), o->pend_lo[o->pcur].as<float>(),
                                         o->pend_stride(), (o->pend_hist + o->pend_count) * o->C, o->ctx->stream);
@@ -560,34 +596,29 @@ int online_host_result(repet_online* o, int64_t n_emit, double* out, int streams
     const int S = streams > 0 ? streams : o->S;
     const int64_t count = (int64_t)S * n_emit * o->C;
     const int blocks = o->also.which < 0 ? 1 : 2;
-    if (count > 0) {
-        HIP_TRY(o->out64.ensure((size_t)count * blocks * sizeof(double)));
-        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * blocks * sizeof(double)));
-        const int64_t dense[3] = {n_emit * o->C, o->C, 1};
-        EmitDst d[2];
-        const int nd = online_outputs(o, o->out64.p, dense, o->out64.as<double>() + count, dense, d);
-        RP_TRY(online_emit(o, d, nd, REPET_F64));
-        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * blocks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (count <= 0) {                                   // nothing to copy: the call still returns behind its launches
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return REPET_OK;
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (count > 0) {
-        std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
-        if (blocks == 2) std::memcpy(o->also.dst, static_cast<double*>(o->host_out) + count, (size_t)count * sizeof(double));
-    }
+    HIP_TRY(o->out64.ensure((size_t)count * blocks * sizeof(double)));
+    const int64_t dense[3] = {n_emit * o->C, o->C, 1};
+    EmitDst d[2];
+    const int nd = online_outputs(o, o->out64.p, dense, o->out64.as<double>() + count, dense, d);
+    RP_TRY(online_emit(o, d, nd, REPET_F64));
+    RP_TRY(online_download(o, o->out64.p, (size_t)count * blocks * sizeof(double)));
+    std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    if (blocks == 2) std::memcpy(o->also.dst, static_cast<double*>(o->host_out) + count, (size_t)count * sizeof(double));
     return REPET_OK;
 }
 
 // device side: the result into the caller's strided destination(s), then the caller's stream behind it
-int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], hipStream_t signal,
+int online_device_result(repet_online* o, int64_t n_emit, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                          int streams = 0) {
-    repet_ctx* c = o->ctx;
     EmitDst d[2];
     const int64_t also_strides[3] = {streams > 0 ? 0 : o->also.strides[0], o->also.strides[1], o->also.strides[2]};
     const int nd = online_outputs(o, dst, dst_strides, o->also.dst, also_strides, d);
     RP_TRY(online_emit(o, d, nd, dst_dtype));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(signal, c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(o->ctx, signal_stream);
 }
 
 // the armed second output is consumed by the emitting call that follows it, whether that call succeeds or not
@@ -623,17 +654,41 @@ int online_check_dst(const repet_online* o, int64_t n_emit, const void* dst, int
     return REPET_OK;
 }
 
-// the engine's stream behind what the caller's stream(s) have enqueued so far (the producer of the chunk, earlier users of dst)
-int online_wait_caller(repet_online* o, hipStream_t wait, hipStream_t signal) {
-    repet_ctx* c = o->ctx;
-    RP_TRY(ensure_io_events(c));
-    HIP_TRY(hipEventRecord(c->io_wait, wait));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
-    if (signal != wait) {
-        HIP_TRY(hipEventRecord(c->io_wait, signal));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->io_wait, 0));
-    }
-    return REPET_OK;
+// Where the result of an emitting call goes, which is all that tells its host form from its device form: a dense float64 host
+// array of `capacity` samples per stream and channel, or strided device memory of `dtype` that `signal_stream` goes on to use.
+struct Sink {
+    bool device = false;
+    double* out = nullptr; int64_t capacity = 0;
+    void* dst = nullptr; int dtype = REPET_F64; const int64_t* strides = nullptr; void* signal_stream = nullptr;
+};
+
+static Sink host_sink(double* out, int64_t capacity) {
+    Sink k;
+    k.out = out; k.capacity = capacity;
+    return k;
+}
+
+static Sink device_sink(void* dst, int dtype, const int64_t* strides, void* signal_stream) {
+    Sink k;
+    k.device = true; k.dst = dst; k.dtype = dtype; k.strides = strides; k.signal_stream = signal_stream;
+    return k;
+}
+
+// before any launch: the destination(s) against what the call is about to emit (too_small: the call's own words for a short host array)
+static int sink_check(const repet_online* o, const Sink& k, int64_t n_emit, const char* too_small, int streams = 0) {
+    if (k.device) return online_check_dst(o, n_emit, k.dst, k.dtype, k.strides, streams);
+    if (n_emit > k.capacity || (n_emit > 0 && !k.out)) return fail(REPET_ERR_BAD_ARG, too_small);
+    return online_check_also_host(o, n_emit, k.out, streams);
+}
+
+// the engine's stream behind what the caller's stream(s) have enqueued so far (the producer of a chunk, earlier users of dst)
+static int sink_begin(repet_online* o, const Sink& k, void* wait_stream) {
+    return k.device ? wait_caller(o->ctx, wait_stream, k.signal_stream) : REPET_OK;
+}
+
+static int sink_deliver(repet_online* o, const Sink& k, int64_t n_emit, int streams = 0) {
+    if (k.device) return online_device_result(o, n_emit, k.dst, k.dtype, k.strides, k.signal_stream, streams);
+    return online_host_result(o, n_emit, k.out, streams);
 }
 
 // a launch has just written the slot's table entry (restart, release, import): nobody holds it any more, and its inbox is empty
@@ -648,7 +703,7 @@ static void online_forget_slot(repet_online* o, int32_t slot) {
 // spectrum (the overlap-add tail of the next hop), the pending samples and their remainders. Enqueues only.
 int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t first_frame) {
     repet_ctx* c = o->ctx;
-    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    online_invalidate_records(o);
     if (n <= 0) return REPET_OK;
     const int64_t FS = o->FS, plane = o->plane(), spec = o->spec_stride(), held = (o->pend_hist + o->pend_count) * o->C;
     ZeroPart parts[kRowCopyParts] = {};
@@ -680,8 +735,7 @@ int online_reset_slots(repet_online* o, const int32_t* slots, int32_t n, int64_t
 int online_check_slots(const repet_online* o, const int32_t* slots, int32_t n) {
     if (!o || n < 0 || (n > 0 && !slots)) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
-    for (int32_t k = 0; k < n; ++k)
-        if (slots[k] < 0 || slots[k] >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    for (int32_t k = 0; k < n; ++k) RP_TRY(check_slot(o, slots[k]));
     return REPET_OK;
 }
 
@@ -853,7 +907,7 @@ int online_import(repet_online* o, int32_t slot, const StateHeader& h, const flo
     repet_ctx* c = o->ctx;
     const StateLayout l = state_layout(o);
     const int64_t delta = std::max<int64_t>(0, l.m + h.hist_rows - o->total_in / o->H);
-    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    online_invalidate_records(o);
     RP_TRY(online_ensure_windows(o, std::max<int64_t>(o->max_push / o->H + 1, o->W / o->H + 1)));
     RP_TRY(online_ensure_pending(o, delta * o->H));
     if (delta > 0) RP_TRY(online_shift_epoch(o, delta));
@@ -904,7 +958,7 @@ static int online_sync_holds(repet_online* o, const int32_t* slots, int32_t n) {
         values.push_back(want ? kSlotHeld : o->start[s]);
     }
     if (ids.empty()) return REPET_OK;
-    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    online_invalidate_records(o);
     o->slots_on = true;
     HIP_TRY(launch_slot_set(o->slot_start.as<int64_t>(), ids.data(), values.data(), (int32_t)ids.size(), c->stream));
     return REPET_OK;
@@ -974,7 +1028,7 @@ static int online_feed_plan(const repet_online* o, const int32_t* slots, const i
     std::vector<unsigned char> seen((size_t)o->S, 0);
     for (int32_t k = 0; k < n_slots; ++k) {
         const int32_t s = slots[k];
-        if (s < 0 || s >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        RP_TRY(check_slot(o, s));
         if (seen[(size_t)s]) return fail(REPET_ERR_BAD_ARG, "online: a slot is named twice in one feed");
         seen[(size_t)s] = 1;
         if (o->start[(size_t)s] == kSlotIdle) return fail(REPET_ERR_BAD_ARG, "online: the slot is idle");
@@ -1025,7 +1079,7 @@ static int online_tick_take(repet_online* o, const std::vector<unsigned char>& r
         changed.push_back(s);
     }
     RP_TRY(online_sync_holds(o, changed.data(), (int32_t)changed.size()));
-    o->em.valid = false; o->tail_valid = false; o->fr.valid = false;
+    online_invalidate_records(o);
     RP_TRY(online_ensure_pending(o, n));
     std::vector<int64_t> rpos((size_t)o->S);
     for (size_t s = 0; s < (size_t)o->S; ++s) rpos[s] = o->q_read[s] * o->C;
@@ -1036,6 +1090,100 @@ static int online_tick_take(repet_online* o, const std::vector<unsigned char>& r
     o->total_in += n;
     for (size_t s = 0; s < (size_t)o->S; ++s)
         if (ready[s]) { o->q_count[s] -= n; o->q_read[s] = (o->q_read[s] + n) % o->feed_cap; }
+    return REPET_OK;
+}
+
+// ---- the emitting calls: one body each for the host and the device form (the public entry points build the Sink) -----------------
+// Every refusal comes before the first launch, in the order a caller of either form has always seen. *n_written is zero from the
+// point each body says and the count of the emission on success alone.
+static const char* const kHeldPush = "online: while a stream is held a push is a whole number of hops (n % step_length == 0)";
+
+// A host chunk (k.device false) is dense [S][n][C] of a dtype up to REPET_I16 and goes through the pinned buffer; a device chunk
+// lies at src_strides, of a dtype up to REPET_BF16, produced on wait_stream.
+static int online_push_impl(repet_online* o, const void* src, int dtype, int64_t n, const int64_t* src_strides, void* wait_stream,
+                            const Sink& k, int64_t* n_written) {
+    if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
+    if (n < 0 || dtype < REPET_F32 || dtype > (k.device ? REPET_BF16 : REPET_I16)) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedPush);
+    if (online_caller_holds(o) > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
+    if (k.device) RP_TRY(check_strides(src_strides));
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
+    RP_TRY(sink_check(o, k, n_emit, "online: output capacity too small (needs n_samples + window_length)"));
+    DeviceGuard guard(o->ctx->device);
+    RP_TRY(sink_begin(o, k, wait_stream));
+    RP_TRY(online_end_starving(o));                             // (after ticks: the slots they starved take part again)
+    const int64_t dense[3] = {n * o->C, o->C, 1};
+    if (!k.device && n > 0) {
+        // the chunk [S][n][C] through the pinned buffer into the staging buffer, then appended to every stream on the device
+        const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
+        RP_TRY(online_upload(o, src, (size_t)o->S * n * o->C * esz));
+        src = o->staging.p;
+    }
+    RP_TRY(online_append(o, src, dtype, n, k.device ? src_strides : dense));
+    RP_TRY(online_process(o, n_new, n_emit, -1, n));
+    RP_TRY(sink_deliver(o, k, n_emit));
+    *n_written = n_emit;
+    return REPET_OK;
+}
+
+static int online_tick_impl(repet_online* o, int64_t hops, const Sink& k, uint8_t* consumed, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    std::vector<unsigned char> ready;
+    int64_t n_ready = 0, n = 0, n_new = 0, n_emit = 0;
+    RP_TRY(online_tick_plan(o, hops, &ready, &n_ready, &n, &n_new, &n_emit));
+    if (n_ready > 0) {                                          // (nobody ready: the tick is not made, and `ready` is all zero)
+        RP_TRY(sink_check(o, k, n_emit, "online: output capacity too small (needs hops * step_length)"));
+        DeviceGuard guard(o->ctx->device);
+        RP_TRY(sink_begin(o, k, k.signal_stream));
+        RP_TRY(online_tick_take(o, ready, n));
+        RP_TRY(online_process(o, n_new, n_emit, -1, n));
+        RP_TRY(sink_deliver(o, k, n_emit));
+        *n_written = n_emit;
+    }
+    if (consumed) std::copy(ready.begin(), ready.end(), consumed);
+    return REPET_OK;
+}
+
+static int online_finish_impl(repet_online* o, const Sink& k, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
+    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
+    RP_TRY(sink_check(o, k, n_emit, "online: output capacity too small"));
+    DeviceGuard guard(o->ctx->device);
+    RP_TRY(sink_begin(o, k, k.signal_stream));
+    RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
+    RP_TRY(online_process(o, n_new, n_emit));
+    RP_TRY(sink_deliver(o, k, n_emit));
+    *n_written = n_emit;
+    o->finished = true;
+    return REPET_OK;
+}
+
+// (streams = 1 throughout: the result is the one slot's, [n_emit][C], and a device sink's strides begin with a 0)
+static int online_finish_stream_impl(repet_online* o, int32_t slot, const Sink& k, int64_t* n_written) {
+    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *n_written = 0;
+    int64_t n_new = 0, n_emit = 0;
+    RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
+    RP_TRY(sink_check(o, k, n_emit, "online: output capacity too small", 1));
+    DeviceGuard guard(o->ctx->device);
+    o->slots_on = true;
+    RP_TRY(sink_begin(o, k, k.signal_stream));
+    RP_TRY(online_hold_slots(o, &slot, 1, false, true));        // a held slot ends as it stands
+    RP_TRY(online_process(o, n_new, n_emit, slot));
+    RP_TRY(sink_deliver(o, k, n_emit, 1));
+    // the call drops its slot's samples: the tail's levels are measured first, and their record outlives the reset
+    bool kept = false;
+    RP_TRY(online_keep_tail_levels(o, &kept));
+    RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
+    o->tail_valid = kept;
+    *n_written = n_emit;
     return REPET_OK;
 }
 
@@ -1079,12 +1227,10 @@ int repet_online_last_emission(repet_online* o, int which, double* out, int64_t 
     DeviceGuard guard(c->device);
     if (count > 0) {
         HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
-        RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
         EmitDst d;
         d.p = o->out64.p; d.which = which; d.strides[0] = n * o->C; d.strides[1] = o->C; d.strides[2] = 1;
         RP_TRY(online_emit(o, &d, 1, REPET_F64));
-        HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(double)));
         std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
     }
     *n_written = n;
@@ -1104,13 +1250,12 @@ int repet_online_last_emission_device(repet_online* o, int which, void* dst, int
     if ((int64_t)o->em.S * o->em.n * o->C > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     EmitDst d;
     d.p = dst; d.which = which;
     for (int k = 0; k < 3; ++k) d.strides[k] = strides[k];
     RP_TRY(online_emit(o, &d, 1, dst_dtype));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    RP_TRY(signal_caller(c, signal_stream));
     *n_written = o->em.n;
     return REPET_OK;
 }
@@ -1134,9 +1279,7 @@ int repet_online_last_levels(repet_online* o, double* out, int64_t capacity_doub
         RP_TRY(online_levels(o, o->levels.as<double>()));
         record = o->levels.as<double>();
     }
-    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, (size_t)count * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(o->host_out, record, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RP_TRY(online_download(o, record, (size_t)count * sizeof(double)));
     std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
     *n_written = count;
     return REPET_OK;
@@ -1149,14 +1292,12 @@ int repet_online_last_levels_device(repet_online* o, void* dst, void* signal_str
     if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     if (o->tail_valid)
         HIP_TRY(hipMemcpyAsync(dst, o->tail_levels(), (size_t)o->C * REPET_LEVEL_FIELDS * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     else
         RP_TRY(online_levels(o, static_cast<double*>(dst)));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 static const char* const kStaleFrames =
@@ -1176,13 +1317,18 @@ static int online_frame_args(const repet_online* o, int which, FrameArgs* a) {
     return REPET_OK;
 }
 
-static int check_band_edges(const repet_online* o, const int32_t* edges, int32_t n_bands) {
-    if (n_bands > REPET_MAX_BANDS) return fail(REPET_ERR_LIMIT, "online: at most REPET_MAX_BANDS (128) bands");
-    if (n_bands < 1 || !edges) return fail(REPET_ERR_BAD_ARG, "online: at least one band and its edges");
+// n_bands + 1 edges (the caller has checked n_bands against its own limits)
+static int check_edges_ascend(const repet_online* o, const int32_t* edges, int32_t n_bands) {
     for (int32_t k = 0; k <= n_bands; ++k)
         if (edges[k] < 0 || edges[k] > o->F || (k > 0 && edges[k] < edges[k - 1]))
             return fail(REPET_ERR_BAD_ARG, "online: band edges are ascending bins in [0, window_length / 2 + 1]");
     return REPET_OK;
+}
+
+static int check_band_edges(const repet_online* o, const int32_t* edges, int32_t n_bands) {
+    if (n_bands > REPET_MAX_BANDS) return fail(REPET_ERR_LIMIT, "online: at most REPET_MAX_BANDS (128) bands");
+    if (n_bands < 1 || !edges) return fail(REPET_ERR_BAD_ARG, "online: at least one band and its edges");
+    return check_edges_ascend(o, edges, n_bands);
 }
 
 // a destination [S][n][C][F] at element strides: non-negative, and no two elements at one address (check_no_overlap's rule)
@@ -1209,16 +1355,6 @@ int repet_online_last_frame_range(repet_online* o, int64_t* first_frame, int64_t
     return REPET_OK;
 }
 
-// the host forms: the result dense in out64, one copy into the pinned buffer, one wait
-static int online_frames_to_host(repet_online* o, void* out, size_t bytes) {
-    repet_ctx* c = o->ctx;
-    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, bytes));
-    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(out, o->host_out, bytes);
-    return REPET_OK;
-}
-
 int repet_online_last_frames(repet_online* o, int which, float* out, int64_t capacity_floats, int64_t* n_written) {
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
@@ -1236,7 +1372,8 @@ int repet_online_last_frames(repet_online* o, int which, float* out, int64_t cap
     HIP_TRY(o->out64.ensure((size_t)count * sizeof(float)));
     const int64_t dense[4] = {o->fr.n * o->C * o->F, (int64_t)o->C * o->F, o->F, 1};
     HIP_TRY(launch_online_frames(a, o->S, o->out64.as<float>(), dense, c->stream));
-    RP_TRY(online_frames_to_host(o, out, (size_t)count * sizeof(float)));
+    RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(float)));
+    std::memcpy(out, o->host_out, (size_t)count * sizeof(float));
     *n_written = count;
     return REPET_OK;
 }
@@ -1253,11 +1390,9 @@ int repet_online_last_frames_device(repet_online* o, int which, void* dst, const
     RP_TRY(online_frame_args(o, which, &a));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     HIP_TRY(launch_online_frames(a, o->S, static_cast<float*>(dst), dst_strides, c->stream));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 int repet_online_last_band_energies(repet_online* o, int which, const int32_t* edges, int32_t n_bands, double* out,
@@ -1278,7 +1413,8 @@ int repet_online_last_band_energies(repet_online* o, int which, const int32_t* e
     DeviceGuard guard(c->device);
     HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
     HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, o->out64.as<double>(), c->stream));
-    RP_TRY(online_frames_to_host(o, out, (size_t)count * sizeof(double)));
+    RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(double)));
+    std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
     *n_written = count;
     return REPET_OK;
 }
@@ -1295,11 +1431,9 @@ int repet_online_last_band_energies_device(repet_online* o, int which, const int
     RP_TRY(online_frame_args(o, which, &a));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, static_cast<double*>(dst), c->stream));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 static const char* const kStaleMatches =
@@ -1358,9 +1492,7 @@ int repet_online_last_matches(repet_online* o, int32_t* count_out, int32_t* age_
     int32_t* age = cnt + rows;
     float* sim = reinterpret_cast<float*>(age + rows * K);
     HIP_TRY(launch_online_matches(a, o->S, cnt, age, sim, c->stream));
-    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, words * 4));
-    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RP_TRY(online_download(o, o->out64.p, words * 4));
     const int32_t* got = static_cast<const int32_t*>(o->host_out);
     std::memcpy(count_out, got, (size_t)rows * 4);
     std::memcpy(age_out, got + rows, (size_t)rows * K * 4);
@@ -1378,12 +1510,10 @@ int repet_online_last_matches_device(repet_online* o, void* count_dst, void* age
     RP_TRY(online_match_args(o, &a));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     HIP_TRY(launch_online_matches(a, o->S, static_cast<int32_t*>(count_dst), static_cast<int32_t*>(age_dst),
                                   static_cast<float*>(similarity_dst), c->stream));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int32_t n_slots, const float* gains) {
@@ -1391,7 +1521,7 @@ int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int3
     if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
     const int32_t n = slots ? n_slots : 1;
     for (int32_t k = 0; k < n; ++k) {
-        if (slots && (slots[k] < 0 || slots[k] >= o->S)) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        if (slots) RP_TRY(check_slot(o, slots[k]));
         RP_TRY(check_background_gain(gains[k]));
     }
     if (n == 0) return REPET_OK;
@@ -1424,7 +1554,7 @@ int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int3
 
 int repet_online_background_gain(repet_online* o, int32_t slot, float* gain_out) {
     if (!o || !gain_out) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    RP_TRY(check_slot(o, slot));
     *gain_out = o->gain[(size_t)slot];
     return REPET_OK;
 }
@@ -1437,14 +1567,11 @@ int repet_online_set_background_band_gains(repet_online* o, const int32_t* slots
     if (gains_rows != 1 && gains_rows != n) return fail(REPET_ERR_BAD_ARG, "online: one row of band gains, or one per slot named");
     if (edges) {
         if (n_bands < 1 || n_bands > o->F) return fail(REPET_ERR_BAD_ARG, "online: between one band and one per bin");
-        for (int32_t k = 0; k <= n_bands; ++k)
-            if (edges[k] < 0 || edges[k] > o->F || (k > 0 && edges[k] < edges[k - 1]))
-                return fail(REPET_ERR_BAD_ARG, "online: band edges are ascending bins in [0, window_length / 2 + 1]");
+        RP_TRY(check_edges_ascend(o, edges, n_bands));
     } else if (n_bands != o->F) {
         return fail(REPET_ERR_BAD_ARG, "online: without edges there is one gain per bin (window_length / 2 + 1 of them)");
     }
-    for (int32_t k = 0; k < n; ++k)
-        if (slots && (slots[k] < 0 || slots[k] >= o->S)) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    for (int32_t k = 0; slots && k < n; ++k) RP_TRY(check_slot(o, slots[k]));
     for (int64_t k = 0; k < (int64_t)gains_rows * n_bands; ++k)
         if (!(gains[k] >= 0.f && gains[k] <= 1.f)) return fail(REPET_ERR_BAD_ARG, "online: a band gain lies in [0, 1]");
     if (o->W > 4096) return fail(REPET_ERR_LIMIT, "online: band gains need a window_length of at most 4096");
@@ -1494,7 +1621,7 @@ int repet_online_set_background_band_gains(repet_online* o, const int32_t* slots
 
 int repet_online_background_band_gains(repet_online* o, int32_t slot, float* out, int32_t capacity) {
     if (!o || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    RP_TRY(check_slot(o, slot));
     if (capacity < o->F) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (window_length / 2 + 1 values)");
     const std::vector<float>& g = o->band_gain[(size_t)slot];
     for (int32_t k = 0; k < o->F; ++k) out[k] = g.empty() ? 0.f : g[(size_t)k];
@@ -1529,7 +1656,6 @@ int repet_online_release_streams(repet_online* o, const int32_t* slots, int32_t 
 }
 
 static const char* const kHoldGrid = "online: a stream can only be held or resumed on a hop boundary (samples pushed % step_length == 0)";
-static const char* const kHeldPush = "online: while a stream is held a push is a whole number of hops (n % step_length == 0)";
 
 int repet_online_hold_streams(repet_online* o, const int32_t* slots, int32_t n) {
     RP_TRY(online_check_slots(o, slots, n));
@@ -1549,7 +1675,7 @@ int repet_online_resume_streams(repet_online* o, const int32_t* slots, int32_t n
 
 int repet_online_stream_held(repet_online* o, int32_t slot, int32_t* held) {
     if (!o || !held) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (slot < 0 || slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    RP_TRY(check_slot(o, slot));
     *held = o->caller_held[(size_t)slot] ? 1 : 0;
     return REPET_OK;
 }
@@ -1584,12 +1710,7 @@ int repet_online_feed(repet_online* o, const int32_t* slots, const int64_t* coun
     DeviceGuard guard(c->device);
     // the rows [n_slots][n][C] through the pinned buffer into the staging buffer, then into the rings on the device
     const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
-    const size_t bytes = (size_t)n_slots * n * o->C * esz;
-    HIP_TRY(hipStreamSynchronize(c->stream));          // a device call may still be running; the pinned buffer is free
-    RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
-    HIP_TRY(o->staging.ensure(bytes));
-    std::memcpy(o->host_in, audio, bytes);
-    HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    RP_TRY(online_upload(o, audio, (size_t)n_slots * n * o->C * esz));
     const int64_t dense[3] = {n * o->C, o->C, 1};
     return online_feed_launch(o, plan, o->staging.p, dtype, n, dense);
 }
@@ -1604,19 +1725,20 @@ int repet_online_feed_device(repet_online* o, const int32_t* slots, const int64_
     if (!src) return fail(REPET_ERR_BAD_ARG, "null argument");
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, wait_stream, signal_stream));
     RP_TRY(online_feed_launch(o, plan, src, dtype, n, src_strides));
     // the caller's stream continues behind the copy: the packet may be overwritten once that stream gets there
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, signal_stream);
 }
 
 int repet_online_queued(repet_online* o, int32_t slot, int64_t* queued) {
     if (!o || !queued) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->feed_cap <= 0) return fail(REPET_ERR_BAD_ARG, kNoFeed);
-    if (slot >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
-    if (slot >= 0) { *queued = o->q_count[(size_t)slot]; return REPET_OK; }
+    if (slot >= 0) {
+        RP_TRY(check_slot(o, slot));
+        *queued = o->q_count[(size_t)slot];
+        return REPET_OK;
+    }
     for (size_t s = 0; s < (size_t)o->S; ++s) queued[s] = o->q_count[s];
     return REPET_OK;
 }
@@ -1630,7 +1752,7 @@ int repet_online_pad_feed(repet_online* o, const int32_t* slots, int32_t n_slots
     else for (int32_t s = 0; s < o->S; ++s) if (o->start[(size_t)s] != kSlotIdle) ids.push_back(s);
     std::vector<int64_t> counts;
     for (int32_t s : ids) {
-        if (s < 0 || s >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+        RP_TRY(check_slot(o, s));
         counts.push_back((o->H - o->q_count[(size_t)s] % o->H) % o->H);
     }
     FeedPlan plan;
@@ -1659,8 +1781,7 @@ int repet_online_clear_feed(repet_online* o, const int32_t* slots, int32_t n_slo
     if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (o->feed_cap <= 0) return fail(REPET_ERR_BAD_ARG, kNoFeed);
     if (slots && n_slots < 0) return fail(REPET_ERR_BAD_ARG, "bad size");
-    for (int32_t k = 0; slots && k < n_slots; ++k)
-        if (slots[k] < 0 || slots[k] >= o->S) return fail(REPET_ERR_BAD_ARG, "online: slot out of range");
+    for (int32_t k = 0; slots && k < n_slots; ++k) RP_TRY(check_slot(o, slots[k]));
     // host counters alone: the launches that filled the rings stay where they are in the stream, and what they wrote is
     // overwritten by the feeds that follow before any take reads it
     if (!slots) { std::fill(o->q_count.begin(), o->q_count.end(), 0); std::fill(o->q_read.begin(), o->q_read.end(), 0); }
@@ -1668,50 +1789,15 @@ int repet_online_clear_feed(repet_online* o, const int32_t* slots, int32_t n_slo
     return REPET_OK;
 }
 
-static void tick_consumed(const repet_online* o, const std::vector<unsigned char>* ready, uint8_t* consumed) {
-    if (!consumed) return;
-    for (size_t s = 0; s < (size_t)o->S; ++s) consumed[s] = ready ? (*ready)[s] : 0;
-}
-
 int repet_online_tick(repet_online* o, int64_t hops, double* out, int64_t capacity, uint8_t* consumed, int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    std::vector<unsigned char> ready;
-    int64_t n_ready = 0, n = 0, n_new = 0, n_emit = 0;
-    RP_TRY(online_tick_plan(o, hops, &ready, &n_ready, &n, &n_new, &n_emit));
-    if (n_ready == 0) { tick_consumed(o, nullptr, consumed); return REPET_OK; }
-    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs hops * step_length)");
-    RP_TRY(online_check_also_host(o, n_emit, out));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_tick_take(o, ready, n));
-    RP_TRY(online_process(o, n_new, n_emit, -1, n));
-    RP_TRY(online_host_result(o, n_emit, out));
-    tick_consumed(o, &ready, consumed);
-    *n_written = n_emit;
-    return REPET_OK;
+    return online_tick_impl(o, hops, host_sink(out, capacity), consumed, n_written);
 }
 
 int repet_online_tick_device(repet_online* o, int64_t hops, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                              uint8_t* consumed, int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    std::vector<unsigned char> ready;
-    int64_t n_ready = 0, n = 0, n_new = 0, n_emit = 0;
-    RP_TRY(online_tick_plan(o, hops, &ready, &n_ready, &n, &n_new, &n_emit));
-    if (n_ready == 0) { tick_consumed(o, nullptr, consumed); return REPET_OK; }
-    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
-    RP_TRY(online_tick_take(o, ready, n));
-    RP_TRY(online_process(o, n_new, n_emit, -1, n));
-    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
-    tick_consumed(o, &ready, consumed);
-    *n_written = n_emit;
-    return REPET_OK;
+    return online_tick_impl(o, hops, device_sink(dst, dst_dtype, dst_strides, signal_stream), consumed, n_written);
 }
 
 int repet_online_stream_emit_count(repet_online* o, int32_t slot, int64_t* n_emit) {
@@ -1721,47 +1807,15 @@ int repet_online_stream_emit_count(repet_online* o, int32_t slot, int64_t* n_emi
 
 int repet_online_finish_stream(repet_online* o, int32_t slot, double* out, int64_t capacity, int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
-    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    RP_TRY(online_check_also_host(o, n_emit, out, 1));
-    DeviceGuard guard(o->ctx->device);
-    o->slots_on = true;
-    RP_TRY(online_hold_slots(o, &slot, 1, false, true));        // a held slot ends as it stands
-    RP_TRY(online_process(o, n_new, n_emit, slot));
-    RP_TRY(online_host_result(o, n_emit, out, 1));
-    bool kept = false;
-    RP_TRY(online_keep_tail_levels(o, &kept));
-    RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
-    o->tail_valid = kept;
-    *n_written = n_emit;
-    return REPET_OK;
+    return online_finish_stream_impl(o, slot, host_sink(out, capacity), n_written);
 }
 
 int repet_online_finish_stream_device(repet_online* o, int32_t slot, void* dst, int dst_dtype, const int64_t dst_strides[2],
                                       void* signal_stream, int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written || !dst_strides) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan_slot(o, slot, &n_new, &n_emit));
-    const int64_t strides[3] = {0, dst_strides[0], dst_strides[1]};
-    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, strides, 1));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    o->slots_on = true;
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
-    RP_TRY(online_hold_slots(o, &slot, 1, false, true));        // a held slot ends as it stands
-    RP_TRY(online_process(o, n_new, n_emit, slot));
-    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, strides, static_cast<hipStream_t>(signal_stream), 1));
-    bool kept = false;
-    RP_TRY(online_keep_tail_levels(o, &kept));
-    RP_TRY(online_reset_slots(o, &slot, 1, kSlotIdle));
-    o->tail_valid = kept;
-    *n_written = n_emit;
-    return REPET_OK;
+    if (!dst_strides) return fail(REPET_ERR_BAD_ARG, "null argument");
+    const int64_t strides[3] = {0, dst_strides[0], dst_strides[1]};        // (the ABI takes the two strides of [n][C])
+    return online_finish_stream_impl(o, slot, device_sink(dst, dst_dtype, strides, signal_stream), n_written);
 }
 
 int repet_online_stream_state_size(repet_online* o, int64_t* header_bytes, int64_t* payload_bytes) {
@@ -1779,10 +1833,8 @@ int repet_online_export_stream(repet_online* o, int32_t slot, void* header_out, 
     DeviceGuard guard(c->device);
     const size_t bytes = (size_t)h.payload_bytes;
     HIP_TRY(o->out64.ensure(bytes));
-    RP_TRY(ensure_pinned(o->host_out, o->host_out_cap, bytes));
     RP_TRY(online_export(o, slot, h, o->out64.as<float>()));
-    HIP_TRY(hipMemcpyAsync(o->host_out, o->out64.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    RP_TRY(online_download(o, o->out64.p, bytes));
     std::memcpy(payload_out, o->host_out, bytes);
     std::memcpy(header_out, &h, sizeof(h));
     return REPET_OK;
@@ -1795,10 +1847,9 @@ int repet_online_export_stream_device(repet_online* o, int32_t slot, void* heade
     RP_TRY(online_export_plan(o, slot, &h));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
     RP_TRY(online_export(o, slot, h, static_cast<float*>(payload_dev)));
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(signal_stream), c->io_done, 0));
+    RP_TRY(signal_caller(c, signal_stream));
     std::memcpy(header_out, &h, sizeof(h));
     return REPET_OK;
 }
@@ -1810,12 +1861,7 @@ int repet_online_import_stream(repet_online* o, int32_t slot, const void* header
     RP_TRY(online_import_check(o, slot, &h));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    const size_t bytes = (size_t)h.payload_bytes;
-    HIP_TRY(hipStreamSynchronize(c->stream));          // a device push may still be running; the pinned buffer is free
-    RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
-    HIP_TRY(o->staging.ensure(bytes));
-    std::memcpy(o->host_in, payload, bytes);
-    HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    RP_TRY(online_upload(o, payload, (size_t)h.payload_bytes));
     return online_import(o, slot, h, o->staging.as<float>());
 }
 
@@ -1827,12 +1873,10 @@ int repet_online_import_stream_device(repet_online* o, int32_t slot, const void*
     RP_TRY(online_import_check(o, slot, &h));
     repet_ctx* c = o->ctx;
     DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(wait_stream)));
+    RP_TRY(wait_caller(c, wait_stream, wait_stream));
     RP_TRY(online_import(o, slot, h, static_cast<const float*>(payload_dev)));
     // the caller's stream continues behind the import: the payload may be reused once that stream gets there
-    HIP_TRY(hipEventRecord(c->io_done, c->stream));
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(wait_stream), c->io_done, 0));
-    return REPET_OK;
+    return signal_caller(c, wait_stream);
 }
 
 int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p, int64_t max_push_samples,
@@ -1914,35 +1958,7 @@ int repet_online_emit_count(repet_online* o, int64_t n, int finishing, int64_t* 
 int repet_online_push_streams(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
                               int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written || (n > 0 && !audio)) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
-    if (n < 0 || dtype < REPET_F32 || dtype > REPET_I16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
-    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedPush);
-    if (online_caller_holds(o) > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
-    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small (needs n_samples + window_length)");
-    RP_TRY(online_check_also_host(o, n_emit, out));
-    RP_TRY(online_end_starving(o));                             // (after ticks: the slots they starved take part again)
-    if (n > 0) {
-        // the chunk [S][n][C] through the pinned buffer into the staging buffer, then appended to every stream on the device
-        const size_t esz = dtype == REPET_F64 ? 8 : (dtype == REPET_F32 ? 4 : 2);
-        const size_t bytes = (size_t)o->S * n * o->C * esz;
-        HIP_TRY(hipStreamSynchronize(c->stream));          // a device push may still be running; the pinned buffer is free
-        RP_TRY(ensure_pinned(o->host_in, o->host_in_cap, bytes));
-        HIP_TRY(o->staging.ensure(bytes));
-        std::memcpy(o->host_in, audio, bytes);
-        HIP_TRY(hipMemcpyAsync(o->staging.p, o->host_in, bytes, hipMemcpyHostToDevice, c->stream));
-        const int64_t dense[3] = {n * o->C, o->C, 1};
-        RP_TRY(online_append(o, o->staging.p, dtype, n, dense));
-    }
-    RP_TRY(online_process(o, n_new, n_emit, -1, n));
-    RP_TRY(online_host_result(o, n_emit, out));
-    *n_written = n_emit;
-    return REPET_OK;
+    return online_push_impl(o, audio, dtype, n, nullptr, nullptr, host_sink(out, capacity), n_written);
 }
 
 int repet_online_push(repet_online* o, const void* audio, int dtype, int64_t n, double* out, int64_t capacity,
@@ -1954,44 +1970,12 @@ int repet_online_push_device(repet_online* o, const void* src, int dtype, int64_
                              void* wait_stream, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                              int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written || (n > 0 && !src)) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (o->finished) return fail(REPET_ERR_BAD_ARG, "online: stream already finished");
-    if (n < 0 || dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "bad size or dtype");
-    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedPush);
-    if (online_caller_holds(o) > 0 && n % o->H) return fail(REPET_ERR_BAD_ARG, kHeldPush);
-    RP_TRY(check_strides(src_strides));
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan(o, n, false, &n_new, &n_emit));
-    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(wait_stream), static_cast<hipStream_t>(signal_stream)));
-    RP_TRY(online_end_starving(o));                             // (after ticks: the slots they starved take part again)
-    RP_TRY(online_append(o, src, dtype, n, src_strides));
-    RP_TRY(online_process(o, n_new, n_emit, -1, n));
-    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
-    *n_written = n_emit;
-    return REPET_OK;
+    return online_push_impl(o, src, dtype, n, src_strides, wait_stream, device_sink(dst, dst_dtype, dst_strides, signal_stream), n_written);
 }
 
 int repet_online_finish_streams(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
-    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
-    if (n_emit > capacity || (n_emit > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    RP_TRY(online_check_also_host(o, n_emit, out));
-    RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
-    RP_TRY(online_process(o, n_new, n_emit));
-    RP_TRY(online_host_result(o, n_emit, out));
-    *n_written = n_emit;
-    o->finished = true;
-    return REPET_OK;
+    return online_finish_impl(o, host_sink(out, capacity), n_written);
 }
 
 int repet_online_finish(repet_online* o, double* out, int64_t capacity, int64_t* n_written) {
@@ -2001,21 +1985,7 @@ int repet_online_finish(repet_online* o, double* out, int64_t capacity, int64_t*
 int repet_online_finish_device(repet_online* o, void* dst, int dst_dtype, const int64_t dst_strides[3], void* signal_stream,
                                int64_t* n_written) {
     AlsoScope also(o);
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    int64_t n_new = 0, n_emit = 0;
-    RP_TRY(online_plan(o, 0, true, &n_new, &n_emit));
-    if (online_any_queued(o)) return fail(REPET_ERR_BAD_ARG, kQueuedEnd);
-    RP_TRY(online_check_dst(o, n_emit, dst, dst_dtype, dst_strides));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_wait_caller(o, static_cast<hipStream_t>(signal_stream), static_cast<hipStream_t>(signal_stream)));
-    RP_TRY(online_resume_all(o));                               // held slots end as they stand, each with its own length
-    RP_TRY(online_process(o, n_new, n_emit));
-    RP_TRY(online_device_result(o, n_emit, dst, dst_dtype, dst_strides, static_cast<hipStream_t>(signal_stream)));
-    *n_written = n_emit;
-    o->finished = true;
-    return REPET_OK;
+    return online_finish_impl(o, device_sink(dst, dst_dtype, dst_strides, signal_stream), n_written);
 }
 
 }  // extern "C"

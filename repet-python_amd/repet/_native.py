@@ -1423,30 +1423,63 @@ class OnlineStreams:
                 raise ValueError("out has negative strides")
         return out, emit_tensor_code(out), tuple(int(st) for st in out.stride())
 
+    def _emit(self, codes, n_emit, on_device, out, dtype, host_call, device_call, shape=None):
+        """The results of an emitting call for ``codes`` -- float64 host arrays, or tensors on the device (``out``, or fresh ones
+        of ``dtype``) -- with the second output armed and the C call made: ``host_call(pointer, n_emit, written)`` or
+        ``device_call(pointer, dtype code, strides, stream handle, written)``, each for the first result. Returns
+        ``(results, stream)``, the torch stream the device call was ordered on (None: host)."""
+        written = C.c_int64()
+        if not on_device:
+            results = [np.empty(shape or (self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
+            _select_output(self._handle(), codes, ptr(results[-1]))
+            check(host_call(ptr(results[0]), n_emit, C.byref(written)))
+            return results, None
+        import torch
+        results, code, strides = self._device_outs(out, n_emit, codes, shape, dtype)
+        stream = torch.cuda.current_stream(results[0].device)
+        lead = (0,) * (3 - len(strides[-1]))          # (a finish_stream tail is (n, C): no stream axis)
+        _select_output(self._handle(), codes, C.c_void_p(results[-1].data_ptr() or None), code, _strides(lead + strides[-1]))
+        check(device_call(C.c_void_p(results[0].data_ptr() or None), code, strides[0], _stream_handle(stream), C.byref(written)))
+        return results, stream
+
     def push(self, chunk, out=None, which="background", dtype=None):
         """Feed ``(S, n, C)`` more samples; returns the ``(S, n_emit, C)`` samples that became final: their background, or
         the signal ``which`` names (a pair of arrays / tensors for "both"). Device chunks: ``out`` (float64, float32, int16,
         float16 or bfloat16) is filled, or a fresh tensor of ``dtype`` (None: float64) returned; see ``repet.online_streams``."""
         codes = which_codes(which)
-        if is_device_tensor(chunk):
-            return self._push_device(chunk, out, codes, dtype)
-        if out is not None:
-            raise ValueError("out is for device chunks (a host chunk returns a new array)")
-        if dtype is not None:
-            raise ValueError("dtype is for device chunks (a host chunk returns a float64 array)")
-        if is_tensor(chunk):
-            chunk = chunk.numpy()
-        a, code = as_input(chunk)
-        self._check_shape(a.shape)
-        n = a.shape[1]
-        n_emit = self.emit_count(n)
-        results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
-        written = C.c_int64()
-        _select_output(self._handle(), codes, ptr(results[-1]))
-        check(lib().repet_online_push_streams(self._handle(), ptr(a), code, n, ptr(results[0]), n_emit, C.byref(written)))
+        on_device = is_device_tensor(chunk)
+        if on_device:
+            if chunk.device.index != self._device:
+                raise ValueError(f"tensor is on {chunk.device}, the streams on device {self._device}")
+            if chunk.dim() != 3:
+                raise ValueError("a chunk is (number_streams, number_samples, number_channels)")
+            self._check_shape(tuple(chunk.shape))
+            x, code, shape, strides = tensor_layout(chunk, batched=True)
+            source = C.c_void_p(x.data_ptr() or None)
+        else:
+            if out is not None:
+                raise ValueError("out is for device chunks (a host chunk returns a new array)")
+            if dtype is not None:
+                raise ValueError("dtype is for device chunks (a host chunk returns a float64 array)")
+            if is_tensor(chunk):
+                chunk = chunk.numpy()
+            x, code = as_input(chunk)
+            self._check_shape(x.shape)
+            shape, source = x.shape, ptr(x)
+        n = shape[1]
+        h = self._handle()
+        results, stream = self._emit(
+            codes, self.emit_count(n), on_device, out, dtype,
+            lambda dst, cap, written: lib().repet_online_push_streams(h, source, code, n, dst, cap, written),
+            lambda dst, dst_code, dst_strides, stream, written: lib().repet_online_push_device(
+                h, source, code, n, _strides(strides), stream, dst, dst_code, _strides(dst_strides), stream, written))
+        if on_device:
+            # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
+            # recorded on it, the caching allocator hands its block out again only once the ingest has read it
+            x.record_stream(stream)
         self._count_push(n)
-        self._last_on_device = False
-        self._emitted_shape = results[0].shape
+        self._last_on_device = on_device
+        self._emitted_shape = tuple(results[0].shape)
         self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
 
@@ -1540,32 +1573,6 @@ class OnlineStreams:
         """``dtype=`` of a call whose result goes to the host unless ``out`` is given or the last push was a device chunk."""
         if dtype is not None and out is None and not self._last_on_device:
             raise ValueError("dtype is for device results (after host chunks the result is a float64 array)")
-
-    def _push_device(self, x, out, codes, dtype=None):
-        import torch
-        if x.device.index != self._device:
-            raise ValueError(f"tensor is on {x.device}, the streams on device {self._device}")
-        if x.dim() != 3:
-            raise ValueError("a chunk is (number_streams, number_samples, number_channels)")
-        self._check_shape(tuple(x.shape))
-        x, code, shape, strides = tensor_layout(x, batched=True)
-        n = shape[1]
-        outs, out_code, out_strides = self._device_outs(out, self.emit_count(n), codes, dtype=dtype)
-        out = outs[0] if len(outs) == 1 else tuple(outs)
-        stream = torch.cuda.current_stream(x.device)
-        written = C.c_int64()
-        _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
-        check(lib().repet_online_push_device(self._handle(), C.c_void_p(x.data_ptr() or None), code, n, _strides(strides),
-                                             _stream_handle(stream), C.c_void_p(outs[0].data_ptr() or None), out_code,
-                                             _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
-        self._emitted_shape = tuple(outs[0].shape)
-        # the current stream waits for the push (an event behind the egress, which is behind the ingest): with the chunk
-        # recorded on it, the caching allocator hands its block out again only once the ingest has read it
-        x.record_stream(stream)
-        self._count_push(n)
-        self._last_on_device = True
-        self._tail_emitted = False
-        return out
 
     @property
     def samples_pushed(self):
@@ -1766,18 +1773,12 @@ class OnlineStreams:
         n = hops * self._hop
         n_emit = self.emit_count(n)
         consumed = np.zeros(self._streams, dtype=np.uint8)
-        written = C.c_int64()
-        if on_device:
-            import torch
-            results, out_code, out_strides = self._device_outs(out, n_emit, codes, dtype=dtype)
-            stream = torch.cuda.current_stream(results[0].device)
-            _select_output(self._handle(), codes, C.c_void_p(results[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
-            check(lib().repet_online_tick_device(self._handle(), hops, C.c_void_p(results[0].data_ptr() or None), out_code,
-                                                 _strides(out_strides[0]), _stream_handle(stream), ptr(consumed), C.byref(written)))
-        else:
-            results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
-            _select_output(self._handle(), codes, ptr(results[-1]))
-            check(lib().repet_online_tick(self._handle(), hops, ptr(results[0]), n_emit, ptr(consumed), C.byref(written)))
+        h = self._handle()
+        results, _ = self._emit(
+            codes, n_emit, on_device, out, dtype,
+            lambda dst, cap, written: lib().repet_online_tick(h, hops, dst, cap, ptr(consumed), written),
+            lambda dst, code, strides, stream, written: lib().repet_online_tick_device(
+                h, hops, dst, code, _strides(strides), stream, ptr(consumed), written))
         self._consumed = consumed.astype(bool)
         if not self._consumed.any():
             return None
@@ -1845,23 +1846,13 @@ class OnlineStreams:
         self._check_dtype(dtype, out)
         slot = self._slot(slot)
         n_emit = self.stream_emit_count(slot)
-        written = C.c_int64()
-        shape = (n_emit, self._channels)
-        if out is not None or self._last_on_device:
-            import torch
-            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, shape, dtype)
-            stream = torch.cuda.current_stream(outs[0].device)
-            _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides((0,) + out_strides[-1]))
-            check(lib().repet_online_finish_stream_device(self._handle(), slot, C.c_void_p(outs[0].data_ptr() or None),
-                                                          out_code, (C.c_int64 * 2)(*out_strides[0]), _stream_handle(stream),
-                                                          C.byref(written)))
-            self._begun[slot] = None
-            self._held.discard(slot)
-            self._tail_emitted = True
-            return outs[0] if len(outs) == 1 else tuple(outs)
-        results = [np.empty(shape, dtype=np.float64) for _ in codes]
-        _select_output(self._handle(), codes, ptr(results[-1]))
-        check(lib().repet_online_finish_stream(self._handle(), slot, ptr(results[0]), n_emit, C.byref(written)))
+        h = self._handle()
+        results, _ = self._emit(
+            codes, n_emit, out is not None or self._last_on_device, out, dtype,
+            lambda dst, cap, written: lib().repet_online_finish_stream(h, slot, dst, cap, written),
+            lambda dst, code, strides, stream, written: lib().repet_online_finish_stream_device(
+                h, slot, dst, code, (C.c_int64 * 2)(*strides), stream, written),
+            shape=(n_emit, self._channels))
         self._begun[slot] = None
         self._held.discard(slot)
         self._tail_emitted = True
@@ -1875,23 +1866,13 @@ class OnlineStreams:
         codes = which_codes(which)
         self._check_dtype(dtype, out)
         n_emit = self.emit_count(0, finishing=True)
-        written = C.c_int64()
-        if out is not None or self._last_on_device:
-            import torch
-            outs, out_code, out_strides = self._device_outs(out, n_emit, codes, dtype=dtype)
-            stream = torch.cuda.current_stream(outs[0].device)
-            _select_output(self._handle(), codes, C.c_void_p(outs[-1].data_ptr() or None), out_code, _strides(out_strides[-1]))
-            check(lib().repet_online_finish_device(self._handle(), C.c_void_p(outs[0].data_ptr() or None), out_code,
-                                                   _strides(out_strides[0]), _stream_handle(stream), C.byref(written)))
-            self._emitted_shape = tuple(outs[0].shape)
-            self._tail_emitted = False
-            self._held.clear()
-            return outs[0] if len(outs) == 1 else tuple(outs)
-        results = [np.empty((self._streams, n_emit, self._channels), dtype=np.float64) for _ in codes]
-        _select_output(self._handle(), codes, ptr(results[-1]))
-        check(lib().repet_online_finish_streams(self._handle(), ptr(results[0]), n_emit, C.byref(written)))
+        h = self._handle()
+        results, _ = self._emit(
+            codes, n_emit, out is not None or self._last_on_device, out, dtype,
+            lambda dst, cap, written: lib().repet_online_finish_streams(h, dst, cap, written),
+            lambda dst, code, strides, stream, written: lib().repet_online_finish_device(h, dst, code, _strides(strides), stream, written))
         self._held.clear()
-        self._emitted_shape = results[0].shape
+        self._emitted_shape = tuple(results[0].shape)
         self._tail_emitted = False
         return results[0] if len(results) == 1 else tuple(results)
 
