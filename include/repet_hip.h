@@ -96,6 +96,35 @@ typedef struct repet_params {
 #define REPET_FLAG_STRICT_REFERENCE 1
 #define REPET_FLAG_REFUSE_NONFINITE 2
 
+/* repet_params.flags -- frames of digital silence in REPET_SIMONLINE (a muted microphone, a decoder that writes exact zeros,
+ * the lead-in of a file). The reference divides such a frame's mean magnitude row by its norm, 0 / 0 (repet.py:1240): the unit
+ * row is NaN, no comparison with it holds (repet.py:1318-1326), the frame's own list is empty, np.median of the empty list is
+ * NaN, and the samples the frame covers are NaN; while the frame sits in the buffer its NaN column also keeps every frame
+ * within similarity_distance of it out of all lists. That is the default here as well (flags without the bit), bit for bit.
+ * REPET_FLAG_SILENT_FRAMES_ZERO (bit 2) is the option, for REPET_SIMONLINE only: through repet_run, repet_ctx_execute(_async),
+ * batch contexts, repet_run_device, and repet_online_open / repet_online_open_streams, which keep `params`. A frame is SILENT
+ * when the fp32 norm the forward STFT computes for its channel-mean magnitude row is exactly 0: exact-zero input gives that, and
+ * so do magnitudes below fp32's square underflow (about 4e-23); a frame with a NaN sample has a NaN norm, is not silent and
+ * keeps the reference's behaviour. Under the option
+ *   - the unit row of a silent frame is all zeros, so the similarity of every pair with a silent member -- the frame with
+ *     itself included -- is 0, by definition, at both refinement levels of the peak picking;
+ *   - a silent frame has no list (count 0) and is in no other frame's list (with sim_distance_frames >= 1 and at least two
+ *     columns that is what the reference's rule gives on the vector with zeros in the silent columns: a zero is never
+ *     strictly above its neighbours);
+ *   - a silent frame's masked spectrum is zero in every channel: it adds 0 to the overlap-add, and the frames around it ring
+ *     into its samples as usual;
+ *   - every other frame is the reference's, decided on a similarity vector whose silent columns are 0.
+ * A frame whose list is empty for another reason (a NaN sample, an exact tie) stays NaN as before. What follows for a live
+ * handle: last_frames of a silent frame is 0 in mixture, background and foreground; last_matches gives count 0, ages -1,
+ * similarities 0 there; last_levels is finite; the background shaped by band gains is 0 there; every egress dtype, hold, feed /
+ * tick, restart, export / import and start_frames keep their contracts (idle, held and pre-start rows are excluded by the
+ * slot's origin as before). A clip without a silent frame gives the same bits with and without the bit. The other four
+ * variants refuse the bit (REPET_ERR_BAD_ARG): original / extended / adaptive compute no similarity, and `sim` under the rule is
+ * not built yet. The stream-state header carries `flags`, so a stream cannot move between a handle with the bit and one
+ * without. REPET_ABI_VERSION stays 4; repet_silent_frames_supported() says that the bit is known. */
+#define REPET_FLAG_SILENT_FRAMES_ZERO 4
+int repet_silent_frames_supported(void);   /* 1. A library without this symbol refuses the bit as unknown. */
+
 /* The nine module-level parameters of the reference (repet.py:42-63), for hosts that do not keep them as Python
  * globals, and the derivation of repet_params from them exactly as the reference's public functions do it
  * (Python round / np.round are half-to-even; so is this). repet_default_settings writes the reference's defaults:

@@ -43,6 +43,9 @@ struct StftArgs {
     int32_t n_batch; int64_t batch_sample_stride; // samples between the starts of consecutive clips
     int64_t batch_spec_stride;                    // elements between clips in X and V (= C*chan_stride)
     int64_t batch_mean_stride;                    // elements between clips in Vm/Vn/P (= Tpad*FS)
+    // (nullable; REPET_FLAG_SILENT_FRAMES_ZERO) silent[b * batch_silent_stride + t] = 1 where the fp32 norm of frame t's mean row
+    // is exactly 0, else 0, for the T frames of this launch; such a frame's unit row (Vn, Vh) is then all zeros instead of 0 / 0
+    unsigned int* silent; int64_t batch_silent_stride;
 };
 hipError_t launch_stft(const StftArgs& a, hipStream_t s);
 // strict reference mode: X and |X| = NaN in every bin of the frames that hold an infinite sample (stft.hip)
@@ -288,6 +291,10 @@ struct PeakRefine {
     // queue of frames whose float64 unit rows are needed (frame = clip * frame_clip_stride + frame row)
     unsigned char* records; int32_t record_bytes; int32_t* lite_list; unsigned int* lite_flag;
     int32_t* frame_list; unsigned int* frame_flag; int64_t frame_clip_stride;
+    // REPET_FLAG_SILENT_FRAMES_ZERO (modes 1 and 2): the unit row of a silent frame is all zeros, so every similarity with a silent
+    // member is exactly +0 -- the frame's own included, lag 0 of its band row. A row whose lag 0 reads 0 has no list, and an
+    // element that reads 0 is no candidate and nobody's rival (peaks.h: peak_value).
+    int32_t silent_zero;
 };
 // batch (nullable): blockIdx.y = clip of a batch of equal-shape matrices; element strides between the clips
 // origin (nullable; modes 1 and 2, the streaming handle's slots): frame number at which clip b's own stream began. The clip's rows
@@ -335,6 +342,7 @@ struct ExactSource {
     int64_t frame_sample0; int32_t W, H, F, FS;
     const double* window64; const double2* twiddle64;      // twiddle64[m] = exp(-2 pi i m / W), m <= W
     double* u64; int64_t u64_clip_stride; unsigned int* u64_gen; int64_t gen_clip_stride;
+    int32_t silent_zero;       // REPET_FLAG_SILENT_FRAMES_ZERO: the float64 unit row of a frame whose norm is exactly 0 is all zeros
 };
 // Decides the rows listed by the first pass again (same matrix arguments as launch_local_maxima; fixed grid, the count is
 // read on the device). scratch: local_maxima_exact_scratch_bytes(n_cols) bytes.
@@ -391,6 +399,10 @@ struct MaskArgs {
     // is frame slot_bias + t + (warm-up length) of the handle: rows with t + slot_bias < slot_start[b] are warm-up rows of that
     // clip whatever first_frame says (the list rows stay numbered from first_frame)
     const int64_t* slot_start; int64_t slot_bias;
+    // mask_sim only (nullable; REPET_FLAG_SILENT_FRAMES_ZERO): StftArgs::silent of the launch that transformed the frames from
+    // frame0 on -- frame row t of clip b is silent where silent[b * silent_batch_stride + t - frame0] != 0. Its mask is 0 in
+    // every bin, as a warm-up row's is: a frame of digital silence contributes nothing instead of NaN.
+    const unsigned int* silent; int64_t silent_batch_stride;
 };
 constexpr int kPadRows = 8;       // rows kept behind the Tpad frame rows of V (2 used)
 constexpr int kMinIdxPitch = 128; // index lists are readable up to the largest network size

@@ -131,6 +131,11 @@ struct repet_ctx {
     bool run_shaped = false, result_shaped = false;
     const float* shaped_bg() const { return result_shaped ? static_cast<const float*>(out_fg.p) : nullptr; }
     int online_start = 0;        // simonline: start_frames of this context (repet_ctx_set_online_start; 0: buffer_frames, the reference)
+    // REPET_FLAG_SILENT_FRAMES_ZERO, for the simonline pipeline or live push being enqueued (SilentZeroScope): run_stft has the
+    // forward kernel flag the silent frames in `silent` (one word per frame row of the launch), make_refine and run_exact_rows
+    // hand the rule to the peak picking, and the pipeline gives the table to the mask kernels
+    bool silent_zero = false;
+    DevBuf silent;
     bool nonfinite_passes() const { return input_not_finite || (strict && input_unscanned); }
     // workspaces
     DevBuf X, V, Vn, P, S, band, beat, idx, cnt, periods, win_periods, frames, tmp_a, tmp_b, tmp_c;
@@ -204,6 +209,12 @@ struct MaskPlaneScope {            // the choice holds for one pipeline; stage e
     ~MaskPlaneScope() { c->mask_plane = false; }
 };
 
+struct SilentZeroScope {           // the rule holds for one pipeline, like the mask plane
+    repet_ctx* c;
+    SilentZeroScope(repet_ctx* ctx, bool on) : c(ctx) { c->silent_zero = on; }
+    ~SilentZeroScope() { c->silent_zero = false; }
+};
+
 struct ModelRef { const float* model; const int32_t* periods; int64_t batch_stride, chan_stride; int32_t cutoff; };
 
 struct BatchInfo { int64_t transport = 0, clips_sent = 0, clips_with_remainders = 0, groups = 0; };
@@ -237,6 +248,7 @@ int exec_extended(repet_ctx* c, const repet_params* p, int64_t first = 0, int64_
 int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg, int64_t N);
 int exec_adaptive(repet_ctx* c, const repet_params* p);
 int check_params(const repet_params* p);
+int check_algo_flags(int algo, const repet_params* p);
 int h2d_pitched(repet_ctx* c, float* dst, int64_t dpitch, const float* src, int64_t rows, int64_t cols, int64_t rows_pad);
 int d2h_pitched(repet_ctx* c, float* dst, const float* src, int64_t spitch, int64_t rows, int64_t cols);
 int ctx_create(int device, repet_ctx** out, bool probe_side_stream);

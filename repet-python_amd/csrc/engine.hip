@@ -392,6 +392,10 @@ int run_stft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t offset, int64
     a.Vh = (vn && split_in_stft(B)) ? c->Vh.p : nullptr;
     a.n_batch = B; a.batch_sample_stride = batch_sample_stride; a.batch_spec_stride = (int64_t)g.C * g.chan_stride;
     a.batch_mean_stride = g.Tpad * g.FS;
+    if (vn && c->silent_zero) {                      // (exec_simonline under REPET_FLAG_SILENT_FRAMES_ZERO: one flag per frame row)
+        HIP_TRY(c->silent.ensure((size_t)B * g.Tpad * sizeof(unsigned int)));
+        a.silent = c->silent.as<unsigned int>(); a.batch_silent_stride = g.Tpad;
+    }
     HIP_TRY(launch_stft(a, c->stream));
     if (c->nonfinite_passes()) HIP_TRY(launch_infinite_frames_fix(a, c->stream));    // (strict reference mode only: see the kernel)
     const double in_b = 4.0 * n * g.C, spec_b = (8.0 + 4.0) * g.F * g.T * g.C, mean_b = 4.0 * g.F * g.T;
@@ -483,8 +487,15 @@ int check_params(const repet_params* p) {
         return fail(REPET_ERR_LIMIT, "window length must be a power of two in [64, 8192]");
     if (p->step_length * 2 != p->window_length) return fail(REPET_ERR_BAD_ARG, "step length must be half the window length");
     if (p->period_lo < 0 || p->cutoff_bins < 0 || p->sim_distance_frames < 0) return fail(REPET_ERR_BAD_ARG, "negative parameter");
-    if (p->flags & ~(REPET_FLAG_STRICT_REFERENCE | REPET_FLAG_REFUSE_NONFINITE))
+    if (p->flags & ~(REPET_FLAG_STRICT_REFERENCE | REPET_FLAG_REFUSE_NONFINITE | REPET_FLAG_SILENT_FRAMES_ZERO))
         return fail(REPET_ERR_BAD_ARG, "unknown bits in repet_params.flags (an ABI-2 caller must zero reserved0)");
+    return REPET_OK;
+}
+
+// the bits of repet_params.flags that only some variants honour (p has passed check_params)
+int check_algo_flags(int algo, const repet_params* p) {
+    if ((p->flags & REPET_FLAG_SILENT_FRAMES_ZERO) && algo != REPET_SIMONLINE)
+        return fail(REPET_ERR_BAD_ARG, "REPET_FLAG_SILENT_FRAMES_ZERO is honoured by REPET_SIMONLINE and the live handles only");
     return REPET_OK;
 }
 
@@ -518,6 +529,8 @@ thread_local ThreadContexts g_thread_ctx;
 extern "C" {
 
 int repet_abi_version(void) { return REPET_ABI_VERSION; }
+
+int repet_silent_frames_supported(void) { return 1; }
 
 int repet_device_count(void) {
     int n = 0;
@@ -651,7 +664,7 @@ int repet_ctx_destroy(repet_ctx* c) {
                       &c->refine_stats, &c->R, &c->Vs, &c->rank_codes, &c->code_planes, &c->median_codes, &c->tiles_big,
                       &c->audio_lo, &c->redo_list, &c->redo_flag, &c->u64, &c->u64_gen, &c->exact_scratch,
                       &c->lite_list, &c->lite_flag, &c->lite_records, &c->frame_list, &c->frame_flag,
-                      &c->seg, &c->nonfinite_word, &c->levels_ws, &c->band_tab, &c->out_fg,
+                      &c->seg, &c->nonfinite_word, &c->levels_ws, &c->band_tab, &c->out_fg, &c->silent,
                       &c->idx, &c->cnt, &c->periods, &c->win_periods, &c->frames, &c->tmp_a, &c->tmp_b, &c->tmp_c})
         b->release();
     for (auto& kv : c->tile_lists) kv.second.buf.release();
@@ -918,6 +931,7 @@ extern "C" {
 int repet_ctx_execute(repet_ctx* c, int algo, const repet_params* p, repet_timing* timing) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(algo, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     DeviceGuard guard(c->device);
     RP_TRY(begin_shaped(c, p));
@@ -939,6 +953,7 @@ int repet_ctx_execute(repet_ctx* c, int algo, const repet_params* p, repet_timin
 int repet_ctx_execute_async(repet_ctx* c, int algo, const repet_params* p) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(algo, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     DeviceGuard guard(c->device);
     RP_TRY(begin_shaped(c, p));
@@ -1023,6 +1038,7 @@ int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_
                                      repet_timing* timing) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(REPET_EXTENDED, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
     if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
@@ -1043,6 +1059,7 @@ int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_
 int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(REPET_EXTENDED, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
     if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
@@ -1224,9 +1241,10 @@ extern "C" {
 
 int repet_run(int algo, const void* audio, int dtype, int64_t n, int32_t ch, const repet_params* p, double* out,
               int device, repet_timing* timing) {
+    RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(algo, p));               // (before a device is touched: a refused call changes nothing)
     repet_ctx* c = nullptr;
     RP_TRY(thread_ctx(device, &c));
-    RP_TRY(check_params(p));
     c->strict = !(p->flags & REPET_FLAG_REFUSE_NONFINITE);
     RP_TRY(repet_ctx_upload(c, audio, dtype, n, ch));
     // (without a timing request nothing waits between the last kernel and the first copy back: the download is ordered behind
@@ -1318,9 +1336,10 @@ int repet_set_run_background_gain(int device, float gain) {
 
 int repet_run_device(int algo, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t in_strides[3],
                      void* dst, int out_dtype, const int64_t out_strides[3], const repet_params* p, int device, void* stream) {
+    RP_TRY(check_params(p));
+    RP_TRY(check_algo_flags(algo, p));
     repet_ctx* c = nullptr;
     RP_TRY(thread_ctx(device, &c));
-    RP_TRY(check_params(p));
     RP_TRY(check_emit_dtype(out_dtype));
     c->strict = !(p->flags & REPET_FLAG_REFUSE_NONFINITE);
     RP_TRY(repet_ctx_upload_device_strided(c, src, dtype, n_clips, n, ch, in_strides, stream));

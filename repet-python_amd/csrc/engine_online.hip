@@ -310,6 +310,11 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
     const float* pend_lo = o->pend_lo[o->pcur].as<float>() + sb * pst;
     const int64_t first_global = o->frames_done - o->hist_valid; // global frame number of window row r0
     const int64_t* starts = o->slots_on ? o->slot_start.as<int64_t>() + sb : nullptr;      // the slots' own first frames
+    // REPET_FLAG_SILENT_FRAMES_ZERO: the forward kernel flags the silent frames among the n_new of this push (one word each, slot
+    // after slot) beside their unit rows; the peak picking reads silence off the band, the mask kernels off the table. Nothing
+    // of it outlives the push: no slide, no readback, no launch more. A handle without the bit hands out no table.
+    const bool silent_zero = (o->p.flags & REPET_FLAG_SILENT_FRAMES_ZERO) != 0;
+    SilentZeroScope silent_scope(c, silent_zero);
 
     if (n_new > 0) {
         StftArgs a{};
@@ -319,6 +324,10 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         a.X = Xb + o->hist_valid * o->FS; a.V = Vb + o->hist_valid * o->FS; a.chan_stride = plane;
         a.Vn = Vnb + o->hist_valid * o->FS;
         a.n_batch = S; a.batch_sample_stride = o->pend_cap; a.batch_spec_stride = spec; a.batch_mean_stride = vns;
+        if (silent_zero) {
+            HIP_TRY(c->silent.ensure((size_t)S * n_new * sizeof(unsigned int)));
+            a.silent = c->silent.as<unsigned int>(); a.batch_silent_stride = n_new;
+        }
         HIP_TRY(launch_stft(a, c->stream));
         // rows behind the new frames up to the next tile boundary must read as zero for the Gram tiles
         const int64_t Tpad = round_up(Tw, kTile);
@@ -366,6 +375,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         m.cutoff = o->p.cutoff_bins; m.pad_row = o->rows_cap - r0; m.frame0 = o->hist_valid;
         m.n_batch = S; m.batch_stride = spec;
         m.slot_start = starts; m.slot_bias = first_global - (o->M - 1);     // row t is the slot's frame first_global + t - start
+        if (silent_zero) { m.silent = c->silent.as<unsigned int>(); m.silent_batch_stride = n_new; }      // (row frame0 + k: new frame k)
         m.idx_batch_stride = std::max<int64_t>(n_active, 0) * KP; m.cnt_batch_stride = std::max<int64_t>(n_active, 0);
         const int64_t first_frame = Tw - std::max<int64_t>(n_active, 0);          // warm-up rows before it are zeroed
         const int max_peaks = (int)std::min<int64_t>(K, ceil_div(o->B, o->p.sim_distance_frames + 1));

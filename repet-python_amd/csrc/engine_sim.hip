@@ -49,6 +49,7 @@ int make_refine(repet_ctx* c, const float* unit_rows, int FS, double threshold, 
     *rf = PeakRefine{};
     rf->unit_rows = unit_rows; rf->pitch = FS; rf->delta = peak_refine_delta(FS, gram_f16_enabled()); rf->min_value = threshold;
     rf->stats = c->refine_stats.as<unsigned int>();
+    rf->silent_zero = c->silent_zero ? 1 : 0;
     if (rows > 0 && rf->delta > 0.0f && peak_exact_delta2() > 0.0) {
         const size_t total = (size_t)rows * clips;
         HIP_TRY(c->redo_list.ensure(total * 2 * sizeof(int32_t)));
@@ -84,6 +85,7 @@ int run_exact_rows(repet_ctx* c, const Tables* tb, const Geo& g, const float* M,
     src.hi = hi; src.lo = lo; src.n_samples = n_samples; src.n_channels = g.C; src.clip_stride = clip_stride;
     src.frame_sample0 = frame_sample0; src.W = g.W; src.H = g.H; src.F = g.F; src.FS = g.FS;
     src.window64 = tb->window64.as<double>(); src.twiddle64 = tb->twiddle64.as<double2>();
+    src.silent_zero = rf.silent_zero;
     const size_t rows = (size_t)n_frames * clips;
     HIP_TRY(c->u64.ensure(rows * g.FS * sizeof(double)));
     if (c->u64_gen.cap < rows * sizeof(unsigned int)) {
@@ -286,6 +288,7 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
 
 int exec_simonline(repet_ctx* c, const repet_params* p) {
     MaskPlaneScope plane(c, mask_plane_wanted(MaskKind::sim_float));
+    SilentZeroScope silent(c, (p->flags & REPET_FLAG_SILENT_FRAMES_ZERO) != 0);
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, p->window_length, &tb));
     const int64_t N = c->n_samples;
@@ -340,6 +343,7 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     }
     MaskArgs m = mask_args(c, g, p->cutoff_bins);
     m.n_batch = nb; m.batch_stride = spec_stride; m.idx_batch_stride = rows_alloc * KP; m.cnt_batch_stride = rows_alloc;
+    if (c->silent_zero) { m.silent = c->silent.as<unsigned int>(); m.silent_batch_stride = g.Tpad; }     // (run_stft's table: frame0 = 0)
     HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), M - 1, max_peaks, c->stream));
     mark(c, "mask_sim", nb * (4.0 + 4.0 * K + (c->mask_plane ? 4.0 : 16.0)) * g.F * (double)rows * g.C, 0);
     if (nb == 1) {

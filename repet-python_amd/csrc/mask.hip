@@ -143,6 +143,11 @@ __device__ __forceinline__ int64_t warm_up_end(const MaskArgs& a, int64_t first_
     const int64_t own = a.slot_start[clip] - a.slot_bias;
     return own > first_frame ? own : first_frame;
 }
+// MaskArgs::silent: frame row t of clip `clip` is a frame of digital silence under REPET_FLAG_SILENT_FRAMES_ZERO (one uniform
+// load per workgroup and frame; a launch without the table runs the code it ran)
+__device__ __forceinline__ bool silent_frame(const MaskArgs& a, int64_t t, int clip) {
+    return a.silent && a.silent[clip * a.silent_batch_stride + t - a.frame0] != 0u;
+}
 __device__ __forceinline__ void emit(const MaskArgs& a, int c, int64_t t, int f, float m) {
     const int64_t o = c * a.chan_stride + t * a.FS + f;
     if (a.mask) a.mask[o] = m;
@@ -244,8 +249,8 @@ __global__ __launch_bounds__(256) void mask_sim_kernel(MaskArgs a, const int* __
     const int nbins = SPLIT ? a.F - 1 : a.F;
     const int nfb = (nbins + 63) >> 6;
     const float* Vc = a.V + c * a.chan_stride;
-    if (t < warm_up_end(a, first_frame, blockIdx.z)) {           // online warm-up frames contribute nothing (repet.py:834)
-        for (int f = threadIdx.x; f < a.F; f += 256) emit(a, c, t, f, 0.f);
+    if (t < warm_up_end(a, first_frame, blockIdx.z) || silent_frame(a, t, blockIdx.z)) {   // online warm-up frames contribute nothing (repet.py:834),
+        for (int f = threadIdx.x; f < a.F; f += 256) emit(a, c, t, f, 0.f);                  // nor does a silent one
         return;
     }
     const int64_t r = t - first_frame;
@@ -322,7 +327,7 @@ __global__ __launch_bounds__(256) void mask_sim_wide_kernel(MaskArgs a, const in
     const int64_t warm_end = warm_up_end(a, first_frame, blockIdx.z);
     // the list of a frame, as the gathers need it: its length (wave-uniform) and entry `lane` (rows of idx hold >= 128 entries)
     auto fetch_list = [&](int64_t t, int& n, int& e) {
-        if (t < warm_end) { n = -1; e = 0; return; }                            // warm-up frame: nothing to gather
+        if (t < warm_end || silent_frame(a, t, blockIdx.z)) { n = -1; e = 0; return; }     // warm-up or silent frame: nothing to gather
         const int64_t r = t - first_frame;
         n = count[r];
         e = idx[r * (int64_t)idx_pitch + lane];
@@ -377,9 +382,9 @@ __global__ __launch_bounds__(256) void mask_sim_wide_kernel(MaskArgs a, const in
         }
     }
     // (the Nyquist bin of a warm-up frame: mask_sim_kernel's emit(0) wrote all F bins; here bin F - 1 of the warm-up frames)
-    if (warm_end > a.frame0 + f_begin && threadIdx.x < kWideRun) {
+    if ((warm_end > a.frame0 + f_begin || a.silent) && threadIdx.x < kWideRun) {
         const int64_t t = a.frame0 + f_begin + threadIdx.x;
-        if (t < warm_end && f_begin + threadIdx.x < f_end) emit(a, c, t, a.F - 1, 0.f);
+        if (f_begin + threadIdx.x < f_end && (t < warm_end || silent_frame(a, t, blockIdx.z))) emit(a, c, t, a.F - 1, 0.f);
     }
 }
 // REPET_MASK_WIDE=0: the one-bin-per-lane kernel for every list length (agreement test / A-B)
@@ -514,7 +519,8 @@ __global__ __launch_bounds__(64) void mask_sim_nyquist_kernel(MaskArgs a, const 
     const int64_t t = first_frame + r;
     // (a slot's warm-up rows: the main kernel's; rows outside [frame0, frame_end) are not this launch's)
     const int64_t t_end = a.frame_end > 0 ? a.frame_end : a.T;
-    const bool active = r0 < n_rows && t >= warm_up_end(a, first_frame, blockIdx.z) && t >= a.frame0 && t < t_end;
+    // (a silent row, MaskArgs::silent: the main kernel's as well -- tested behind the range checks, the table covers [frame0, frame_end))
+    const bool active = r0 < n_rows && t >= warm_up_end(a, first_frame, blockIdx.z) && t >= a.frame0 && t < t_end && !silent_frame(a, t, blockIdx.z);
     const float* Vc = a.V + c * a.chan_stride;
     const int n = count[r];
     const int* list = idx + r * (int64_t)idx_pitch;

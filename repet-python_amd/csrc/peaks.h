@@ -37,7 +37,23 @@ struct PeakArgs {
     const float* seg; int seg_pitch;
     const int64_t* origin;         // (nullable) PeakBatch::origin
     int start;                     // PeakBatch::start (n when the batch names none): with an origin, rows before start - 1 have no list
+    int silent_zero;               // PeakRefine::silent_zero (the kernels that scan rows carry it as a template argument as well)
 };
+
+// REPET_FLAG_SILENT_FRAMES_ZERO (modes 1 and 2). A silent frame's unit row is all zeros, so the similarity of every pair with a
+// silent member is exactly +0: that includes the frame's own, lag 0 of its band row in either layout. Similarities of magnitude
+// spectra are >= 0, so on the vector with zeros in the silent columns a zero is never strictly above a neighbour and never
+// keeps a positive element from being: the row is decided with -inf in their place. An element that reads 0 is then no
+// candidate and nobody's rival -- the exact ties among the zeros of a long mute take none of the kAmbCap / kRivalCap entries --
+// and the row of a silent frame has no list, the way a row younger than start_frames has none.
+// An exact 0 does not IDENTIFY a silent column -- a pair of sounding frames whose products all underflow reads +0 as well -- it
+// is EQUIVALENT to one for the decision: a 0 never wins and never blocks a positive element, whoever it belongs to. The
+// equivalence rests on the row's other elements being >= 0. The fp32 Gram kernel guarantees that; the f16-split one computes
+// hi hi' + hi lo' + lo hi' with lo of either sign, so a pair orthogonal to within its 1e-6 rounding could read just below 0,
+// and next to such an element the reference's rule could let a zero stand where -inf does not. Frames of audio are nowhere
+// near orthogonal (the window's main lobe alone overlaps), and the tests ask for the float64 statement's lists on every row.
+// Only lag 0 of a row -- a frame's similarity with itself, about 1 unless the frame is silent -- is read as a test OF silence.
+__device__ __forceinline__ bool silent_row(const PeakArgs& a, int64_t j) { return a.M[(j - a.shift) * a.pitch] == 0.0f; }
 
 // diagnostics counters (common.h: kStatShards): the copy of this workgroup
 __device__ __forceinline__ void stat_add(unsigned int* stats, int k, unsigned int v) {
@@ -124,6 +140,16 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // float64 cosine similarity of two fp32 rows (one wave, result in every lane). The rows are unit vectors up
 // to fp32 rounding, so their float64 norms are divided out again: the value then depends on the fp32
 // spectra alone, not on how the fp32 Gram kernel accumulated them.
+// A zero row has the similarity 0 with every row, itself included: a definition, not 0 / sqrt(0). Deliberately NOT gated by
+// silent_zero, although the float64 unit-row kernels beside it are: without the option no list can name a zero row (a silent
+// frame's row is NaN there, idle and pre-start rows are excluded by the slot's origin), so q == 0 is never met and no result
+// of `sim`, `simonline` or a handle without the bit moves; gating it would thread a flag through every caller of
+// exact_similarity2 / exact_similarity_list for a compare and a select per pair. Under the option the peak kernels keep
+// silent columns out of these calls as well (peak_value): the guard is the definition R1 asks for, not a path that runs.
+__device__ __forceinline__ double cosine_f64(double xy, double xx, double yy) {
+    const double q = xx * yy;
+    return q == 0.0 ? 0.0 : xy / sqrt(q);
+}
 __device__ __forceinline__ void exact_similarity2(const float* __restrict__ x, const float* __restrict__ y0,
                                                   const float* __restrict__ y1, int len4, int lane, double* e0, double* e1) {
     const float4* x4 = reinterpret_cast<const float4*>(x);
@@ -157,8 +183,8 @@ __device__ __forceinline__ void exact_similarity2(const float* __restrict__ x, c
     yy0 = wave_sum_f64(yy0);
     xy1 = wave_sum_f64(xy1);
     yy1 = wave_sum_f64(yy1);
-    *e0 = xy0 / sqrt(xx * yy0);
-    *e1 = xy1 / sqrt(xx * yy1);
+    *e0 = cosine_f64(xy0, xx, yy0);
+    *e1 = cosine_f64(xy1, xx, yy1);
 }
 
 // The same similarities for a LIST of rows against one row x (rows of up to 1 280 bins: x stays in registers, the next
@@ -228,7 +254,7 @@ __device__ __forceinline__ void exact_similarity_list(const float* __restrict__ 
         }
         xy = wave_sum_f64(xy);
         yy = wave_sum_f64(yy);
-        store(it, xy / sqrt(xx * yy));
+        store(it, cosine_f64(xy, xx, yy));
 #pragma unroll
         for (int u = 0; u < 5; ++u) q[u] = r[u];
     }
@@ -293,6 +319,13 @@ __device__ __forceinline__ float4 max4(float4 a, float4 b) {
     return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
 }
 __device__ __forceinline__ float nan_to_inf(float v) { return (v != v) ? INFINITY : v; }
+// what the kernels make of a raw element: NaN counts as +inf; ZS (silent_zero, above): an exact 0 counts as -inf, which is
+// equivalent for the decision to the 0 of a silent column (it does not say that the column IS silent)
+template <bool ZS>
+__device__ __forceinline__ float peak_value(float v) {
+    if constexpr (ZS) return (v == 0.0f) ? -INFINITY : nan_to_inf(v);
+    else return nan_to_inf(v);
+}
 
 // the wavefront-per-row kernel (peaks_wave.hip); hipErrorNotSupported when the shape is outside its range
 hipError_t launch_local_maxima_wave(const PeakArgs& a, int64_t n_rows, int n_batch, hipStream_t s, PeakLaunch* info = nullptr);

@@ -51,7 +51,8 @@ __device__ __forceinline__ int wave_prefix_slot(bool flag, int* counter, int lan
 // STAGE 0: the whole row in one workgroup. STAGE 1 / 2: rows too long for that (one row of a 10-minute clip is 100 KB
 // of LDS, i.e. one workgroup per CU and 11 ms for the matrix) are cut into segments with a halo of d elements on both
 // sides: stage 1 finds (and refines) the strict maxima of one segment per workgroup, stage 2 ranks them per row.
-template <int QMAX, int STAGE>
+// ZS (STAGE 0, modes 1 and 2): PeakArgs::silent_zero, see peaks.h
+template <int QMAX, int STAGE, bool ZS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ? 4 : (QMAX <= 16 ? 2 : 1), QMAX <= 16 ? 8 : 1))) void local_maxima_kernel(PeakArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* M4 = reinterpret_cast<float4*>(smem);              // groups float4 (row, then window maxima)
@@ -81,6 +82,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
         return;
     }
     const int64_t j = a.row0 + r;           // absolute row (mode 1: current frame)
+    if constexpr (ZS) {
+        if (silent_row(a, j)) {                 // a silent frame: no list (uniform per workgroup)
+            for (int k = tid; k < a.number; k += 256) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
+            if (tid == 0) a.count[r] = 0;
+            return;
+        }
+    }
     const int n = row_columns(a, j);        // (uniform per workgroup) a.n, or j + 1 while the stream's buffer is filling
     if (tid == 0) { n_peak = 0; n_amb = 0; n_riv = 0; n_unl = 0; n_close = 0; }
     float dlt = a.delta;                    // 0: no refinement
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
         // circular-buffer order of the online variant: column c holds frame j - ((j - c) mod B)
         int l = (int)(j - i) % n;
         if (l < 0) l += n;
-        return nan_to_inf(a.M[(a.mode == 2 ? j - a.shift : j - l - a.shift) * a.pitch + l]);     // mode 2: the look-back band
+        return peak_value<ZS>(a.M[(a.mode == 2 ? j - a.shift : j - l - a.shift) * a.pitch + l]);     // mode 2: the look-back band
     };
 
     const bool vec_ok = (a.mode == 0) && ((a.pitch & 3) == 0);
@@ -484,11 +492,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QMAX <= 8 ?
     if (tid == 0) a.count[r] = kept;
 }
 
-template <int QMAX, int STAGE>
+template <int QMAX, int STAGE, bool ZS = false>
 static hipError_t launch_one(const PeakArgs& a, dim3 grid, size_t bytes, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&local_maxima_kernel<QMAX, STAGE>), (int)bytes);
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&local_maxima_kernel<QMAX, STAGE, ZS>), (int)bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((local_maxima_kernel<QMAX, STAGE>), grid, dim3(256), bytes, s, a);
+    hipLaunchKernelGGL((local_maxima_kernel<QMAX, STAGE, ZS>), grid, dim3(256), bytes, s, a);
     return hipGetLastError();
 }
 
@@ -499,6 +507,7 @@ static hipError_t launch_by_size(const PeakArgs& a, dim3 grid, size_t bytes, hip
     auto go = [&](auto tag) -> hipError_t {
         constexpr int QMAX = decltype(tag)::value;
         if (qmax_out) *qmax_out = QMAX;
+        if constexpr (STAGE == 0) { if (a.silent_zero) return launch_one<QMAX, 0, true>(a, grid, bytes, s); }
         return launch_one<QMAX, STAGE>(a, grid, bytes, s);
     };
     if (per_thread <= 1) return go(std::integral_constant<int, 1>{});
@@ -543,6 +552,7 @@ hipError_t launch_local_maxima(const float* M, int64_t n_rows, int64_t row0, int
     a.min_value64 = min_value;
     a.seg = seg; a.seg_pitch = seg_pitch;
     a.start = (batch && batch->start > 0) ? batch->start : n_cols;
+    a.silent_zero = (refine && refine->silent_zero && mode != 0) ? 1 : 0;
     if (refine && refine->unit_rows && refine->delta > 0.0f && (refine->pitch & 3) == 0) {
         a.unit = refine->unit_rows; a.unit_pitch = refine->pitch; a.delta = refine->delta;
         a.min_value64 = refine->min_value; a.stats = refine->stats;

@@ -258,12 +258,13 @@ __device__ __forceinline__ void wave_unit_row_f64(const ExactSource& s, int logM
         exact_wave_sync();
     }
     const double nrm = sqrt(wave_sum_f64(part));
+    const bool mute = s.silent_zero && nrm == 0.0;             // ExactSource::silent_zero: a silent frame's row is all zeros
     double* out = s.u64 + (int64_t)clip * s.u64_clip_stride + fr * (int64_t)s.FS;
     if (ACC_REGS) {
 #pragma unroll
-        for (int jj = 0; jj < kAcc; ++jj) { const int k = lane + 64 * jj; if (k < s.FS) out[k] = (k < F) ? acc[jj] / nrm : 0.0; }
+        for (int jj = 0; jj < kAcc; ++jj) { const int k = lane + 64 * jj; if (k < s.FS) out[k] = (k < F && !mute) ? acc[jj] / nrm : 0.0; }
     } else {
-        for (int k = lane; k < s.FS; k += 64) out[k] = (k < F) ? accw[k] / nrm : 0.0;
+        for (int k = lane; k < s.FS; k += 64) out[k] = (k < F && !mute) ? accw[k] / nrm : 0.0;
     }
 }
 
@@ -391,9 +392,10 @@ __device__ __forceinline__ void wave_unit_row_f64_reg(const ExactSource& s, int 
 #pragma unroll
     for (int jj = 0; jj < 17; ++jj) { const int k = lane + 64 * jj; acc[jj] = acc[jj] / (double)C; if (k < F) part += acc[jj] * acc[jj]; }
     const double nrm = sqrt(wave_sum_f64(part));
+    const bool mute = s.silent_zero && nrm == 0.0;             // ExactSource::silent_zero: a silent frame's row is all zeros
     double* out = s.u64 + (int64_t)clip * s.u64_clip_stride + fr * (int64_t)s.FS;
 #pragma unroll
-    for (int jj = 0; jj < 17; ++jj) { const int k = lane + 64 * jj; if (k < s.FS) out[k] = (k < F) ? acc[jj] / nrm : 0.0; }
+    for (int jj = 0; jj < 17; ++jj) { const int k = lane + 64 * jj; if (k < s.FS) out[k] = (k < F && !mute) ? acc[jj] / nrm : 0.0; }
     USTAMP(3)
 }
 
@@ -636,11 +638,12 @@ __global__ __launch_bounds__(256, KQ == 1 ? 4 : 1) void unit_rows_f64_wg_kernel(
         if (lane == 0) red[wave] = part;
         __syncthreads();
         const double nrm = sqrt(red[0] + red[1] + red[2] + red[3]);
+        const bool mute = s.silent_zero && nrm == 0.0;         // ExactSource::silent_zero: a silent frame's row is all zeros
         double* out = s.u64 + (int64_t)clip * s.u64_clip_stride + fr * (int64_t)s.FS;
 #pragma unroll
         for (int q = 0; q < kWgQ * 4 + 1; ++q) {
             const int k = tid + 256 * q;
-            if (k < s.FS) out[k] = (k < F) ? acc[q] / nrm : 0.0;
+            if (k < s.FS) out[k] = (k < F && !mute) ? acc[q] / nrm : 0.0;
         }
         if (tid == 0) { *g = x.gen; stat_add(x.stats, 9, 1u); }
     }
@@ -715,7 +718,8 @@ __global__ __launch_bounds__(kExactThreads) void local_maxima_exact_kernel(Exact
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = i0 + kExactThreads * u + tid;
-                if (i < x.n4) { R.v[i] = i < n ? nan_to_inf(e[u]) : -INFINITY; R.st[i] = 0u; }
+                // (silent_zero: an exact 0 decides as a silent column's 0 does, peaks.h)
+                if (i < x.n4) { R.v[i] = i < n ? (a.silent_zero ? peak_value<true>(e[u]) : nan_to_inf(e[u])) : -INFINITY; R.st[i] = 0u; }
             }
         }
         __syncthreads();
@@ -1042,6 +1046,7 @@ hipError_t launch_local_maxima_exact(const float* M, int64_t row0, int32_t n_col
     a.unit = refine->unit_rows; a.unit_pitch = refine->pitch; a.delta = refine->delta;
     a.min_value64 = refine->min_value; a.stats = refine->stats;
     a.start = (batch && batch->start > 0) ? batch->start : n_cols;
+    a.silent_zero = (refine->silent_zero && mode != 0) ? 1 : 0;
     if (batch && batch->n_batch > 0) {
         a.m_stride = batch->m_stride; a.idx_stride = batch->idx_stride; a.cnt_stride = batch->cnt_stride;
         a.unit_stride = batch->unit_stride;

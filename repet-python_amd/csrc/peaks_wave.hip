@@ -523,7 +523,8 @@ __device__ __forceinline__ void wave_finish_row(const PeakArgs& a, const WaveLds
 // tolerance band of the near-tie refinement widens "maximum" to "within delta of the maximum": a segment whose two largest
 // values are within delta of each other has its 32 elements read. Everything behind the candidates (decide(), rivals,
 // float64 verdicts, ranking, second level) is the sweep kernel's own code: same decisions element for element.
-template <int RD, bool SEG>
+// ZS (!SEG, modes 1 and 2): PeakArgs::silent_zero, see peaks.h
+template <int RD, bool SEG, bool ZS = false>
 // One wavefront per WORKGROUP: rows take 30 .. 140 us (the refinement of near-ties varies), and a workgroup's LDS and
 // registers are only handed back when its last wave is done (s_memrealtime spans of every row: tools/peak_stamps.py).
 __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64_t n_rows, int lds_per_wave) {
@@ -544,6 +545,13 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
         return;
     }
     const int64_t j = a.row0 + r;                            // absolute row (mode 1: current frame)
+    if constexpr (ZS) {
+        if (silent_row(a, j)) {                              // a silent frame: no list (uniform per wavefront)
+            for (int k = lane; k < a.number; k += 64) a.idx[r * (int64_t)a.idx_pitch + k] = -1;
+            if (lane == 0) a.count[r] = 0;
+            return;
+        }
+    }
     const int n = a.n = row_columns(a, j);                   // (uniform per wavefront) everything below, wave_finish_row included, sees the row's own length
     float dlt = a.delta;                                     // 0: no refinement
 
@@ -849,7 +857,7 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
                         int i = jm - l;
                         i += i < 0 ? n : 0;                                   // (l < n: one wrap at most)
                         const int p_ = i - s0;                                 // place in the chunk
-                        if (l < n) flat[4 * phys4(p_ >> 2) + (p_ & 3)] = nan_to_inf(vals[k]);
+                        if (l < n) flat[4 * phys4(p_ >> 2) + (p_ & 3)] = peak_value<ZS>(vals[k]);
                     }
                 }
             } else {
@@ -870,7 +878,7 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
                     const int i0 = s0 + 4 * (64 * q + lane);
                     float v[4];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = (i0 + k >= 0 && i0 + k < n) ? nan_to_inf(e[4 * q + k]) : -INFINITY;
+                    for (int k = 0; k < 4; ++k) v[k] = (i0 + k >= 0 && i0 + k < n) ? peak_value<ZS>(e[4 * q + k]) : -INFINITY;
                     L.buf[phys4(64 * q + lane)] = make_float4(v[0], v[1], v[2], v[3]);
                 }
             }
@@ -1059,7 +1067,7 @@ __global__ __launch_bounds__(64) void local_maxima_wave_kernel(PeakArgs a, int64
                         val[b] = fetch_inside(pos[b] >= 0 ? pos[b] : i);
                     }
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) val[b] = nan_to_inf(val[b]);
+                    for (int b = 0; b < 4; ++b) val[b] = peak_value<ZS>(val[b]);
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         const int k = pos[b];
@@ -1178,11 +1186,12 @@ extern "C" int repet_debug_wave_spans(unsigned long long* out, int rows) {
 static bool wave_shape(int n_cols, int d, int* cap_out);
 static bool wave_kernel_off();
 
-template <int RD, bool SEG = false>
+template <int RD, bool SEG = false, bool ZS = false>
 static hipError_t launch_wave_rd(const PeakArgs& a, int64_t n_rows, int n_batch, int bytes, int per_wave, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&local_maxima_wave_kernel<RD, SEG>), bytes);
+    if constexpr (!SEG && !ZS) { if (a.silent_zero) return launch_wave_rd<RD, false, true>(a, n_rows, n_batch, bytes, per_wave, s); }
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&local_maxima_wave_kernel<RD, SEG, ZS>), bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((local_maxima_wave_kernel<RD, SEG>), dim3((unsigned)n_rows, (unsigned)n_batch), dim3(64), bytes, s, a, n_rows, per_wave);
+    hipLaunchKernelGGL((local_maxima_wave_kernel<RD, SEG, ZS>), dim3((unsigned)n_rows, (unsigned)n_batch), dim3(64), bytes, s, a, n_rows, per_wave);
     return hipGetLastError();
 }
 

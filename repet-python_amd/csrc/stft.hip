@@ -331,6 +331,7 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(3, 
     if (a.Vn) a.Vn += b * a.batch_mean_stride;
     if (a.Vh) a.Vh = static_cast<_Float16*>(a.Vh) + 2 * b * a.batch_mean_stride;
     if (a.P) a.P += b * a.batch_mean_stride;
+    if (a.silent) a.silent += b * a.batch_silent_stride;
     {
         float2 wreg[LOADS], treg[kTwLoads];
 #pragma unroll
@@ -465,14 +466,17 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(3, 
 #pragma unroll
         for (int w = 0; w < kFftThreads / kWave; ++w) total += red[w];
         const float norm = sqrtf(total);
+        const bool mute = a.silent && norm == 0.f;  // silent_frames = "zero" (see stft_kernel)
+        if (a.silent && tid == 0) a.silent[t] = mute ? 1u : 0u;
         FSTAMP(0, 5)                               // channel mean, norm reduction
 #pragma unroll
         for (int i = 0; i < SLOTS; ++i) {
             const int k = tid + kFftThreads * i;
             if (k <= N) {
+                const float unit = mute ? 0.f : acc[i] / norm;
                 if (a.Vm) a.Vm[row + k] = acc[i];
-                if (a.Vn) a.Vn[row + k] = acc[i] / norm;
-                if (a.Vh) store_split_f16(a.Vh, row + k, acc[i] / norm);
+                if (a.Vn) a.Vn[row + k] = unit;
+                if (a.Vh) store_split_f16(a.Vh, row + k, unit);
                 if (a.P) a.P[row + k] = acc[i] * acc[i];
             }
         }
@@ -519,6 +523,7 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
     if (a.Vn) a.Vn += b * a.batch_mean_stride;
     if (a.Vh) a.Vh = static_cast<_Float16*>(a.Vh) + 2 * b * a.batch_mean_stride;
     if (a.P) a.P += b * a.batch_mean_stride;
+    if (a.silent) a.silent += b * a.batch_silent_stride;
 
     FftTwiddles<kTables ? 4 : N> ft;                // register twiddles only where the tables do not fit in LDS
     if (kTables) {
@@ -647,13 +652,18 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(W <
 #pragma unroll
         for (int w = 0; w < kFftThreads / kWave; ++w) total += red[w];
         const float norm = sqrtf(total);     // 0 for a silent frame: 0/0 = NaN like repet.py:1220
+        // silent_frames = "zero" (StftArgs::silent): the frame whose norm is EXACTLY 0 is flagged and gets the unit row 0 -- its
+        // similarity with every frame, itself included, is then 0. A NaN sample makes the norm NaN: not silent, the reference's row.
+        const bool mute = a.silent && norm == 0.f;
+        if (a.silent && tid == 0) a.silent[t] = mute ? 1u : 0u;
 #pragma unroll
         for (int i = 0; i < SLOTS; ++i) {
             const int k = tid + kFftThreads * i;
             if (k <= N) {
+                const float unit = mute ? 0.f : acc[i] / norm;
                 if (a.Vm) a.Vm[row + k] = acc[i];
-                if (a.Vn) a.Vn[row + k] = acc[i] / norm;
-                if (a.Vh) store_split_f16(a.Vh, row + k, acc[i] / norm);
+                if (a.Vn) a.Vn[row + k] = unit;
+                if (a.Vh) store_split_f16(a.Vh, row + k, unit);
                 if (a.P) a.P[row + k] = acc[i] * acc[i];
             }
         }
@@ -1021,6 +1031,7 @@ __global__ __launch_bounds__(256) void stft_wave_kernel(StftArgs a, int frames_p
     if (a.Vn) a.Vn += b * a.batch_mean_stride;
     if (a.Vh) a.Vh = static_cast<_Float16*>(a.Vh) + 2 * b * a.batch_mean_stride;
     if (a.P) a.P += b * a.batch_mean_stride;
+    if (a.silent) a.silent += b * a.batch_silent_stride;
 
     for (int i = tid; i < W; i += 256) tw[i] = a.twiddle[i];
     for (int i = tid; i < N; i += 256) win[i] = make_float2(a.window[2 * i], a.window[2 * i + 1]);
@@ -1091,11 +1102,14 @@ __global__ __launch_bounds__(256) void stft_wave_kernel(StftArgs a, int frames_p
             if (lane == 0) red[wave] = ss;
             __syncthreads();
             const float norm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));   // 0 for a silent frame: NaN row
+            const bool mute = a.silent && norm == 0.f;                         // silent_frames = "zero" (see stft_kernel): flagged, row 0
+            if (a.silent && tid == 0) a.silent[t] = mute ? 1u : 0u;
             for (int k = tid; k < a.FS; k += 256) {
                 const float m = (k <= N) ? vst[(df * C) * a.FS + k] : 0.f;
+                const float unit = (k <= N && !mute) ? m / norm : 0.f;
                 if (a.Vm) a.Vm[row + k] = m;
-                if (a.Vn) a.Vn[row + k] = (k <= N) ? m / norm : 0.f;
-                if (a.Vh) store_split_f16(a.Vh, row + k, (k <= N) ? m / norm : 0.f);
+                if (a.Vn) a.Vn[row + k] = unit;
+                if (a.Vh) store_split_f16(a.Vh, row + k, unit);
                 if (a.P) a.P[row + k] = m * m;
             }
             __syncthreads();                  // red[] and vst are reused

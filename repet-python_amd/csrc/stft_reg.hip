@@ -397,7 +397,11 @@ __global__ __launch_bounds__(64 * kFwdWaves) void stft_reg_kernel(StftArgs a, in
         const float norm = sqrtf(ss);        // 0 for a silent frame: 0/0 = NaN like repet.py:1220
         // (the row times the correctly rounded reciprocal: seventeen IEEE divisions were 180 instructions per frame in a
         // kernel bound by instruction issue; a silent frame gives 0 * inf = NaN, as 0 / 0 did)
-        const float inv_norm = 1.0f / norm;
+        // silent_frames = "zero" (StftArgs::silent; see stft_kernel in stft.hip): the frame whose norm is exactly 0 is flagged and its
+        // row is 0 * 0 (wave-uniform)
+        const bool mute = a.silent && norm == 0.f;
+        if (a.silent && lane == 0) a.silent[b * a.batch_silent_stride + t] = mute ? 1u : 0u;
+        const float inv_norm = mute ? 0.f : 1.0f / norm;
         const int64_t mrow = b * a.batch_mean_stride + row;
         float* Vm = a.Vm ? a.Vm + mrow : nullptr;
         float* Vn = a.Vn ? a.Vn + mrow : nullptr;

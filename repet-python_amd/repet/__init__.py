@@ -121,16 +121,18 @@ def release_workspaces():
 
 
 def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
-                     levels=False, dtype=None, band_gains=None):
+                     levels=False, dtype=None, band_gains=None, flags=0):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
     has checked, or None. ``levels``: also the level record of the result (one reduction launch more, two for a long clip), under
-    the same gain. ``band_gains``: ``(edges, g)`` that ``separate`` has checked with ``band_gain_rows``, or None."""
+    the same gain. ``band_gains``: ``(edges, g)`` that ``separate`` has checked with ``band_gain_rows``, or None. ``flags``: bits
+    ``separate`` adds to this call's ``Params.flags`` (``silent_frames``)."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
     params = derive_params(sampling_frequency)
+    params.flags |= flags
     layout = _native.tensor_layout(audio_signal, batched)
     x, shape = layout[0], layout[2]
     result_shape = shape if x.dim() == 3 else shape[1:]
@@ -210,7 +212,7 @@ def simonline(audio_signal, sampling_frequency):
 
 
 def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
-             background_band_gains=None, band_edges=None):
+             silent_frames="reference", background_band_gains=None, band_edges=None):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
     batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
     clips one after another). Returns a float64 tensor on the tensor's device -- one of ``dtype``, where given -- or fills
@@ -250,9 +252,14 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     and the largest magnitudes of mixture, background and foreground, the samples and those whose mixture is not finite), a
     float64 tensor ``(C, 8)`` -- ``(B, C, 8)`` for a batch -- on the tensor's device, reduced there from the float64 values the
     egress forms (whatever ``which`` and the dtype of ``out`` are, under this call's ``background_gain``), with no host wait.
-    Deterministic: the same call returns the same bits. See :func:`online_streams` for the fields."""
+    Deterministic: the same call returns the same bits. See :func:`online_streams` for the fields.
+
+    ``silent_frames`` (``algo="simonline"`` only): "reference" (default) answers a frame of digital silence with NaN, as the
+    reference does; "zero" separates through it, see :func:`online`. For this call alone. ValueError, before the library is
+    touched, for any other string and for "zero" with another ``algo``. Pass it, and the band gains behind it, by keyword."""
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
+    flags = _native.silent_frames_flag(silent_frames, algo)
     _native.which_codes(which)
     if background_gain is not None:
         if which not in ("foreground", "both"):
@@ -270,10 +277,10 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
-                            background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains)
+                            background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains, flags=flags)
 
 
-def online(sampling_frequency, number_channels, start_length=None):
+def online(sampling_frequency, number_channels, start_length=None, silent_frames="reference"):
     """Streaming form of :func:`simonline` (the reference needs the whole signal up front): returns an object with
     ``push(chunk) -> newly final background samples`` and ``finish() -> the remaining ones``. The module parameters are
     snapshotted now; the concatenated output equals ``simonline`` of the concatenated input.
@@ -307,12 +314,27 @@ def online(sampling_frequency, number_channels, start_length=None):
     bit. Below ``start_length`` the foreground is still the input, as today, and a stream can be finished once it has
     ``(start_frames - 2) * step_length + window_length`` samples. While ``j <= similarity_distance`` (in frames) a young
     frame's only similar frame is itself: its mask is 1, so the whole input counts as background and the foreground is
-    silent. A sensible ``start_length`` is therefore at least two or three times ``similarity_distance``."""
+    silent. A sensible ``start_length`` is therefore at least two or three times ``similarity_distance``.
+
+    ``silent_frames`` ("reference", the default, or "zero"; the ``silent_frames`` property): what the stream makes of whole
+    frames of digital silence -- a muted microphone, a decoder that writes exact zeros, the lead-in of a file. The reference
+    divides such a frame's mean magnitude row by its norm, 0 / 0: the frame's samples come out NaN (background, foreground,
+    ``last_levels``, ``last_frames``; only an int16 destination hides it), and while the frame sits in the 10-s buffer no frame
+    within ``similarity_distance`` of it can be anybody's similar frame. "zero": a frame whose float32 norm is exactly 0 (exact
+    zeros; magnitudes below about 4e-23 count too; a frame with a NaN sample does not) gets the unit row 0, so its similarity
+    with every frame, itself included, is 0; it has no similar frames (``last_matches``: count 0, ages -1, similarities 0), is
+    in no other frame's list, and adds 0 to the overlap-add (``last_frames`` is 0 there in all three signals, the frames around
+    it ring into its samples as usual); every other frame is the reference's on a similarity vector with zeros in the silent
+    columns. A stream without a silent frame gives the same bits under either rule. A frame whose list is empty for another
+    reason (a NaN sample, an exact tie) stays NaN. The rule belongs to the handle: ``import_stream`` refuses a state exported
+    under the other one. Any other string is a ValueError."""
     params = derive_params(sampling_frequency)
+    params.flags |= _native.silent_frames_flag(silent_frames)
     return _OnlineSeparator(params, number_channels, _device, _native.start_frames_for(params, sampling_frequency, start_length))
 
 
-def online_streams(sampling_frequency, number_channels, number_streams, max_push_samples=None, start_length=None):
+def online_streams(sampling_frequency, number_channels, number_streams, max_push_samples=None, start_length=None,
+                   silent_frames="reference"):
     """Many live streams at once: ``number_streams`` streams of ``number_channels`` channels at one sampling frequency in ONE
     streaming handle on the device of :func:`set_device`, pushed in lockstep. ``push(chunk, out=None)`` takes a chunk
     ``(number_streams, n, number_channels)`` -- a host array, or a ROCm tensor (the dtypes :func:`separate` takes, any strides)
@@ -480,8 +502,16 @@ def online_streams(sampling_frequency, number_channels, number_streams, max_push
     cost. While a young frame's number is at most ``similarity_distance`` (in frames) its only similar frame is itself: the
     mask is 1, the whole input counts as background and the foreground is silent, so a sensible ``start_length`` is at least
     two or three times ``similarity_distance``; below ``start_length`` the foreground is still the input. The value belongs
-    to the handle, not to a stream: an imported stream goes on under the importing handle's."""
+    to the handle, not to a stream: an imported stream goes on under the importing handle's.
+
+    ``silent_frames`` ("reference", the default, or "zero"; the ``silent_frames`` property): what every slot makes of whole
+    frames of digital silence, see :func:`online`. Under "zero" a muted slot emits a finite background and foreground,
+    ``last_levels`` stays finite, ``last_frames`` and the background shaped by band gains are 0 on the silent frames,
+    ``last_matches`` reports count 0 there, and the mute does not keep the frames around it out of the other frames' lists;
+    ``hold``, ``feed`` / ``tick``, ``restart``, ``export_stream`` / ``import_stream`` and ``start_length`` work as they do
+    without it, at the same launches per push. A stream moves only between handles opened with the same rule."""
     params = derive_params(sampling_frequency)
+    params.flags |= _native.silent_frames_flag(silent_frames)
     return _native.OnlineStreams(params, number_channels, number_streams, _device, max_push_samples or 0,
                                  _native.start_frames_for(params, sampling_frequency, start_length))
 

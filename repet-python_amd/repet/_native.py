@@ -22,6 +22,8 @@ MAX_STAGES = 16
 ERR_BAD_ARG, ERR_TOO_SHORT, ERR_HIP, ERR_OOM, ERR_LIMIT = -1, -2, -3, -4, -5
 FLAG_STRICT_REFERENCE = 1      # (ABI 3 opt-in; the default since ABI 4)
 FLAG_REFUSE_NONFINITE = 2
+FLAG_SILENT_FRAMES_ZERO = 4    # simonline and the live handles: frames of digital silence are separated, not answered with NaN
+SILENT_FRAMES = {"reference": 0, "zero": FLAG_SILENT_FRAMES_ZERO}
 # what an emitting call of a live handle, or the egress of a tensor call, delivers (REPET_OUT_* of include/repet_hip.h);
 # "both" is the Python layer's pair (background, foreground) from one pass
 OUT_BACKGROUND, OUT_FOREGROUND, OUT_MIXTURE = 0, 1, 2
@@ -289,6 +291,7 @@ _SIGNATURES = {
     "repet_online_last_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_ctx_result_levels_device": (C.c_int, [_P, _P, _P]),
     "repet_emit_dtype_supported": (C.c_int, [C.c_int]),
+    "repet_silent_frames_supported": (C.c_int, []),
     "repet_online_hold_streams": (C.c_int, [_P, _P, C.c_int32]),
     "repet_online_resume_streams": (C.c_int, [_P, _P, C.c_int32]),
     "repet_online_stream_held": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
@@ -887,6 +890,26 @@ def default_context(device=0):
     return ctx
 
 
+def silent_frames_flag(silent_frames, algo="simonline"):
+    """The bit of ``Params.flags`` for ``silent_frames`` ("reference": 0, "zero": FLAG_SILENT_FRAMES_ZERO). ValueError for any
+    other value, and for a rule other than the reference's with a variant other than simonline: nothing has run by then."""
+    if not isinstance(silent_frames, str):
+        # (in ``repet.separate`` the keyword sits in front of ``background_band_gains``: a caller who passed the band gains as
+        # the ninth positional argument lands here)
+        raise ValueError('silent_frames is "reference" or "zero", not a %s: pass background_band_gains and band_edges of '
+                         'repet.separate by keyword (silent_frames was added in front of them)' % type(silent_frames).__name__)
+    if silent_frames not in SILENT_FRAMES:
+        raise ValueError(f'silent_frames is "reference" or "zero", not {silent_frames!r}')
+    flag = SILENT_FRAMES[silent_frames]
+    if flag and algo != "simonline":
+        raise ValueError(f'silent_frames={silent_frames!r} goes with algo="simonline" and the live handles only, not {algo!r}')
+    return flag
+
+
+def _silent_frames_of(params):
+    return "zero" if params.flags & FLAG_SILENT_FRAMES_ZERO else "reference"
+
+
 def start_frames_for(params, sampling_frequency, start_length):
     """``start_length`` in seconds as frames, derived as buffer_frames is and clamped to [1, buffer_frames]; None stays None (the
     handle is then opened as it always was)."""
@@ -1206,7 +1229,13 @@ class OnlineSeparator:
         if lib().repet_device_count() < 1:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open(int(device), self._channels, C.byref(params), C.byref(self._h)))
+        self._silent_frames = _silent_frames_of(params)
         _set_start_frames(self, start_frames)
+
+    @property
+    def silent_frames(self):
+        """What the stream makes of frames of digital silence (``silent_frames`` of ``repet.online``): "reference" or "zero"."""
+        return self._silent_frames
 
     @property
     def start_frames(self):
@@ -1357,6 +1386,7 @@ class OnlineStreams:
             raise RuntimeError("no HIP device visible: the REPET engine has no CPU fallback")
         check(lib().repet_online_open_streams(self._device, self._streams, self._channels, C.byref(params),
                                               int(max_push_samples or 0), C.byref(self._h)))
+        self._silent_frames = _silent_frames_of(params)
         _set_start_frames(self, start_frames)
         self._pushed = 0                              # samples per slot pushed so far
         self._emitted_shape = (self._streams, 0, self._channels)
@@ -1372,6 +1402,12 @@ class OnlineStreams:
     def shape(self):
         """(number_streams, number_channels)"""
         return self._streams, self._channels
+
+    @property
+    def silent_frames(self):
+        """What every slot makes of frames of digital silence (``silent_frames`` of ``repet.online_streams``): "reference" or
+        "zero". The handle's, for every slot and every restart; ``import_stream`` refuses a state exported under the other rule."""
+        return self._silent_frames
 
     @property
     def start_frames(self):

@@ -52,15 +52,27 @@ preallocated tensors on the device (no host wait of its own).
 ``--band-gains N``: the one-handle cases with ``set_background_band_gains`` of N mel bands (``repet.band_edges(fs, N)``) with
 distinct gains made right after the open, so every timed push carries the second, shaped inverse STFT (use it with ``--which
 foreground`` or ``both``). ``--band-gains-change-every K`` (with it): the bands are set again, with the gains rotated, before
-every K-th timed push (outside the clock), so those pushes also bring the tables up to date."""
+every K-th timed push (outside the clock), so those pushes also bring the tables up to date.
+
+``--silent-frames LEGS`` (a comma list of ``off``, ``zero``, ``zero-muted``): instead, what ``silent_frames="zero"`` costs. One
+handle of S slots per leg, device chunks of one hop, each push timed with a synchronize, the legs taking turns for ``--rounds``
+rounds of ``--timed`` pushes each (every handle goes on with its own streams): ``off`` never names the option, ``zero`` sets it on
+streams without silence, ``zero-muted`` sets it on streams of which a quarter of the 10-s buffer -- the frames from 207 to 97
+before the end of the warm-up, layout D of tests/silence_reference.py at this rate -- is digital silence and stays in the buffer
+through every timed push; a ``--timed`` x ``--rounds`` that would let the mute leave the buffer is refused before anything runs.
+The legs take turns in the order given, and rotate by one from round to round so that no leg always runs first. ``--label TEXT``
+goes into the document as ``build`` (the commit that was measured). Reported per leg: the median of every round, their range, and the ratio of the medians over all rounds
+to the ``off`` leg's. ``REPET_PACKAGE_DIR`` (environment): the directory of the package to time in place of ``repet-python_amd``
+-- the ``off`` leg runs on a build without the option, which is how a parent commit is timed on the same machine."""
 import argparse
 import json
+import os
 import sys
 import time
 
 import numpy as np
 
-sys.path[:0] = ["repet-python_amd", "."]
+sys.path[:0] = [os.environ.get("REPET_PACKAGE_DIR", "repet-python_amd"), "."]
 import repet  # noqa: E402
 from repet_synth import synth  # noqa: E402
 
@@ -458,8 +470,64 @@ def feed_one_handle(xs, fs, timed, warm_s, packet=882):
             "calls_timed": len(both), "ragged_ticks_timed": len(ragged)}
 
 
+def silent_frames_legs(xs, fs, legs, timed, warm_s, rounds):
+    import torch
+    S, N, ch = xs.shape
+    p = repet.derive_params(fs)
+    hop, B = p.step_length, p.buffer_frames
+    warm = int(round(warm_s * fs / hop)) * hop
+    muted = np.array(xs)
+    first = warm - 207 * hop + 3
+    muted[:, first: first + 110 * hop + p.window_length] = 0
+    end = warm + (3 + rounds * timed) * hop                    # the last timed push ends here
+    if end > N or first < end - B * hop:                       # (before anything runs on the device)
+        raise SystemExit("--silent-frames: %d rounds of %d pushes leave the clip, or let the mute leave the 10-s buffer" % (rounds, timed))
+    handles, sources, lat = {}, {}, {}
+    for leg in legs:
+        kw = {} if leg == "off" else {"silent_frames": "zero"}
+        handles[leg] = repet.online_streams(fs, ch, S, max_push_samples=hop, **kw)
+        sources[leg] = torch.tensor(muted if leg == "zero-muted" else xs, device="cuda:0")
+        lat[leg] = []
+        pos = 0
+        while pos < warm:                                      # fill the buffer in half-second pushes
+            n = min(fs // 2, warm - pos)
+            handles[leg].push(sources[leg][:, pos:pos + n])
+            pos += n
+        for _ in range(3):                                     # the per-push workspaces take their size
+            handles[leg].push(sources[leg][:, pos:pos + hop])
+            pos += hop
+    torch.cuda.synchronize()
+    for r in range(rounds):
+        start = pos + r * timed * hop
+        for leg in legs[r % len(legs):] + legs[:r % len(legs)]:
+            h, src, at, mine = handles[leg], sources[leg], start, []
+            for _ in range(timed):
+                t0 = time.perf_counter()
+                h.push(src[:, at:at + hop])
+                torch.cuda.synchronize()
+                mine.append(time.perf_counter() - t0)
+                at += hop
+            lat[leg].append(mine)
+    out = {}
+    for leg in legs:
+        handles[leg].close()
+        medians = [round(float(np.median(np.array(m) * 1e3)), 4) for m in lat[leg]]
+        out[leg] = {"per_hop_ms_median_by_round": medians, "per_hop_ms_range": [min(medians), max(medians)],
+                    "per_hop_ms_median": round(float(np.median(np.concatenate(lat[leg]) * 1e3)), 4), "pushes_timed": rounds * timed}
+    if "off" in out:
+        for leg in legs:
+            out[leg]["ratio_to_off"] = round(out[leg]["per_hop_ms_median"] / out["off"]["per_hop_ms_median"], 4)
+    if "zero" in out and "zero-muted" in out:
+        out["zero-muted"]["ratio_to_zero"] = round(out["zero-muted"]["per_hop_ms_median"] / out["zero"]["per_hop_ms_median"], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--silent-frames", default=None, metavar="LEGS",
+                    help="the silent-frames leg: a comma list of off / zero / zero-muted (see above)")
+    ap.add_argument("--label", default=None, help="with --silent-frames: recorded as `build`, the commit that was measured")
+    ap.add_argument("--rounds", type=int, default=3, help="with --silent-frames: rounds the legs take turns for")
     ap.add_argument("--feed", type=int, default=0, help="1: the feed leg (feed / tick of slots fed at their own pace)")
     ap.add_argument("--hold", type=int, default=0, metavar="K", help="the hold leg: pushes of one hop with K of the slots held")
     ap.add_argument("--migrate", type=int, default=0, help="1: the migrate leg (export_stream / import_stream per call)")
@@ -494,6 +562,19 @@ def main():
     args = ap.parse_args()
     fs, ch, warm_s = 44100, 2, 11
     streams = [int(s) for s in args.streams.split(",")]
+    if args.silent_frames:
+        legs = args.silent_frames.split(",")
+        if not legs or any(leg not in ("off", "zero", "zero-muted") for leg in legs):
+            ap.error("--silent-frames takes a comma list of off, zero, zero-muted")
+        hop = repet.derive_params(fs).step_length
+        result = {"fs": fs, "channels": ch, "rounds": args.rounds, "legs": legs, "cases": []}
+        if args.label:
+            result["build"] = args.label
+        for S in streams:
+            xs = stream_signals(S, warm_s + 1 + (args.rounds * args.timed + 8) * hop / fs, fs, ch)
+            result["cases"].append(dict({"streams": S}, **silent_frames_legs(xs, fs, legs, args.timed, warm_s, args.rounds)))
+        print(json.dumps(result, indent=1))
+        return
     if args.feed > 0:
         hop = repet.derive_params(fs).step_length
         result = {"fs": fs, "channels": ch, "cases": []}
