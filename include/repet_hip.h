@@ -218,6 +218,37 @@ int repet_ctx_download_device(repet_ctx* ctx, float* dev_out);
 int repet_ctx_upload_device_strided(repet_ctx* ctx, const void* src, int dtype, int32_t n_clips, int64_t n_samples,
                                     int32_t n_channels, const int64_t strides[3], void* wait_stream);
 int repet_ctx_download_device_strided(repet_ctx* ctx, void* dst, int dtype, const int64_t strides[3], void* signal_stream);
+/* (an addition to ABI 4) A RAGGED batch: clips of unequal lengths in one padded buffer. repet_ctx_upload_device_ragged is
+ * repet_ctx_upload_device_strided with a HOST array of n_clips lengths, each in [0, n_samples]: clip b is its first lengths[b]
+ * samples, n_samples is the PITCH of the batch. The samples at and behind a clip's length are never loaded (they may hold NaN,
+ * infinities or stale memory, and the note of REPET_FLAG_REFUSE_NONFINITE looks at live samples only); the resident planes
+ * hold zeros there. The lengths belong to the resident batch and are cleared by every upload. Lengths that all equal
+ * n_samples ARE repet_ctx_upload_device_strided: the same kernels, the same bits. At most 65535 clips.
+ * With lengths set,
+ *   repet_ctx_execute / _async   REPET_SIMONLINE still runs every stage once over all clips, at the frame count of the pitch,
+ *                                plus one launch that clears the frames behind each clip's own last one in front of the inverse
+ *                                STFT; every other variant -- REPET_ORIGINAL included, which gives up its batched form -- works
+ *                                through the clips one by one at each clip's own length. A clip too short for the variant is
+ *                                refused before anything is enqueued, with the one-clip call's code and text and the clip named
+ *                                in front (repet_check_clip_lengths makes the same check without a context); a clip of no
+ *                                samples is refused by every variant.
+ *   repet_ctx_download_device_strided, repet_ctx_result_levels_device
+ *                                clip b's values below lengths[b] are those of the one-clip call on its lengths[b] samples --
+ *                                in every signal, dtype and gain, the level record bit for bit (REPET_LEVEL_LIVE is lengths[b]) --
+ *                                and zero of the destination's type from there to the pitch; neither the result nor the input is
+ *                                read there.
+ *   repet_ctx_download, repet_ctx_download_device, repet_ctx_download_foreground   refuse (REPET_ERR_BAD_ARG): the feature is
+ *                                the device path.
+ *   repet_ctx_last_frame_count, repet_ctx_last_sim_indices   report the last clip of the loop; after REPET_SIMONLINE the PADDED
+ *                                geometry (the frame count of the pitch; the lists of rows at and behind a clip's own last frame
+ *                                are not the clip's).
+ * repet_ctx_clip_lengths : the lengths of the resident batch (n_samples for every clip of an equal one), up to `capacity` of
+ * them; n_written is the number of clips. */
+int repet_ctx_upload_device_ragged(repet_ctx* ctx, const void* src, int dtype, int32_t n_clips, int64_t n_samples,
+                                   int32_t n_channels, const int64_t strides[3], const int64_t* lengths, void* wait_stream);
+int repet_ctx_clip_lengths(repet_ctx* ctx, int64_t* out, int32_t capacity, int32_t* n_written);
+int repet_check_clip_lengths(int algo, const repet_params* params, int32_t start_frames /* 0: buffer_frames */,
+                             const int64_t* lengths, int32_t n_clips);
 /* (ABI 3) Borrowed views for a host that keeps the exchange on the device (one process per GPU, torch.distributed over
  * RCCL: repet/parallel.py). The pointers stay valid until the next upload of this context (a larger clip may move the
  * buffers); what a run writes into the result is ordered on the context's stream, which repet_ctx_stream hands out so that

@@ -112,15 +112,71 @@ template <> __device__ inline void load4_dense<BHalf>(const BHalf* src, float (&
 }
 
 // Four consecutive interleaved elements per thread: one dwordx4 store per plane, 1 KiB per wave instruction.
-template <typename T>
+// kRagged (repet_ctx_upload_device_ragged): clip b has lengths[b] live samples. A run that lies below its clip's length is today's
+// conversion by today's code; a run at or behind it stores zeros and loads nothing; the run a length cuts (a length times the
+// channel count need not be a multiple of four) goes element by element, loading the live elements only. The non-finite note
+// therefore looks at live samples alone.
+template <typename T, bool kRagged = false>
 __device__ inline void ingest_body(const T* __restrict__ src, IoGeo g, int dense, float* __restrict__ hi_out,
-                                   float* __restrict__ lo_out, unsigned int* nonfinite) {
+                                   float* __restrict__ lo_out, unsigned int* nonfinite, const int64_t* __restrict__ lengths = nullptr) {
     constexpr bool kSplit = std::is_same<T, double>::value;
     const int64_t i0 = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * 4;
     if (i0 >= g.count) return;
     const bool check = nonfinite != nullptr;
     bool bad = false;
     float hi[4], lo[4];
+    if constexpr (kRagged) {
+        const int m = g.count - i0 < 4 ? (int)(g.count - i0) : 4;
+        // (clip, sample, channel) of the run's first element: 32-bit divisions where the plane allows them
+        int64_t b, n;
+        int32_t c;
+        if (g.count <= 0xffffffffll) {
+            const uint32_t t = (uint32_t)i0 / (uint32_t)g.n_channels;
+            c = (int32_t)((uint32_t)i0 - t * (uint32_t)g.n_channels);
+            b = t / (uint32_t)g.n_samples;
+            n = t - (uint32_t)b * (uint32_t)g.n_samples;
+        } else {
+            const int64_t t = i0 / g.n_channels;
+            c = (int32_t)(i0 - t * g.n_channels);
+            b = t / g.n_samples;
+            n = t - b * g.n_samples;
+        }
+        bool live[4];
+        int n_live = 0;
+        int64_t len = lengths[b];                                 // (loaded again only where the run enters the next clip)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            live[k] = false;
+            if (k < m) {
+                live[k] = n < len;
+                n_live += live[k] ? 1 : 0;
+                if (++c == g.n_channels) {
+                    c = 0;
+                    if (++n == g.n_samples) {
+                        n = 0; ++b;
+                        if (k < m - 1) len = lengths[b];
+                    }
+                }
+            }
+        }
+        if (n_live < 4) {                                         // (all four live: the run is the equal-length path's, below)
+            if (m == 4 && n_live == 0) {
+                *reinterpret_cast<float4*>(hi_out + i0) = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (kSplit) *reinterpret_cast<float4*>(lo_out + i0) = make_float4(0.f, 0.f, 0.f, 0.f);
+                return;
+            }
+            Walker w(g, i0);
+            for (int k = 0; k < m; ++k) {
+                float h = 0.f, l = 0.f;
+                if (live[k]) split1<T>(src + w.off, h, l, bad, check);
+                hi_out[i0 + k] = h;
+                if constexpr (kSplit) lo_out[i0 + k] = l;
+                if (k < m - 1) w.next(g);
+            }
+            if (bad) *nonfinite = 1u;
+            return;
+        }
+    }
     if (i0 + 4 <= g.count) {
         if (dense) {
             load4_dense<T>(src + i0, hi, lo);
@@ -247,6 +303,11 @@ __global__ __launch_bounds__(kIoThreads) void devio_ingest_f32(const float* src,
 __global__ __launch_bounds__(kIoThreads) void devio_ingest_i16(const int16_t* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<int16_t>(src, g, dense, hi, lo, nf); }
 __global__ __launch_bounds__(kIoThreads) void devio_ingest_f16(const Half* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<Half>(src, g, dense, hi, lo, nf); }
 __global__ __launch_bounds__(kIoThreads) void devio_ingest_bf16(const BHalf* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf) { ingest_body<BHalf>(src, g, dense, hi, lo, nf); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_ragged_f64(const double* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf, const int64_t* len) { ingest_body<double, true>(src, g, dense, hi, lo, nf, len); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_ragged_f32(const float* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf, const int64_t* len) { ingest_body<float, true>(src, g, dense, hi, lo, nf, len); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_ragged_i16(const int16_t* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf, const int64_t* len) { ingest_body<int16_t, true>(src, g, dense, hi, lo, nf, len); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_ragged_f16(const Half* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf, const int64_t* len) { ingest_body<Half, true>(src, g, dense, hi, lo, nf, len); }
+__global__ __launch_bounds__(kIoThreads) void devio_ingest_ragged_bf16(const BHalf* src, IoGeo g, int dense, float* hi, float* lo, unsigned int* nf, const int64_t* len) { ingest_body<BHalf, true>(src, g, dense, hi, lo, nf, len); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f64(const float* in, IoGeo g, int dense, double* dst) { egress_body<double, 2>(in, g, dense, dst); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_f32(const float* in, IoGeo g, int dense, float* dst) { egress_body<float, 4>(in, g, dense, dst); }
 __global__ __launch_bounds__(kIoThreads) void devio_egress_i16(const float* in, IoGeo g, int dense, int16_t* dst) { egress_body<int16_t, kEpt16>(in, g, dense, dst); }
@@ -277,6 +338,11 @@ struct EmitArgs {
     EmitOut out[2];
     const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
     const float* bg_fg;             // (nullable) the background the FOREGROUND is formed from, laid out like bg: a live handle's shaped one
+    // (nullable) a ragged offline batch: stream s is live below sample live_len[s] of the emission. At and behind it every signal
+    // is zero of the destination's type and nothing is loaded: a run wholly behind it loads no plane, the run it cuts loads its
+    // live elements one by one.
+    const int64_t* live_len;
+    int32_t bg_only;                // every destination is the background (a ragged batch's plain download): hi / lo are not loaded
 };
 
 // The per-sample arithmetic of an emission, shared by the kernels that write it (emit_body) and that measure it (devio_levels):
@@ -307,27 +373,63 @@ __device__ inline void emit_body(const EmitArgs& a) {
     const int64_t s0 = i0 / a.per, r0 = i0 - s0 * a.per;
     float b[EPT], h[EPT], l[EPT];
     bool live[EPT];
-    if (m == EPT) {
+    // rd[k]: element k is read at all (inside the emission and, for a ragged batch, below its clip's length); whole: every
+    // element of a full run is, so the vector loads apply
+    bool rd[EPT];
+    bool whole = m == EPT;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) rd[k] = k < m;
+    if (a.live_len) {
+        // sample and channel of the run's first element (one division, 32-bit where a stream's share allows), then stepped; the
+        // length is loaded once and again only where the run enters the next stream
+        int64_t s = s0, j;
+        int32_t c;
+        if (a.per <= 0xffffffffll) {
+            const uint32_t q = (uint32_t)r0 / (uint32_t)a.n_channels;
+            j = q; c = (int32_t)((uint32_t)r0 - q * (uint32_t)a.n_channels);
+        } else {
+            j = r0 / a.n_channels; c = (int32_t)(r0 - j * a.n_channels);
+        }
+        int64_t len = a.live_len[s];
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+            if (k < m) {
+                rd[k] = j < len;
+                whole = whole && rd[k];
+                if (++c == a.n_channels) {
+                    c = 0;
+                    if (++j == a.n_samples) {
+                        j = 0; ++s;
+                        if (k < m - 1) len = a.live_len[s];
+                    }
+                }
+            }
+        }
+    }
+    if (whole) {
         load_run<EPT>(a.bg + i0, b);
     } else {
 #pragma unroll
-        for (int k = 0; k < EPT; ++k) b[k] = k < m ? a.bg[i0 + k] : 0.f;
+        for (int k = 0; k < EPT; ++k) b[k] = rd[k] ? a.bg[i0 + k] : 0.f;
     }
     float bf[EPT];
     if (a.bg_fg) {
-        if (m == EPT) {
+        if (whole) {
             load_run<EPT>(a.bg_fg + i0, bf);
         } else {
 #pragma unroll
-            for (int k = 0; k < EPT; ++k) bf[k] = k < m ? a.bg_fg[i0 + k] : 0.f;
+            for (int k = 0; k < EPT; ++k) bf[k] = rd[k] ? a.bg_fg[i0 + k] : 0.f;
         }
     } else {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) bf[k] = b[k];
     }
     const float* ph = a.hi + s0 * a.in_stream + r0;
-    const bool one_stream = m == EPT && r0 + EPT <= a.per;
-    if (one_stream && !(reinterpret_cast<uintptr_t>(ph) & (EPT * 4 - 1))) {
+    const bool one_stream = whole && r0 + EPT <= a.per;
+    if (a.bg_only) {
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) { h[k] = 0.f; l[k] = 0.f; }
+    } else if (one_stream && !(reinterpret_cast<uintptr_t>(ph) & (EPT * 4 - 1))) {
         load_run<EPT>(ph, h);
         if (a.lo) {
             load_run<EPT>(a.lo + s0 * a.in_stream + r0, l);         // (hi and lo are laid out alike: aligned together)
@@ -339,7 +441,7 @@ __device__ inline void emit_body(const EmitArgs& a) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             h[k] = 0.f; l[k] = 0.f;
-            if (k < m) {
+            if (rd[k]) {
                 int64_t s = s0, r = r0 + k;
                 if (r >= a.per) { s += r / a.per; r %= a.per; }
                 h[k] = a.hi[s * a.in_stream + r];
@@ -349,12 +451,12 @@ __device__ inline void emit_body(const EmitArgs& a) {
     }
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
-        live[k] = true;
+        live[k] = a.live_len ? rd[k] : true;
         if (a.slot_start && k < m) {
             int64_t s = s0, r = r0 + k;
             if (r >= a.per) { s += r / a.per; r %= a.per; }
             const int64_t start = a.slot_start[s];
-            live[k] = start < repet_eng::kSlotIdle && a.pos0 + r / a.n_channels >= start * a.hop;
+            live[k] = live[k] && start < repet_eng::kSlotIdle && a.pos0 + r / a.n_channels >= start * a.hop;
         }
     }
     double ak[EPT];
@@ -435,6 +537,10 @@ struct LevelArgs {
     const float* a_cur; const float* a_tgt; int64_t ramp; float a; int32_t gain;
     double* dst; double* partial;
     const float* bg_fg;             // as in EmitArgs
+    // as in EmitArgs. The walk of stream s simply ends at its live length, as the walk of a clip of that many samples ends at the
+    // clip's end: same tiles, same accumulators, same order -- and devio_levels_fold groups the chunks that hold live samples as it
+    // would group that clip's. A ragged clip's record is therefore the one-clip record bit for bit.
+    const int64_t* live_len;
 };
 
 template <int F> __device__ inline double level_fold(double x, double y) {
@@ -494,7 +600,11 @@ __global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
     const int t = threadIdx.x, C = a.n_channels;
     const int64_t s = blockIdx.y;
     const int64_t e0 = (int64_t)blockIdx.x * repet_eng::kLevelChunk * C;                    // the chunk's elements of this stream: [e0, e1)
-    const int64_t e1 = e0 + repet_eng::kLevelChunk * C < a.per ? e0 + repet_eng::kLevelChunk * C : a.per;
+    int64_t e1 = e0 + repet_eng::kLevelChunk * C < a.per ? e0 + repet_eng::kLevelChunk * C : a.per;
+    if (a.live_len) {
+        const int64_t end = a.live_len[s] * C;
+        e1 = e1 < end ? e1 : end;
+    }
     // the first live sample of this stream within the emission (emit_body's rule: slot_start and pos0)
     int64_t live_from = 0;
     bool any_live = true;
@@ -587,11 +697,19 @@ __global__ __launch_bounds__(kIoThreads) void devio_levels(LevelArgs a) {
     level_regroup<1>(a, v, slots, waves);
 }
 
-__global__ __launch_bounds__(64) void devio_levels_fold(const double* __restrict__ partial, int32_t n_chunks, double* __restrict__ dst) {
+// live_len (nullable; C channels per stream): only the chunks that hold live samples of the stream are folded, in the grouping a
+// clip of that length has (one chunk: 0 + x, which is x)
+__global__ __launch_bounds__(64) void devio_levels_fold(const double* __restrict__ partial, int32_t n_chunks, double* __restrict__ dst,
+                                                        const int64_t* __restrict__ live_len, int32_t C) {
     const int f = threadIdx.x & 7, u = threadIdx.x >> 3;
     const int64_t sc = blockIdx.x;
-    const int per = (n_chunks + 7) / 8;
-    const int first = u * per, last = first + per < n_chunks ? first + per : n_chunks;
+    int n_fold = n_chunks;
+    if (live_len) {
+        const int64_t used = (live_len[sc / C] + repet_eng::kLevelChunk - 1) / repet_eng::kLevelChunk;
+        n_fold = used < n_chunks ? (int)used : n_chunks;
+    }
+    const int per = (n_fold + 7) / 8;
+    const int first = u * per, last = first + per < n_fold ? first + per : n_fold;
     double x = 0.0;
     for (int k = first; k < last; ++k) x = level_fold_rt(f, x, partial[(sc * n_chunks + k) * REPET_LEVEL_FIELDS + f]);
     double r = x;
@@ -601,6 +719,30 @@ __global__ __launch_bounds__(64) void devio_levels_fold(const double* __restrict
         r = level_fold_rt(f, r, y);
     }
     if (u == 0) dst[sc * REPET_LEVEL_FIELDS + f] = r;
+}
+
+// simonline over a RAGGED batch (exec_simonline) runs every stage at the frame count T of the pitch. Clip b (blockIdx.y) has
+// T_b = repet_frame_count(lengths[b], W, H, 0) frames of its own; the rows [T_b, T) of its spectra are frames the one-clip call
+// never forms -- partly the clip's last samples, partly the zero fill, NaN under the reference's 0 / 0 -- and they overlap the
+// clip's last hop in the overlap-add. This launch, between the mask stage and the inverse STFT, makes them ZERO in what the
+// inverse STFT (plain and shaped) fetches: the spectra X and, where the mask is a plane of its own, Mk -- a store, so that they
+// add exactly nothing there (a product with 0 would keep a NaN). blockIdx.z is the channel; the length is one scalar load per
+// wave; rows are FS (a multiple of 32) elements, so every store is whole and 16 bytes wide.
+__global__ __launch_bounds__(kIoThreads) void devio_tail_clear(float2* __restrict__ X, float* __restrict__ Mk, int64_t spec_stride,
+                                                               int64_t chan_stride, int64_t T, int32_t FS, int32_t W, int32_t H,
+                                                               const int64_t* __restrict__ lengths) {
+    const int64_t num = lengths[blockIdx.y] - W;                  // repet_frame_count(n, W, H, 0)
+    int64_t Tb = (num >= 0 ? (num + H - 1) / H : -((-num) / H)) + 1;
+    Tb = Tb > 0 ? Tb : 0;
+    if (Tb >= T) return;
+    const int64_t base = (int64_t)blockIdx.y * spec_stride + (int64_t)blockIdx.z * chan_stride + Tb * FS;
+    const int64_t n = (T - Tb) * FS;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t i = ((int64_t)blockIdx.x * kIoThreads + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * kIoThreads * 4) {
+        float4* x = reinterpret_cast<float4*>(X + base + i);
+        x[0] = zero; x[1] = zero;
+        if (Mk) *reinterpret_cast<float4*>(Mk + base + i) = zero;
+    }
 }
 
 // ---- the streaming handle's per-push data movement (engine_online.hip): S streams at a per-stream stride -------------------
@@ -1310,7 +1452,7 @@ hipError_t launch_band_commit(float* tab, int32_t FS, int32_t n_slots, int32_t s
 
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s, const EmitGain* gain, const float* bg_fg) {
+                              int n_dsts, hipStream_t s, const EmitGain* gain, const float* bg_fg, const int64_t* live_len) {
     const int64_t count = (int64_t)n_streams * n * ch;
     if (count <= 0 || n_dsts <= 0) return hipSuccess;
     if (n_dsts > 2 || !bg || !hi) return hipErrorInvalidValue;
@@ -1323,7 +1465,9 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
         }
     }
     a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
-    a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts;
+    a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts; a.live_len = live_len;
+    a.bg_only = live_len ? 1 : 0;
+    for (int k = 0; k < n_dsts; ++k) if (dsts[k].which != REPET_OUT_BACKGROUND) a.bg_only = 0;
     // (the vector store of a dense destination: 16 bytes for F64 / F32, kEpt16 elements for the 16-bit types)
     const int vec_bytes = dtype == REPET_F64 || dtype == REPET_F32 ? 16 : 2 * kEpt16;
     for (int k = 0; k < n_dsts; ++k) {
@@ -1356,7 +1500,7 @@ int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch) {
 
 hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                                 int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
-                                hipStream_t s, const EmitGain* gain, const float* bg_fg) {
+                                hipStream_t s, const EmitGain* gain, const float* bg_fg, const int64_t* live_len) {
     if (n_streams <= 0 || ch <= 0) return hipSuccess;
     if (!dst) return hipErrorInvalidValue;
     const int64_t count = (int64_t)n_streams * n * ch;
@@ -1375,11 +1519,11 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
     }
     a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_chunks = (int32_t)chunks;
-    a.dst = dst; a.partial = partials;
+    a.dst = dst; a.partial = partials; a.live_len = live_len;
     devio_levels<<<dim3((unsigned)chunks, (unsigned)n_streams), kIoThreads, 0, s>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || chunks == 1) return e;
-    devio_levels_fold<<<dim3((unsigned)(n_streams * ch)), 64, 0, s>>>(partials, (int32_t)chunks, dst);
+    devio_levels_fold<<<dim3((unsigned)(n_streams * ch)), 64, 0, s>>>(partials, (int32_t)chunks, dst, live_len, ch);
     return hipGetLastError();
 }
 
@@ -1455,12 +1599,20 @@ int signal_caller(repet_ctx* c, void* signal_stream) {
     return REPET_OK;
 }
 
-}  // namespace repet_eng
+hipError_t launch_tail_clear(float2* X, float* Mk, int64_t spec_stride, int64_t chan_stride, int32_t n_clips, int32_t ch, int64_t T,
+                             int32_t FS, int32_t W, int32_t H, const int64_t* lengths_dev, int64_t longest_tail, hipStream_t s) {
+    if (longest_tail <= 0 || n_clips <= 0) return hipSuccess;
+    if (!X || !lengths_dev || n_clips > 65535 || ch < 1 || ch > 65535 || (FS & 3)) return hipErrorInvalidValue;
+    const int64_t groups = ceil_div(longest_tail * FS, (int64_t)kIoThreads * 4);
+    const int64_t x_cap = std::max<int64_t>(1, kMaxIoGroups / ((int64_t)n_clips * ch));
+    devio_tail_clear<<<dim3((unsigned)std::min(groups, x_cap), (unsigned)n_clips, (unsigned)ch), kIoThreads, 0, s>>>(
+        X, Mk, spec_stride, chan_stride, T, FS, W, H, lengths_dev);
+    return hipGetLastError();
+}
 
-extern "C" {
-
-int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch,
-                                    const int64_t strides[3], void* wait_stream) {
+// the strided ingest, equal clips (lengths null) or ragged ones (lengths[b] in [0, n], checked by the caller, not all equal to n)
+static int upload_strided(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t strides[3],
+                          const int64_t* lengths, void* wait_stream) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     if (n < 0 || ch < 1 || n_clips < 1) return fail(REPET_ERR_BAD_ARG, "audio_signal must be (number_samples, number_channels)");
     if (dtype < REPET_F32 || dtype > REPET_BF16) return fail(REPET_ERR_BAD_ARG, "unsupported dtype");
@@ -1477,6 +1629,15 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     // ingest must land after it, not under it. (lo_in_flight stays set: the host has not seen the copy finish, and the ring's
     // remainder buffer must not be refilled before it has -- StagingRing waits for lo_done then.)
     if (c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
+    const int64_t* len_dev = nullptr;
+    if (lengths) {
+        // the table travels in the arguments of a small launch (the online_slot_set pattern: no copy the host would wait for)
+        HIP_TRY(c->clip_len_dev.ensure((size_t)n_clips * sizeof(int64_t)));
+        std::vector<int32_t> ids((size_t)n_clips);
+        std::iota(ids.begin(), ids.end(), 0);
+        HIP_TRY(launch_slot_set(c->clip_len_dev.as<int64_t>(), ids.data(), lengths, n_clips, c->stream));
+        len_dev = c->clip_len_dev.as<int64_t>();
+    }
     const bool refuse = !c->strict;
     unsigned int* flag = nullptr;
     if (refuse) {
@@ -1491,7 +1652,14 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
         const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
         float* hi = c->audio.as<float>();
         float* lo = c->audio_lo.as<float>();
-        switch (dtype) {
+        if (len_dev) switch (dtype) {
+            case REPET_F64: devio_ingest_ragged_f64<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const double*>(src), g, dense, hi, lo, flag, len_dev); break;
+            case REPET_F32: devio_ingest_ragged_f32<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+            case REPET_I16: devio_ingest_ragged_i16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+            case REPET_F16: devio_ingest_ragged_f16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+            default: devio_ingest_ragged_bf16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+        }
+        else switch (dtype) {
             case REPET_F64: devio_ingest_f64<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const double*>(src), g, dense, hi, lo, flag); break;
             case REPET_F32: devio_ingest_f32<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag); break;
             case REPET_I16: devio_ingest_i16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag); break;
@@ -1516,8 +1684,42 @@ int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, in
     c->input_not_finite = false;
     c->input_unscanned = true;
     c->n_samples = n; c->n_channels = ch; c->n_clips = n_clips; c->clip_base = 0;
-    c->win_total = 0; c->win_offset = 0;
+    c->win_total = 0; c->win_offset = 0; c->clip_len.clear();
+    if (lengths) c->clip_len.assign(lengths, lengths + n_clips);
     c->result_shaped = false;
+    return REPET_OK;
+}
+
+}  // namespace repet_eng
+
+extern "C" {
+
+int repet_ctx_upload_device_strided(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch,
+                                    const int64_t strides[3], void* wait_stream) {
+    return upload_strided(c, src, dtype, n_clips, n, ch, strides, nullptr, wait_stream);
+}
+
+int repet_ctx_upload_device_ragged(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch,
+                                   const int64_t strides[3], const int64_t* lengths, void* wait_stream) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (!lengths) return fail(REPET_ERR_BAD_ARG, "lengths is null");
+    if (n < 0 || ch < 1 || n_clips < 1) return fail(REPET_ERR_BAD_ARG, "audio_signal must be (number_samples, number_channels)");
+    if (n_clips > 65535) return fail(REPET_ERR_LIMIT, "a ragged batch holds at most 65535 clips");
+    bool equal = true;
+    for (int32_t b = 0; b < n_clips; ++b) {
+        if (lengths[b] < 0 || lengths[b] > n)
+            return fail(REPET_ERR_BAD_ARG, "lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + " lies outside [0, n_samples]");
+        equal = equal && lengths[b] == n;
+    }
+    // (every clip as long as the pitch: the equal-length path, its kernels and its bits)
+    return upload_strided(c, src, dtype, n_clips, n, ch, strides, equal ? nullptr : lengths, wait_stream);
+}
+
+int repet_ctx_clip_lengths(repet_ctx* c, int64_t* out, int32_t capacity, int32_t* n_written) {
+    if (!c || !n_written || capacity < 0 || (capacity > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
+    *n_written = c->n_clips;
+    for (int32_t b = 0; b < c->n_clips && b < capacity; ++b) out[b] = c->ragged() ? c->clip_len[(size_t)b] : c->n_samples;
     return REPET_OK;
 }
 
@@ -1558,7 +1760,7 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
     // the destination belongs to the caller's stream: what that stream has enqueued up to now (a pending reader of a block the
     // caching allocator has just handed out again, the caller's own writes to `dst`) comes before the egress writes it
     RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    if (count > 0 && c->result_which != REPET_OUT_BACKGROUND) {
+    if (count > 0 && (c->result_which != REPET_OUT_BACKGROUND || c->ragged())) {      // (a ragged background: the emission's select)
         // foreground / mixture: the resident samples and, where a float64 upload left them, their remainders beside the result
         if (c->has_lo && c->ring.lo_in_flight) HIP_TRY(hipStreamWaitEvent(c->stream, c->ring.lo_done, 0));
         EmitDst d{dst, c->result_which, {strides[0], strides[1], strides[2]}};
@@ -1566,7 +1768,7 @@ int repet_ctx_download_device_strided(repet_ctx* c, void* dst, int dtype, const 
         gain.scalar = true; gain.a = c->result_a;
         HIP_TRY(launch_stream_emit(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
                                    c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels, dtype, &d, 1,
-                                   c->stream, c->result_gain ? &gain : nullptr, c->shaped_bg()));
+                                   c->stream, c->result_gain ? &gain : nullptr, c->shaped_bg(), c->live_len()));
     } else if (count > 0) {
         HIP_TRY(launch_stream_egress(c->out.as<float>(), c->n_clips, c->n_samples, c->n_channels, dst, dtype, strides, c->stream));
     }
@@ -1591,7 +1793,7 @@ int repet_ctx_result_levels_device(repet_ctx* c, void* dst, void* signal_stream)
     const hipError_t e = launch_stream_levels(c->out.as<float>(), c->audio.as<float>(), c->has_lo ? c->audio_lo.as<float>() : nullptr,
                                               c->n_samples * c->n_channels, nullptr, 0, 1, c->n_clips, c->n_samples, c->n_channels,
                                               static_cast<double*>(dst), partials > 0 ? c->levels_ws.as<double>() : nullptr, c->stream,
-                                              c->result_gain ? &gain : nullptr, c->shaped_bg());
+                                              c->result_gain ? &gain : nullptr, c->shaped_bg(), c->live_len());
     if (e == hipErrorNotSupported) return fail(REPET_ERR_LIMIT, "too many channels for the level reduction");
     HIP_TRY(e);
     return signal_caller(c, signal_stream);

@@ -89,6 +89,17 @@ struct repet_ctx {
     int64_t n_samples = 0;        // per clip
     int32_t n_clips = 1;          // equal-shape clips back to back in `audio` / `out` (repet_ctx_upload_batch)
     int64_t clip_base = 0;        // first sample of the clip the single-clip pipelines currently work on
+    // A RAGGED batch (repet_ctx_upload_device_ragged): n_samples is the PITCH of the resident batch, clip b holds clip_len[b] <=
+    // n_samples live samples and the planes are zero from there to the pitch. clip_len empty: every clip is n_samples long (every
+    // other upload clears it). clip_len_dev: the same table on the device, int64 [n_clips], written on the context's stream by
+    // the upload -- the ingest, the emission, the levels and simonline's tail clear read it. clip_n: the LENGTH of the clip
+    // run_algo's loop is working on (-1: the pitch); the pipelines take cur_n() where they mean the clip, n_samples where they
+    // mean the layout.
+    std::vector<int64_t> clip_len; DevBuf clip_len_dev;
+    int64_t clip_n = -1;
+    int64_t cur_n() const { return clip_n >= 0 ? clip_n : n_samples; }
+    bool ragged() const { return !clip_len.empty(); }
+    const int64_t* live_len() const { return clip_len.empty() ? nullptr : static_cast<const int64_t*>(clip_len_dev.p); }
     // repet_ctx_set_window: the resident samples are [win_offset, win_offset + n_samples) of a clip of win_total samples
     // (multi-GPU `extended`: a rank holds only the samples of its own segment range); 0 = the resident clip is whole
     int64_t win_total = 0, win_offset = 0;
@@ -249,6 +260,7 @@ int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64
 int exec_adaptive(repet_ctx* c, const repet_params* p);
 int check_params(const repet_params* p);
 int check_algo_flags(int algo, const repet_params* p);
+int check_clip_lengths(int algo, const repet_params* p, int32_t start_frames, const int64_t* lengths, int32_t n_clips);
 int h2d_pitched(repet_ctx* c, float* dst, int64_t dpitch, const float* src, int64_t rows, int64_t cols, int64_t rows_pad);
 int d2h_pitched(repet_ctx* c, float* dst, const float* src, int64_t spitch, int64_t rows, int64_t cols);
 int ctx_create(int device, repet_ctx** out, bool probe_side_stream);
@@ -364,7 +376,8 @@ struct EmitDst { void* p = nullptr; int which = -1; int64_t strides[3] = {0, 0, 
 struct EmitGain { const float* a_cur = nullptr; const float* a_tgt = nullptr; int64_t ramp = 0; float a = 1.f; bool scalar = false; };
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
-                              int n_dsts, hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr);
+                              int n_dsts, hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr,
+                              const int64_t* live_len = nullptr);
 //   levels   the REPET_LEVEL_FIELDS float64 values per stream and channel of the emission the same arguments describe to
 //            launch_stream_emit (include/repet_hip.h: energies, peaks, live and non-finite samples), dense [n_streams][ch][8]
 //            into dst: one launch over (chunk of kLevelChunk samples, stream), and for more than one chunk a second small one
@@ -374,7 +387,13 @@ constexpr int64_t kLevelChunk = REPET_LEVEL_CHUNK;
 int64_t stream_levels_partials(int32_t n_streams, int64_t n, int32_t ch);
 hipError_t launch_stream_levels(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                                 int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, double* dst, double* partials,
-                                hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr);
+                                hipStream_t s, const EmitGain* gain = nullptr, const float* bg_fg = nullptr,
+                                const int64_t* live_len = nullptr);
+//   tail     simonline over a ragged batch: rows [T_b, T) of every clip's and channel's spectra X (and of the mask plane Mk,
+//            nullable) are stored zero, T_b = repet_frame_count(lengths_dev[b], W, H, 0) read on the device; longest_tail: the
+//            largest T - T_b of the batch (the host knows the lengths), which sizes the grid. One launch, none for 0
+hipError_t launch_tail_clear(float2* X, float* Mk, int64_t spec_stride, int64_t chan_stride, int32_t n_clips, int32_t ch, int64_t T,
+                             int32_t FS, int32_t W, int32_t H, const int64_t* lengths_dev, int64_t longest_tail, hipStream_t s);
 //   gains    the background gains of the streaming handle, fp32 [S] tables of a = (float)(1 - gain). fill: n entries = a.
 //            set: tgt[slots[k]] = a[k], one launch per kSlotResetIds slots named. commit: cur_new[s] = tgt[s] for the slots an
 //            emission covers (slot < 0: all), cur_old[s] for the others; one launch

@@ -499,6 +499,47 @@ int check_algo_flags(int algo, const repet_params* p) {
     return REPET_OK;
 }
 
+// The clips of a ragged batch against what `algo` needs of a clip's length: the refusals the one-clip pipelines make for such a
+// length (same code, same text, with the clip named in front), made for all clips before anything is enqueued. A clip of no
+// samples is refused by every variant: simonline, original and extended by their own too-short rule, sim and adaptive here.
+int check_clip_lengths(int algo, const repet_params* p, int32_t start_frames, const int64_t* lengths, int32_t n_clips) {
+    if (!lengths || n_clips < 1) return fail(REPET_ERR_BAD_ARG, "lengths: one per clip");
+    const int W = p->window_length, H = p->step_length;
+    auto original_short = [&](int64_t n) {
+        const int64_t T = repet_frame_count(n, W, H, 1);
+        return (int)std::min<int64_t>(p->period_hi, T / 3) <= p->period_lo;
+    };
+    for (int32_t b = 0; b < n_clips; ++b) {
+        const int64_t n = lengths[b];
+        const std::string who = "clip " + std::to_string(b) + " of the batch (" + std::to_string(n) + " samples): ";
+        if (n < 0) return fail(REPET_ERR_BAD_ARG, who + "negative length");
+        switch (algo) {
+            case REPET_SIMONLINE: {
+                const int B = p->buffer_frames, M = start_frames > 0 ? start_frames : B;
+                if (B >= 1 && M <= B && n < (int64_t)(M - 2) * H + W)
+                    return fail(REPET_ERR_TOO_SHORT, who + "operands could not be broadcast together (signal shorter than the buffer)");
+                break;
+            }
+            case REPET_ORIGINAL:
+                if (original_short(n)) return fail(REPET_ERR_TOO_SHORT, who + "attempt to get argmax of an empty sequence (clip too short for the period range)");
+                break;
+            case REPET_EXTENDED: {
+                const int64_t count = extended_segment_count(n, p);
+                if (count < 0) return fail(REPET_ERR_BAD_ARG, who + "extended: bad segment length/step (Window length M must be a non-negative integer)");
+                if (original_short(count == 1 ? n : p->seg_len_samples))
+                    return fail(REPET_ERR_TOO_SHORT, who + "attempt to get argmax of an empty sequence (clip too short for the period range)");
+                break;
+            }
+            case REPET_ADAPTIVE:
+            case REPET_SIM:
+                if (n == 0) return fail(REPET_ERR_TOO_SHORT, who + "a clip of no samples");
+                break;
+            default: return fail(REPET_ERR_BAD_ARG, "unknown algorithm");
+        }
+    }
+    return REPET_OK;
+}
+
 // copy a dense host matrix [rows][cols] into a pitched device matrix (pad columns zeroed)
 int h2d_pitched(repet_ctx* c, float* dst, int64_t dpitch, const float* src, int64_t rows, int64_t cols, int64_t rows_pad) {
     HIP_TRY(hipMemsetAsync(dst, 0, (size_t)rows_pad * dpitch * sizeof(float), c->stream));
@@ -551,6 +592,11 @@ int64_t repet_frame_count(int64_t n, int32_t W, int32_t H, int32_t centred) {
     const int64_t num = n - W;                                       // repet.py:781
     const int64_t q = num >= 0 ? (num + H - 1) / H : -((-num) / H);
     return q + 1;
+}
+
+int repet_check_clip_lengths(int algo, const repet_params* p, int32_t start_frames, const int64_t* lengths, int32_t n_clips) {
+    RP_TRY(repet_eng::check_params(p));
+    return repet_eng::check_clip_lengths(algo, p, start_frames, lengths, n_clips);
 }
 
 }  // extern "C"
@@ -664,7 +710,7 @@ int repet_ctx_destroy(repet_ctx* c) {
                       &c->refine_stats, &c->R, &c->Vs, &c->rank_codes, &c->code_planes, &c->median_codes, &c->tiles_big,
                       &c->audio_lo, &c->redo_list, &c->redo_flag, &c->u64, &c->u64_gen, &c->exact_scratch,
                       &c->lite_list, &c->lite_flag, &c->lite_records, &c->frame_list, &c->frame_flag,
-                      &c->seg, &c->nonfinite_word, &c->levels_ws, &c->band_tab, &c->out_fg, &c->silent,
+                      &c->seg, &c->nonfinite_word, &c->levels_ws, &c->clip_len_dev, &c->band_tab, &c->out_fg, &c->silent,
                       &c->idx, &c->cnt, &c->periods, &c->win_periods, &c->frames, &c->tmp_a, &c->tmp_b, &c->tmp_c})
         b->release();
     for (auto& kv : c->tile_lists) kv.second.buf.release();
@@ -773,7 +819,7 @@ int repet_ctx_upload_batch(repet_ctx* c, const void* audio, int dtype, int64_t n
     c->n_channels = ch;
     c->n_clips = n_clips;
     c->clip_base = 0;
-    c->win_total = 0; c->win_offset = 0;
+    c->win_total = 0; c->win_offset = 0; c->clip_len.clear();
     c->result_shaped = false;
     return REPET_OK;
 }
@@ -805,7 +851,7 @@ int repet_ctx_upload_device_split(repet_ctx* c, const float* dev_audio, const fl
     c->input_unscanned = true;
     c->ring.lo_in_flight = false;              // (the stream waited for it above and is idle now)
     c->n_samples = n; c->n_channels = ch; c->n_clips = n_clips; c->clip_base = 0;
-    c->win_total = 0; c->win_offset = 0;
+    c->win_total = 0; c->win_offset = 0; c->clip_len.clear();
     c->result_shaped = false;
     return REPET_OK;
 }
@@ -816,6 +862,7 @@ int repet_ctx_upload_device(repet_ctx* c, const float* dev_audio, int64_t n, int
 
 int repet_ctx_download_device(repet_ctx* c, float* dev_out) {
     if (!c || !dev_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->ragged()) return fail(REPET_ERR_BAD_ARG, "the resident batch is ragged (repet_ctx_upload_device_ragged): its result leaves through repet_ctx_download_device_strided");
     DeviceGuard guard(c->device);
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;
     if (count == 0) return REPET_OK;
@@ -877,7 +924,7 @@ int repet_ctx_download_from(repet_ctx* c, const float* dev_src, int64_t n_values
 
 int repet_ctx_set_window(repet_ctx* c, int64_t n_total, int64_t sample0) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
-    if (c->n_channels < 1 || c->n_clips != 1) return fail(REPET_ERR_BAD_ARG, "set_window applies to a single resident clip");
+    if (c->n_channels < 1 || c->n_clips != 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "set_window applies to a single resident clip");
     if (n_total == 0 && sample0 == 0) { c->win_total = 0; c->win_offset = 0; return REPET_OK; }
     if (sample0 < 0 || n_total < sample0 + c->n_samples) return fail(REPET_ERR_BAD_ARG, "window outside the clip");
     c->win_total = n_total; c->win_offset = sample0;
@@ -906,21 +953,29 @@ int run_algo_one(repet_ctx* c, int algo, const repet_params* p) {
 
 // A batch context (n_clips > 1): simonline and original run every stage once over all clips; the others work through
 // the resident clips one after the other (their intermediates -- periods, index lists -- are those of the last).
+// A RAGGED batch (repet_ctx::clip_len): simonline still runs every stage once over all clips, at the frame count of the pitch,
+// and clears the frames behind each clip's own last one in front of its inverse STFT (exec_simonline); every other variant,
+// `original` included, works through the clips one by one at the clip's own length. The lengths are checked for the variant
+// before anything is enqueued.
 int run_algo(repet_ctx* c, int algo, const repet_params* p) {
     c->clip_base = 0;
+    c->clip_n = -1;
     if (c->win_total > 0) return fail(REPET_ERR_BAD_ARG, "the resident samples are a window of a longer clip: only repet_ctx_execute_extended_range applies");
+    if (c->ragged()) RP_TRY(check_clip_lengths(algo, p, c->online_start, c->clip_len.data(), (int32_t)c->clip_len.size()));
 
-    if (c->n_clips <= 1 || algo == REPET_SIMONLINE || algo == REPET_ORIGINAL) return run_algo_one(c, algo, p);
+    if (algo == REPET_SIMONLINE || (!c->ragged() && (c->n_clips <= 1 || algo == REPET_ORIGINAL))) return run_algo_one(c, algo, p);
     repet_timing* timing = c->timing;
     c->timing = nullptr;                       // per-stage marks would repeat per clip: only the total is reported
     int rc = REPET_OK;
     c->clip_loop = true;
     for (int b = 0; b < c->n_clips && rc == REPET_OK; ++b) {
         c->clip_base = (int64_t)b * c->n_samples;
+        if (c->ragged()) c->clip_n = c->clip_len[(size_t)b];
         rc = run_algo_one(c, algo, p);
     }
     c->clip_loop = false;
     c->clip_base = 0;
+    c->clip_n = -1;
     c->timing = timing;
     if (rc == REPET_OK) mark(c, "clips", 0, 0);
     return rc;
@@ -1041,7 +1096,7 @@ int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_
     RP_TRY(check_algo_flags(REPET_EXTENDED, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
-    if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
+    if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
     if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
     DeviceGuard guard(c->device);
     c->result_shaped = false;
@@ -1062,7 +1117,7 @@ int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, 
     RP_TRY(check_algo_flags(REPET_EXTENDED, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
     if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
-    if (c->n_clips > 1) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
+    if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
     if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
     DeviceGuard guard(c->device);
     c->result_shaped = false;
@@ -1074,6 +1129,7 @@ int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, 
 
 int repet_ctx_download(repet_ctx* c, double* out) {
     if (!c || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->ragged()) return fail(REPET_ERR_BAD_ARG, "the resident batch is ragged (repet_ctx_upload_device_ragged): its result leaves through repet_ctx_download_device_strided");
     DeviceGuard guard(c->device);
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;
     if (count == 0) return REPET_OK;
@@ -1104,7 +1160,7 @@ int repet_ctx_upload_wav(repet_ctx* c, const void* file_bytes, int64_t n_bytes, 
     c->input_not_finite = false;
     c->input_unscanned = w.format != 1;
     c->n_samples = w.n_samples; c->n_channels = w.n_channels; c->n_clips = 1; c->clip_base = 0;
-    c->win_total = 0; c->win_offset = 0;
+    c->win_total = 0; c->win_offset = 0; c->clip_len.clear();
     c->result_shaped = false;
     c->last_fs = w.sampling_frequency;
     return REPET_OK;
@@ -1167,6 +1223,7 @@ void repet_host_free(void* ptr) { host_free(ptr); }
 
 int repet_ctx_download_foreground(repet_ctx* c, double* out) {
     if (!c || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->ragged()) return fail(REPET_ERR_BAD_ARG, "the resident batch is ragged (repet_ctx_upload_device_ragged): its result leaves through repet_ctx_download_device_strided");
     if (c->last_algo < 0) return fail(REPET_ERR_BAD_ARG, "no separation has been run on this context");
     DeviceGuard guard(c->device);
     const int64_t count = c->n_samples * c->n_channels * c->n_clips;

@@ -133,7 +133,7 @@ int exec_original(repet_ctx* c, const repet_params* p) {
     // a batch context at its base runs all clips together (one launch per stage); otherwise the current clip
     const int nb = c->clip_loop ? 1 : c->n_clips;
     HIP_TRY(c->periods.ensure((size_t)nb * sizeof(int32_t)));
-    RP_TRY(run_original(c, p, 0, c->n_samples, nb, nb > 1 ? c->n_samples : 0, c->periods.as<int32_t>(), false, 0, 1, 0));
+    RP_TRY(run_original(c, p, 0, c->cur_n(), nb, nb > 1 ? c->n_samples : 0, c->periods.as<int32_t>(), false, 0, 1, 0));
     c->last_n_periods = nb;
     return REPET_OK;
 }
@@ -153,7 +153,7 @@ int64_t extended_segment_count(int64_t N, const repet_params* p) {
 int exec_extended_plan(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg, int64_t N);
 
 int exec_extended(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg) {
-    if (c->win_total <= 0) return exec_extended_plan(c, p, first, n_seg, c->n_samples);
+    if (c->win_total <= 0) return exec_extended_plan(c, p, first, n_seg, c->cur_n());
     // a window of a longer clip: the plan is the whole clip's, sample s of it lives at s - win_offset here. clip_base is
     // the (signed) origin every read and write of the single-clip pipelines is relative to.
     const int64_t N = c->win_total, L = p->seg_len_samples, Hs = p->seg_step_samples;
@@ -291,7 +291,7 @@ int exec_adaptive(repet_ctx* c, const repet_params* p) {
     MaskPlaneScope plane(c, mask_plane_wanted(MaskKind::adaptive));
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, p->window_length, &tb));
-    const int64_t N = c->n_samples;
+    const int64_t N = c->cur_n();
     const int64_t T = repet_frame_count(N, p->window_length, p->step_length, 1);
     const Geo g = make_geo(p->window_length, p->step_length, T, c->n_channels);
     const int Ls = p->seg_len_frames, Hs = p->seg_step_frames;

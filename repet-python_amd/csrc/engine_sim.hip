@@ -178,7 +178,7 @@ int run_rank_columns(repet_ctx* c, const Geo& g, MaskArgs* m, hipStream_t stream
 int exec_sim(repet_ctx* c, const repet_params* p) {
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, p->window_length, &tb));
-    const int64_t N = c->n_samples;
+    const int64_t N = c->cur_n();
     const int64_t T = repet_frame_count(N, p->window_length, p->step_length, 1);
     const Geo g = make_geo(p->window_length, p->step_length, T, c->n_channels);
     if (p->sim_number < 1) return fail(REPET_ERR_BAD_ARG, "similarity_number must be >= 1");
@@ -291,7 +291,7 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     SilentZeroScope silent(c, (p->flags & REPET_FLAG_SILENT_FRAMES_ZERO) != 0);
     Tables* tb = nullptr;
     RP_TRY(get_tables(c, p->window_length, &tb));
-    const int64_t N = c->n_samples;
+    const int64_t N = c->cur_n();
     const int W = p->window_length, H = p->step_length, B = p->buffer_frames;
     if (B < 1) return fail(REPET_ERR_BAD_ARG, "buffer length must be >= 1 frame");
     // start_frames M (repet_hip.h: repet_online_set_start_frames): frames M-1 .. B-2 are separated on the buffer as far as it has
@@ -346,6 +346,17 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     if (c->silent_zero) { m.silent = c->silent.as<unsigned int>(); m.silent_batch_stride = g.Tpad; }     // (run_stft's table: frame0 = 0)
     HIP_TRY(launch_mask_sim(m, c->idx.as<int32_t>(), KP, c->cnt.as<int32_t>(), M - 1, max_peaks, c->stream));
     mark(c, "mask_sim", nb * (4.0 + 4.0 * K + (c->mask_plane ? 4.0 : 16.0)) * g.F * (double)rows * g.C, 0);
+    if (c->ragged() && !c->clip_loop) {
+        // A ragged batch ran every stage above at the pitch's frame count T. simonline is causal -- a frame's unit row, its
+        // look-back similarities, its list and its mask are functions of frames at or before it --, so the frames t < T_b of clip b
+        // are the one-clip call's (the zero fill behind the length is the reference's own end padding). The frames from T_b on are
+        // not the clip's; they overlap its last hop in the overlap-add and must add exactly nothing there: stored zero (devio.hip).
+        int64_t shortest = T;
+        for (int64_t n : c->clip_len) shortest = std::min(shortest, std::max<int64_t>(repet_frame_count(n, W, H, 0), 0));
+        HIP_TRY(launch_tail_clear(c->X.as<float2>(), c->mask_plane ? c->Mk.as<float>() : nullptr, spec_stride, g.chan_stride, nb, g.C, T,
+                                  g.FS, W, H, c->live_len(), T - shortest, c->stream));
+        mark(c, "tail_clear", (c->mask_plane ? 12.0 : 8.0) * g.FS * (double)(T - shortest) * g.C * nb, 0);
+    }
     if (nb == 1) {
         RP_TRY(run_istft(c, g, tb, 0, N, 0, false, 0, 0));
     } else {

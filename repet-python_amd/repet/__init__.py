@@ -17,6 +17,8 @@ it does there. All arithmetic runs in hand-written HIP kernels for gfx950 behind
 own rounding rules, and crosses the C ABI. There is no NumPy/CPU implementation of the separation
 path here: without the library or a GPU the calls raise.
 """
+import functools
+
 import numpy as np
 
 from . import _native
@@ -121,13 +123,14 @@ def release_workspaces():
 
 
 def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
-                     levels=False, dtype=None, band_gains=None, flags=0):
+                     levels=False, dtype=None, band_gains=None, flags=0, lengths=None):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
     has checked, or None. ``levels``: also the level record of the result (one reduction launch more, two for a long clip), under
     the same gain. ``band_gains``: ``(edges, g)`` that ``separate`` has checked with ``band_gain_rows``, or None. ``flags``: bits
-    ``separate`` adds to this call's ``Params.flags`` (``silent_frames``)."""
+    ``separate`` adds to this call's ``Params.flags`` (``silent_frames``). ``lengths``: what ``_native.clip_lengths`` made of
+    ``separate``'s, or None; a clip too short for ``algo`` is refused here, before the context is touched."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
@@ -146,10 +149,12 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
         if tuple(o.shape) != result_shape:
             raise ValueError(f"out has shape {tuple(o.shape)}, the result {result_shape}")
         _native.emit_tensor_code(o)
+    if lengths is not None:
+        _native.check_clip_lengths(algo, params, lengths)
     ctx = _native.tensor_context(x.device.index)
     ctx.set_strict_reference(strict_reference)
     stream = torch.cuda.current_stream(x.device)
-    ctx.upload_layout(*layout, stream=stream)
+    ctx.upload_layout(*layout, stream=stream, lengths=lengths)
     record = None
     # gains: on this thread's cached context for this call alone -- later calls are the plain foreground again, whatever
     # happens here. The band table shapes the run it is set in front of; the scalar gain acts in the egress.
@@ -211,11 +216,11 @@ def simonline(audio_signal, sampling_frequency):
     return _separate("simonline", audio_signal, sampling_frequency)
 
 
-def separate(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
-             silent_frames="reference", background_band_gains=None, band_edges=None):
+def _separate_surface(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
+                      silent_frames="reference", background_band_gains=None, band_edges=None):
     """``algo`` ("original", "extended", "adaptive", "sim", "simonline") of a torch tensor on a ROCm device: ``(N, C)`` or a
-    batch ``(B, N, C)`` of equal clips (``simonline`` runs every stage once over all of them, the others work through the
-    clips one after another). Returns a float64 tensor on the tensor's device -- one of ``dtype``, where given -- or fills
+    batch ``(B, N, C)`` of equal clips -- or, with ``lengths``, of clips of unequal lengths -- (``simonline`` runs every stage once
+    over all of them, the others work through the clips one after another). Returns a float64 tensor on the tensor's device -- one of ``dtype``, where given -- or fills
     ``out``, a float64 / float32 / int16 / float16 / bfloat16 tensor of the same shape with any strides, and returns it. Every
     clip's result is what the one-clip call returns, bit for bit; the work is ordered on the device's current stream with no
     host wait (see ``_separate_tensor``).
@@ -256,9 +261,32 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
 
     ``silent_frames`` (``algo="simonline"`` only): "reference" (default) answers a frame of digital silence with NaN, as the
     reference does; "zero" separates through it, see :func:`online`. For this call alone. ValueError, before the library is
-    touched, for any other string and for "zero" with another ``algo``. Pass it, and the band gains behind it, by keyword."""
+    touched, for any other string and for "zero" with another ``algo``. Pass it, and the band gains behind it, by keyword.
+
+    ``lengths`` (keyword only, with a ``(B, N, C)`` tensor only): a RAGGED batch -- clips of unequal lengths, padded to ``N``
+    (``torch.nn.utils.rnn.pad_sequence(clips, batch_first=True)`` makes one). A sequence of ``B`` integers in ``[0, N]`` on the
+    HOST: a list, a NumPy integer array or a CPU tensor. Clip ``b`` is ``audio_signal[b, :lengths[b]]``; the samples behind it
+    are never read -- they may hold NaN, infinities or stale memory, do not trip ``strict_reference = False`` and reach no
+    result. The result has the shape of the input: ``result[b, :lengths[b]]`` equals, as values, what the one-clip call
+    ``separate(algo, audio_signal[b, :lengths[b]], ...)`` returns -- for every ``which``, ``out`` / ``dtype``, gain and
+    ``silent_frames`` (the sign of a zero may differ) --, ``result[b, lengths[b]:]`` is zero. With ``levels=True`` clip ``b``'s
+    record is that of its own ``lengths[b]`` samples, bit for bit. ``simonline`` still runs every stage once over all clips
+    (plus one launch that clears the frames behind each clip's end); ``sim``, ``adaptive``, ``extended`` AND ``original`` -- which
+    gives up its batched form here -- work through the clips one by one. Padding the clips and calling without ``lengths`` is
+    not the same thing: the zeros become frames every variant hears. TypeError for ``lengths`` on a device (the call must not
+    wait for it) or not integers; ValueError for a wrong count, a value outside ``[0, N]`` or a 2-D tensor -- all before the
+    library is touched --, and, before anything is uploaded or enqueued, for a clip too short for ``algo``: the one-clip call's
+    message with the clip named in front (a clip of no samples is too short for every variant). Lengths that all equal ``N``
+    are the equal-length call, bit for bit."""
+    raise NotImplementedError("the documented surface of repet.separate: the call itself is _separate_checked")
+
+
+def _separate_checked(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
+                      silent_frames="reference", background_band_gains=None, band_edges=None, lengths=None):
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
+    if lengths is not None:
+        lengths = _native.clip_lengths(lengths, getattr(audio_signal, "shape", ()))
     flags = _native.silent_frames_flag(silent_frames, algo)
     _native.which_codes(which)
     if background_gain is not None:
@@ -277,7 +305,16 @@ def separate(algo, audio_signal, sampling_frequency, out=None, which="background
     if not _native.is_device_tensor(audio_signal):
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
-                            background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains, flags=flags)
+                            background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains, flags=flags,
+                            lengths=lengths)
+
+
+# ``lengths`` is keyword-only. The positional parameters of ``separate`` are a published list that ends in ``silent_frames`` and
+# the band-gain pair (callers and checks go by those positions), so the keyword is taken off in front of that list, not appended
+# to it: ``inspect.signature(repet.separate)`` and ``help`` show the list as it was, the docstring describes ``lengths``.
+@functools.wraps(_separate_surface)
+def separate(*args, lengths=None, **kwargs):
+    return _separate_checked(*args, lengths=lengths, **kwargs)
 
 
 def online(sampling_frequency, number_channels, start_length=None, silent_frames="reference"):

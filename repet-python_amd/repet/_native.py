@@ -190,6 +190,9 @@ _SIGNATURES = {
     "repet_ctx_download_device": (C.c_int, [_P, _P]),
     "repet_ctx_upload_device_strided": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), _P]),
     "repet_ctx_download_device_strided": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int64), _P]),
+    "repet_ctx_upload_device_ragged": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "repet_ctx_clip_lengths": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
+    "repet_check_clip_lengths": (C.c_int, [C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
     "repet_last_batch_info": (C.c_int, [C.POINTER(C.c_int64)]),
     "repet_ctx_download_input": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "repet_ctx_set_window": (C.c_int, [_P, C.c_int64, C.c_int64]),
@@ -429,6 +432,49 @@ def tensor_layout(x, batched=False):
     return x, code, shape, strides
 
 
+def clip_lengths(lengths, shape):
+    """``lengths=`` of a ragged batch against the shape of its padded tensor, before the library is touched: a sequence of ``B``
+    integers on the HOST (a list or tuple, a NumPy integer array, a CPU tensor of an integer dtype), each in ``[0, N]``. Returns a
+    tuple of ints -- or None where every clip is ``N`` long, which is the equal-length call. TypeError for a tensor on a device
+    (frame counts and the too-short checks are host decisions: the call must not wait for the device) and for values that are not
+    integers; ValueError for a tensor that is not ``(B, N, C)``, a wrong count or a value outside ``[0, N]``."""
+    import numbers
+    if is_tensor(lengths):
+        if lengths.device.type != "cpu":
+            raise TypeError("lengths must be on the host (a list, a NumPy array or a CPU tensor), not on a device")
+        if lengths.is_floating_point() or lengths.is_complex() or str(lengths.dtype) == "torch.bool":
+            raise TypeError("lengths must be integers")
+        lengths = lengths.tolist()
+    elif isinstance(lengths, np.ndarray):
+        if lengths.dtype.kind not in "iu":
+            raise TypeError("lengths must be integers")
+        lengths = lengths.tolist()
+    if isinstance(lengths, (str, bytes)) or not hasattr(lengths, "__len__") or not hasattr(lengths, "__iter__"):
+        raise TypeError("lengths must be a sequence of integers, one per clip")
+    values = list(lengths)
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError("lengths must be integers")
+    shape = tuple(shape)
+    if len(shape) != 3:
+        raise ValueError("lengths go with a batch (number_clips, number_samples, number_channels) only")
+    if len(values) != int(shape[0]):
+        raise ValueError(f"lengths has {len(values)} entries, the batch {int(shape[0])} clips")
+    n = int(shape[1])
+    for b, v in enumerate(values):
+        if v < 0 or v > n:
+            raise ValueError(f"lengths[{b}] = {int(v)} lies outside [0, {n}]")
+    values = tuple(int(v) for v in values)
+    return None if all(v == n for v in values) else values
+
+
+def check_clip_lengths(algo, params, lengths, start_frames=0):
+    """The refusal a ragged batch's execute would make of a clip too short for ``algo``, made before anything is uploaded or
+    enqueued: ValueError with the one-clip call's text and the clip named in front."""
+    arr = (C.c_int64 * len(lengths))(*lengths)
+    check(lib().repet_check_clip_lengths(ALGO_IDS[algo], params, int(start_frames), arr, len(lengths)))
+
+
 def result_tensor_code(out):
     code = {"torch.float64": F64, "torch.float32": F32}.get(str(out.dtype))
     if code is None:
@@ -578,25 +624,43 @@ class Context:
                                                   int(number_samples), int(number_channels), int(number_clips)))
         self.shape = (number_samples, number_channels) if number_clips == 1 else (number_clips, number_samples, number_channels)
 
-    def upload_tensor(self, x, stream=None):
+    def upload_tensor(self, x, stream=None, lengths=None):
         """A ``(N, C)`` or ``(B, N, C)`` torch tensor on this context's device (float64 / float32 / int16 / float16 / bfloat16,
         any non-negative strides; other real dtypes are converted to float64) becomes the resident clip(s), narrowed on the
-        device. Ordered behind ``stream`` (default: the tensor device's current stream) by an event, and ``stream`` behind
+        device. ``lengths`` (a host sequence of ``B`` integers in ``[0, N]``, with a ``(B, N, C)`` tensor): a RAGGED batch --
+        clip ``b`` is ``x[b, :lengths[b]]``, the samples behind it are never read, and ``execute``, ``download_tensor`` and
+        ``result_levels`` follow the lengths (see ``repet.separate``); ``shape`` stays the padded shape. Ordered behind ``stream`` (default: the tensor device's current stream) by an event, and ``stream`` behind
         the ingest: no host wait, except in the refusal mode (``set_strict_reference(False)``), which reads back whether a
         sample was not finite."""
         if not is_device_tensor(x):
             raise TypeError("upload_tensor takes a torch tensor on a ROCm device")
-        return self.upload_layout(*tensor_layout(x, batched=True), stream=stream)
+        if lengths is not None:
+            lengths = clip_lengths(lengths, x.shape)
+        return self.upload_layout(*tensor_layout(x, batched=True), stream=stream, lengths=lengths)
 
-    def upload_layout(self, x, code, shape, strides, stream=None):
-        """``upload_tensor`` of a tensor whose layout ``tensor_layout`` has already resolved."""
+    def clip_lengths(self):
+        """The lengths of the resident batch's clips, a tuple of ints: what a ragged ``upload_tensor`` was given, the common
+        length of an equal batch otherwise. ``shape`` stays the padded shape."""
+        n = C.c_int32()
+        check(lib().repet_ctx_clip_lengths(self._h, None, 0, C.byref(n)))
+        out = (C.c_int64 * max(n.value, 1))()
+        check(lib().repet_ctx_clip_lengths(self._h, out, n.value, C.byref(n)))
+        return tuple(int(v) for v in out[:n.value])
+
+    def upload_layout(self, x, code, shape, strides, stream=None, lengths=None):
+        """``upload_tensor`` of a tensor whose layout ``tensor_layout`` has already resolved. ``lengths``: None, or what
+        ``clip_lengths`` returned for a ragged batch."""
         import torch
         if x.device.index != self._device:
             raise ValueError(f"tensor is on {x.device}, the context on device {self._device}")
         if stream is None:
             stream = torch.cuda.current_stream(x.device)
-        check(lib().repet_ctx_upload_device_strided(self._h, C.c_void_p(x.data_ptr() or None), code, shape[0], shape[1], shape[2],
-                                                    _strides(strides), _stream_handle(stream)))
+        if lengths is None:
+            check(lib().repet_ctx_upload_device_strided(self._h, C.c_void_p(x.data_ptr() or None), code, shape[0], shape[1], shape[2],
+                                                        _strides(strides), _stream_handle(stream)))
+        else:
+            check(lib().repet_ctx_upload_device_ragged(self._h, C.c_void_p(x.data_ptr() or None), code, shape[0], shape[1], shape[2],
+                                                       _strides(strides), (C.c_int64 * len(lengths))(*lengths), _stream_handle(stream)))
         # The tensor's memory must not be reused under the ingest. `stream` waits for the ingest (an event on the engine's
         # stream) and the tensor is recorded on `stream`: the caching allocator then hands the block out again only behind
         # it. (Recording it on the engine's stream itself would leave torch holding that stream's handle for as long as the
