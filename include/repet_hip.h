@@ -181,8 +181,9 @@ int repet_ctx_upload(repet_ctx* ctx, const void* audio, int dtype, int64_t n_sam
 /* n_clips equal-shape clips back to back, audio[n_clips][n_samples][n_channels] (a Python loop over
  * repet.simonline(clip, fs), BASELINE.json configs[4]). execute then separates every clip: simonline runs each
  * stage ONCE over all clips (one launch per stage instead of one per clip and stage), the other variants work
- * through the resident clips one after the other. download / download_foreground return
- * [n_clips][n_samples][n_channels]; the integer intermediates are those of the last clip. */
+ * through the resident clips one after the other (repet_ctx_last_clip_passes tells which way a run went). download /
+ * download_foreground return [n_clips][n_samples][n_channels]; the integer intermediates of a variant that works through the
+ * clips are those of the last clip. */
 int repet_ctx_upload_batch(repet_ctx* ctx, const void* audio, int dtype, int64_t n_samples, int32_t n_channels,
                            int32_t n_clips);
 int repet_ctx_execute(repet_ctx* ctx, int algo, const repet_params* p, repet_timing* timing /* nullable */);
@@ -465,6 +466,17 @@ int repet_ctx_last_periods(repet_ctx* ctx, int32_t* out, int32_t capacity, int32
 int repet_ctx_last_sim_indices(repet_ctx* ctx, int32_t* idx_out, int32_t* count_out, int32_t n_rows,
                                int32_t number);
 int repet_ctx_last_frame_count(repet_ctx* ctx, int64_t* n_frames);
+/* The lists of clip `clip` of a batch context whose last run kept every clip's (REPET_SIMONLINE over a batch): n_rows = the
+ * rows of one clip. clip 0 is repet_ctx_last_sim_indices itself, argument for argument (n_rows may also be the rows of all
+ * clips): after a run that worked through the clips one after the other, and after a single clip, it is the only clip
+ * accepted, and the lists are the last clip's. REPET_ERR_BAD_ARG for a clip the lists do not hold. */
+int repet_ctx_last_sim_indices_clip(repet_ctx* ctx, int32_t clip, int32_t* idx_out, int32_t* count_out, int32_t n_rows,
+                                    int32_t number);
+/* How often the last repet_ctx_execute / _async enqueued its variant's pipeline: 1 for a single clip and for a batch that
+ * went through every stage together (REPET_SIMONLINE, REPET_ORIGINAL over equal clips), n_clips for a variant, or a ragged
+ * batch, that works through the clips one after the other. 0 before the first run. Detect the entry point by its symbol; the
+ * ABI version is unchanged. */
+int repet_ctx_last_clip_passes(repet_ctx* ctx, int32_t* passes);
 /* sim: which form of np.median (repet.py:1535) the last run took -- 0 the selection network on the float magnitudes,
  * 1 the packed 16-bit network on the rank codes (rank.hip), 2 the bit-sliced selection on the same codes (mask_bits.hip).
  * All three give the same bits; REPET_MEDIAN=f32|rank forces the first two. */

@@ -117,6 +117,7 @@ struct repet_ctx {
     hipEvent_t aux_start = nullptr, aux_main_done = nullptr, aux_done = nullptr;
     std::function<int()> pre_synthesis;      // run_original calls it (once) right before its inverse STFT
     bool clip_loop = false;       // true while run_algo works through the clips one by one
+    int32_t last_clip_passes = 0; // how often the last execute enqueued its variant's pipeline (repet_ctx_last_clip_passes)
     int32_t n_channels = 0;
     bool strict = true;           // samples that are not finite are let through as repet.py lets them (all five variants); false: REPET_FLAG_REFUSE_NONFINITE
     bool input_not_finite = false;   // the resident clip came from a host array that held such samples

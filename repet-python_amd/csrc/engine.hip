@@ -956,14 +956,16 @@ int run_algo_one(repet_ctx* c, int algo, const repet_params* p) {
 // A RAGGED batch (repet_ctx::clip_len): simonline still runs every stage once over all clips, at the frame count of the pitch,
 // and clears the frames behind each clip's own last one in front of its inverse STFT (exec_simonline); every other variant,
 // `original` included, works through the clips one by one at the clip's own length. The lengths are checked for the variant
-// before anything is enqueued.
+// before anything is enqueued. last_clip_passes counts how often the variant's pipeline is enqueued: 1, or the number of clips.
 int run_algo(repet_ctx* c, int algo, const repet_params* p) {
     c->clip_base = 0;
     c->clip_n = -1;
     if (c->win_total > 0) return fail(REPET_ERR_BAD_ARG, "the resident samples are a window of a longer clip: only repet_ctx_execute_extended_range applies");
     if (c->ragged()) RP_TRY(check_clip_lengths(algo, p, c->online_start, c->clip_len.data(), (int32_t)c->clip_len.size()));
 
+    c->last_clip_passes = 1;
     if (algo == REPET_SIMONLINE || (!c->ragged() && (c->n_clips <= 1 || algo == REPET_ORIGINAL))) return run_algo_one(c, algo, p);
+    c->last_clip_passes = c->n_clips;
     repet_timing* timing = c->timing;
     c->timing = nullptr;                       // per-stage marks would repeat per clip: only the total is reported
     int rc = REPET_OK;
@@ -1101,7 +1103,7 @@ int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_
     DeviceGuard guard(c->device);
     c->result_shaped = false;
     begin_timing(c, timing);
-    c->last_algo = REPET_EXTENDED;
+    c->last_algo = REPET_EXTENDED; c->last_clip_passes = 1;
     c->last_n_periods = 0;
     int rc = exec_extended(c, p, first, n_seg);
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -1122,7 +1124,7 @@ int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, 
     DeviceGuard guard(c->device);
     c->result_shaped = false;
     c->timing = nullptr;
-    c->last_algo = REPET_EXTENDED;
+    c->last_algo = REPET_EXTENDED; c->last_clip_passes = 1;
     c->last_n_periods = 0;
     return exec_extended(c, p, first, n_seg);
 }

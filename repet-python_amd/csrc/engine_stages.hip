@@ -873,6 +873,28 @@ int repet_ctx_last_sim_indices(repet_ctx* c, int32_t* idx_out, int32_t* count_ou
     return REPET_OK;
 }
 
+int repet_ctx_last_sim_indices_clip(repet_ctx* c, int32_t clip, int32_t* idx_out, int32_t* count_out, int32_t n_rows, int32_t number) {
+    if (!c || !idx_out || !count_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    // (clip 0 takes what repet_ctx_last_sim_indices takes: the rows of one clip, or of all clips back to back)
+    const bool all = clip == 0 && n_rows == c->last_idx_rows * c->last_idx_batch;
+    if ((n_rows != c->last_idx_rows && !all) || number != c->last_idx_number) return fail(REPET_ERR_BAD_ARG, "shape does not match the last run");
+    if (clip < 0 || clip >= c->last_idx_batch) return fail(REPET_ERR_BAD_ARG, "the last run kept no lists of that clip");
+    DeviceGuard guard(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));               // (behind a run that was only enqueued)
+    if (n_rows > 0) {
+        HIP_TRY(hipMemcpy2D(idx_out, (size_t)number * sizeof(int32_t), c->idx.as<int32_t>() + (size_t)clip * c->last_idx_rows * c->last_idx_pitch,
+                            (size_t)c->last_idx_pitch * sizeof(int32_t), (size_t)number * sizeof(int32_t), n_rows, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(count_out, c->cnt.as<int32_t>() + (size_t)clip * c->last_idx_rows, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return REPET_OK;
+}
+
+int repet_ctx_last_clip_passes(repet_ctx* c, int32_t* passes) {
+    if (!c || !passes) return fail(REPET_ERR_BAD_ARG, "null argument");
+    *passes = c->last_clip_passes;
+    return REPET_OK;
+}
+
 int repet_ctx_last_median_codes(repet_ctx* c, uint32_t* out, int64_t n_frames, int32_t n_bins) {
     if (!c || !out) return fail(REPET_ERR_BAD_ARG, "null argument");
     if (c->last_median_path != 2 || !c->median_codes.p) return fail(REPET_ERR_BAD_ARG, "the last run did not take the bit-sliced selection");

@@ -249,6 +249,8 @@ _SIGNATURES = {
     "repet_ctx_last_median_path": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "repet_ctx_last_median_codes": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     "repet_ctx_last_sim_indices": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
+    "repet_ctx_last_sim_indices_clip": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
+    "repet_ctx_last_clip_passes": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "repet_ctx_last_frame_count": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "repet_ctx_last_refine_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "repet_ctx_last_exact_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -937,11 +939,24 @@ class Context:
         (buffer_frames). Checked against buffer_frames when a run executes (ValueError for a larger value)."""
         check(lib().repet_ctx_set_online_start(self._h, int(start_frames)))
 
-    def last_sim_indices(self, n_rows, number):
+    def last_sim_indices(self, n_rows, number, clip=0):
+        """The index lists of the last sim / simonline run. ``clip``: of a batch whose run kept every clip's lists (simonline
+        over a batch), that clip's, with ``n_rows`` the rows of one clip; ``clip=0`` also takes the rows of all clips, back to
+        back. After a run that worked through the clips one after the other only ``clip=0`` is accepted, and the lists are the
+        last clip's, as ever."""
         idx = np.empty((max(n_rows, 1), number), dtype=np.int32)
         cnt = np.empty(max(n_rows, 1), dtype=np.int32)
-        check(lib().repet_ctx_last_sim_indices(self._h, ptr(idx), ptr(cnt), n_rows, number))
+        check(lib().repet_ctx_last_sim_indices_clip(self._h, int(clip), ptr(idx), ptr(cnt), n_rows, number))
         return idx[:n_rows], cnt[:n_rows]
+
+    @property
+    def last_clip_passes(self):
+        """How often the last execute enqueued its variant's pipeline: 1 for a single clip and for a batch that went through
+        every stage together (``simonline``, ``original`` over equal clips), the number of clips for a variant, or a ragged
+        batch, that works through the clips one after the other."""
+        v = C.c_int32()
+        check(lib().repet_ctx_last_clip_passes(self._h, C.byref(v)))
+        return v.value
 
 
 _default_ctx = {}
