@@ -1,6 +1,7 @@
 // Shared by the translation units of the host orchestration (engine*.hip): the context, its workspaces, the error plumbing
 // and the helpers one pipeline file calls in another.
-//   engine.hip         contexts, tables, Gram / STFT wrappers, timing, uploads and downloads, the C ABI's core entry points
+//   engine.hip         contexts, tables, Gram / STFT wrappers, the pipelines' inverse STFT (istft_args, enqueue_istft), timing, uploads
+//                      and downloads, the C ABI's core entry points (the four executes are one body: execute)
 //   engine_period.hip  original, extended, adaptive (the period family)
 //   engine_sim.hip     sim, simonline, the peak picking's refinement plumbing
 //   engine_batch.hip   repet_run_batch over several devices, the RCCL transport
@@ -296,14 +297,22 @@ int ensure_spectra(repet_ctx* c, const Geo& g, bool want_vn, bool want_p, int B 
 int run_stft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t offset, int64_t n, int centred, bool vn, bool p,
              int B = 1, int64_t batch_sample_stride = 0, bool p_as_planes = false);
 MaskArgs mask_args(repet_ctx* c, const Geo& g, int cutoff);
+// The inverse STFT of a pipeline (engine.hip, beside mask_args). istft_args: what every pipeline derives from the context --
+// spectra, the mask plane or null, strides, channels, T / FS / W, twiddles, out = c->out, scale; the caller adds what is its own
+// (trim, n_out, out_offset, accumulate_weighted, fades, the residue-class fields of `extended`). istft_clips: the batch fields of
+// `count` independent clips, no cross-fade. istft_rc: the launcher's hipError_t as a return code (its refusal is REPET_ERR_LIMIT).
+// enqueue_istft: the `n_launches` prepared launches of one pipeline, the timing marks scaled by `count` clips or segments of
+// n_out samples and, under band gains, the shaped twins. run_istft: one clip through all of it.
+IstftOlaArgs istft_args(repet_ctx* c, const Geo& g, const Tables* tb);
+void istft_clips(IstftOlaArgs& a, int count, int64_t spec_stride, int64_t out_stride);
+int istft_rc(hipError_t e);
 void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr);
+int enqueue_istft(repet_ctx* c, const Geo& g, const IstftOlaArgs* launches, int n_launches, int count, int64_t n_out);
 int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
               bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr = nullptr);
 // the shaped background of a run under band gains (engine.hip, beside run_istft): the checks and the buffer before anything is
-// enqueued, the twin of an inverse STFT just enqueued, its timing mark, the twin of a clear of `out` (values, not samples)
+// enqueued, the twin of a clear of `out` (values, not samples); the twins of the inverse STFTs are enqueue_istft's
 int begin_shaped(repet_ctx* c, const repet_params* p);
-int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain);
-void mark_shaped(repet_ctx* c, double bytes);
 int clear_shaped(repet_ctx* c, int64_t first_value, int64_t n_values);
 // device-side I/O (devio.hip): argument checks of caller layouts, the context's ordering events and the two waits made of them
 int check_strides(const int64_t* strides);

@@ -412,7 +412,26 @@ MaskArgs mask_args(repet_ctx* c, const Geo& g, int cutoff) {
     return m;
 }
 
-// masked spectrum -> inverse FFT + overlap-add (one fused kernel) -> c->out
+// the inverse-STFT arguments every pipeline derives from the context (mask_args' counterpart); the rest is the caller's
+IstftOlaArgs istft_args(repet_ctx* c, const Geo& g, const Tables* tb) {
+    IstftOlaArgs a{};
+    a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C;
+    a.T = g.T; a.FS = g.FS; a.W = g.W; a.twiddle = tb->twiddle.as<float2>(); a.out = c->out.as<float>(); a.scale = (float)(1.0 / tb->cola);
+    return a;
+}
+
+// a batch of independent clips: clip b reads its spectra at b * spec_stride and writes at out_offset + b * out_stride, no cross-fade
+void istft_clips(IstftOlaArgs& a, int count, int64_t spec_stride, int64_t out_stride) {
+    a.n_batch = count; a.batch_first = 0; a.batch_step = 1; a.batch_total = count; a.batch_local0 = 0;
+    a.batch_spec_stride = spec_stride; a.batch_out_stride = out_stride; a.overlap = 0;
+}
+
+int istft_rc(hipError_t e) {
+    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
+    HIP_TRY(e);
+    return REPET_OK;
+}
+
 // the repeating-segment models of a batch for the inverse STFT (IstftOlaArgs::model)
 void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr) {
     if (!mr) return;
@@ -420,29 +439,12 @@ void apply_model(IstftOlaArgs& a, repet_ctx*, const ModelRef* mr) {
     a.model_batch_stride = mr->batch_stride; a.model_chan_stride = mr->chan_stride; a.cutoff = mr->cutoff;
 }
 
-int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
-              bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr) {
-    IstftOlaArgs a{};
-    a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.W = g.W;
-    a.twiddle = tb->twiddle.as<float2>(); a.trim = trim; a.out = c->out.as<float>(); a.n_out = n_out;
-    a.out_offset = c->clip_base + out_offset; a.scale = (float)(1.0 / tb->cola);
-    a.accumulate_weighted = weighted ? 1 : 0; a.fade_in = fade_in; a.fade_out = fade_out;
-    apply_model(a, c, mr);
-    hipError_t e = launch_istft_ola(a, c->stream);
-    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-    HIP_TRY(e);
-    mark(c, "istft_ola", (mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n_out * g.C, 0);      // (a model: a third of a plane at most)
-    RP_TRY(launch_istft_shaped(c, a));
-    mark_shaped(c, (mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n_out * g.C);
-    return REPET_OK;
-}
-
 // The shaped twin of an inverse STFT the pipeline has just enqueued (repet_ctx::run_shaped; nothing otherwise): the same
 // arguments -- mask plane, model or masked-in-place spectrum, batch, cross-fade, channel groups -- with the table's factor rows
 // beside them, into out_fg instead of out. One row for every frame (G_split beyond any frame). A batch of CLIPS (no
 // cross-fade) takes a row per clip where the table has one; the segments of `extended` and the clips a batch context works
 // through one by one take the row of their clip.
-int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain) {
+static int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain) {
     if (!c->run_shaped) return REPET_OK;
     IstftOlaArgs a = plain;
     const bool clips = a.n_batch > 0 && a.accumulate_weighted == 0;
@@ -452,14 +454,35 @@ int launch_istft_shaped(repet_ctx* c, const IstftOlaArgs& plain) {
     a.G = c->band_tab.as<float>() + row * a.FS;
     a.G_batch_stride = clips && c->band_rows > 1 ? a.FS : 0;
     a.G_split = INT64_MAX;
-    const hipError_t e = launch_istft_ola(a, c->stream);
-    if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-    HIP_TRY(e);
+    return istft_rc(launch_istft_ola(a, c->stream));
+}
+
+static void mark_shaped(repet_ctx* c, double bytes) {
+    if (c->run_shaped) mark(c, "istft_ola_shaped", bytes, 0);
+}
+
+// The inverse STFT of a pipeline: masked spectrum -> inverse FFT + overlap-add (one fused kernel) -> c->out, in `n_launches`
+// prepared launches (one, or one per residue class of `extended`'s cross-fade) over `count` clips or segments of n_out samples.
+// In this order on c->stream, which the timing marks -- events on the stream -- make observable: every plain launch, the
+// "istft_ola" mark, under band gains the shaped twin of every launch, the "istft_ola_shaped" mark.
+int enqueue_istft(repet_ctx* c, const Geo& g, const IstftOlaArgs* launches, int n_launches, int count, int64_t n_out) {
+    for (int i = 0; i < n_launches; ++i) RP_TRY(istft_rc(launch_istft_ola(launches[i], c->stream)));
+    // per cell: the spectrum, and the mask plane or the model (a third of a plane at most) where the launch reads one
+    const bool model = n_launches > 0 && launches[0].model;
+    const double bytes = count * ((model ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n_out * g.C);
+    mark(c, "istft_ola", bytes, 0);
+    for (int i = 0; i < n_launches; ++i) RP_TRY(launch_istft_shaped(c, launches[i]));
+    mark_shaped(c, bytes);
     return REPET_OK;
 }
 
-void mark_shaped(repet_ctx* c, double bytes) {
-    if (c->run_shaped) mark(c, "istft_ola_shaped", bytes, 0);
+int run_istft(repet_ctx* c, const Geo& g, const Tables* tb, int64_t trim, int64_t n_out, int64_t out_offset,
+              bool weighted, int64_t fade_in, int64_t fade_out, const ModelRef* mr) {
+    IstftOlaArgs a = istft_args(c, g, tb);
+    a.trim = trim; a.n_out = n_out; a.out_offset = c->clip_base + out_offset;
+    a.accumulate_weighted = weighted ? 1 : 0; a.fade_in = fade_in; a.fade_out = fade_out;
+    apply_model(a, c, mr);
+    return enqueue_istft(c, g, &a, 1, 1, n_out);
 }
 
 // a clear of `out` the pipeline enqueues (extended), repeated for the shaped background
@@ -982,57 +1005,60 @@ int run_algo(repet_ctx* c, int algo, const repet_params* p) {
     if (rc == REPET_OK) mark(c, "clips", 0, 0);
     return rc;
 }
-}  // namespace repet_eng
-extern "C" {
 
-int repet_ctx_execute(repet_ctx* c, int algo, const repet_params* p, repet_timing* timing) {
+// The four execute entry points. range null: run_algo, under the band table in force (begin_shaped). range = {first, n_seg}:
+// exec_extended over those segments of a single resident clip -- it refuses a set table instead, keeps the last run's index
+// lists (last_idx_rows / last_idx_batch) and is no step of a timing series. blocking: waits for the stream and fills `timing`
+// (nullable); otherwise a full run records its block of the timing series while one is open and has steps left.
+static int execute(repet_ctx* c, int algo, const repet_params* p, const int64_t* range, bool blocking, repet_timing* timing) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     RP_TRY(check_params(p));
     RP_TRY(check_algo_flags(algo, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
-    DeviceGuard guard(c->device);
-    RP_TRY(begin_shaped(c, p));
-    begin_timing(c, timing);
-    c->last_algo = algo;
-    c->last_n_periods = 0;
-    c->last_idx_rows = 0;
-    c->last_idx_batch = 1;
-    int rc = run_algo(c, algo, p);
-    c->result_shaped = rc == REPET_OK && c->run_shaped;
-    c->run_shaped = false;
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == REPET_OK && e != hipSuccess) rc = fail(REPET_ERR_HIP, std::string("execute: ") + hipGetErrorString(e));
-    if (rc == REPET_OK) end_timing(c);
-    c->timing = nullptr;
-    return rc;
-}
-
-int repet_ctx_execute_async(repet_ctx* c, int algo, const repet_params* p) {
-    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
-    RP_TRY(check_params(p));
-    RP_TRY(check_algo_flags(algo, p));
-    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
-    DeviceGuard guard(c->device);
-    RP_TRY(begin_shaped(c, p));
-    c->timing = nullptr;
-    const bool timed = c->series_on && c->series_steps < c->series_cap;
-    if (timed) {
-        c->event_base = c->series_steps * (REPET_MAX_STAGES + 1);
-        begin_timing(c, &c->series_timing);
+    if (range) {
+        if (range[1] < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
+        if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
+        if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
     }
+    DeviceGuard guard(c->device);
+    if (range) c->result_shaped = false;
+    else RP_TRY(begin_shaped(c, p));
+    const bool series = !blocking && !range && c->series_on && c->series_steps < c->series_cap;
+    if (series) c->event_base = c->series_steps * (REPET_MAX_STAGES + 1);
+    begin_timing(c, blocking ? timing : series ? &c->series_timing : nullptr);
     c->last_algo = algo;
     c->last_n_periods = 0;
-    c->last_idx_rows = 0;
-    c->last_idx_batch = 1;
-    const int rc = run_algo(c, algo, p);
-    c->result_shaped = rc == REPET_OK && c->run_shaped;
-    c->run_shaped = false;
-    if (timed && c->timing) {
+    int rc;
+    if (range) {
+        c->last_clip_passes = 1;
+        rc = exec_extended(c, p, range[0], range[1]);
+    } else {
+        c->last_idx_rows = 0;
+        c->last_idx_batch = 1;
+        rc = run_algo(c, algo, p);
+        c->result_shaped = rc == REPET_OK && c->run_shaped;
+        c->run_shaped = false;
+    }
+    if (blocking) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == REPET_OK && e != hipSuccess) rc = fail(REPET_ERR_HIP, std::string("execute: ") + hipGetErrorString(e));
+        if (rc == REPET_OK) end_timing(c);
+    } else if (series && c->timing) {
         c->series_marks = c->n_marks;
         c->series_steps++;
     }
     c->timing = nullptr;
     return rc;
+}
+}  // namespace repet_eng
+extern "C" {
+
+int repet_ctx_execute(repet_ctx* c, int algo, const repet_params* p, repet_timing* timing) {
+    return execute(c, algo, p, nullptr, true, timing);
+}
+
+int repet_ctx_execute_async(repet_ctx* c, int algo, const repet_params* p) {
+    return execute(c, algo, p, nullptr, false, nullptr);
 }
 
 int repet_ctx_timing_series_begin(repet_ctx* c, int32_t n_steps) {
@@ -1093,40 +1119,13 @@ int64_t repet_extended_segment_count(int64_t n_samples, const repet_params* p) {
 
 int repet_ctx_execute_extended_range(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg,
                                      repet_timing* timing) {
-    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
-    RP_TRY(check_params(p));
-    RP_TRY(check_algo_flags(REPET_EXTENDED, p));
-    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
-    if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
-    if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
-    if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
-    DeviceGuard guard(c->device);
-    c->result_shaped = false;
-    begin_timing(c, timing);
-    c->last_algo = REPET_EXTENDED; c->last_clip_passes = 1;
-    c->last_n_periods = 0;
-    int rc = exec_extended(c, p, first, n_seg);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == REPET_OK && e != hipSuccess) rc = fail(REPET_ERR_HIP, std::string("execute: ") + hipGetErrorString(e));
-    if (rc == REPET_OK) end_timing(c);
-    c->timing = nullptr;
-    return rc;
+    const int64_t range[2] = {first, n_seg};
+    return execute(c, REPET_EXTENDED, p, range, true, timing);
 }
 
 int repet_ctx_execute_extended_range_async(repet_ctx* c, const repet_params* p, int64_t first, int64_t n_seg) {
-    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
-    RP_TRY(check_params(p));
-    RP_TRY(check_algo_flags(REPET_EXTENDED, p));
-    if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
-    if (n_seg < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
-    if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
-    if (c->band_any) return fail(REPET_ERR_BAD_ARG, "segment ranges do not take band gains (repet_ctx_set_background_band_gains): clear the table first");
-    DeviceGuard guard(c->device);
-    c->result_shaped = false;
-    c->timing = nullptr;
-    c->last_algo = REPET_EXTENDED; c->last_clip_passes = 1;
-    c->last_n_periods = 0;
-    return exec_extended(c, p, first, n_seg);
+    const int64_t range[2] = {first, n_seg};
+    return execute(c, REPET_EXTENDED, p, range, false, nullptr);
 }
 
 int repet_ctx_download(repet_ctx* c, double* out) {

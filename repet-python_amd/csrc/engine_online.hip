@@ -389,9 +389,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
         a.n_out = n_emit; a.out_offset = 0; a.scale = (float)(1.0 / tb->cola);
         a.n_batch = S; a.batch_first = 0; a.batch_step = 1; a.batch_total = S; a.batch_local0 = 0;
         a.batch_spec_stride = spec; a.batch_out_stride = n_emit; a.overlap = 0;
-        hipError_t e = launch_istft_ola(a, c->stream);
-        if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-        HIP_TRY(e);
+        RP_TRY(istft_rc(launch_istft_ola(a, c->stream)));
         if (o->bands_on) {
             // band gains: the rows of the slots this call inverts, brought up to date where a set (or the call before) left a mark
             const int mode = n_new > 0 ? kBandCommit : kBandCarry;
@@ -418,9 +416,7 @@ int online_process(repet_online* o, int64_t n_new, int64_t n_emit, int slot = -1
             HIP_TRY(o->outs.ensure((size_t)S * n_emit * o->C * sizeof(float)));
             a.out = o->outs.as<float>();
             a.G = o->band_rows(sb); a.G_batch_stride = (int64_t)kBandRows * o->FS; a.G_split = o->hist_valid;
-            e = launch_istft_ola(a, c->stream);
-            if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-            HIP_TRY(e);
+            RP_TRY(istft_rc(launch_istft_ola(a, c->stream)));
             o->em.shaped = true;
         }
     }

@@ -84,29 +84,19 @@ int run_original(repet_ctx* c, const repet_params* p, int64_t offset, int64_t n,
         RP_TRY(run_istft(c, g, tb, g.W - g.H, n, offset, false, 0, 0, mr));
     } else if (!weighted) {
         // independent clips of a batch context: clip b is written at offset + b*hop, no cross-fade
-        IstftOlaArgs a{};
-        a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.W = g.W;
-        a.twiddle = tb->twiddle.as<float2>(); a.trim = g.W - g.H; a.out = c->out.as<float>(); a.n_out = n;
-        a.out_offset = c->clip_base + offset; a.scale = (float)(1.0 / tb->cola); a.accumulate_weighted = 0;
-        a.n_batch = B; a.batch_first = 0; a.batch_step = 1; a.batch_total = B; a.batch_local0 = 0;
-        a.batch_spec_stride = (int64_t)g.C * g.chan_stride; a.batch_out_stride = hop; a.overlap = 0;
+        IstftOlaArgs a = istft_args(c, g, tb);
+        a.trim = g.W - g.H; a.n_out = n; a.out_offset = c->clip_base + offset; a.accumulate_weighted = 0;
+        istft_clips(a, B, (int64_t)g.C * g.chan_stride, hop);
         apply_model(a, c, mr);
-        hipError_t e = launch_istft_ola(a, c->stream);
-        if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-        HIP_TRY(e);
-        mark(c, "istft_ola", B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C), 0);
-        RP_TRY(launch_istft_shaped(c, a));
-        mark_shaped(c, B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C));
+        RP_TRY(enqueue_istft(c, g, &a, 1, B, n));
     } else {
         // segments that overlap in the output must not be accumulated concurrently: one launch per residue
         // class modulo ceil(n / hop) (2 for the default 10 s / 5 s), each class writes disjoint samples
         const int classes = hop > 0 ? (int)ceil_div(n, hop) : 1;
-        std::vector<IstftOlaArgs> twins;                          // (band gains: the same launches again, behind the mark)
+        std::vector<IstftOlaArgs> launches;
         for (int k = 0; k < classes && k < B; ++k) {
-            IstftOlaArgs a{};
-            a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.W = g.W;
-            a.twiddle = tb->twiddle.as<float2>(); a.trim = g.W - g.H; a.out = c->out.as<float>(); a.n_out = n;
-            a.out_offset = c->clip_base; a.scale = (float)(1.0 / tb->cola);
+            IstftOlaArgs a = istft_args(c, g, tb);
+            a.trim = g.W - g.H; a.n_out = n; a.out_offset = c->clip_base;
             // class 0 of the first batch tiles its span of the cleared output exactly when the segment length is a whole
             // number of steps, and nothing has been added there yet: it stores, the other classes add
             a.accumulate_weighted = (k == 0 && c->ola_first_batch && hop > 0 && n == (int64_t)classes * hop) ? 2 : 1;
@@ -115,14 +105,9 @@ int run_original(repet_ctx* c, const repet_params* p, int64_t offset, int64_t n,
             a.batch_out_stride = hop > 0 ? hop : 0; a.overlap = overlap;
             if (hop == 0) a.out_offset = c->clip_base + offset;   // single (last) segment: explicit offset, j = seg_first
             apply_model(a, c, mr);
-            hipError_t e = launch_istft_ola(a, c->stream);
-            if (e == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-            HIP_TRY(e);
-            if (c->run_shaped) twins.push_back(a);
+            launches.push_back(a);
         }
-        mark(c, "istft_ola", B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C), 0);
-        for (const IstftOlaArgs& a : twins) RP_TRY(launch_istft_shaped(c, a));
-        mark_shaped(c, B * ((mr ? 8.0 + 4.0 / 3 : c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * n * g.C));
+        RP_TRY(enqueue_istft(c, g, launches.data(), (int)launches.size(), B, n));
     }
     c->last_T = T;
     return REPET_OK;

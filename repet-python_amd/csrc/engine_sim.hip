@@ -360,18 +360,10 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
     if (nb == 1) {
         RP_TRY(run_istft(c, g, tb, 0, N, 0, false, 0, 0));
     } else {
-        IstftOlaArgs a{};
-        a.Y = c->X.as<float2>(); a.M = c->mask_plane ? c->Mk.as<float>() : nullptr; a.chan_stride = g.chan_stride; a.n_channels = g.C; a.T = g.T; a.FS = g.FS; a.W = g.W;
-        a.twiddle = tb->twiddle.as<float2>(); a.trim = 0; a.out = c->out.as<float>(); a.n_out = N;
-        a.out_offset = 0; a.scale = (float)(1.0 / tb->cola); a.accumulate_weighted = 0;
-        a.n_batch = nb; a.batch_first = 0; a.batch_step = 1; a.batch_total = nb; a.batch_local0 = 0;
-        a.batch_spec_stride = spec_stride; a.batch_out_stride = N; a.overlap = 0;
-        hipError_t e2 = launch_istft_ola(a, c->stream);
-        if (e2 == hipErrorInvalidValue) return fail(REPET_ERR_LIMIT, "too many channels for the fused inverse STFT");
-        HIP_TRY(e2);
-        mark(c, "istft_ola", nb * ((c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * N * g.C), 0);
-        RP_TRY(launch_istft_shaped(c, a));
-        mark_shaped(c, nb * ((c->mask_plane ? 12.0 : 8.0) * g.F * g.T * g.C + 4.0 * N * g.C));
+        IstftOlaArgs a = istft_args(c, g, tb);
+        a.trim = 0; a.n_out = N; a.out_offset = 0; a.accumulate_weighted = 0;
+        istft_clips(a, nb, spec_stride, N);
+        RP_TRY(enqueue_istft(c, g, &a, 1, nb, N));
     }
     c->last_T = T; c->last_idx_rows = rows; c->last_idx_pitch = KP; c->last_idx_number = K;
     c->last_idx_batch = rows >= 1 ? nb : 1;       // rows_alloc == rows then: the clips' lists are contiguous
