@@ -876,6 +876,46 @@ int repet_online_last_band_energies(repet_online* h, int which, const int32_t* e
 int repet_online_last_band_energies_device(repet_online* h, int which, const int32_t* edges, int32_t n_bands,
                                            void* dst, void* signal_stream);
 
+/* (still ABI 4: additions only -- look the symbols up to detect them) The SPECTRA OF A TENSOR CALL: the same three signals, under
+ * the same contract, for the frames of the clip(s) an offline context separates (repet_ctx_execute / _async), without a second
+ * STFT and without a host wait. An offline pipeline forgets its spectra as it goes -- a variant that works through a batch clip
+ * by clip reuses the workspaces for the next clip --, so the request is ARMED on the context before the run and served behind
+ * every pass of it:
+ * repet_ctx_request_frames : arm. `which` as above. edges == NULL (n_bands 0): fp32 frames at `dst` on the context's device,
+ *                   element (b, j, c, f) at dst_strides[0] * b + [1] * j + [2] * c + [3] * f floats (non-negative; the elements
+ *                   must not overlap), for clip b < n_clips, frame j < T, channel c, bin f < F. edges != NULL: the float64 band
+ *                   energies of repet_online_last_band_energies, dense dst[n_clips][T][C][n_bands] (dst_strides is ignored),
+ *                   with the same deterministic reduction. T = repet_result_frame_count(algo, params, n_samples) with n_samples
+ *                   the resident clip length (of a ragged batch: the pitch). The context's stream goes behind what
+ *                   `signal_stream` has enqueued so far (the destination's earlier users); `signal_stream` goes behind the
+ *                   launch that writes the last clip when the run is enqueued. A second request replaces the first.
+ * repet_ctx_clear_requests : drop an armed request. Host only.
+ * An armed request serves exactly the NEXT repet_ctx_execute / _async (or ranged execute) and is then dropped, also when that
+ * execute fails. That execute refuses, with REPET_ERR_BAD_ARG and before it enqueues anything: REPET_EXTENDED and the ranged
+ * executes (the segments overlap and cross-fade: there is no single spectrogram), a context whose resident samples are a window
+ * of a longer clip (repet_ctx_set_window), band edges beyond F of the run's window_length, overlapping destination elements.
+ * The frame grid: REPET_ORIGINAL, REPET_ADAPTIVE, REPET_SIM have T = ceil(n / H) + 1 frames, frame j beginning at sample
+ * j * H - W / 2 (the reference's centred STFT); REPET_SIMONLINE has the online count, frame j beginning at sample j * H, and its
+ * warm-up frames -- j < start_frames - 1 under repet_ctx_set_online_start, else j < buffer_frames - 1 -- have background 0 and
+ * foreground == mixture. Of a ragged batch, clip b's frames at or past its OWN frame count are zero in all three signals,
+ * whatever the padding holds (it is not read). The background is the magnitude of the masked bin as the variant's inverse STFT
+ * fetches it: a pipeline leaves the masked spectrum in place (form 0), as the spectrum and a mask plane (1), or as the spectrum,
+ * the repeating-segment model and the period (2), and the launch forms |X|, |X * mask| or |X * soft_mask(|X|, model)| with the
+ * inverse kernels' own roundings -- in every form equal to the mixture, to the bit, in the high-pass bins. The spectra are the
+ * plain call's: the background gains (scalar or by band) do not change them. Windows of 8192 samples are served (form 0).
+ * A run with nothing armed enqueues exactly what it always did; a served one adds ONE launch per pass -- one for a single clip
+ * and for the batches that go through every stage together, one per clip otherwise (repet_ctx_last_clip_passes) -- and a timing
+ * stage "result_frames" behind the inverse STFT's (the longest stage list -- sim's on rank codes with every kernel marked
+ * (REPET_RANK_OVERLAP=0), segment records by a pass of their own and band gains set -- then holds 13 of REPET_MAX_STAGES entries).
+ * repet_result_frame_count      : T for `algo` and n_samples >= 0; -1 for REPET_EXTENDED, an unknown algo or bad params. Host
+ *                   arithmetic, no device.
+ * repet_ctx_last_spectrum_form  : the form (0, 1, 2) the last pass of the last run left; REPET_ERR_BAD_ARG before the first run. */
+int repet_ctx_request_frames(repet_ctx* ctx, int which, const int32_t* edges /* nullable */, int32_t n_bands, void* dst,
+                             const int64_t dst_strides[4], void* signal_stream);
+int repet_ctx_clear_requests(repet_ctx* ctx);
+int64_t repet_result_frame_count(int algo, const repet_params* params, int64_t n_samples);
+int repet_ctx_last_spectrum_form(repet_ctx* ctx, int32_t* form);
+
 /* (still ABI 4: additions only -- look the symbols up to detect them) The SIMILAR FRAMES the last push matched: for every frame
  * a live handle decides which earlier frames of the stream's buffer it resembles, and the frame's mask is the median over exactly
  * those (repet.py:855-866: the similarity vector of the frame against the buffer, its peaks, the list). For the n_frames frames

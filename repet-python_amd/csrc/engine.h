@@ -119,6 +119,22 @@ struct repet_ctx {
     std::function<int()> pre_synthesis;      // run_original calls it (once) right before its inverse STFT
     bool clip_loop = false;       // true while run_algo works through the clips one by one
     int32_t last_clip_passes = 0; // how often the last execute enqueued its variant's pipeline (repet_ctx_last_clip_passes)
+    // What the pass a pipeline has just enqueued left in the spectra workspaces (record_spectrum, where each exec_* ends: the
+    // scopes forget the form when the pipeline returns): form 0 X masked in place, 1 X and the plane Mk, 2 X, the model Wm
+    // and the period slots; nb clips of T frames each, chan_stride floats between channel planes; warm: the frames before it
+    // carry no background (simonline). form -1: no pass yet.
+    struct SpectrumRecord {
+        int form = -1; const float* model = nullptr; const int32_t* periods = nullptr;
+        int64_t model_batch_stride = 0, model_chan_stride = 0; int32_t cutoff = 0, model_rows = 0;
+        int32_t W = 0, H = 0, F = 0, FS = 0, C = 0, nb = 0, centred = 1; int64_t T = 0, chan_stride = 0, warm = 0;
+    } spectrum;
+    // repet_ctx_request_frames: armed for exactly the next execute, which checks it against its own geometry before it enqueues
+    // anything, serves it behind every pass (run_algo) and drops it, whatever becomes of the run. n_bands 0: whole frames
+    // (fp32, element strides); otherwise band energies (float64, dense). n_frames: the pitch's frame count, set by the execute.
+    struct FramesRequest {
+        bool armed = false; int which = 0; int32_t n_bands = 0; int32_t edges[REPET_MAX_BANDS + 1] = {};
+        void* dst = nullptr; int64_t strides[4] = {0, 0, 0, 0}; void* signal_stream = nullptr; int64_t n_frames = 0;
+    } frames_req;
     int32_t n_channels = 0;
     bool strict = true;           // samples that are not finite are let through as repet.py lets them (all five variants); false: REPET_FLAG_REFUSE_NONFINITE
     bool input_not_finite = false;   // the resident clip came from a host array that held such samples
@@ -267,6 +283,11 @@ int h2d_pitched(repet_ctx* c, float* dst, int64_t dpitch, const float* src, int6
 int d2h_pitched(repet_ctx* c, float* dst, const float* src, int64_t spitch, int64_t rows, int64_t cols);
 int ctx_create(int device, repet_ctx** out, bool probe_side_stream);
 int run_algo_one(repet_ctx* c, int algo, const repet_params* p);
+// the tensor calls' requests (engine.hip, beside run_algo): what a pass left (every exec_* records it where it ends), the frame
+// grid of a variant, and the launch behind a pass whose first clip is clip `clip0` of the destination
+void record_spectrum(repet_ctx* c, const Geo& g, int nb, int64_t warm, int centred, const ModelRef* mr, int model_rows);
+int64_t result_frame_count(int algo, const repet_params* p, int64_t n_samples);
+int serve_requests(repet_ctx* c, int clip0);
 int run_algo(repet_ctx* c, int algo, const repet_params* p);
 int get_tables(repet_ctx* c, int W, Tables** out);
 int upload_twiddle_only(repet_ctx* c, int W, const float2** tw);
@@ -439,6 +460,22 @@ struct FrameArgs {
 };
 hipError_t launch_online_frames(const FrameArgs& a, int32_t n_streams, float* dst, const int64_t strides[4], hipStream_t s);
 hipError_t launch_online_bands(const FrameArgs& a, int32_t n_streams, const int32_t* edges, int32_t n_bands, double* dst, hipStream_t s);
+//   result   (result_frames.hip) the spectra of the pass an offline pipeline has just enqueued, in the form it left them (0 in
+//            place, 1 with the plane Mk, 2 with the model rows and the clips' periods): n_frames rows are written per clip, the
+//            rows below `live` -- the pass's own frame count, further lowered per clip by lengths_dev (nullable: the sample counts
+//            of a ragged batch, turned into frame counts with W, H, centred) -- from the workspaces, the others zero; rows below
+//            `warm` have no background. frames: fp32 at element strides [4] (clip, frame, channel, bin); bands: float64, dense
+//            [n_frames][C][n_bands] per clip, clips clip_stride doubles apart. One launch each, none for n_frames == 0
+struct ResultFrameArgs {
+    const float* V; const float2* X; const float* Mk; const float* model; const int32_t* periods;
+    int64_t chan_stride, spec_stride, model_batch_stride, model_chan_stride;
+    int32_t FS, F, C, which, form, cutoff, model_rows;
+    int64_t n_frames, live, warm;
+    const int64_t* lengths_dev; int32_t W, H, centred;
+};
+hipError_t launch_result_frames(const ResultFrameArgs& a, int32_t n_clips, float* dst, const int64_t strides[4], hipStream_t s);
+hipError_t launch_result_bands(const ResultFrameArgs& a, int32_t n_clips, const int32_t* edges, int32_t n_bands, double* dst,
+                               int64_t clip_stride, hipStream_t s);
 //   matches  (matches.hip) the similar-frame lists of the frames a push completed, read from what its peak picking left: list
 //            row r of slot s at idx + s * idx_stride + r * idx_pitch (cnt likewise), for record frame n_frames - n_active + r;
 //            the entries are window rows, record frame 0 being row `hist`; band: the similarities, LP lags per row, in the

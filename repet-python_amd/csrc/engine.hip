@@ -974,6 +974,90 @@ int run_algo_one(repet_ctx* c, int algo, const repet_params* p) {
     }
 }
 
+// ---- the requests of a tensor call (repet_ctx_request_frames): recorded, checked, served ----
+
+void record_spectrum(repet_ctx* c, const Geo& g, int nb, int64_t warm, int centred, const ModelRef* mr, int model_rows) {
+    repet_ctx::SpectrumRecord& r = c->spectrum;
+    r = repet_ctx::SpectrumRecord{};
+    r.form = mr ? 2 : c->mask_plane ? 1 : 0;
+    if (mr) {
+        r.model = mr->model; r.periods = mr->periods; r.model_batch_stride = mr->batch_stride; r.model_chan_stride = mr->chan_stride;
+        r.cutoff = mr->cutoff; r.model_rows = model_rows;
+    }
+    r.W = g.W; r.H = g.H; r.F = g.F; r.FS = g.FS; r.C = g.C; r.nb = nb; r.centred = centred;
+    r.T = g.T; r.chan_stride = g.chan_stride; r.warm = warm;
+}
+
+// the frame grid of a variant's spectra: simonline frames begin at j * H, the others' at j * H - W / 2 (-1: no single grid)
+int64_t result_frame_count(int algo, const repet_params* p, int64_t n_samples) {
+    if (algo < REPET_ORIGINAL || algo > REPET_SIMONLINE || algo == REPET_EXTENDED || n_samples < 0) return -1;
+    return std::max<int64_t>(repet_frame_count(n_samples, p->window_length, p->step_length, algo == REPET_SIMONLINE ? 0 : 1), 0);
+}
+
+// destination elements that do not overlap (check_no_overlap of devio.hip, over four dimensions)
+static int check_no_overlap4(const int64_t* strides, const int64_t* size) {
+    int order[4] = {0, 1, 2, 3};
+    std::sort(order, order + 4, [&](int a, int b) { return strides[a] < strides[b]; });
+    int64_t span = 0;
+    for (int k : order) {
+        if (size[k] <= 1) continue;
+        if (strides[k] <= span) return fail(REPET_ERR_BAD_ARG, "the destination's elements overlap (an expanded or aliasing view)");
+        span += strides[k] * (size[k] - 1);
+    }
+    return REPET_OK;
+}
+
+// An armed request against the run that is about to serve it, before anything is enqueued. ranged: an execute of a segment range.
+static int check_requests(repet_ctx* c, int algo, const repet_params* p, bool ranged) {
+    repet_ctx::FramesRequest& q = c->frames_req;
+    if (!q.armed) return REPET_OK;
+    if (algo == REPET_EXTENDED || ranged)
+        return fail(REPET_ERR_BAD_ARG, "frames: the segments of `extended` overlap and cross-fade, there is no single spectrogram to hand out");
+    if (c->win_total > 0) return fail(REPET_ERR_BAD_ARG, "frames: the resident samples are a window of a longer clip");
+    const int32_t F = p->window_length / 2 + 1;
+    if (q.n_bands > 0 && q.edges[q.n_bands] > F)
+        return fail(REPET_ERR_BAD_ARG, "frames: band edges are ascending bins in [0, window_length / 2 + 1]");
+    q.n_frames = result_frame_count(algo, p, c->n_samples);
+    if (q.n_frames < 0) return fail(REPET_ERR_BAD_ARG, "unknown algorithm");
+    if (c->n_clips > 65535 || q.n_frames * c->n_channels > 0x7fffffff) return fail(REPET_ERR_LIMIT, "frames: too many clips or frames for one launch");
+    if (q.n_bands == 0) {
+        const int64_t size[4] = {c->n_clips, q.n_frames, c->n_channels, F};
+        RP_TRY(check_no_overlap4(q.strides, size));
+    }
+    return REPET_OK;
+}
+
+// Behind a pass (run_algo): the launch of the armed request, for the rec.nb clips the pass covered, the first of them clip
+// `clip0` of the destination. Nothing armed: nothing enqueued, no mark.
+int serve_requests(repet_ctx* c, int clip0) {
+    const repet_ctx::FramesRequest& q = c->frames_req;
+    if (!q.armed) return REPET_OK;
+    const repet_ctx::SpectrumRecord& r = c->spectrum;
+    if (r.form < 0 || clip0 + r.nb > c->n_clips) return fail(REPET_ERR_BAD_ARG, "internal: the pass left no record of its spectra");
+    ResultFrameArgs a{};
+    a.V = c->V.as<float>(); a.X = c->X.as<float2>(); a.Mk = r.form == 1 ? c->Mk.as<float>() : nullptr;
+    a.model = r.model; a.periods = r.periods; a.model_batch_stride = r.model_batch_stride; a.model_chan_stride = r.model_chan_stride;
+    a.chan_stride = r.chan_stride; a.spec_stride = (int64_t)r.C * r.chan_stride;
+    a.FS = r.FS; a.F = r.F; a.C = r.C; a.which = q.which; a.form = r.form; a.cutoff = r.cutoff; a.model_rows = r.model_rows;
+    a.n_frames = q.n_frames; a.live = r.T; a.warm = r.warm;
+    // a ragged batch in ONE pass (simonline) ran at the pitch's frame count: the clips' own counts come from the device table
+    a.lengths_dev = (c->ragged() && !c->clip_loop) ? c->live_len() : nullptr;
+    a.W = r.W; a.H = r.H; a.centred = r.centred;
+    hipError_t e;
+    if (q.n_bands > 0) {
+        const int64_t clip_stride = q.n_frames * r.C * q.n_bands;
+        e = launch_result_bands(a, r.nb, q.edges, q.n_bands, static_cast<double*>(q.dst) + clip0 * clip_stride, clip_stride, c->stream);
+    } else {
+        e = launch_result_frames(a, r.nb, static_cast<float*>(q.dst) + clip0 * q.strides[0], q.strides, c->stream);
+    }
+    if (e == hipErrorInvalidValue) return fail(REPET_ERR_BAD_ARG, "frames: the pass's spectra do not fit the request");
+    HIP_TRY(e);
+    // per cell: V, and for the other two signals X and a mask value (the model row is a third of a plane at most)
+    const double cell = q.which == REPET_OUT_MIXTURE ? 4.0 : 12.0 + (r.form == 1 ? 4.0 : r.form == 2 ? 4.0 / 3 : 0.0);
+    mark(c, "result_frames", r.nb * (double)r.T * r.C * r.F * (cell + (q.n_bands > 0 ? 0.0 : 4.0)), 0);
+    return REPET_OK;
+}
+
 // A batch context (n_clips > 1): simonline and original run every stage once over all clips; the others work through
 // the resident clips one after the other (their intermediates -- periods, index lists -- are those of the last).
 // A RAGGED batch (repet_ctx::clip_len): simonline still runs every stage once over all clips, at the frame count of the pitch,
@@ -987,7 +1071,10 @@ int run_algo(repet_ctx* c, int algo, const repet_params* p) {
     if (c->ragged()) RP_TRY(check_clip_lengths(algo, p, c->online_start, c->clip_len.data(), (int32_t)c->clip_len.size()));
 
     c->last_clip_passes = 1;
-    if (algo == REPET_SIMONLINE || (!c->ragged() && (c->n_clips <= 1 || algo == REPET_ORIGINAL))) return run_algo_one(c, algo, p);
+    if (algo == REPET_SIMONLINE || (!c->ragged() && (c->n_clips <= 1 || algo == REPET_ORIGINAL))) {
+        RP_TRY(run_algo_one(c, algo, p));
+        return serve_requests(c, 0);
+    }
     c->last_clip_passes = c->n_clips;
     repet_timing* timing = c->timing;
     c->timing = nullptr;                       // per-stage marks would repeat per clip: only the total is reported
@@ -997,6 +1084,8 @@ int run_algo(repet_ctx* c, int algo, const repet_params* p) {
         c->clip_base = (int64_t)b * c->n_samples;
         if (c->ragged()) c->clip_n = c->clip_len[(size_t)b];
         rc = run_algo_one(c, algo, p);
+        // (clip b's spectra are gone when clip b + 1 starts in the same workspaces: its slice is written behind its own pass)
+        if (rc == REPET_OK) rc = serve_requests(c, b);
     }
     c->clip_loop = false;
     c->clip_base = 0;
@@ -1010,11 +1099,21 @@ int run_algo(repet_ctx* c, int algo, const repet_params* p) {
 // exec_extended over those segments of a single resident clip -- it refuses a set table instead, keeps the last run's index
 // lists (last_idx_rows / last_idx_batch) and is no step of a timing series. blocking: waits for the stream and fills `timing`
 // (nullable); otherwise a full run records its block of the timing series while one is open and has steps left.
+static int execute_armed(repet_ctx* c, int algo, const repet_params* p, const int64_t* range, bool blocking, repet_timing* timing);
+
+// An armed request (repet_ctx_request_frames) serves exactly this execute and is dropped with it, also when it fails.
 static int execute(repet_ctx* c, int algo, const repet_params* p, const int64_t* range, bool blocking, repet_timing* timing) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    const int rc = execute_armed(c, algo, p, range, blocking, timing);
+    c->frames_req.armed = false;
+    return rc;
+}
+
+static int execute_armed(repet_ctx* c, int algo, const repet_params* p, const int64_t* range, bool blocking, repet_timing* timing) {
     RP_TRY(check_params(p));
     RP_TRY(check_algo_flags(algo, p));
     if (c->n_channels < 1) return fail(REPET_ERR_BAD_ARG, "no clip uploaded");
+    RP_TRY(check_requests(c, algo, p, range != nullptr));
     if (range) {
         if (range[1] < 0) return fail(REPET_ERR_BAD_ARG, "negative segment count");
         if (c->n_clips > 1 || c->ragged()) return fail(REPET_ERR_BAD_ARG, "segment ranges apply to a single resident clip, not to a batch context");
@@ -1036,6 +1135,8 @@ static int execute(repet_ctx* c, int algo, const repet_params* p, const int64_t*
         c->last_idx_rows = 0;
         c->last_idx_batch = 1;
         rc = run_algo(c, algo, p);
+        // (the destination of a request belongs to the caller's stream again behind the last pass's launch)
+        if (rc == REPET_OK && c->frames_req.armed) rc = signal_caller(c, c->frames_req.signal_stream);
         c->result_shaped = rc == REPET_OK && c->run_shaped;
         c->run_shaped = false;
     }
@@ -1109,6 +1210,60 @@ int repet_ctx_synchronize(repet_ctx* c) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
     DeviceGuard guard(c->device);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return REPET_OK;
+}
+
+int repet_ctx_request_frames(repet_ctx* c, int which, const int32_t* edges, int32_t n_bands, void* dst, const int64_t dst_strides[4],
+                             void* signal_stream) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    if (which < REPET_OUT_BACKGROUND || which > REPET_OUT_MIXTURE)
+        return fail(REPET_ERR_BAD_ARG, "which must be REPET_OUT_BACKGROUND, REPET_OUT_FOREGROUND or REPET_OUT_MIXTURE");
+    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
+    repet_ctx::FramesRequest q{};
+    if (edges) {
+        if (n_bands < 1) return fail(REPET_ERR_BAD_ARG, "frames: at least one band");
+        if (n_bands > REPET_MAX_BANDS) return fail(REPET_ERR_LIMIT, "frames: more than REPET_MAX_BANDS bands");
+        for (int32_t k = 0; k <= n_bands; ++k) {
+            if (edges[k] < 0 || (k > 0 && edges[k] < edges[k - 1]))
+                return fail(REPET_ERR_BAD_ARG, "frames: band edges are ascending bins in [0, window_length / 2 + 1]");
+            q.edges[k] = edges[k];
+        }
+        q.n_bands = n_bands;
+    } else {
+        if (n_bands != 0) return fail(REPET_ERR_BAD_ARG, "frames: bands need their edges");
+        if (!dst_strides) return fail(REPET_ERR_BAD_ARG, "strides is null");
+        for (int k = 0; k < 4; ++k) {
+            if (dst_strides[k] < 0) return fail(REPET_ERR_BAD_ARG, "negative stride (make the tensor contiguous first)");
+            q.strides[k] = dst_strides[k];
+        }
+    }
+    q.which = which; q.dst = dst; q.signal_stream = signal_stream;
+    DeviceGuard guard(c->device);
+    // the destination belongs to the caller's stream: the context's stream, and so every launch that writes it, goes behind
+    // what that stream has enqueued so far
+    RP_TRY(wait_caller(c, signal_stream, signal_stream));
+    q.armed = true;
+    c->frames_req = q;
+    return REPET_OK;
+}
+
+int repet_ctx_clear_requests(repet_ctx* c) {
+    if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
+    c->frames_req.armed = false;
+    return REPET_OK;
+}
+
+int64_t repet_result_frame_count(int algo, const repet_params* p, int64_t n_samples) {
+    if (check_params(p) != REPET_OK) return -1;
+    const int64_t t = result_frame_count(algo, p, n_samples);
+    if (t < 0) (void)fail(REPET_ERR_BAD_ARG, "frames: REPET_ORIGINAL, REPET_ADAPTIVE, REPET_SIM or REPET_SIMONLINE, and a sample count >= 0");
+    return t;
+}
+
+int repet_ctx_last_spectrum_form(repet_ctx* c, int32_t* form) {
+    if (!c || !form) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (c->spectrum.form < 0) return fail(REPET_ERR_BAD_ARG, "no separation has been run on this context");
+    *form = c->spectrum.form;
     return REPET_OK;
 }
 

@@ -109,6 +109,7 @@ int run_original(repet_ctx* c, const repet_params* p, int64_t offset, int64_t n,
         }
         RP_TRY(enqueue_istft(c, g, launches.data(), (int)launches.size(), B, n));
     }
+    record_spectrum(c, g, B, 0, 1, mr, model_rows);          // (before ModelScope and the caller's MaskPlaneScope forget the form)
     c->last_T = T;
     return REPET_OK;
 }
@@ -307,6 +308,7 @@ int exec_adaptive(repet_ctx* c, const repet_params* p) {
     HIP_TRY(launch_mask_adaptive(mask_args(c, g, p->cutoff_bins), c->periods.as<int32_t>(), p->filter_order, c->stream));
     mark(c, "mask_adaptive", (4.0 + 4.0 * p->filter_order + 16.0) * g.F * T * g.C, 0);
     RP_TRY(run_istft(c, g, tb, g.W - g.H, N, 0, false, 0, 0));
+    record_spectrum(c, g, 1, 0, 1, nullptr, 0);
     c->last_T = T;
     c->last_n_periods = (int32_t)T;
     return REPET_OK;

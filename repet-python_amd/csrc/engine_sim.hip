@@ -282,6 +282,7 @@ int exec_sim(repet_ctx* c, const repet_params* p) {
             mark(c, "mask_sim", (4.0 + 4.0 * K + (c->mask_plane ? 4.0 : 16.0)) * g.F * T * g.C, 0);
     }
     RP_TRY(run_istft(c, g, tb, g.W - g.H, N, 0, false, 0, 0));
+    record_spectrum(c, g, 1, 0, 1, nullptr, 0);
     c->last_T = T; c->last_idx_rows = T; c->last_idx_pitch = KP; c->last_idx_number = K;
     return REPET_OK;
 }
@@ -365,6 +366,7 @@ int exec_simonline(repet_ctx* c, const repet_params* p) {
         istft_clips(a, nb, spec_stride, N);
         RP_TRY(enqueue_istft(c, g, &a, 1, nb, N));
     }
+    record_spectrum(c, g, nb, M - 1, 0, nullptr, 0);          // (frames before M - 1 are the warm-up: no background)
     c->last_T = T; c->last_idx_rows = rows; c->last_idx_pitch = KP; c->last_idx_number = K;
     c->last_idx_batch = rows >= 1 ? nb : 1;       // rows_alloc == rows then: the clips' lists are contiguous
     return REPET_OK;

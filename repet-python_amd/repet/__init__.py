@@ -123,14 +123,16 @@ def release_workspaces():
 
 
 def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=False, which="background", background_gain=None,
-                     levels=False, dtype=None, band_gains=None, flags=0, lengths=None):
+                     levels=False, dtype=None, band_gains=None, flags=0, lengths=None, frames=None):
     """A torch tensor on a ROCm device: ingest, run and egress on the tensor's own device, ordered on its current stream by
     events (no host wait; the refusal mode ``strict_reference = False`` waits once, for the non-finite check). ``which``
     selects what the egress writes; "both" is two egress launches behind one run. ``background_gain``: a float that ``separate``
     has checked, or None. ``levels``: also the level record of the result (one reduction launch more, two for a long clip), under
     the same gain. ``band_gains``: ``(edges, g)`` that ``separate`` has checked with ``band_gain_rows``, or None. ``flags``: bits
     ``separate`` adds to this call's ``Params.flags`` (``silent_frames``). ``lengths``: what ``_native.clip_lengths`` made of
-    ``separate``'s, or None; a clip too short for ``algo`` is refused here, before the context is touched."""
+    ``separate``'s, or None; a clip too short for ``algo`` is refused here, before the context is touched. ``frames``: what
+    ``_native.frames_request`` made of ``separate``'s ``frames`` / ``frame_bands`` / ``frames_out``, or None; the spectra are
+    armed on the context in front of the run and returned behind the result (and the levels)."""
     import torch
     names = ("background", "foreground") if which == "both" else (which,)
     _native.which_codes(which)
@@ -161,6 +163,11 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
     try:
         if band_gains is not None:
             ctx.set_background_band_gains(band_gains[1], band_gains[0], window_length=params.window_length)
+        if frames is not None:
+            signal, edges, spectra, spectra_shape = frames
+            if spectra is None:
+                spectra = torch.empty(spectra_shape, dtype=torch.float32 if edges is None else torch.float64, device=x.device)
+            ctx.request_frames(algo, params, signal, spectra, bands=edges, stream=stream)
         ctx.execute_async(algo, params)
         if background_gain is not None:
             ctx.set_background_gain(background_gain)
@@ -172,8 +179,11 @@ def _separate_tensor(algo, audio_signal, sampling_frequency, out=None, batched=F
             ctx.set_background_gain(0.0)
         if band_gains is not None:
             ctx.clear_background_band_gains()
+        if frames is not None:
+            ctx.clear_requests()                  # (dropped by the execute; still armed only where the call failed before it)
     results = results if which == "both" else results[0]
-    return (results, record) if levels else results
+    extras = ((record,) if levels else ()) + ((spectra,) if frames is not None else ())
+    return (results,) + extras if extras else results
 
 
 def _separate(algo, audio_signal, sampling_frequency):
@@ -277,14 +287,39 @@ def _separate_surface(algo, audio_signal, sampling_frequency, out=None, which="b
     wait for it) or not integers; ValueError for a wrong count, a value outside ``[0, N]`` or a 2-D tensor -- all before the
     library is touched --, and, before anything is uploaded or enqueued, for a clip too short for ``algo``: the one-clip call's
     message with the clip named in front (a clip of no samples is too short for every variant). Lengths that all equal ``N``
-    are the equal-length call, bit for bit."""
+    are the equal-length call, bit for bit.
+
+    ``frames`` (keyword only): "mixture", "background" or "foreground" -- also return the SPECTRA the call decided, as a tensor
+    behind the result: the order is ``result[, levels][, frames]``. float32 ``(T, C, F)`` for an ``(N, C)`` input, ``(B, T, C,
+    F)`` for a batch, ``F = window_length / 2 + 1``, ``T = repet.frame_count(algo, N, sampling_frequency)``, on the input's
+    device, ordered as the result is: no second STFT, no host wait, no readback. The contract is the live handles'
+    (``last_frames``): the mixture is the magnitude spectrogram as the forward transform stored it, bit for bit; the background
+    is the magnitude of the masked bin as the variant's inverse STFT fetches it, so it equals the mixture to the bit in the
+    high-pass bins ``1 .. cutoff``; the foreground is mixture - background, 0 where a rounding makes that negative, NaN where
+    either is NaN. "original", "adaptive" and "sim" frame ``j`` begins at sample ``j * H - W / 2``; "simonline" frame ``j`` at
+    ``j * H``, and its warm-up frames (``j < buffer_frames - 1``) have background 0 and foreground = mixture. With ``lengths``,
+    clip ``b``'s frames at or past ``repet.frame_count(algo, lengths[b], ...)`` are zero in all three signals. The gains do not
+    change the spectra. One launch more per pass of the variant's pipeline (one per clip where the clips are worked through
+    one by one); a call without ``frames`` enqueues what it always did.
+    ``frame_bands`` (with ``frames``): ``n_bands + 1`` ascending bin edges in ``[0, F]``, at most 128 bands
+    (``repet.band_edges(fs, 32)`` fits): float64 band energies ``(..., T, C, n_bands)`` instead, each the sum of
+    ``float64(m) ** 2`` over the band's bins, reduced in a fixed order (the same call returns the same bits).
+    ``frames_out`` (with ``frames``): the destination, a float32 tensor of the frames' shape with any non-overlapping strides --
+    float64 and dense for bands -- on the input's device; it is returned in the frames' place.
+    ValueError, before the library is touched, for an unknown ``frames``, ``frame_bands`` or ``frames_out`` without ``frames``,
+    bad edges, a destination of the wrong shape, dtype or device, and ``algo="extended"`` (its segments overlap and cross-fade:
+    there is no single spectrogram)."""
     raise NotImplementedError("the documented surface of repet.separate: the call itself is _separate_checked")
 
 
 def _separate_checked(algo, audio_signal, sampling_frequency, out=None, which="background", background_gain=None, levels=False, dtype=None,
-                      silent_frames="reference", background_band_gains=None, band_edges=None, lengths=None):
+                      silent_frames="reference", background_band_gains=None, band_edges=None, lengths=None, frames=None,
+                      frame_bands=None, frames_out=None):
     if algo not in _native.ALGO_IDS:
         raise ValueError(f"unknown algorithm {algo!r}")
+    if frames is not None or frame_bands is not None or frames_out is not None:
+        frames = _native.frames_request(algo, derive_params(sampling_frequency), frames, frame_bands, frames_out,
+                                        getattr(audio_signal, "shape", ()), getattr(audio_signal, "device", None))
     if lengths is not None:
         lengths = _native.clip_lengths(lengths, getattr(audio_signal, "shape", ()))
     flags = _native.silent_frames_flag(silent_frames, algo)
@@ -306,15 +341,24 @@ def _separate_checked(algo, audio_signal, sampling_frequency, out=None, which="b
         raise TypeError("separate takes a torch tensor on a ROCm device (host arrays: repet.<algo>, repet.run_batch)")
     return _separate_tensor(algo, audio_signal, sampling_frequency, out=out, batched=True, which=which,
                             background_gain=background_gain, levels=bool(levels), dtype=dtype, band_gains=band_gains, flags=flags,
-                            lengths=lengths)
+                            lengths=lengths, frames=frames)
 
 
 # ``lengths`` is keyword-only. The positional parameters of ``separate`` are a published list that ends in ``silent_frames`` and
 # the band-gain pair (callers and checks go by those positions), so the keyword is taken off in front of that list, not appended
 # to it: ``inspect.signature(repet.separate)`` and ``help`` show the list as it was, the docstring describes ``lengths``.
+# ``frames``, ``frame_bands`` and ``frames_out`` are keyword-only in the same way.
 @functools.wraps(_separate_surface)
-def separate(*args, lengths=None, **kwargs):
-    return _separate_checked(*args, lengths=lengths, **kwargs)
+def separate(*args, lengths=None, frames=None, frame_bands=None, frames_out=None, **kwargs):
+    return _separate_checked(*args, lengths=lengths, frames=frames, frame_bands=frame_bands, frames_out=frames_out, **kwargs)
+
+
+def frame_count(algo, number_samples, sampling_frequency):
+    """Frames ``T`` of the spectra ``separate(..., frames=...)`` returns for clips of ``number_samples`` samples at
+    ``sampling_frequency``: ``ceil(N / H) + 1`` for "original", "adaptive" and "sim" (the reference's centred STFT, frame ``j``
+    begins at sample ``j * H - W / 2``), the online count for "simonline" (frame ``j`` begins at ``j * H``). Host arithmetic: no
+    device is needed. ValueError for "extended", which has no single frame grid."""
+    return _native.result_frame_count(algo, derive_params(sampling_frequency), number_samples)
 
 
 def online(sampling_frequency, number_channels, start_length=None, silent_frames="reference"):

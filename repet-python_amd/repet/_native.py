@@ -316,6 +316,10 @@ _SIGNATURES = {
     "repet_online_clear_feed": (C.c_int, [_P, _P, C.c_int32]),
     "repet_online_tick": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
     "repet_online_tick_device": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "repet_ctx_request_frames": (C.c_int, [_P, C.c_int, _P, C.c_int32, _P, _P, _P]),
+    "repet_ctx_clear_requests": (C.c_int, [_P]),
+    "repet_result_frame_count": (C.c_int64, [C.c_int, C.POINTER(Params), C.c_int64]),
+    "repet_ctx_last_spectrum_form": (C.c_int, [_P, C.POINTER(C.c_int32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -847,13 +851,23 @@ class Context:
         check(lib().repet_ctx_result_wav(self._h, code, F64 if item == 8 else F32, ptr(image), image.size, C.byref(written)))
         image[:written.value].tofile(audio_file)
 
+    def _serves(self, algo, params):
+        """An armed request was sized for one run: any other run refuses it (and drops it) before the library is called."""
+        armed, self._armed = getattr(self, "_armed", None), None
+        if armed is not None and armed != (ALGO_IDS[algo] if isinstance(algo, str) else algo, params.window_length,
+                                           params.step_length, tuple(self.shape)):
+            self.clear_requests()
+            raise ValueError("the frames were requested for another algorithm, window or resident clip than this run's")
+
     def execute(self, algo, params, timing=False):
+        self._serves(algo, params)
         t = Timing() if timing else None
         check(lib().repet_ctx_execute(self._h, ALGO_IDS[algo] if isinstance(algo, str) else algo,
                                       C.byref(params), C.byref(t) if timing else None))
         return t.as_dict() if timing else None
 
     def execute_async(self, algo, params):
+        self._serves(algo, params)
         check(lib().repet_ctx_execute_async(self._h, ALGO_IDS[algo] if isinstance(algo, str) else algo, C.byref(params)))
 
     def synchronize(self):
@@ -956,6 +970,43 @@ class Context:
         batch, that works through the clips one after the other."""
         v = C.c_int32()
         check(lib().repet_ctx_last_clip_passes(self._h, C.byref(v)))
+        return v.value
+
+    def request_frames(self, algo, params, which, out, bands=None, stream=None):
+        """Arm a request for the spectra of the NEXT ``execute`` / ``execute_async``, which must be the one of ``algo`` and
+        ``params`` on the clip(s) resident now (repet_ctx_request_frames): ``which`` ("mixture", "background", "foreground") of
+        every frame into ``out``, a tensor on this context's device -- float32 ``(T, C, F)`` or ``(B, T, C, F)`` with any
+        non-overlapping strides, or with ``bands`` (``n_bands + 1`` bin edges) dense float64 ``(..., T, C, n_bands)`` --,
+        ``T = result_frame_count(algo, params, N)``. Served behind every pass of that run on the engine's stream,
+        which goes behind ``stream`` (default: the device's current one) now; ``stream`` goes behind the last launch when the
+        run is enqueued. The request is dropped with that execute, also when it fails; ``clear_requests`` drops it before.
+        ValueError for whatever ``repet.separate`` refuses of its ``frames`` keywords, and from a run other than the one named."""
+        import torch
+        if self.shape is None:
+            raise ValueError("no clip uploaded")
+        _, edges, _, _ = frames_request(algo if isinstance(algo, str) else {v: k for k, v in ALGO_IDS.items()}.get(algo), params, which,
+                                        bands, out, self.shape, torch.device("cuda", self._device))
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        strides = tuple(int(st) for st in out.stride())
+        strides = (0,) * (4 - len(strides)) + strides
+        check(lib().repet_ctx_request_frames(self._h, WHICH_CODES[which], None if edges is None else ptr(edges),
+                                             0 if edges is None else edges.size - 1, C.c_void_p(out.data_ptr() or None),
+                                             (C.c_int64 * 4)(*strides), _stream_handle(stream)))
+        self._armed = (ALGO_IDS[algo] if isinstance(algo, str) else algo, params.window_length, params.step_length, tuple(self.shape))
+        return out
+
+    def clear_requests(self):
+        """Drop an armed request (host only)."""
+        self._armed = None
+        check(lib().repet_ctx_clear_requests(self._h))
+
+    @property
+    def last_spectrum_form(self):
+        """How the last pass of the last run left its masked spectrum: 0 masked in place, 1 the spectrum and a mask plane,
+        2 the spectrum, the repeating-segment model and the period (the inverse STFT forms the mask as it fetches)."""
+        v = C.c_int32()
+        check(lib().repet_ctx_last_spectrum_form(self._h, C.byref(v)))
         return v.value
 
 
@@ -1172,6 +1223,61 @@ def band_edge_array(bands):
     except (TypeError, ValueError):
         raise ValueError("bands is a sequence of n_bands + 1 integer bin edges") from None
     return np.ascontiguousarray(wide.astype(np.int32))
+
+
+MAX_BANDS = 128                # REPET_MAX_BANDS
+FRAME_SIGNALS = ("mixture", "background", "foreground")
+
+
+def result_frame_count(algo, params, number_samples):
+    """Frames of the spectra a tensor call of ``algo`` hands out for clips of ``number_samples`` samples
+    (repet_result_frame_count): host arithmetic, no device. ValueError for "extended" (no single frame grid)."""
+    if algo not in ALGO_IDS:
+        raise ValueError(f"unknown algorithm {algo!r}")
+    t = lib().repet_result_frame_count(ALGO_IDS[algo], params, int(number_samples))
+    if t < 0:
+        raise ValueError(lib().repet_last_error().decode(errors="replace"))
+    return int(t)
+
+
+def frames_request(algo, params, frames, frame_bands, frames_out, shape, device):
+    """``frames=`` / ``frame_bands=`` / ``frames_out=`` of ``repet.separate`` for an input of ``shape`` on ``device``, checked on
+    the host alone: None when nothing is asked, else ``(frames, edges or None, frames_out or None, result shape)``. ValueError for
+    everything the call refuses."""
+    if frames is None:
+        if frame_bands is not None or frames_out is not None:
+            raise ValueError("frame_bands and frames_out go with frames")
+        return None
+    if not isinstance(frames, str) or frames not in FRAME_SIGNALS:
+        raise ValueError(f'frames is "mixture", "background" or "foreground", not {frames!r}')
+    if algo == "extended":
+        raise ValueError('frames: the segments of "extended" overlap and cross-fade, there is no single spectrogram to hand out')
+    bins = params.window_length // 2 + 1
+    edges = None
+    if frame_bands is not None:
+        edges = band_edge_array(frame_bands)
+        if edges.size - 1 > MAX_BANDS:
+            raise ValueError(f"frame_bands: at most {MAX_BANDS} bands")
+        if edges[0] < 0 or edges[-1] > bins or (np.diff(edges.astype(np.int64)) < 0).any():
+            raise ValueError(f"frame_bands: band edges are ascending bins in [0, {bins}]")
+    shape = tuple(int(d) for d in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("audio_signal must be (number_samples, number_channels) or a batch of such clips")
+    count = result_frame_count(algo, params, shape[-2])
+    result_shape = shape[:-2] + (count, shape[-1], bins if edges is None else edges.size - 1)
+    if frames_out is not None:
+        name = "torch.float32" if edges is None else "torch.float64"
+        if not is_tensor(frames_out):
+            raise ValueError(f"frames_out must be a {name} tensor on the input's device")
+        if frames_out.device != device:
+            raise ValueError(f"frames_out must be a tensor on {device}")
+        if str(frames_out.dtype) != name:
+            raise ValueError(f"the frames are {name}, frames_out is {frames_out.dtype}")
+        if tuple(frames_out.shape) != result_shape:
+            raise ValueError(f"frames_out has shape {tuple(frames_out.shape)}, the frames {result_shape}")
+        if edges is not None and not frames_out.is_contiguous():
+            raise ValueError("frames_out must be dense (contiguous) for band energies")
+    return frames, edges, frames_out, result_shape
 
 
 def _ask_frames(handle, code, edges):
