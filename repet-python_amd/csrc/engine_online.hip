@@ -19,8 +19,9 @@ using namespace repet_eng;
 // A slot may also sit out pushes (repet_online_hold_streams): held, it reads as idle on the device while its share of the buffers
 // stays where it is (launch_slide_held) and its first frame moves along with the handle on the host.
 // Every emitting call (push, tick, finish, finish_stream) has one body, online_*_impl; its host and device entry points differ in
-// the Sink they build. The waits on the caller's streams are the context's (engine.h: wait_caller / signal_caller), the pinned
-// round trips of the host forms online_download / online_upload.
+// the Sink they build; every read-back call (last_*, export, import) likewise, online_read_*_impl behind a Reader. The waits on the
+// caller's streams are the context's (engine.h: wait_caller / signal_caller), the pinned round trips of the host forms
+// online_download / online_upload.
 // =====================================================================================================
 struct repet_online {
     repet_ctx* ctx = nullptr;       // stream, tables, tile cache, scratch buffers
@@ -95,12 +96,12 @@ struct repet_online {
     // until the next fade, so last_emission replays a fade from the tables that made it, whatever was set since. Until the first
     // set (gains_on) no kernel is given a table.
     // Levels (repet_online_last_levels*): computed on demand from what `em` describes, so a handle that is never asked runs
-    // nothing for them. `levels` holds the record on its way to the host ([S][C][8] float64) and behind it the record of a
-    // finish_stream tail ([C][8]): that call drops its slot's samples, so it measures the tail itself -- on a handle that has
-    // been asked for levels before (levels_on) -- and tail_valid says the kept record is the last emission's.
+    // nothing for them. `levels` holds the record of a finish_stream tail ([C][8] float64): that call drops its slot's samples, so
+    // it measures the tail itself -- on a handle that has been asked for levels before (levels_on) -- and tail_valid says the kept
+    // record is the last emission's.
     DevBuf levels;
     bool levels_on = false, tail_valid = false;
-    double* tail_levels() const { return levels.as<double>() + (int64_t)S * C * REPET_LEVEL_FIELDS; }
+    double* tail_levels() const { return levels.as<double>(); }
     // Frames (repet_online_last_frames* / last_band_energies*): where the spectra of the frames the last push or finish completed
     // lie. After the push's slide flipped `cur` they are rows [row0, row0 + n) of every slot's planes of X[win] / V[win], the
     // window that was current DURING the push; the first of them is handle frame `first`. Nothing writes that window before
@@ -569,17 +570,12 @@ static int online_levels(repet_online* o, double* dst) {
     return REPET_OK;
 }
 
-static int online_ensure_levels(repet_online* o) {
-    HIP_TRY(o->levels.ensure((size_t)(o->S + 1) * o->C * REPET_LEVEL_FIELDS * sizeof(double)));
-    return REPET_OK;
-}
-
 // finish_stream is about to drop its slot's samples: on a handle that has been asked for levels, the tail is measured now.
 // (A tail the pending buffer no longer holds is not measured: last_levels then refuses as last_emission does.)
 static int online_keep_tail_levels(repet_online* o, bool* kept) {
     *kept = false;
     if (!o->levels_on || !o->em.valid || o->em.off + o->em.n > o->pend_cap) return REPET_OK;
-    RP_TRY(online_ensure_levels(o));
+    HIP_TRY(o->levels.ensure((size_t)o->C * REPET_LEVEL_FIELDS * sizeof(double)));
     RP_TRY(online_levels(o, o->tail_levels()));
     *kept = true;
     return REPET_OK;
@@ -695,6 +691,49 @@ static int sink_begin(repet_online* o, const Sink& k, void* wait_stream) {
 static int sink_deliver(repet_online* o, const Sink& k, int64_t n_emit, int streams = 0) {
     if (k.device) return online_device_result(o, n_emit, k.dst, k.dtype, k.strides, k.signal_stream, streams);
     return online_host_result(o, n_emit, k.out, streams);
+}
+
+// The Sink's counterpart for the read-back calls (last_emission, last_levels, last_frames, last_band_energies, last_matches, export,
+// import): where a record goes, which again is all that tells the host form from the device form. `n` host arrays of `capacity`
+// elements (or rows) each, or `n` device pointers that `stream`, the caller's, goes on to use. An import reads part[0] instead.
+struct Reader {
+    bool device = false;
+    int n = 1;
+    void* part[3] = {nullptr, nullptr, nullptr};
+    int64_t capacity = 0;
+    void* stream = nullptr;
+};
+
+static Reader host_reader(void* out, int64_t capacity) { return Reader{false, 1, {out}, capacity, nullptr}; }
+static Reader device_reader(void* dst, void* stream) { return Reader{true, 1, {dst}, 0, stream}; }
+
+// before any launch: every part is there, and a host array holds `count` elements
+static int read_check(const Reader& r, int64_t count) {
+    bool bad = !r.device && r.capacity < count;
+    for (int k = 0; k < r.n; ++k) bad = bad || !r.part[k];
+    return bad ? fail(REPET_ERR_BAD_ARG, r.device ? "null destination" : "online: output capacity too small") : REPET_OK;
+}
+
+// Before the launch: the engine's stream behind what the caller's has enqueued so far (earlier users of the destination), and where
+// the launch writes its parts of bytes[k]: the caller's memory, or one block of the handle's that read_deliver takes apart.
+static int read_begin(repet_online* o, const Reader& r, const size_t* bytes, void** at) {
+    size_t total = 0, off = 0;
+    for (int k = 0; k < r.n; ++k) total += bytes[k];
+    if (r.device) RP_TRY(wait_caller(o->ctx, r.stream, r.stream));
+    else HIP_TRY(o->out64.ensure(total));
+    for (int k = 0; k < r.n; off += bytes[k++]) at[k] = r.device ? r.part[k] : o->out64.as<char>() + off;
+    return REPET_OK;
+}
+
+// Behind the launch: the caller's stream, or one pinned round trip of the block (the handle's own unless `from` names another) and
+// the host arrays out of it.
+static int read_deliver(repet_online* o, const Reader& r, const size_t* bytes, const void* from = nullptr) {
+    if (r.device) return signal_caller(o->ctx, r.stream);
+    size_t total = 0, off = 0;
+    for (int k = 0; k < r.n; ++k) total += bytes[k];
+    RP_TRY(online_download(o, from ? from : o->out64.p, total));
+    for (int k = 0; k < r.n; off += bytes[k++]) std::memcpy(r.part[k], static_cast<char*>(o->host_out) + off, bytes[k]);
+    return REPET_OK;
 }
 
 // a launch has just written the slot's table entry (restart, release, import): nobody holds it any more, and its inbox is empty
@@ -1222,88 +1261,82 @@ int repet_online_also_emit(repet_online* o, int which, void* dst, int dtype, con
     return REPET_OK;
 }
 
-int repet_online_last_emission(repet_online* o, int which, double* out, int64_t capacity, int64_t* n_written) {
+static const char* const kStaleLevels = "online: the last emission is stale (a push, finish, restart or release came after it)";
+
+// ---- the read-back calls: one body each for the host and the device form (the public entry points build the Reader) -------------
+// Every refusal comes before the first launch and before the DeviceGuard, per form in the order and with the words its callers have
+// always seen; so does what each exit leaves in *n_written / *n_rows. A device form without such a counter passes a local.
+
+// The host form is float64 and dense (dst_strides null); a device destination lies at dst_strides, with stride 0 for the stream axis
+// of a finish_stream tail. The device form waits and signals even for an empty emission, the host form does no device work for one.
+static int online_read_emission_impl(repet_online* o, int which, const Reader& r, int dtype, const int64_t* dst_strides, int64_t* n_written) {
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     RP_TRY(check_which(which));
-    if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, "online: the last emission is stale (a push, finish, restart or release came after it)");
+    if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, kStaleLevels);
     const int64_t n = o->em.n, count = (int64_t)o->em.S * n * o->C;
-    if (n > capacity || (count > 0 && !out)) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    if (count > 0) {
-        HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
-        EmitDst d;
-        d.p = o->out64.p; d.which = which; d.strides[0] = n * o->C; d.strides[1] = o->C; d.strides[2] = 1;
-        RP_TRY(online_emit(o, &d, 1, REPET_F64));
-        RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(double)));
-        std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    EmitDst d;
+    d.which = which; d.strides[0] = n * o->C; d.strides[1] = o->C; d.strides[2] = 1;
+    if (r.device) {
+        RP_TRY(check_emit_dtype(dtype));
+        RP_TRY(check_strides(dst_strides));
+        for (int k = 0; k < 3; ++k) d.strides[k] = k == 0 && o->em.slot >= 0 ? 0 : dst_strides[k];
+        RP_TRY(check_no_overlap(d.strides, o->em.S, n, o->C));
+        if (count > 0) RP_TRY(read_check(r, count));
+    } else if (n > r.capacity || (count > 0 && !r.part[0])) {
+        return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    }
+    DeviceGuard guard(o->ctx->device);
+    if (r.device || count > 0) {
+        const size_t bytes = (size_t)count * sizeof(double);
+        RP_TRY(read_begin(o, r, &bytes, &d.p));
+        RP_TRY(online_emit(o, &d, 1, dtype));
+        RP_TRY(read_deliver(o, r, &bytes));
     }
     *n_written = n;
     return REPET_OK;
 }
 
-int repet_online_last_emission_device(repet_online* o, int which, void* dst, int dst_dtype, const int64_t dst_strides[3],
-                                      void* signal_stream, int64_t* n_written) {
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    RP_TRY(check_which(which));
-    if (!o->em.valid) return fail(REPET_ERR_BAD_ARG, "online: the last emission is stale (a push, finish, restart or release came after it)");
-    RP_TRY(check_emit_dtype(dst_dtype));
-    RP_TRY(check_strides(dst_strides));
-    const int64_t strides[3] = {o->em.slot < 0 ? dst_strides[0] : 0, dst_strides[1], dst_strides[2]};
-    RP_TRY(check_no_overlap(strides, o->em.S, o->em.n, o->C));
-    if ((int64_t)o->em.S * o->em.n * o->C > 0 && !dst) return fail(REPET_ERR_BAD_ARG, "null destination");
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    EmitDst d;
-    d.p = dst; d.which = which;
-    for (int k = 0; k < 3; ++k) d.strides[k] = strides[k];
-    RP_TRY(online_emit(o, &d, 1, dst_dtype));
-    RP_TRY(signal_caller(c, signal_stream));
-    *n_written = o->em.n;
-    return REPET_OK;
+int repet_online_last_emission(repet_online* o, int which, double* out, int64_t capacity, int64_t* n_written) {
+    return online_read_emission_impl(o, which, host_reader(out, capacity), REPET_F64, nullptr, n_written);
 }
 
-static const char* const kStaleLevels = "online: the last emission is stale (a push, finish, restart or release came after it)";
+int repet_online_last_emission_device(repet_online* o, int which, void* dst, int dst_dtype, const int64_t dst_strides[3],
+                                      void* signal_stream, int64_t* n_written) {
+    return online_read_emission_impl(o, which, device_reader(dst, signal_stream), dst_dtype, dst_strides, n_written);
+}
 
-int repet_online_last_levels(repet_online* o, double* out, int64_t capacity_doubles, int64_t* n_written) {
+// float64 [S][C][REPET_LEVEL_FIELDS], dense in either form. A finish_stream tail's record was kept when the call was made and is
+// not reduced again: the host form downloads it where it lies, the device form copies it.
+static int online_read_levels_impl(repet_online* o, const Reader& r, int64_t* n_written) {
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     o->levels_on = true;
     if (!o->em.valid && !o->tail_valid) return fail(REPET_ERR_BAD_ARG, kStaleLevels);
     const int64_t count = (int64_t)(o->tail_valid ? 1 : o->em.S) * o->C * REPET_LEVEL_FIELDS;
-    *n_written = count;
-    if (!out || capacity_doubles < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    *n_written = count;                                         // (a short or null host array is told the count it needs)
+    RP_TRY(read_check(r, count));
     *n_written = 0;
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_ensure_levels(o));
-    const double* record = o->tail_levels();
-    if (!o->tail_valid) {
-        RP_TRY(online_levels(o, o->levels.as<double>()));
-        record = o->levels.as<double>();
-    }
-    RP_TRY(online_download(o, record, (size_t)count * sizeof(double)));
-    std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
+    DeviceGuard guard(o->ctx->device);
+    const size_t bytes = (size_t)count * sizeof(double);
+    void* at = nullptr;
+    RP_TRY(read_begin(o, r, &bytes, &at));
+    if (!o->tail_valid)
+        RP_TRY(online_levels(o, static_cast<double*>(at)));
+    else if (r.device)
+        HIP_TRY(hipMemcpyAsync(at, o->tail_levels(), bytes, hipMemcpyDeviceToDevice, o->ctx->stream));
+    RP_TRY(read_deliver(o, r, &bytes, o->tail_valid ? o->tail_levels() : nullptr));
     *n_written = count;
     return REPET_OK;
 }
 
+int repet_online_last_levels(repet_online* o, double* out, int64_t capacity_doubles, int64_t* n_written) {
+    return online_read_levels_impl(o, host_reader(out, capacity_doubles), n_written);
+}
+
 int repet_online_last_levels_device(repet_online* o, void* dst, void* signal_stream) {
-    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
-    o->levels_on = true;
-    if (!o->em.valid && !o->tail_valid) return fail(REPET_ERR_BAD_ARG, kStaleLevels);
-    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    if (o->tail_valid)
-        HIP_TRY(hipMemcpyAsync(dst, o->tail_levels(), (size_t)o->C * REPET_LEVEL_FIELDS * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    else
-        RP_TRY(online_levels(o, static_cast<double*>(dst)));
-    return signal_caller(c, signal_stream);
+    int64_t n = 0;
+    return online_read_levels_impl(o, device_reader(dst, signal_stream), &n);
 }
 
 static const char* const kStaleFrames =
@@ -1361,85 +1394,58 @@ int repet_online_last_frame_range(repet_online* o, int64_t* first_frame, int64_t
     return REPET_OK;
 }
 
-int repet_online_last_frames(repet_online* o, int which, float* out, int64_t capacity_floats, int64_t* n_written) {
+// The frames (bands false: float32 [S][n][C][F], at dst_strides on the device and dense on the host) or their band energies
+// (float64 [S][n][C][n_bands], dense in either form). An empty record is OK with nothing enqueued: the host form says so before it
+// looks at its array, the device form after it has checked its destination.
+static int online_read_frames_impl(repet_online* o, int which, bool bands, const int32_t* edges, int32_t n_bands, const Reader& r,
+                                   const int64_t* dst_strides, int64_t* n_written) {
     if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_written = 0;
     RP_TRY(check_which(which));
+    if (bands) RP_TRY(check_band_edges(o, edges, n_bands));
     if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
-    const int64_t count = (int64_t)o->S * o->fr.n * o->C * o->F;
+    const int64_t size[4] = {o->S, o->fr.n, o->C, bands ? n_bands : o->F};
+    const int64_t dense[4] = {size[1] * size[2] * size[3], size[2] * size[3], size[3], 1}, count = size[0] * dense[0];
+    if (r.device || count > 0) {
+        *n_written = count;                                     // (a short or null host array is told the count it needs)
+        if (r.device && !bands) RP_TRY(check_frame_strides(dst_strides, size));
+        RP_TRY(read_check(r, count));
+        *n_written = 0;
+    }
     if (count == 0) return REPET_OK;
-    *n_written = count;
-    if (!out || capacity_floats < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    *n_written = 0;
     FrameArgs a;
     RP_TRY(online_frame_args(o, which, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    HIP_TRY(o->out64.ensure((size_t)count * sizeof(float)));
-    const int64_t dense[4] = {o->fr.n * o->C * o->F, (int64_t)o->C * o->F, o->F, 1};
-    HIP_TRY(launch_online_frames(a, o->S, o->out64.as<float>(), dense, c->stream));
-    RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(float)));
-    std::memcpy(out, o->host_out, (size_t)count * sizeof(float));
+    DeviceGuard guard(o->ctx->device);
+    const size_t bytes = (size_t)count * (bands ? sizeof(double) : sizeof(float));
+    void* at = nullptr;
+    RP_TRY(read_begin(o, r, &bytes, &at));
+    if (bands)
+        HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, static_cast<double*>(at), o->ctx->stream));
+    else
+        HIP_TRY(launch_online_frames(a, o->S, static_cast<float*>(at), r.device ? dst_strides : dense, o->ctx->stream));
+    RP_TRY(read_deliver(o, r, &bytes));
     *n_written = count;
     return REPET_OK;
 }
 
+int repet_online_last_frames(repet_online* o, int which, float* out, int64_t capacity_floats, int64_t* n_written) {
+    return online_read_frames_impl(o, which, false, nullptr, 0, host_reader(out, capacity_floats), nullptr, n_written);
+}
+
 int repet_online_last_frames_device(repet_online* o, int which, void* dst, const int64_t dst_strides[4], void* signal_stream) {
-    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
-    RP_TRY(check_which(which));
-    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
-    const int64_t size[4] = {o->S, o->fr.n, o->C, o->F};
-    RP_TRY(check_frame_strides(dst_strides, size));
-    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
-    if (o->fr.n <= 0) return REPET_OK;
-    FrameArgs a;
-    RP_TRY(online_frame_args(o, which, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    HIP_TRY(launch_online_frames(a, o->S, static_cast<float*>(dst), dst_strides, c->stream));
-    return signal_caller(c, signal_stream);
+    int64_t n = 0;
+    return online_read_frames_impl(o, which, false, nullptr, 0, device_reader(dst, signal_stream), dst_strides, &n);
 }
 
 int repet_online_last_band_energies(repet_online* o, int which, const int32_t* edges, int32_t n_bands, double* out,
                                     int64_t capacity_doubles, int64_t* n_written) {
-    if (!o || !n_written) return fail(REPET_ERR_BAD_ARG, "null argument");
-    *n_written = 0;
-    RP_TRY(check_which(which));
-    RP_TRY(check_band_edges(o, edges, n_bands));
-    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
-    const int64_t count = (int64_t)o->S * o->fr.n * o->C * n_bands;
-    if (count == 0) return REPET_OK;
-    *n_written = count;
-    if (!out || capacity_doubles < count) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
-    *n_written = 0;
-    FrameArgs a;
-    RP_TRY(online_frame_args(o, which, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    HIP_TRY(o->out64.ensure((size_t)count * sizeof(double)));
-    HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, o->out64.as<double>(), c->stream));
-    RP_TRY(online_download(o, o->out64.p, (size_t)count * sizeof(double)));
-    std::memcpy(out, o->host_out, (size_t)count * sizeof(double));
-    *n_written = count;
-    return REPET_OK;
+    return online_read_frames_impl(o, which, true, edges, n_bands, host_reader(out, capacity_doubles), nullptr, n_written);
 }
 
 int repet_online_last_band_energies_device(repet_online* o, int which, const int32_t* edges, int32_t n_bands, void* dst,
                                            void* signal_stream) {
-    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
-    RP_TRY(check_which(which));
-    RP_TRY(check_band_edges(o, edges, n_bands));
-    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleFrames);
-    if (!dst) return fail(REPET_ERR_BAD_ARG, "null destination");
-    if (o->fr.n <= 0) return REPET_OK;
-    FrameArgs a;
-    RP_TRY(online_frame_args(o, which, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    HIP_TRY(launch_online_bands(a, o->S, edges, n_bands, static_cast<double*>(dst), c->stream));
-    return signal_caller(c, signal_stream);
+    int64_t n = 0;
+    return online_read_frames_impl(o, which, true, edges, n_bands, device_reader(dst, signal_stream), nullptr, &n);
 }
 
 static const char* const kStaleMatches =
@@ -1477,49 +1483,38 @@ int repet_online_match_capacity(repet_online* o, int32_t* capacity) {
     return REPET_OK;
 }
 
-int repet_online_last_matches(repet_online* o, int32_t* count_out, int32_t* age_out, float* similarity_out, int64_t capacity_rows,
-                              int64_t* n_rows) {
+// count int32 [S][n], age int32 and similarity float32 [S][n][K], dense in either form. The host form with no array at all asks for
+// the rows; a partly null or short set is refused with the rows still in *n_rows.
+static int online_read_matches_impl(repet_online* o, const Reader& r, int64_t* n_rows) {
     if (!o || !n_rows) return fail(REPET_ERR_BAD_ARG, "null argument");
     *n_rows = 0;
     if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleMatches);
     const int64_t rows = (int64_t)o->S * o->fr.n, K = online_max_peaks(o);
     *n_rows = rows;
-    if (rows == 0 || (!count_out && !age_out && !similarity_out)) return REPET_OK;
-    if (!count_out || !age_out || !similarity_out || capacity_rows < rows) return fail(REPET_ERR_BAD_ARG, "online: output capacity too small");
+    if (!r.device && (rows == 0 || (!r.part[0] && !r.part[1] && !r.part[2]))) return REPET_OK;
+    RP_TRY(read_check(r, rows));
     *n_rows = 0;
+    if (rows == 0) return REPET_OK;
     MatchArgs a;
     RP_TRY(online_match_args(o, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    // count | age | similarity, one after the other: one copy
-    const size_t words = (size_t)rows * (1 + 2 * K);
-    HIP_TRY(o->out64.ensure(words * 4));
-    int32_t* cnt = o->out64.as<int32_t>();
-    int32_t* age = cnt + rows;
-    float* sim = reinterpret_cast<float*>(age + rows * K);
-    HIP_TRY(launch_online_matches(a, o->S, cnt, age, sim, c->stream));
-    RP_TRY(online_download(o, o->out64.p, words * 4));
-    const int32_t* got = static_cast<const int32_t*>(o->host_out);
-    std::memcpy(count_out, got, (size_t)rows * 4);
-    std::memcpy(age_out, got + rows, (size_t)rows * K * 4);
-    std::memcpy(similarity_out, got + rows + rows * K, (size_t)rows * K * 4);
+    DeviceGuard guard(o->ctx->device);
+    const size_t bytes[3] = {(size_t)rows * 4, (size_t)rows * K * 4, (size_t)rows * K * 4};
+    void* at[3];
+    RP_TRY(read_begin(o, r, bytes, at));
+    HIP_TRY(launch_online_matches(a, o->S, static_cast<int32_t*>(at[0]), static_cast<int32_t*>(at[1]), static_cast<float*>(at[2]), o->ctx->stream));
+    RP_TRY(read_deliver(o, r, bytes));
     *n_rows = rows;
     return REPET_OK;
 }
 
+int repet_online_last_matches(repet_online* o, int32_t* count_out, int32_t* age_out, float* similarity_out, int64_t capacity_rows,
+                              int64_t* n_rows) {
+    return online_read_matches_impl(o, Reader{false, 3, {count_out, age_out, similarity_out}, capacity_rows, nullptr}, n_rows);
+}
+
 int repet_online_last_matches_device(repet_online* o, void* count_dst, void* age_dst, void* similarity_dst, void* signal_stream) {
-    if (!o) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (!o->fr.valid) return fail(REPET_ERR_BAD_ARG, kStaleMatches);
-    if (!count_dst || !age_dst || !similarity_dst) return fail(REPET_ERR_BAD_ARG, "null destination");
-    if (o->fr.n <= 0) return REPET_OK;
-    MatchArgs a;
-    RP_TRY(online_match_args(o, &a));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    HIP_TRY(launch_online_matches(a, o->S, static_cast<int32_t*>(count_dst), static_cast<int32_t*>(age_dst),
-                                  static_cast<float*>(similarity_dst), c->stream));
-    return signal_caller(c, signal_stream);
+    int64_t n = 0;
+    return online_read_matches_impl(o, Reader{true, 3, {count_dst, age_dst, similarity_dst}, 0, signal_stream}, &n);
 }
 
 int repet_online_set_background_gain(repet_online* o, const int32_t* slots, int32_t n_slots, const float* gains) {
@@ -1831,58 +1826,52 @@ int repet_online_stream_state_size(repet_online* o, int64_t* header_bytes, int64
     return REPET_OK;
 }
 
-int repet_online_export_stream(repet_online* o, int32_t slot, void* header_out, void* payload_out) {
-    if (!o || !header_out || !payload_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+// the 4-byte alignment refusal is the device form's alone; the header goes out once the payload's launch is enqueued (device) or
+// has been waited for (host)
+static int online_read_export_impl(repet_online* o, int32_t slot, void* header_out, const Reader& r) {
+    if (!o || !header_out || !r.part[0]) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (r.device && (reinterpret_cast<uintptr_t>(r.part[0]) & 3)) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
     StateHeader h;
     RP_TRY(online_export_plan(o, slot, &h));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
+    DeviceGuard guard(o->ctx->device);
     const size_t bytes = (size_t)h.payload_bytes;
-    HIP_TRY(o->out64.ensure(bytes));
-    RP_TRY(online_export(o, slot, h, o->out64.as<float>()));
-    RP_TRY(online_download(o, o->out64.p, bytes));
-    std::memcpy(payload_out, o->host_out, bytes);
+    void* at = nullptr;
+    RP_TRY(read_begin(o, r, &bytes, &at));
+    RP_TRY(online_export(o, slot, h, static_cast<float*>(at)));
+    RP_TRY(read_deliver(o, r, &bytes));
     std::memcpy(header_out, &h, sizeof(h));
     return REPET_OK;
+}
+
+int repet_online_export_stream(repet_online* o, int32_t slot, void* header_out, void* payload_out) {
+    return online_read_export_impl(o, slot, header_out, host_reader(payload_out, 0));
 }
 
 int repet_online_export_stream_device(repet_online* o, int32_t slot, void* header_out, void* payload_dev, void* signal_stream) {
-    if (!o || !header_out || !payload_dev) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (reinterpret_cast<uintptr_t>(payload_dev) & 3) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
+    return online_read_export_impl(o, slot, header_out, device_reader(payload_dev, signal_stream));
+}
+
+// The data flows the other way: r.part[0] is read, through the pinned buffer (host) or where it lies behind the caller's stream
+// (device), which then continues behind the import: the payload may be reused once that stream gets there.
+static int online_import_impl(repet_online* o, int32_t slot, const void* header, const Reader& r) {
+    if (!o || !header || !r.part[0]) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (r.device && (reinterpret_cast<uintptr_t>(r.part[0]) & 3)) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
     StateHeader h;
-    RP_TRY(online_export_plan(o, slot, &h));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, signal_stream, signal_stream));
-    RP_TRY(online_export(o, slot, h, static_cast<float*>(payload_dev)));
-    RP_TRY(signal_caller(c, signal_stream));
-    std::memcpy(header_out, &h, sizeof(h));
-    return REPET_OK;
+    std::memcpy(&h, header, sizeof(h));
+    RP_TRY(online_import_check(o, slot, &h));
+    DeviceGuard guard(o->ctx->device);
+    if (r.device) RP_TRY(wait_caller(o->ctx, r.stream, r.stream));
+    else RP_TRY(online_upload(o, r.part[0], (size_t)h.payload_bytes));
+    RP_TRY(online_import(o, slot, h, static_cast<const float*>(r.device ? r.part[0] : o->staging.p)));
+    return r.device ? signal_caller(o->ctx, r.stream) : REPET_OK;
 }
 
 int repet_online_import_stream(repet_online* o, int32_t slot, const void* header, const void* payload) {
-    if (!o || !header || !payload) return fail(REPET_ERR_BAD_ARG, "null argument");
-    StateHeader h;
-    std::memcpy(&h, header, sizeof(h));
-    RP_TRY(online_import_check(o, slot, &h));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(online_upload(o, payload, (size_t)h.payload_bytes));
-    return online_import(o, slot, h, o->staging.as<float>());
+    return online_import_impl(o, slot, header, host_reader(const_cast<void*>(payload), 0));
 }
 
 int repet_online_import_stream_device(repet_online* o, int32_t slot, const void* header, const void* payload_dev, void* wait_stream) {
-    if (!o || !header || !payload_dev) return fail(REPET_ERR_BAD_ARG, "null argument");
-    if (reinterpret_cast<uintptr_t>(payload_dev) & 3) return fail(REPET_ERR_BAD_ARG, "online: the payload must be 4-byte aligned");
-    StateHeader h;
-    std::memcpy(&h, header, sizeof(h));
-    RP_TRY(online_import_check(o, slot, &h));
-    repet_ctx* c = o->ctx;
-    DeviceGuard guard(c->device);
-    RP_TRY(wait_caller(c, wait_stream, wait_stream));
-    RP_TRY(online_import(o, slot, h, static_cast<const float*>(payload_dev)));
-    // the caller's stream continues behind the import: the payload may be reused once that stream gets there
-    return signal_caller(c, wait_stream);
+    return online_import_impl(o, slot, header, device_reader(const_cast<void*>(payload_dev), wait_stream));
 }
 
 int repet_online_open_streams(int device, int32_t n_streams, int32_t n_channels, const repet_params* p, int64_t max_push_samples,

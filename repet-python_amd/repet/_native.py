@@ -42,22 +42,49 @@ LEVEL_CHUNK = 4096             # REPET_LEVEL_CHUNK: samples of one stream per wo
 Matches = collections.namedtuple("Matches", ["count", "age", "similarity"])
 
 
+def device_out(out, shape, device, dtype=None, dtype_words="", dense=False, name="out", what="the result"):
+    """The one check of a device ``out=`` tensor: on cuda:``device``, of ``dtype`` (None: any; ``dtype_words`` is the refusal,
+    formatted with ``want`` and ``got``), of ``shape`` (``what`` has it) and dense, or else at least free of negative strides.
+    ``name`` is what the messages call the tensor. ValueError otherwise, before anything runs."""
+    import torch
+    dev = torch.device("cuda", device)
+    if not is_device_tensor(out) or out.device != dev:
+        raise ValueError(f"{name} must be a tensor on {dev}")
+    if dtype is not None and out.dtype != dtype:
+        raise ValueError(dtype_words.format(want=dtype, got=out.dtype))
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(out.shape)}, {what} {tuple(shape)}")
+    if dense and not out.is_contiguous():
+        raise ValueError(f"{name} must be dense (contiguous)")
+    if not dense and any(st < 0 for st in out.stride()):
+        raise ValueError(f"{name} has negative strides")
+    return out
+
+
 def levels_out(out, shape, device):
     """``out=`` of a levels call: None (a fresh float64 tensor of ``shape`` on cuda:``device``), or a dense float64 tensor of
     that shape there. ValueError otherwise, before anything runs."""
     import torch
-    dev = torch.device("cuda", device)
     if out is None:
-        return torch.empty(shape, dtype=torch.float64, device=dev)
-    if not is_device_tensor(out) or out.device != dev:
-        raise ValueError(f"out must be a tensor on {dev}")
-    if out.dtype != torch.float64:
-        raise ValueError(f"levels are float64, out is {out.dtype}")
-    if tuple(out.shape) != tuple(shape):
-        raise ValueError(f"out has shape {tuple(out.shape)}, the levels {tuple(shape)}")
-    if not out.is_contiguous():
-        raise ValueError("out must be dense (contiguous)")
-    return out
+        return torch.empty(shape, dtype=torch.float64, device=torch.device("cuda", device))
+    return device_out(out, shape, device, torch.float64, "levels are float64, out is {got}", dense=True, what="the levels")
+
+
+def read_back(device, on_device, shapes, dtypes, host_call, device_call, outs=None):
+    """A record of a live handle, one body for its host and device forms: NumPy arrays of ``shapes`` and ``dtypes`` filled by
+    ``host_call(*arrays)``, or (``on_device``) tensors on cuda:``device`` filled by ``device_call(*tensors, stream handle)``
+    behind the current stream with no host wait. ``outs``: the destinations, already checked (None: fresh ones). Either call
+    returns the library's code. Returns the tuple of results."""
+    if not on_device:
+        results = outs or tuple(np.empty(shape, dtype=dtype) for shape, dtype in zip(shapes, dtypes))
+        check(host_call(*results))
+        return results
+    import torch
+    dev = torch.device("cuda", device)
+    results = outs or tuple(torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+                            for shape, dtype in zip(shapes, dtypes))
+    check(device_call(*results, _stream_handle(torch.cuda.current_stream(dev))))
+    return results
 
 
 def which_codes(which):
@@ -1156,15 +1183,10 @@ def _export_state(handle, slot, device=None):
     """export_stream of ``slot``: a host payload (device None), or a tensor on cuda:``device`` behind its current stream."""
     hb, pb = _state_sizes(handle)
     header = C.create_string_buffer(hb)
-    if device is None:
-        payload = np.empty(pb, dtype=np.uint8)
-        check(lib().repet_online_export_stream(handle, slot, header, ptr(payload)))
-    else:
-        import torch
-        dev = torch.device("cuda", device)
-        payload = torch.empty(pb, dtype=torch.uint8, device=dev)
-        check(lib().repet_online_export_stream_device(handle, slot, header, C.c_void_p(payload.data_ptr()),
-                                                      _stream_handle(torch.cuda.current_stream(dev))))
+    payload, = read_back(
+        device, device is not None, [pb], [np.uint8],
+        lambda p: lib().repet_online_export_stream(handle, slot, header, ptr(p)),
+        lambda p, stream: lib().repet_online_export_stream_device(handle, slot, header, C.c_void_p(p.data_ptr()), stream))
     return StreamState(header.raw, payload)
 
 
@@ -1202,6 +1224,16 @@ def _import_state(handle, slot, state, device):
         payload = np.ascontiguousarray(payload).reshape(-1)
         check(lib().repet_online_import_stream(handle, slot, state.header, ptr(payload)))
     return fields
+
+
+def _last_levels(handle, device, shape, out, on_device):
+    """``last_levels`` of a live handle whose record has ``shape``: see ``OnlineStreams.last_levels``."""
+    n = C.c_int64()
+    return read_back(
+        device, out is not None or on_device, [shape], [np.float64],
+        lambda r: lib().repet_online_last_levels(handle, ptr(r), r.size, C.byref(n)),
+        lambda t, stream: lib().repet_online_last_levels_device(handle, C.c_void_p(t.data_ptr()), stream),
+        None if out is None else (levels_out(out, shape, device),))[0]
 
 
 def _frame_range(handle):
@@ -1285,9 +1317,8 @@ def _ask_frames(handle, code, edges):
     record, and launches nothing."""
     n = C.c_int64()
     if edges is None:
-        check(lib().repet_online_last_frames(handle, code, None, 0, C.byref(n)))
-    else:
-        check(lib().repet_online_last_band_energies(handle, code, ptr(edges), edges.size - 1, None, 0, C.byref(n)))
+        return lib().repet_online_last_frames(handle, code, None, 0, C.byref(n))
+    return lib().repet_online_last_band_energies(handle, code, ptr(edges), edges.size - 1, None, 0, C.byref(n))
 
 
 def _last_frames(handle, device, lead, bins, which, bands, out, on_device):
@@ -1305,44 +1336,29 @@ def _last_frames(handle, device, lead, bins, which, bands, out, on_device):
     if out is not None and not is_tensor(out):
         if not isinstance(out, np.ndarray) or out.dtype != np_dtype or out.shape != shape or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous {np.dtype(np_dtype).name} array of shape {shape}, or a tensor on the device")
-    if is_tensor(out) or (out is None and on_device):
+    on_device = is_tensor(out) or (out is None and on_device)
+    if on_device and out is not None:
         import torch
-        dev = torch.device("cuda", device)
-        t_dtype = torch.float32 if edges is None else torch.float64
-        if out is None:
-            out = torch.empty(shape, dtype=t_dtype, device=dev)
-        else:
-            if not is_device_tensor(out) or out.device != dev:
-                raise ValueError(f"out must be a tensor on {dev}")
-            if out.dtype != t_dtype:
-                raise ValueError(f"the result is {t_dtype}, out is {out.dtype}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
-            if any(st < 0 for st in out.stride()):
-                raise ValueError("out has negative strides")
-            if edges is not None and not out.is_contiguous():
-                raise ValueError("out must be dense (contiguous)")
-        stream = torch.cuda.current_stream(dev)
-        if not out.numel():
-            _ask_frames(handle, codes[0], edges)
-        elif edges is not None:
-            check(lib().repet_online_last_band_energies_device(handle, codes[0], ptr(edges), edges.size - 1, C.c_void_p(out.data_ptr()),
-                                                               _stream_handle(stream)))
-        else:
-            strides = tuple(int(st) for st in out.stride())
-            strides = (0,) * (4 - len(strides)) + strides
-            check(lib().repet_online_last_frames_device(handle, codes[0], C.c_void_p(out.data_ptr()), (C.c_int64 * 4)(*strides),
-                                                        _stream_handle(stream)))
-        return out
-    result = np.empty(shape, dtype=np_dtype) if out is None else out
-    n = C.c_int64()
-    if not result.size:
-        _ask_frames(handle, codes[0], edges)
-    elif edges is not None:
-        check(lib().repet_online_last_band_energies(handle, codes[0], ptr(edges), edges.size - 1, ptr(result), result.size, C.byref(n)))
-    else:
-        check(lib().repet_online_last_frames(handle, codes[0], ptr(result), result.size, C.byref(n)))
-    return result
+        device_out(out, shape, device, torch.float32 if edges is None else torch.float64, "the result is {want}, out is {got}",
+                   dense=edges is not None)
+    code, n = codes[0], C.c_int64()
+
+    def host_call(r):
+        if not r.size:
+            return _ask_frames(handle, code, edges)
+        if edges is None:
+            return lib().repet_online_last_frames(handle, code, ptr(r), r.size, C.byref(n))
+        return lib().repet_online_last_band_energies(handle, code, ptr(edges), edges.size - 1, ptr(r), r.size, C.byref(n))
+
+    def device_call(t, stream):
+        if not t.numel():
+            return _ask_frames(handle, code, edges)
+        if edges is None:
+            strides = (0,) * (4 - t.dim()) + tuple(int(st) for st in t.stride())
+            return lib().repet_online_last_frames_device(handle, code, C.c_void_p(t.data_ptr()), (C.c_int64 * 4)(*strides), stream)
+        return lib().repet_online_last_band_energies_device(handle, code, ptr(edges), edges.size - 1, C.c_void_p(t.data_ptr()), stream)
+
+    return read_back(device, on_device, [shape], [np_dtype], host_call, device_call, None if out is None else (out,))[0]
 
 
 def _match_capacity(handle):
@@ -1355,7 +1371,6 @@ def match_outs(out, shapes, device):
     """``out=`` of ``last_matches`` against the three shapes of the result: a triple of dense tensors on cuda:``device``, int32,
     int32 and float32. ValueError otherwise, before anything runs."""
     import torch
-    dev = torch.device("cuda", device)
     try:
         outs = tuple(out)
     except TypeError:
@@ -1363,14 +1378,7 @@ def match_outs(out, shapes, device):
     if len(outs) != 3:
         raise ValueError("out is a triple of tensors (count, age, similarity)")
     for name, t, shape, dtype in zip(Matches._fields, outs, shapes, (torch.int32, torch.int32, torch.float32)):
-        if not is_device_tensor(t) or t.device != dev:
-            raise ValueError(f"out: {name} must be a tensor on {dev}")
-        if t.dtype != dtype:
-            raise ValueError(f"out: {name} is {dtype}, not {t.dtype}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"out: {name} has shape {tuple(t.shape)}, the result {shape}")
-        if not t.is_contiguous():
-            raise ValueError(f"out: {name} must be dense (contiguous)")
+        device_out(t, shape, device, dtype, f"out: {name} is {{want}}, not {{got}}", dense=True, name=f"out: {name}")
     return outs
 
 
@@ -1380,23 +1388,14 @@ def _last_matches(handle, device, lead, out, on_device):
     _, count = _frame_range(handle)
     k = _match_capacity(handle)
     shapes = (tuple(lead) + (count,), tuple(lead) + (count, k), tuple(lead) + (count, k))
-    if out is not None or on_device:
-        import torch
-        dev = torch.device("cuda", device)
-        if out is None:
-            outs = tuple(torch.empty(shape, dtype=dtype, device=dev)
-                         for shape, dtype in zip(shapes, (torch.int32, torch.int32, torch.float32)))
-        else:
-            outs = match_outs(out, shapes, device)
-        if outs[0].numel():
-            check(lib().repet_online_last_matches_device(handle, *(C.c_void_p(t.data_ptr()) for t in outs),
-                                                         _stream_handle(torch.cuda.current_stream(dev))))
-        return Matches(*outs)
-    outs = tuple(np.empty(shape, dtype=dtype) for shape, dtype in zip(shapes, (np.int32, np.int32, np.float32)))
     n = C.c_int64()
-    if outs[0].size:
-        check(lib().repet_online_last_matches(handle, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), outs[0].size, C.byref(n)))
-    return Matches(*outs)
+    # (an empty record: nothing is asked of the library)
+    return Matches(*read_back(
+        device, out is not None or on_device, shapes, (np.int32, np.int32, np.float32),
+        lambda c, a, s: c.size and lib().repet_online_last_matches(handle, ptr(c), ptr(a), ptr(s), c.size, C.byref(n)),
+        lambda c, a, s, stream: c.numel() and lib().repet_online_last_matches_device(
+            handle, *(C.c_void_p(t.data_ptr()) for t in (c, a, s)), stream),
+        None if out is None else match_outs(out, shapes, device)))
 
 
 class OnlineSeparator:
@@ -1459,10 +1458,7 @@ class OnlineSeparator:
     def last_levels(self):
         """The levels (``repet.LEVELS``) of what the last ``push`` / ``finish`` emitted: a float64 array ``(C, 8)``, reduced on
         the device; see ``repet.online_streams``. ValueError once another call has followed."""
-        result = np.empty((self._channels, LEVEL_FIELDS), dtype=np.float64)
-        n = C.c_int64()
-        check(lib().repet_online_last_levels(self._h, ptr(result), result.size, C.byref(n)))
-        return result
+        return _last_levels(self._h, self._device, (self._channels, LEVEL_FIELDS), None, False)
 
     @property
     def last_frame_range(self):
@@ -1631,17 +1627,11 @@ class OnlineStreams:
 
     def _device_out(self, out, n_emit, shape=None, dtype=None):
         import torch
-        device = torch.device("cuda", self._device)
         shape = shape or (self._streams, n_emit, self._channels)
         if out is None:
-            out = torch.empty(shape, dtype=dtype or torch.float64, device=device)
+            out = torch.empty(shape, dtype=dtype or torch.float64, device=torch.device("cuda", self._device))
         else:
-            if not is_device_tensor(out) or out.device != device:
-                raise ValueError(f"out must be a tensor on {device}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"out has shape {tuple(out.shape)}, the result {shape}")
-            if any(st < 0 for st in out.stride()):
-                raise ValueError("out has negative strides")
+            device_out(out, shape, self._device)
         return out, emit_tensor_code(out), tuple(int(st) for st in out.stride())
 
     def _emit(self, codes, n_emit, on_device, out, dtype, host_call, device_call, shape=None):
@@ -1723,17 +1713,15 @@ class OnlineStreams:
         rc = lib().repet_online_last_emission(self._handle(), codes[0], None, 1 << 62, C.byref(n))
         if rc != ERR_BAD_ARG or b"capacity" not in lib().repet_last_error():
             check(rc)
-        shape = self._emitted_shape
-        if out is not None or self._last_on_device:
-            import torch
-            (out,), out_code, (strides,) = self._device_outs(out, shape[1], codes, shape, dtype)
-            stream = torch.cuda.current_stream(out.device)
-            check(lib().repet_online_last_emission_device(self._handle(), codes[0], C.c_void_p(out.data_ptr() or None), out_code,
-                                                          _strides(strides), _stream_handle(stream), C.byref(n)))
-            return out
-        result = np.empty(shape, dtype=np.float64)
-        check(lib().repet_online_last_emission(self._handle(), codes[0], ptr(result), shape[1], C.byref(n)))
-        return result
+        shape, h = self._emitted_shape, self._handle()
+        on_device = out is not None or self._last_on_device
+        outs, out_code, strides = self._device_outs(out, shape[1], codes, shape, dtype) if on_device else (None, F64, None)
+        return read_back(
+            self._device, on_device, [shape], [np.float64],
+            lambda r: lib().repet_online_last_emission(h, codes[0], ptr(r), shape[1], C.byref(n)),
+            lambda t, stream: lib().repet_online_last_emission_device(
+                h, codes[0], C.c_void_p(t.data_ptr() or None), out_code, _strides(strides[0]), stream, C.byref(n)),
+            outs)[0]
 
     def last_levels(self, out=None):
         """The levels (``repet.LEVELS``, eight float64 values per stream and channel) of exactly the samples the last ``push`` /
@@ -1742,16 +1730,7 @@ class OnlineStreams:
         push was a device chunk -- then with no host wait. Reduced on the device on demand; see ``repet.online_streams``.
         ValueError for a wrong ``out`` (before anything runs) and once a push, finish, restart or release has followed."""
         shape = (self._channels, LEVEL_FIELDS) if self._tail_emitted else (self._streams, self._channels, LEVEL_FIELDS)
-        if out is not None or self._last_on_device:
-            import torch
-            out = levels_out(out, shape, self._device)
-            stream = torch.cuda.current_stream(out.device)
-            check(lib().repet_online_last_levels_device(self._handle(), C.c_void_p(out.data_ptr()), _stream_handle(stream)))
-            return out
-        result = np.empty(shape, dtype=np.float64)
-        n = C.c_int64()
-        check(lib().repet_online_last_levels(self._handle(), ptr(result), result.size, C.byref(n)))
-        return result
+        return _last_levels(self._handle(), self._device, shape, out, self._last_on_device)
 
     @property
     def last_frame_range(self):

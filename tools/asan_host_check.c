@@ -186,6 +186,26 @@ static void check_context_calls(void) {
     CHECK(repet_online_set_start_frames(NULL, 40) != REPET_OK);
     CHECK(repet_online_start_frames(NULL, &n32) != REPET_OK && n32 == 7);
     CHECK(repet_ctx_set_online_start(NULL, 40) != REPET_OK);
+    /* the read-back calls of a live handle, host and device form: a null handle is refused and the counter is left alone */
+    {
+        const int64_t strides[4] = {8, 4, 2, 1};
+        const int32_t edges[2] = {0, 1};
+        n64 = 7;
+        CHECK(repet_online_last_emission(NULL, REPET_OUT_FOREGROUND, out, 1, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_emission_device(NULL, REPET_OUT_FOREGROUND, out, REPET_F64, strides, NULL, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_levels(NULL, out, 8, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_levels_device(NULL, out, NULL) != REPET_OK);
+        CHECK(repet_online_last_frames(NULL, REPET_OUT_FOREGROUND, fout, 8, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_frames_device(NULL, REPET_OUT_FOREGROUND, fout, strides, NULL) != REPET_OK);
+        CHECK(repet_online_last_band_energies(NULL, REPET_OUT_FOREGROUND, edges, 1, out, 8, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_band_energies_device(NULL, REPET_OUT_FOREGROUND, edges, 1, out, NULL) != REPET_OK);
+        CHECK(repet_online_last_matches(NULL, &n32, &n32, fout, 1, &n64) != REPET_OK && n64 == 7);
+        CHECK(repet_online_last_matches_device(NULL, &n32, &n32, fout, NULL) != REPET_OK);
+        CHECK(repet_online_export_stream(NULL, 0, out, fout) != REPET_OK);
+        CHECK(repet_online_export_stream_device(NULL, 0, out, fout, NULL) != REPET_OK);
+        CHECK(repet_online_import_stream(NULL, 0, out, fout) != REPET_OK);
+        CHECK(repet_online_import_stream_device(NULL, 0, out, fout, NULL) != REPET_OK);
+    }
 
     const int devices = repet_device_count();
     repet_ctx* ctx = NULL;
