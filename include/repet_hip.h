@@ -409,6 +409,22 @@ int repet_selfsim(repet_ctx* ctx, const float* v, int64_t n_frames, int32_t n_fr
  * [n_frames][ceil(n_frames / 32)]. */
 int repet_selfsim_records(repet_ctx* ctx, const float* v, int64_t n_frames, int32_t n_freq, float* s_out, float* max_out,
                           float* second_out, int32_t* at_out);
+/* (still ABI 4: an addition -- look the symbol up to detect it) The similarity-matrix KERNELS as `sim` launches them, for tests:
+ * rows[n_frames][n_freq] are taken as UNIT rows as they are (normalise != 0: made unit rows first, vn_out[Tpad][FS] brings them
+ * back), with Tpad = round_up(n_frames, 128), FS = round_up(n_freq, 32), TS = round_up(n_frames, 64).
+ *   form     0 what `sim` picks for n_frames, 1 fp32, 2 f16-split 128 x 128 tiles, 3 f16-split 256 x 256 tiles (2 and 3 at any
+ *            n_frames >= 1);
+ *   records  0 none, 1 as `sim` gets them (form 3: the kernel's epilogue, else a pass over S), 2 always by the pass over S;
+ *   prefill  the byte every device buffer of the call holds before anything runs.
+ * geo_out[8] = Tpad, FS, TS, seg_pitch, the form that ran, the records' source (0 none, 1 epilogue, 2 pass), the padded length
+ * of the tile list, the tile edge. s_out == NULL: nothing runs, geo_out says what would (size the arrays from it). s_out[n_frames]
+ * [TS] is the whole pitched image; max_out / second_out / at_out [n_frames][seg_pitch] (records != 0); planes_out
+ * [round_up(n_frames, tile edge)][2 FS] f16 halves, per 32 bins [hi 32 | lo 32] (forms 2 and 3); kernel_out: the kernel's name.
+ * REPET_ERR_BAD_ARG: a null argument, n_frames < 1, n_freq < 1, form or records out of range. REPET_ERR_LIMIT: n_frames > 4096
+ * or n_freq > 8192. */
+int repet_debug_gram_full_stage(repet_ctx* ctx, const float* rows, int64_t n_frames, int32_t n_freq, int32_t form, int32_t records,
+                                int32_t normalise, int32_t prefill, int64_t* geo_out, float* s_out, float* max_out, float* second_out,
+                                int32_t* at_out, uint16_t* planes_out, float* vn_out, char* kernel_out, int32_t kernel_cap);
 
 /* _similaritymatrix, repet.py:1228-1246 (the online variant's frame-vs-buffer similarity):
  * a[TA][F], b[TB][F] frame-major magnitudes -> s[TA][TB] cosine similarities. */

@@ -297,6 +297,12 @@ int run_band_window_sum(repet_ctx* c, const float* band, int64_t T, int LP, int 
                         int64_t band_batch_stride, int64_t beat_batch_stride);
 bool gram_f16_enabled();
 bool gram_big_enabled();
+// run_gram_full = the choice of a form (gram_full_form) + its execution (exec_gram_full)
+enum GramFullForm { kFullAuto = 0, kFullF32 = 1, kFullF16 = 2, kFullF16Big = 3 };
+bool gram_segments_in_epilogue();
+int gram_full_form(int64_t T, bool unit_rows);
+int exec_gram_full(repet_ctx* c, int form, const float* A, int64_t T, int FS, float* S, int64_t TS, bool planes_ready, float* seg,
+                   int seg_pitch, bool* seg_written, bool seg_in_epilogue);
 int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int64_t TS, bool unit_rows = false,
                   bool planes_ready = false, float* seg = nullptr, int seg_pitch = 0, bool* seg_written = nullptr);
 bool band_rows_on_f16(repet_ctx* c, int64_t T, int FS, int n_lags, int B, int64_t a_stride);

@@ -148,14 +148,27 @@ bool gram_big_enabled() {
     return on;
 }
 
+// REPET_GRAM_SEGMENTS=0: the records by the pass over S also behind the 256 x 256 kernel (the agreement of the two is held by
+// tests/test_gpu_gram_full_stages.py through the stage entry, which takes the source as an argument)
+bool gram_segments_in_epilogue() {
+    static const bool on = [] { const char* e = getenv("REPET_GRAM_SEGMENTS"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+// The choice: which of the forms (GramFullForm, engine.h) run_gram_full takes for these arguments ...
+int gram_full_form(int64_t T, bool unit_rows) {
+    if (!unit_rows || !gram_f16_enabled()) return kFullF32;     // the f16 split is safe for unit rows only (components in [0, 1])
+    return gram_big_enabled() && T >= 8 * gram_big_tile() ? kFullF16Big : kFullF16;
+}
+
+// ... and its execution (the stage entry repet_debug_gram_full_stage runs a form of its own choosing through this half: the
+// kernels take any T >= 1, the 2 048-frame threshold belongs to the choice)
 // seg (nullable): segment records of S's rows for the peak picking (peaks.h), pitch seg_pitch: written by the 256 x 256
-// kernel's epilogue, by a pass over S behind the other kernels
-int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int64_t TS, bool unit_rows,
-                  bool planes_ready, float* seg, int seg_pitch, bool* seg_written) {
+// kernel's epilogue (seg_in_epilogue), by a pass over S behind the other kernels
+int exec_gram_full(repet_ctx* c, int form, const float* A, int64_t T, int FS, float* S, int64_t TS, bool planes_ready, float* seg,
+                   int seg_pitch, bool* seg_written, bool seg_in_epilogue) {
     if (seg_written) *seg_written = false;             // (the caller then runs launch_segment_maxima itself, as a stage of its own)
-    // REPET_GRAM_SEGMENTS=0: the records by the pass over S also behind the 256 x 256 kernel (agreement test of the epilogue's)
-    static const bool seg_in_epilogue = [] { const char* e = getenv("REPET_GRAM_SEGMENTS"); return !(e && e[0] == '0'); }();
-    if (unit_rows && gram_f16_enabled() && gram_big_enabled() && T >= 8 * gram_big_tile()) {
+    if (form == kFullF16Big) {
         const int bt = gram_big_tile();
         const int nb = (int)ceil_div(T, bt);
         if (c->tiles_big_nb != nb) {
@@ -182,7 +195,7 @@ int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int
     }
     const int2* tiles; int n;
     RP_TRY(get_tiles(c, T, 1 << 30, &tiles, &n));
-    if (unit_rows && gram_f16_enabled()) {      // rows are unit vectors (components in [0, 1]): safe for the f16 split
+    if (form == kFullF16) {
         const int64_t count = round_up(T, kTile) * FS;
         if (!planes_ready) {
             HIP_TRY(c->Vh.ensure((size_t)count * 4));
@@ -192,9 +205,16 @@ int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int
         if (seg && !seg_written) HIP_TRY(launch_segment_maxima(S, T, (int)T, TS, seg, seg_pitch, c->stream));
         return REPET_OK;
     }
+    if (form != kFullF32) return fail(REPET_ERR_BAD_ARG, "internal: form of the full Gram");
     HIP_TRY(launch_gram_full(A, T, FS, S, TS, tiles, n, c->stream));
     if (seg && !seg_written) HIP_TRY(launch_segment_maxima(S, T, (int)T, TS, seg, seg_pitch, c->stream));
     return REPET_OK;
+}
+
+int run_gram_full(repet_ctx* c, const float* A, int64_t T, int FS, float* S, int64_t TS, bool unit_rows,
+                  bool planes_ready, float* seg, int seg_pitch, bool* seg_written) {
+    return exec_gram_full(c, gram_full_form(T, unit_rows), A, T, FS, S, TS, planes_ready, seg, seg_pitch, seg_written,
+                          gram_segments_in_epilogue());
 }
 // unit_rows: A holds unit vectors (the similarity band of simonline), safe for the f16-split kernel; the beat-spectrum
 // bands (power spectra, wide dynamic range) stay on the exact-fp32 one. B clips: a_stride / band_stride in elements.

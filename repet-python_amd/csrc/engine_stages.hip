@@ -315,6 +315,85 @@ int repet_debug_gram_band_stage(repet_ctx* c, const float* rows, int32_t B, int6
     return REPET_OK;
 }
 
+// ---- stage entry of the full similarity matrix (tests/test_gpu_gram_full_stages.py) --------------------------------------
+// exec_gram_full -- the second half of run_gram_full -- on rows (T, F) laid out as `sim` lays out its unit rows: Tpad =
+// round_up(T, 128) rows of pitch FS, pad rows and pad bins zero; S (T, TS = round_up(T, 64)); the records (T, 3, seg_pitch).
+// The rows are taken as given (the caller passes unit rows); normalise: launch_unit_rows runs on them first and vn_out
+// (Tpad, FS) brings back what it wrote. form: 0 as gram_full_form picks for unit rows, 1 fp32, 2 f16-split 128 x 128, 3
+// f16-split 256 x 256 -- 2 and 3 at any T (the 2 048-frame threshold belongs to the choice). records: 0 none, 1 as `sim`
+// gets them (the epilogue of form 3, a pass over S otherwise), 2 always by launch_segment_maxima. Every device buffer -- the
+// rows, S, the records, the context's planes out to round_up(T, 256) rows -- is filled with the byte `prefill` first, so with
+// form 3 the plane rows [Tpad, round_up(T, 256)) still hold it when the kernel reads them. geo_out[8] = Tpad, FS, TS,
+// seg_pitch, the form that ran, the records' source (0 none, 1 epilogue, 2 pass over S), the tile list's padded length, the
+// tile edge; with s_out null nothing runs and geo_out holds what WOULD run. s_out (T, TS) whole, guard columns included;
+// top_out / second_out / at_out (T, seg_pitch); planes_out (round_up(T, tile edge), 2 FS) halves for forms 2 and 3.
+// REPET_ERR_BAD_ARG: a null argument, T < 1, F < 1, form or records out of range; REPET_ERR_LIMIT: T > 4096 or F > 8192 (the
+// entry's own caps: S is T x TS floats).
+int repet_debug_gram_full_stage(repet_ctx* c, const float* rows, int64_t T, int32_t F, int32_t form, int32_t records, int32_t normalise,
+                                int32_t prefill, int64_t* geo_out, float* s_out, float* top_out, float* second_out, int32_t* at_out,
+                                uint16_t* planes_out, float* vn_out, char* kernel_out, int32_t kernel_cap) {
+    if (!c || !geo_out) return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (T < 1 || F < 1) return fail(REPET_ERR_BAD_ARG, "bad size");
+    if (T > 4096 || F > 8192) return fail(REPET_ERR_LIMIT, "this entry takes at most 4096 rows of at most 8192 bins");
+    if (form < kFullAuto || form > kFullF16Big)
+        return fail(REPET_ERR_BAD_ARG, "form: 0 as production picks, 1 fp32, 2 f16 128 x 128 tiles, 3 f16 256 x 256 tiles");
+    if (records < 0 || records > 2) return fail(REPET_ERR_BAD_ARG, "records: 0 none, 1 as production gets them, 2 by the pass over S");
+    const int FS = (int)round_up(F, kFreqAlign);
+    const int64_t Tpad = round_up(T, kTile), TS = round_up(T, 64);
+    const int seg_pitch = segment_pitch((int)TS);
+    const int ran = form != kFullAuto ? form : gram_full_form(T, true);
+    const int edge = ran == kFullF16Big ? gram_big_tile() : kTile;
+    const int64_t plane_rows = round_up(T, edge);
+    const int source = records == 0 ? 0 : (records == 1 && ran == kFullF16Big && gram_segments_in_epilogue()) ? 1 : 2;
+    std::vector<int2> list;
+    const int64_t geo[8] = {Tpad, FS, TS, seg_pitch, ran, source, gram_tile_list((int)ceil_div(T, edge), 1 << 30, &list), edge};
+    std::memcpy(geo_out, geo, sizeof(geo));
+    if (!s_out) return REPET_OK;
+    if (!rows || (records && (!top_out || !second_out || !at_out)) || (ran != kFullF32 && !planes_out) || (normalise && !vn_out))
+        return fail(REPET_ERR_BAD_ARG, "null argument");
+    DeviceGuard guard(c->device);
+    const size_t a_bytes = (size_t)Tpad * FS * sizeof(float), s_bytes = (size_t)T * TS * sizeof(float);
+    const size_t seg_bytes = (size_t)T * 3 * seg_pitch * sizeof(float), plane_bytes = (size_t)round_up(T, gram_big_tile()) * FS * 4;
+    Scratch Ad, Sd, Gd, Raw;
+    HIP_TRY(Ad.b.ensure(a_bytes));
+    HIP_TRY(Sd.b.ensure(s_bytes));
+    HIP_TRY(Gd.b.ensure(seg_bytes));
+    HIP_TRY(hipMemsetAsync(Ad.b.p, prefill & 255, a_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(Sd.b.p, prefill & 255, s_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(Gd.b.p, prefill & 255, seg_bytes, c->stream));
+    if (ran != kFullF32) {                            // more than exec_gram_full will ask for: it then finds the buffer large enough
+        HIP_TRY(c->Vh.ensure(plane_bytes));
+        HIP_TRY(hipMemsetAsync(c->Vh.p, prefill & 255, plane_bytes, c->stream));
+    }
+    if (normalise) {
+        HIP_TRY(Raw.b.ensure((size_t)T * F * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(Raw.b.p, rows, (size_t)T * F * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (Tpad > T) HIP_TRY(hipMemsetAsync(Ad.b.as<float>() + (size_t)T * FS, 0, (size_t)(Tpad - T) * FS * sizeof(float), c->stream));
+        HIP_TRY(launch_unit_rows(Raw.b.as<float>(), Ad.b.as<float>(), T, F, FS, c->stream));
+    } else {
+        RP_TRY(h2d_pitched(c, Ad.b.as<float>(), FS, rows, T, F, Tpad));
+    }
+    RP_TRY(exec_gram_full(c, ran, Ad.b.as<float>(), T, FS, Sd.b.as<float>(), TS, false, records ? Gd.b.as<float>() : nullptr, seg_pitch,
+                          nullptr, source == 1));
+    HIP_TRY(hipMemcpyAsync(s_out, Sd.b.p, s_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (records)
+        for (int plane = 0; plane < 3; ++plane) {
+            void* dst = plane == 0 ? (void*)top_out : plane == 1 ? (void*)second_out : (void*)at_out;
+            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)seg_pitch * 4, Gd.b.as<float>() + (size_t)plane * seg_pitch, (size_t)3 * seg_pitch * 4,
+                                     (size_t)seg_pitch * 4, (size_t)T, hipMemcpyDeviceToHost, c->stream));
+        }
+    if (ran != kFullF32)
+        HIP_TRY(hipMemcpyAsync(planes_out, c->Vh.p, (size_t)plane_rows * FS * 4, hipMemcpyDeviceToHost, c->stream));
+    if (normalise) HIP_TRY(hipMemcpyAsync(vn_out, Ad.b.p, a_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (kernel_out && kernel_cap > 0) {
+        std::strncpy(kernel_out, ran == kFullF32 ? "gram_kernel<GRAM_FULL>" : ran == kFullF16 ? "gram_f16_kernel<false>" : "gram_f16_big_pipe_kernel",
+                     (size_t)kernel_cap - 1);
+        kernel_out[kernel_cap - 1] = 0;
+    }
+    return REPET_OK;
+}
+
 // run_band_window_sum -> launch_periods -> (T_expand > 0) launch_expand_periods on a band (B, T, LP) given as it is, LP a
 // multiple of 64: window w covers frames [start0 + w step, + len). beat_out (B, n_windows, LP), win_periods_out (B,
 // n_windows), frame_periods_out (T_expand) from the first clip's window periods (null with T_expand = 0). The beat rows

@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256) void gram_f16_kernel(const _Float16* __restric
     // SOURCE chunk): no staging registers (three sets of 32 were a third of the register file) and no ds_write_b128
     // traffic (32 KB per K-tile at 79 B/clk was more LDS time than the fragment reads). One barrier per K-tile, in its
     // middle; the DMA pieces of tile k+2 and the fragment reads of the next half tile ride between the MFMAs, the
-    // fragments into a second register set. Same products in the same order as every other f16-split kernel.
+    // fragments into a second register set. Same products in the same order as every other f16-split kernel (held bit for bit by
+    // tests/test_gpu_gram_full_stages.py: the band against the full matrix, the 256 x 256 kernel against this one).
     const unsigned grow = (unsigned)(2 * FS);
     const int prow = lane >> 2;
     const _Float16* src_lane[8];

@@ -3,7 +3,8 @@
 //
 // Same arithmetic as gram_f16.hip (every fp32 unit-row component as hi + lo f16 halves, hi hi' + hi lo' + lo hi' on
 // v_mfma_f32_32x32x16_f16, fp32 accumulators, the three products of a K-step in the same order), so the matrix is
-// bit-identical to that kernel's. What changes is what the 128 x 128 kernel was bound by -- the LDS, not the matrix cores:
+// bit-identical to that kernel's (held by tests/test_gpu_gram_full_stages.py: test_the_256_kernel_is_bit_identical_to_the_
+// 128_kernel; the same module holds the symmetry and the epilogue's records against a pass over S). What changes is what the 128 x 128 kernel was bound by -- the LDS, not the matrix cores:
 //   per K-tile of 32 components it wrote 32 KB to LDS (415 cycles of the CU's 79 B/clk ds_write_b128 path) and its four
 //   waves read 64 KB of fragments back (256 cycles) for 768 cycles of MFMA per SIMD; two workgroups per CU made that
 //   1 340 LDS cycles against 768 MFMA cycles.

@@ -866,6 +866,56 @@ def _gram_band_stage(rows, n_lags, clip_stride=None, form="auto", unit_rows=Fals
     return out
 
 
+GRAM_FULL_FORMS = {"auto": 0, "f32": 1, "f16_128": 2, "f16_256": 3}
+_GRAM_FULL_FORM_NAMES = {v: k for k, v in GRAM_FULL_FORMS.items()}
+_GRAM_RECORD_SOURCES = {0: None, 1: "epilogue", 2: "pass"}
+
+
+def _gram_full_stage(rows, form="auto", records=0, normalise=False, prefill=0, choice_only=False):
+    """The similarity matrix of ``sim`` as the pipeline runs it (``exec_gram_full``, the second half of ``run_gram_full``;
+    ``repet_debug_gram_full_stage``). ``rows`` (T, F) fp32, taken as unit rows as they are; ``normalise``: made unit rows on the
+    device first ("Vn" (Tpad, FS) brings them back). ``form``: "auto" (what ``gram_full_form`` picks for T), "f32", "f16_128",
+    "f16_256" (both at any T). ``records``: 0 none, 1 as ``sim`` gets them (the epilogue of "f16_256", a pass over S otherwise),
+    2 always by the pass over S. Returns a dict: "S" (T, TS) the whole pitched image as the kernel left it over the byte
+    ``prefill``; with records "top", "second" (float32) and "at" (int32), each (T, seg_pitch); for the f16 forms "planes"
+    (round_up(T, tile), 2 FS) float16; "form" (the one that ran), "records" (None, "epilogue" or "pass"), "kernel", "n_tiles",
+    "tile", "Tpad", "FS", "TS", "seg_pitch". ``choice_only``: nothing runs, only what would and the sizes come back; ``rows`` may
+    then be a (T, F) shape."""
+    import ctypes as C
+    if choice_only and isinstance(rows, tuple):
+        x, (t, f) = None, rows
+    else:
+        x = _f32(rows)
+        t, f = x.shape
+    geo = (C.c_int64 * 8)()
+    name = C.create_string_buffer(64)
+    fn = _native.lib().repet_debug_gram_full_stage
+    ctx = _native.default_context(_device).handle
+    opt = lambda a: None if a is None else _native.ptr(a)
+
+    def call(s, top, second, at, planes, vn):
+        _native.check(fn(ctx, opt(x), t, f, GRAM_FULL_FORMS.get(form, form), int(records), int(bool(normalise)), int(prefill), geo, opt(s), opt(top),
+                         opt(second), opt(at), opt(planes), opt(vn), name, len(name)))
+
+    call(None, None, None, None, None, None)
+    tpad, fs, ts, seg_pitch, ran, source, n_tiles, tile = (int(v) for v in geo)
+    out = {"form": _GRAM_FULL_FORM_NAMES[ran], "records": _GRAM_RECORD_SOURCES[source], "n_tiles": n_tiles, "tile": tile, "Tpad": tpad,
+           "FS": fs, "TS": ts, "seg_pitch": seg_pitch}
+    if choice_only:
+        return out
+    s = np.empty((t, ts), dtype=np.float32)
+    top, second = (np.empty((t, seg_pitch), dtype=np.float32) for _ in range(2)) if records else (None, None)
+    at = np.empty((t, seg_pitch), dtype=np.int32) if records else None
+    planes = np.empty((-(-t // tile) * tile, 2 * fs), dtype=np.float16) if ran != 1 else None
+    vn = np.empty((tpad, fs), dtype=np.float32) if normalise else None
+    call(s, top, second, at, planes, vn)
+    out.update(S=s, kernel=name.value.decode())
+    for key, value in (("top", top), ("second", second), ("at", at), ("planes", planes), ("Vn", vn)):
+        if value is not None:
+            out[key] = value
+    return out
+
+
 def _band_periods_stage(band, n_freq, start0, step, length, n_windows, lo, hi, n_lags_for_clamp, n_lags=None, t_expand=0, prefill=0):
     """``run_band_window_sum`` -> ``launch_periods`` -> (``t_expand`` > 0) ``launch_expand_periods`` on a band (B, T, LP) or
     (T, LP) fp32, LP a multiple of 64 (``n_lags`` defaults to LP): window w covers frames [start0 + w step, + length). Returns

@@ -1,7 +1,8 @@
 """Float64 references of the chain rows -> banded Gram -> windowed diagonal sums -> argmax -> per-frame periods, written from
 the formulas in the comments of gram.hip / gram_f16.hip and from oracle/repet_oracle.py, not from the kernels.
 tests/test_gram_reference.py pins the chain to the oracle on the CPU; tests/test_gpu_gram_band_stages.py holds the HIP
-kernels against it."""
+kernels against it. The full similarity matrix, its segment records and the unit rows (tests/test_gpu_gram_full_stages.py) are
+the same statements without the band."""
 import numpy as np
 
 from stft_reference import decode_planes, row_scale, split_planes  # noqa: F401  (re-exported: one restatement of the split)
@@ -83,6 +84,67 @@ def split_band_bound(rows, scale, n_lags, lookback=False):
     ad = a @ d.T
     g = ad + ad.T + d @ d.T + 2.0 ** -22 * ((a + d) @ (a + d).T)
     return band_of_gram(g, n_lags, lookback)
+
+
+# ---- the full matrix (tests/test_gpu_gram_full_stages.py): the same statements without the band ------------------------------
+def full64(rows):
+    """S[i][j] = row i . row j in float64; rows (T, F)."""
+    r = np.asarray(rows, dtype=np.float64)
+    return r @ r.T
+
+
+def full_abs64(rows):
+    """sum_k |a_k b_k| of every entry: the scale of the fp32 kernel's accumulation bound."""
+    r = np.abs(np.asarray(rows, dtype=np.float64))
+    return r @ r.T
+
+
+def three_product_full(planes, inv):
+    """three_product_band for every pair of rows: (sum (hi hi' + hi lo' + lo hi') inv_i inv_j, the same sum of |products|), both
+    (T, T) float64, from the planes (T, 2 FS) the kernel read."""
+    hi, lo = plane_halves(planes)
+    inv = np.broadcast_to(np.asarray(inv, dtype=np.float64), hi.shape[:1])
+    outer = inv[:, None] * inv[None, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        hl = hi @ lo.T
+        g = (hi @ hi.T + hl + hl.T) * outer
+        ah, al = np.abs(hi), np.abs(lo)
+        ahl = ah @ al.T
+        s = (ah @ ah.T + ahl + ahl.T) * outer
+    return g, s
+
+
+def split_full_bound(rows, scale):
+    """split_band_bound for every pair of rows: |three-product matrix - float64 matrix| at most sum (|a| db + |b| da + da db) with
+    da, db the split bound, + the dropped lo lo' <= 2^-22 of each |a' b'|."""
+    a = np.abs(np.asarray(rows, dtype=np.float64))
+    d = split_error(rows, scale)
+    ad = a @ d.T
+    return ad + ad.T + d @ d.T + 2.0 ** -22 * ((a + d) @ (a + d).T)
+
+
+def segment_records(s, t):
+    """The segment records of the rows of s[:t, :t] (peaks.h): for every aligned run of 32 columns (the last one ragged) the
+    largest value with NaN counted as +inf, the largest of the run's OTHER elements (-inf for a run with one live column) and the
+    offset of the largest inside the run, the lowest among equals. Returns (top, second, at), each (t, ceil(t / 32)), the values in
+    the dtype of s."""
+    s = np.asarray(s)[:t, :t]
+    n_seg = -(-t // 32)
+    padded = np.full((t, n_seg * 32), -np.inf, dtype=s.dtype)
+    padded[:, :t] = np.where(np.isnan(s), np.inf, s)
+    runs = padded.reshape(t, n_seg, 32)
+    at = np.argmax(runs, axis=2)                                  # (the lowest index among equals)
+    top = np.take_along_axis(runs, at[:, :, None], axis=2)[:, :, 0]
+    others = runs.copy()
+    np.put_along_axis(others, at[:, :, None], -np.inf, axis=2)
+    return top, others.max(axis=2), at.astype(np.int32)
+
+
+def unit_rows64(rows):
+    """row / ||row|| in float64 (repet.py:1220 for a frame-major matrix); a zero row gives NaN."""
+    r = np.asarray(rows, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return r / np.sqrt(np.sum(r * r, axis=-1, keepdims=True))
 
 
 def window_sums64(band, n_lags, n_freq, start0, step, length, n_windows):
