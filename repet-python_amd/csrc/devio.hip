@@ -747,7 +747,8 @@ __global__ __launch_bounds__(kIoThreads) void devio_tail_clear(float2* __restric
 
 // ---- the streaming handle's per-push data movement (engine_online.hip): S streams at a per-stream stride -------------------
 // Grids are streams (y) x four-element slots (x), both capped and walked grid-stride; every store of a whole slot is one
-// dwordx4. kRowCopyParts parts (z) per launch.
+// dwordx4. kRowCopyParts parts (z) per launch. append, feed and take align their slots on the destination offset and walk them
+// themselves; every other kernel that moves rows (copies, held slide, slot reset, slot export / import) calls move_part.
 constexpr int kMaxIoGroups = 4096;        // workgroups of one launch (16 per CU and more: several rounds of the grid)
 
 // Append: stream b's chunk [n][C] (strided source of any dtype; IoGeo's clip = stream) goes to hi / lo at b * d_stream + d_off,
@@ -796,81 +797,83 @@ __global__ __launch_bounds__(kIoThreads) void online_append_i16(const int16_t* s
 __global__ __launch_bounds__(kIoThreads) void online_append_f16(const Half* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<Half>(src, g, s, hi, lo, ds, off); }
 __global__ __launch_bounds__(kIoThreads) void online_append_bf16(const BHalf* src, IoGeo g, int32_t s, float* hi, float* lo, int64_t ds, int64_t off) { append_body<BHalf>(src, g, s, hi, lo, ds, off); }
 
-// Row copies: part z moves `blocks` runs of `len` floats of every stream (or writes zeros where src is null). Slots of four
-// consecutive floats of a run; a whole slot is one dwordx4 store where the destination side is aligned (RowCopy::dst_vec)
-// and one dwordx4 load where the source side is (src_vec), element accesses otherwise.
-struct RowCopyDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream; int32_t src_vec, dst_vec; int64_t row_len, frame0; };
+// ---- runs of floats moved in slots of four: the one body of the row copies, the held slide, the slot reset and the slot
+// export / import below. A part moves `blocks` runs of `len` floats; slot q of it is four consecutive floats of one run. A whole
+// slot is one dwordx4 store where the destination side is aligned (dst_vec) and one dwordx4 load where the source side is
+// (src_vec), element accesses otherwise. fill_run (host, below) is the one place that fills a part and decides the two flags; a
+// value-initialised part is empty (no slots).
+struct RunPart {
+    const float* src = nullptr; float* dst = nullptr;
+    int64_t len = 0, slots_per_block = 1, blocks = 0, src_block = 0, dst_block = 0;
+    int32_t src_vec = 0, dst_vec = 0;
+};
+
+// Slot q of part p, between the bases a kernel worked out for its stream or slot: element i of a run is src[blk * src_block + i]
+// for i >= zero_below and zero below it -- the source is never read there, so src may point in front of what the source holds.
+// Nothing is stored at or behind `len` (a kernel may cut the part's own). load4: a whole slot may be loaded as one dwordx4.
+__device__ inline void move_slot(const RunPart& p, int64_t q, const float* src, float* dst, int64_t len, int64_t zero_below, bool load4) {
+    const int64_t blk = q / p.slots_per_block;
+    const int64_t i0 = (q - blk * p.slots_per_block) * 4;
+    if (i0 >= len) return;
+    float* d = dst + blk * p.dst_block + i0;
+    const int64_t so = blk * p.src_block + i0;
+    if (i0 + 4 <= len && p.dst_vec) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i0 >= zero_below) {
+            if (load4) v = *reinterpret_cast<const float4*>(src + so);
+            else v = make_float4(src[so], src[so + 1], src[so + 2], src[so + 3]);
+        } else if (i0 + 4 > zero_below) {                         // the slot the boundary cuts
+            float e[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = i0 + k >= zero_below ? src[so + k] : 0.f;
+            v = make_float4(e[0], e[1], e[2], e[3]);
+        }
+        *reinterpret_cast<float4*>(d) = v;
+    } else {
+        const int64_t m = len - i0 < 4 ? len - i0 : 4;
+        for (int64_t k = 0; k < m; ++k) d[k] = i0 + k >= zero_below ? src[so + k] : 0.f;
+    }
+}
+
+// the workgroups of grid x walk the part's slots grid-stride. A null source is the boundary at len: the part stores zeros.
+__device__ inline void move_part(const RunPart& p, const float* src, float* dst, int64_t len, int64_t zero_below, bool load4) {
+    const int64_t slots = p.slots_per_block * p.blocks;
+    if (!src) zero_below = len;
+    for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads)
+        move_slot(p, q, src, dst, len, zero_below, load4);
+}
+
+// Row copies: part z moves its runs for every stream (or writes zeros where src is null), stream b at b * src_stream /
+// b * dst_stream floats. A part with row_len > 0 covers frame rows: see engine.h.
+struct RowCopyDev { RunPart run; int64_t src_stream, dst_stream, row_len, frame0; };
 struct RowCopyArgs { RowCopyDev part[repet_eng::kRowCopyParts]; int32_t n_streams; const int64_t* slot_start; };
 
 __global__ __launch_bounds__(kIoThreads) void online_row_copies(RowCopyArgs a) {
-    const RowCopyDev p = a.part[blockIdx.z];
-    const int64_t slots = p.slots_per_block * p.blocks;
+    const RowCopyDev& p = a.part[blockIdx.z];
     for (int64_t b = blockIdx.y; b < a.n_streams; b += gridDim.y) {
-        int64_t len = p.len;
+        int64_t len = p.run.len;
         if (p.row_len > 0) {                                      // only the frame rows before the slot's own first frame
             const int64_t rows = a.slot_start ? a.slot_start[b] - p.frame0 : 0;
-            len = rows <= 0 ? 0 : (rows < p.len / p.row_len ? rows * p.row_len : p.len);
+            len = rows <= 0 ? 0 : (rows < p.run.len / p.row_len ? rows * p.row_len : p.run.len);
         }
-        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
-            const int64_t blk = q / p.slots_per_block;
-            const int64_t i0 = (q - blk * p.slots_per_block) * 4;
-            if (i0 >= len) continue;
-            float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
-            const float* s = p.src ? p.src + b * p.src_stream + blk * p.src_block + i0 : nullptr;
-            if (i0 + 4 <= len && p.dst_vec) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (s) {
-                    if (p.src_vec) v = *reinterpret_cast<const float4*>(s);
-                    else v = make_float4(s[0], s[1], s[2], s[3]);
-                }
-                *reinterpret_cast<float4*>(d) = v;
-            } else {
-                const int64_t m = len - i0 < 4 ? len - i0 : 4;
-                for (int64_t k = 0; k < m; ++k) d[k] = s ? s[k] : 0.f;
-            }
-        }
+        move_part(p.run, p.run.src ? p.run.src + b * p.src_stream : nullptr, p.run.dst + b * p.dst_stream, len, 0, p.run.src_vec != 0);
     }
 }
 
 // The slide of a push during which slots are HELD (repet_online_hold_streams): the row copies above, except that a stream whose
 // table entry is kSlotHeld takes element i of a run from `held_delta` floats further on in its source (<= 0: its content stays
-// where it is while the others' moves down) for i >= zero_below, and zero below it -- the source is never read there, so the
-// offset may point in front of the stream's share (the runs in front of a held slot's content while the handle's history
-// grows). Slots of four floats as above; plain vector stores.
-struct SlideDev { const float* src; float* dst; int64_t len, slots_per_block, blocks, src_block, dst_block, src_stream, dst_stream, held_delta, zero_below; int32_t src_vec, dst_vec, held_vec; };
+// where it is while the others' moves down) for i >= zero_below, and zero below it -- the offset may point in front of the
+// stream's share (the runs in front of a held slot's content while the handle's history grows). held_vec: src_vec of the
+// shifted source.
+struct SlideDev { RunPart run; int64_t src_stream, dst_stream, held_delta, zero_below; int32_t held_vec; };
 struct SlideArgs { SlideDev part[repet_eng::kRowCopyParts]; int32_t n_streams; const int64_t* slot_start; };
 
 __global__ __launch_bounds__(kIoThreads) void online_slide_held(SlideArgs a) {
-    const SlideDev p = a.part[blockIdx.z];
-    const int64_t slots = p.slots_per_block * p.blocks;
+    const SlideDev& p = a.part[blockIdx.z];
     for (int64_t b = blockIdx.y; b < a.n_streams; b += gridDim.y) {
         const bool held = a.slot_start[b] == repet_eng::kSlotHeld;
-        const int64_t zb = held ? p.zero_below : 0;
-        const int64_t base = b * p.src_stream + (held ? p.held_delta : 0);
-        const bool vec = held ? p.held_vec != 0 : p.src_vec != 0;
-        for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
-            const int64_t blk = q / p.slots_per_block;
-            const int64_t i0 = (q - blk * p.slots_per_block) * 4;
-            if (i0 >= p.len) continue;
-            float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
-            const int64_t so = base + blk * p.src_block + i0;
-            if (i0 + 4 <= p.len && p.dst_vec) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (i0 >= zb) {
-                    if (vec) v = *reinterpret_cast<const float4*>(p.src + so);
-                    else v = make_float4(p.src[so], p.src[so + 1], p.src[so + 2], p.src[so + 3]);
-                } else if (i0 + 4 > zb) {                         // the slot the boundary cuts
-                    float e[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) e[k] = i0 + k >= zb ? p.src[so + k] : 0.f;
-                    v = make_float4(e[0], e[1], e[2], e[3]);
-                }
-                *reinterpret_cast<float4*>(d) = v;
-            } else {
-                const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
-                for (int64_t k = 0; k < m; ++k) d[k] = i0 + k >= zb ? p.src[so + k] : 0.f;
-            }
-        }
+        move_part(p.run, p.run.src + b * p.src_stream + (held ? p.held_delta : 0), p.run.dst + b * p.dst_stream, p.run.len,
+                  held ? p.zero_below : 0, held ? p.held_vec != 0 : p.run.src_vec != 0);
     }
 }
 
@@ -997,8 +1000,8 @@ __global__ __launch_bounds__(kIoThreads) void online_take(TakeArgs a) {
 }
 
 // Slot reset (restart / release of slots of the streaming handle): workgroups (x, slot of the list, part) write the part's
-// runs of zeros into that slot's share of the buffers, and one thread per slot its new first frame.
-struct ZeroPartDev { float* dst; int64_t len, slots_per_block, blocks, dst_block, dst_stream; int32_t vec; };
+// runs of zeros (no part has a source) into that slot's share of the buffers, and one thread per slot its new first frame.
+struct ZeroPartDev { RunPart run; int64_t dst_stream; };
 struct SlotResetArgs {
     ZeroPartDev part[repet_eng::kRowCopyParts]; int64_t* slot_start; int64_t value; int32_t n_slots;
     unsigned short slot[repet_eng::kSlotResetIds];
@@ -1007,53 +1010,20 @@ struct SlotResetArgs {
 __global__ __launch_bounds__(kIoThreads) void online_slot_reset(SlotResetArgs a) {
     const int64_t b = a.slot[blockIdx.y];
     if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) a.slot_start[b] = a.value;
-    const ZeroPartDev p = a.part[blockIdx.z];
-    const int64_t slots = p.slots_per_block * p.blocks;
-    for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
-        const int64_t blk = q / p.slots_per_block;
-        const int64_t i0 = (q - blk * p.slots_per_block) * 4;
-        float* d = p.dst + b * p.dst_stream + blk * p.dst_block + i0;
-        if (i0 + 4 <= p.len && p.vec) {
-            *reinterpret_cast<float4*>(d) = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
-            for (int64_t k = 0; k < m; ++k) d[k] = 0.f;
-        }
-    }
+    const ZeroPartDev& p = a.part[blockIdx.z];
+    move_part(p.run, nullptr, p.run.dst + b * p.dst_stream, p.run.len, 0, false);
 }
 
-// Slot export / import (a live stream moved between handles): part z moves `blocks` runs of `len` floats between ONE slot's
-// share of the handle's strided buffers and the dense payload, slots of four floats as in the row copies. Element i of a run
-// is src[src_off + blk * src_block + i] for i >= zero_below and zero below it (the source is never read there: src_off may be
-// negative, the run right-aligned on what the source holds). The import also writes the slot's first frame and, where the
-// handle's epoch moved with it, adds `shift` to the first frame of every other live slot (one workgroup, plain stores).
-struct SlotMoveDev { const float* src; float* dst; int64_t src_off, len, slots_per_block, blocks, src_block, dst_block, zero_below; int32_t src_vec, dst_vec; };
+// Slot export / import (a live stream moved between handles): part y moves its runs between ONE slot's share of the handle's
+// strided buffers and the dense payload. Element i of a run is src[src_off + blk * src_block + i] for i >= zero_below and zero
+// below it (src_off may be negative, the run right-aligned on what the source holds). The import also writes the slot's first
+// frame and, where the handle's epoch moved with it, adds `shift` to the first frame of every other live slot (one workgroup,
+// plain stores).
+struct SlotMoveDev { RunPart run; int64_t src_off, zero_below; };
 struct SlotMoveArgs { SlotMoveDev part[repet_eng::kRowCopyParts]; int64_t* slot_start; int64_t value, shift; int32_t slot, n_slots; };
 
 __device__ inline void slot_move_body(const SlotMoveDev& p) {
-    const int64_t slots = p.slots_per_block * p.blocks;
-    for (int64_t q = (int64_t)blockIdx.x * kIoThreads + threadIdx.x; q < slots; q += (int64_t)gridDim.x * kIoThreads) {
-        const int64_t blk = q / p.slots_per_block;
-        const int64_t i0 = (q - blk * p.slots_per_block) * 4;
-        float* d = p.dst + blk * p.dst_block + i0;
-        const int64_t so = p.src_off + blk * p.src_block + i0;
-        if (i0 + 4 <= p.len && p.dst_vec) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i0 >= p.zero_below) {
-                if (p.src_vec) v = *reinterpret_cast<const float4*>(p.src + so);
-                else v = make_float4(p.src[so], p.src[so + 1], p.src[so + 2], p.src[so + 3]);
-            } else if (i0 + 4 > p.zero_below) {                   // the slot the boundary cuts
-                float e[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) e[k] = i0 + k >= p.zero_below ? p.src[so + k] : 0.f;
-                v = make_float4(e[0], e[1], e[2], e[3]);
-            }
-            *reinterpret_cast<float4*>(d) = v;
-        } else {
-            const int64_t m = p.len - i0 < 4 ? p.len - i0 : 4;
-            for (int64_t k = 0; k < m; ++k) d[k] = i0 + k >= p.zero_below ? p.src[so + k] : 0.f;
-        }
-    }
+    move_part(p.run, p.run.src ? p.run.src + p.src_off : nullptr, p.run.dst, p.run.len, p.zero_below, p.run.src_vec != 0);
 }
 
 __global__ __launch_bounds__(kIoThreads) void online_slot_export(SlotMoveArgs a) { slot_move_body(a.part[blockIdx.y]); }
@@ -1154,6 +1124,23 @@ static dim3 stream_grid(int64_t slots, int32_t n_streams, int parts) {
     return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(slots, kIoThreads), x_cap)), (unsigned)y, (unsigned)parts);
 }
 
+// one side of a part takes dwordx4 accesses: a 16-byte base, and every stride and offset it is reached through a multiple of four
+static bool vec_side(const float* base, int64_t block, int64_t stream) {
+    return !(reinterpret_cast<uintptr_t>(base) & 15) && !(block & 3) && !(stream & 3);
+}
+
+// fills the part move_part walks and returns its slots, for the grid (0, and the part left empty, where there is nothing to move)
+static int64_t fill_run(RunPart& r, const float* src, float* dst, int64_t len, int64_t blocks, int64_t src_block, int64_t dst_block,
+                        int64_t src_stream = 0, int64_t dst_stream = 0) {
+    r = RunPart{};
+    if (len <= 0 || blocks <= 0) return 0;
+    r.src = src; r.dst = dst; r.len = len; r.slots_per_block = ceil_div(len, 4); r.blocks = blocks;
+    r.src_block = src_block; r.dst_block = dst_block;
+    r.dst_vec = vec_side(dst, dst_block, dst_stream) ? 1 : 0;
+    r.src_vec = src && vec_side(src, src_block, src_stream) ? 1 : 0;
+    return r.slots_per_block * blocks;
+}
+
 hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
                                 float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s) {
     if (n <= 0 || n_streams <= 0) return hipSuccess;
@@ -1176,22 +1163,11 @@ hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_stream
     a.n_streams = n_streams;
     a.slot_start = slot_start;
     int64_t most = 1;
-    auto aligned = [](const float* p, int64_t b1, int64_t b2) {
-        return !(reinterpret_cast<uintptr_t>(p) & 15) && !(b1 & 3) && !(b2 & 3);
-    };
-    for (int k = 0; k < kRowCopyParts; ++k) {
-        RowCopyDev& d = a.part[k];
-        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) {      // an empty part: no slots
-            d = RowCopyDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            continue;
-        }
+    for (int k = 0; k < n_parts; ++k) {
         const RowCopy& p = parts[k];
-        d.src = p.src; d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
-        d.src_block = p.src_block; d.dst_block = p.dst_block; d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
-        d.dst_vec = aligned(p.dst, p.dst_block, p.dst_stream) ? 1 : 0;
-        d.src_vec = p.src && aligned(p.src, p.src_block, p.src_stream) ? 1 : 0;
-        d.row_len = p.row_len; d.frame0 = p.frame0;
-        most = std::max(most, d.slots_per_block * d.blocks);
+        RowCopyDev& d = a.part[k];
+        most = std::max(most, fill_run(d.run, p.src, p.dst, p.len, p.blocks, p.src_block, p.dst_block, p.src_stream, p.dst_stream));
+        d.src_stream = p.src_stream; d.dst_stream = p.dst_stream; d.row_len = p.row_len; d.frame0 = p.frame0;
     }
     online_row_copies<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
@@ -1204,23 +1180,16 @@ hipError_t launch_slide_held(const RowCopy* parts, const HeldShift* shifts, int 
     a.n_streams = n_streams;
     a.slot_start = slot_start;
     int64_t most = 1;
-    auto aligned = [](const float* p, int64_t b1, int64_t b2) {
-        return !(reinterpret_cast<uintptr_t>(p) & 15) && !(b1 & 3) && !(b2 & 3);
-    };
-    for (int k = 0; k < kRowCopyParts; ++k) {
-        SlideDev& d = a.part[k];
-        d = SlideDev{nullptr, nullptr, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;      // an empty part: no slots
+    for (int k = 0; k < n_parts; ++k) {
         const RowCopy& p = parts[k];
         const HeldShift& h = shifts[k];
+        if (p.len <= 0 || p.blocks <= 0) continue;                // an empty part: no slots
         if (!p.src || !p.dst || p.row_len != 0 || h.delta > 0 || h.zero_below < 0) return hipErrorInvalidValue;
-        d.src = p.src; d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
-        d.src_block = p.src_block; d.dst_block = p.dst_block; d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
+        SlideDev& d = a.part[k];
+        most = std::max(most, fill_run(d.run, p.src, p.dst, p.len, p.blocks, p.src_block, p.dst_block, p.src_stream, p.dst_stream));
+        d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
         d.held_delta = h.delta; d.zero_below = std::min(h.zero_below, p.len);
-        d.dst_vec = aligned(p.dst, p.dst_block, p.dst_stream) ? 1 : 0;
-        d.src_vec = aligned(p.src, p.src_block, p.src_stream) ? 1 : 0;
-        d.held_vec = d.src_vec && !(h.delta & 3) ? 1 : 0;
-        most = std::max(most, d.slots_per_block * d.blocks);
+        d.held_vec = d.run.src_vec && !(h.delta & 3) ? 1 : 0;
     }
     online_slide_held<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
@@ -1313,15 +1282,10 @@ hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* 
     SlotResetArgs a{};
     a.slot_start = slot_start; a.value = value;
     int64_t most = 1;
-    for (int k = 0; k < kRowCopyParts; ++k) {
-        ZeroPartDev& d = a.part[k];
-        d = ZeroPartDev{nullptr, 0, 1, 0, 0, 0, 0};
-        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;
+    for (int k = 0; k < n_parts; ++k) {
         const ZeroPart& p = parts[k];
-        d.dst = p.dst; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
-        d.dst_block = p.dst_block; d.dst_stream = p.dst_stream;
-        d.vec = !(reinterpret_cast<uintptr_t>(p.dst) & 15) && !(p.dst_block & 3) && !(p.dst_stream & 3) ? 1 : 0;
-        most = std::max(most, d.slots_per_block * d.blocks);
+        most = std::max(most, fill_run(a.part[k].run, nullptr, p.dst, p.len, p.blocks, 0, p.dst_block, 0, p.dst_stream));
+        a.part[k].dst_stream = p.dst_stream;
     }
     for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
         a.n_slots = std::min<int32_t>(kSlotResetIds, n_slots - first);
@@ -1336,18 +1300,15 @@ hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* 
 // the parts of a slot move as the kernels take them; returns the slots of the longest part (-1: a part the kernels cannot take)
 static int64_t slot_move_args(const SlotMove* parts, int n_parts, SlotMoveArgs& a) {
     int64_t most = 1;
-    for (int k = 0; k < kRowCopyParts; ++k) {
-        SlotMoveDev& d = a.part[k];
-        d = SlotMoveDev{nullptr, nullptr, 0, 0, 1, 0, 0, 0, 0, 0, 0};
-        if (k >= n_parts || parts[k].len <= 0 || parts[k].blocks <= 0) continue;
+    for (int k = 0; k < n_parts; ++k) {
         const SlotMove& p = parts[k];
+        if (p.len <= 0 || p.blocks <= 0) continue;
         const bool reads = p.src && p.zero_below < p.len;
         if (!p.dst || p.zero_below < 0 || (!p.src && p.zero_below < p.len) || (reads && p.src_off + p.zero_below < 0)) return -1;
-        d.src = p.src; d.dst = p.dst; d.src_off = p.src_off; d.len = p.len; d.slots_per_block = ceil_div(p.len, 4); d.blocks = p.blocks;
-        d.src_block = p.src_block; d.dst_block = p.dst_block; d.zero_below = std::min(p.zero_below, p.len);
-        d.dst_vec = !(reinterpret_cast<uintptr_t>(p.dst) & 15) && !(p.dst_block & 3) ? 1 : 0;
-        d.src_vec = reads && !(reinterpret_cast<uintptr_t>(p.src) & 15) && !(p.src_off & 3) && !(p.src_block & 3) ? 1 : 0;
-        most = std::max(most, d.slots_per_block * d.blocks);
+        SlotMoveDev& d = a.part[k];
+        most = std::max(most, fill_run(d.run, p.src, p.dst, p.len, p.blocks, p.src_block, p.dst_block));
+        d.src_off = p.src_off; d.zero_below = std::min(p.zero_below, p.len);
+        d.run.src_vec = d.run.src_vec && reads && !(p.src_off & 3) ? 1 : 0;
     }
     return most;
 }
@@ -1450,6 +1411,15 @@ hipError_t launch_band_commit(float* tab, int32_t FS, int32_t n_slots, int32_t s
     return hipGetLastError();
 }
 
+// the gain fields of EmitArgs / LevelArgs from a caller's EmitGain (null: no gain, the fields stay zero)
+template <typename Args> static hipError_t set_gain(Args& a, const EmitGain* gain) {
+    if (!gain) return hipSuccess;
+    if (gain->scalar) { a.gain = kGainScalar; a.a = gain->a; return hipSuccess; }
+    if (!gain->a_tgt || gain->ramp < 0 || (gain->ramp > 0 && !gain->a_cur)) return hipErrorInvalidValue;
+    a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
+    return hipSuccess;
+}
+
 hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo, int64_t in_stream, const int64_t* slot_start,
                               int64_t pos0, int64_t hop, int32_t n_streams, int64_t n, int32_t ch, int dtype, const EmitDst* dsts,
                               int n_dsts, hipStream_t s, const EmitGain* gain, const float* bg_fg, const int64_t* live_len) {
@@ -1457,13 +1427,7 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
     if (count <= 0 || n_dsts <= 0) return hipSuccess;
     if (n_dsts > 2 || !bg || !hi) return hipErrorInvalidValue;
     EmitArgs a{};
-    if (gain) {
-        if (gain->scalar) { a.gain = kGainScalar; a.a = gain->a; }
-        else {
-            if (!gain->a_tgt || gain->ramp < 0 || (gain->ramp > 0 && !gain->a_cur)) return hipErrorInvalidValue;
-            a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
-        }
-    }
+    if (set_gain(a, gain) != hipSuccess) return hipErrorInvalidValue;
     a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.count = count; a.per = n * ch; a.n_samples = n;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_out = n_dsts; a.live_len = live_len;
     a.bg_only = live_len ? 1 : 0;
@@ -1510,13 +1474,7 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
     LevelArgs a{};
     a.tile = level_tile(ch);
     if (a.tile <= 0) return hipErrorNotSupported;
-    if (gain) {
-        if (gain->scalar) { a.gain = kGainScalar; a.a = gain->a; }
-        else {
-            if (!gain->a_tgt || gain->ramp < 0 || (gain->ramp > 0 && !gain->a_cur)) return hipErrorInvalidValue;
-            a.gain = kGainTables; a.a_cur = gain->a_cur; a.a_tgt = gain->a_tgt; a.ramp = gain->ramp;
-        }
-    }
+    if (set_gain(a, gain) != hipSuccess) return hipErrorInvalidValue;
     a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_chunks = (int32_t)chunks;
     a.dst = dst; a.partial = partials; a.live_len = live_len;

@@ -404,3 +404,32 @@ def test_host_form_equals_device_form():
     assert headers[2].tobytes() == headers[0].tobytes() and again.tobytes() == host_payload.tobytes()
     handle.close()
     twin.close()
+
+
+@pytest.mark.parametrize("lead", [1, 2, 3])
+def test_a_payload_that_is_only_4_byte_aligned_carries_the_same_bits(lead):
+    """A device payload that begins ``lead`` floats behind a 16-byte boundary: the export stores it element by element, the import
+    gathers its loads one by one. Both hand on the bits of the host forms, and the export writes nothing around the payload."""
+    L = lib()
+    x = signal()[:, :40 * H]
+    handle, twin = open_handle(), open_handle()
+    handle.push(x)
+    twin.push(x[::-1])
+    h, t = handle._handle(), twin._handle()
+    hb, pb = state_sizes(h)
+    headers = [np.zeros(hb, dtype=np.uint8) for _ in range(3)]
+    host_payload, again = np.full(pb // 4, SENT, dtype=np.float32), np.full(pb // 4, SENT, dtype=np.float32)
+    room = dev((pb // 4 + 4,), torch.float32)
+    assert room.data_ptr() % 16 == 0
+    odd = room[lead:lead + pb // 4]
+    assert L.repet_online_export_stream(h, 1, ptr(headers[0]), ptr(host_payload)) == 0
+    assert L.repet_online_export_stream_device(h, 1, ptr(headers[1]), dptr(odd), stream()) == 0
+    assert host_payload.any() and (host_payload != np.float32(SENT)).all()
+    same_bits(odd, host_payload)
+    untouched(room[:lead], room[lead + pb // 4:])
+    assert headers[0].tobytes() == headers[1].tobytes()
+    assert L.repet_online_import_stream_device(t, 0, ptr(headers[1]), dptr(odd), stream()) == 0, L.repet_last_error().decode()
+    assert L.repet_online_export_stream(t, 0, ptr(headers[2]), ptr(again)) == 0, L.repet_last_error().decode()
+    assert headers[2].tobytes() == headers[0].tobytes() and again.tobytes() == host_payload.tobytes()
+    handle.close()
+    twin.close()
