@@ -1118,6 +1118,26 @@ using namespace repet;
 
 namespace repet_eng {
 
+thread_local DevioReport* devio_report = nullptr;
+
+// the grid of a launch, on its way into the <<< >>> (engine.h: DevioReport)
+static dim3 noted(dim3 grid) {
+    if (devio_report) {
+        ++devio_report->launches;
+        devio_report->grid[0] = grid.x; devio_report->grid[1] = grid.y; devio_report->grid[2] = grid.z;
+    }
+    return grid;
+}
+static int noted_dense(int k, bool dense) {
+    if (devio_report) devio_report->dense[k] = dense ? 1 : 0;
+    return dense ? 1 : 0;
+}
+// part k as the kernel will take it (held_vec < 0: the launcher has none)
+static void noted_part(int k, const RunPart& r, int held_vec = -1) {
+    if (!devio_report) return;
+    devio_report->src_vec[k] = r.src_vec; devio_report->dst_vec[k] = r.dst_vec; devio_report->held_vec[k] = held_vec;
+}
+
 static dim3 stream_grid(int64_t slots, int32_t n_streams, int parts) {
     const int64_t y = std::min<int64_t>(n_streams, 65535);
     const int64_t x_cap = std::max<int64_t>(1, kMaxIoGroups / (y * parts));
@@ -1148,11 +1168,11 @@ hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, i
     IoGeo g{n * ch * n_streams, n, ch, src_strides[0], src_strides[1], src_strides[2]};
     const dim3 grid = stream_grid(ceil_div((dst_off & 3) + n * ch, 4), n_streams, 1);
     switch (dtype) {
-        case REPET_F64: online_append_f64<<<grid, kIoThreads, 0, s>>>(static_cast<const double*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
-        case REPET_F32: online_append_f32<<<grid, kIoThreads, 0, s>>>(static_cast<const float*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
-        case REPET_I16: online_append_i16<<<grid, kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
-        case REPET_F16: online_append_f16<<<grid, kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
-        default: online_append_bf16<<<grid, kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_F64: online_append_f64<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const double*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_F32: online_append_f32<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const float*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_I16: online_append_i16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        case REPET_F16: online_append_f16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
+        default: online_append_bf16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, n_streams, hi, lo, dst_stream, dst_off); break;
     }
     return hipGetLastError();
 }
@@ -1168,8 +1188,9 @@ hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_stream
         RowCopyDev& d = a.part[k];
         most = std::max(most, fill_run(d.run, p.src, p.dst, p.len, p.blocks, p.src_block, p.dst_block, p.src_stream, p.dst_stream));
         d.src_stream = p.src_stream; d.dst_stream = p.dst_stream; d.row_len = p.row_len; d.frame0 = p.frame0;
+        noted_part(k, d.run);
     }
-    online_row_copies<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
+    online_row_copies<<<noted(stream_grid(most, n_streams, n_parts)), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1190,8 +1211,9 @@ hipError_t launch_slide_held(const RowCopy* parts, const HeldShift* shifts, int 
         d.src_stream = p.src_stream; d.dst_stream = p.dst_stream;
         d.held_delta = h.delta; d.zero_below = std::min(h.zero_below, p.len);
         d.held_vec = d.run.src_vec && !(h.delta & 3) ? 1 : 0;
+        noted_part(k, d.run, d.held_vec);
     }
-    online_slide_held<<<stream_grid(most, n_streams, n_parts), kIoThreads, 0, s>>>(a);
+    online_slide_held<<<noted(stream_grid(most, n_streams, n_parts)), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1204,7 +1226,7 @@ hipError_t launch_slot_set(int64_t* slot_start, const int32_t* slots, const int6
     for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
         g.n = std::min<int32_t>(kSlotResetIds, n_slots - first);
         for (int32_t k = 0; k < g.n; ++k) { g.slot[k] = (unsigned short)slots[first + k]; g.value[k] = values[first + k]; }
-        online_slot_set<<<1, kIoThreads, 0, s>>>(g);
+        online_slot_set<<<noted(dim3(1)), kIoThreads, 0, s>>>(g);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1236,11 +1258,11 @@ hipError_t launch_feed(const void* src, int dtype, int64_t n, int32_t ch, const 
         if (most == 0) continue;
         const dim3 grid = stream_grid(ceil_div(3 + most * ch, 4), a.n_rows, 1);
         switch (dtype) {
-            case REPET_F64: online_feed_f64<<<grid, kIoThreads, 0, s>>>(static_cast<const double*>(src), g, a); break;
-            case REPET_F32: online_feed_f32<<<grid, kIoThreads, 0, s>>>(static_cast<const float*>(src), g, a); break;
-            case REPET_I16: online_feed_i16<<<grid, kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, a); break;
-            case REPET_F16: online_feed_f16<<<grid, kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, a); break;
-            case REPET_BF16: online_feed_bf16<<<grid, kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, a); break;
+            case REPET_F64: online_feed_f64<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const double*>(src), g, a); break;
+            case REPET_F32: online_feed_f32<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const float*>(src), g, a); break;
+            case REPET_I16: online_feed_i16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, a); break;
+            case REPET_F16: online_feed_f16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, a); break;
+            case REPET_BF16: online_feed_bf16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, a); break;
             default: return hipErrorInvalidValue;
         }
         const hipError_t e = hipGetLastError();
@@ -1268,7 +1290,7 @@ hipError_t launch_take(const float* hi, const float* lo, int64_t ring_stride, in
             if (rpos[first + k] < 0 || rpos[first + k] >= ring_len) return hipErrorInvalidValue;
             a.rpos[k] = (int32_t)rpos[first + k];
         }
-        online_take<<<stream_grid(ceil_div((dst_off & 3) + len, 4), a.n_slots, 1), kIoThreads, 0, s>>>(a);
+        online_take<<<noted(stream_grid(ceil_div((dst_off & 3) + len, 4), a.n_slots, 1)), kIoThreads, 0, s>>>(a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1286,11 +1308,12 @@ hipError_t launch_slot_reset(int64_t* slot_start, int64_t value, const int32_t* 
         const ZeroPart& p = parts[k];
         most = std::max(most, fill_run(a.part[k].run, nullptr, p.dst, p.len, p.blocks, 0, p.dst_block, 0, p.dst_stream));
         a.part[k].dst_stream = p.dst_stream;
+        noted_part(k, a.part[k].run);
     }
     for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
         a.n_slots = std::min<int32_t>(kSlotResetIds, n_slots - first);
         for (int32_t k = 0; k < a.n_slots; ++k) a.slot[k] = (unsigned short)slots[first + k];
-        online_slot_reset<<<stream_grid(most, a.n_slots, kRowCopyParts), kIoThreads, 0, s>>>(a);
+        online_slot_reset<<<noted(stream_grid(most, a.n_slots, kRowCopyParts)), kIoThreads, 0, s>>>(a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1309,6 +1332,7 @@ static int64_t slot_move_args(const SlotMove* parts, int n_parts, SlotMoveArgs& 
         most = std::max(most, fill_run(d.run, p.src, p.dst, p.len, p.blocks, p.src_block, p.dst_block));
         d.src_off = p.src_off; d.zero_below = std::min(p.zero_below, p.len);
         d.run.src_vec = d.run.src_vec && reads && !(p.src_off & 3) ? 1 : 0;
+        noted_part(k, d.run);
     }
     return most;
 }
@@ -1322,7 +1346,7 @@ hipError_t launch_slot_export(const SlotMove* parts, int n_parts, hipStream_t s)
     SlotMoveArgs a{};
     const int64_t most = slot_move_args(parts, n_parts, a);
     if (most < 0) return hipErrorInvalidValue;
-    online_slot_export<<<slot_move_grid(most), kIoThreads, 0, s>>>(a);
+    online_slot_export<<<noted(slot_move_grid(most)), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1333,7 +1357,7 @@ hipError_t launch_slot_import(const SlotMove* parts, int n_parts, int64_t* slot_
     const int64_t most = slot_move_args(parts, n_parts, a);
     if (most < 0) return hipErrorInvalidValue;
     a.slot_start = slot_start; a.value = value; a.shift = shift; a.slot = slot; a.n_slots = n_slots;
-    online_slot_import<<<slot_move_grid(most), kIoThreads, 0, s>>>(a);
+    online_slot_import<<<noted(slot_move_grid(most)), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1344,18 +1368,18 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
     IoGeo g{count, n, ch, strides[0], strides[1], strides[2]};
     if (dtype == REPET_F64) {
         const dim3 grid((unsigned)ceil_div(ceil_div(count, 2), kIoThreads));
-        devio_egress_f64<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<double*>(dst));
+        devio_egress_f64<<<noted(grid), kIoThreads, 0, s>>>(in, g, noted_dense(0, is_dense(dst, g, n_streams, 16)), static_cast<double*>(dst));
     } else if (dtype == REPET_F32) {
         const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
-        devio_egress_f32<<<grid, kIoThreads, 0, s>>>(in, g, is_dense(dst, g, n_streams, 16) ? 1 : 0, static_cast<float*>(dst));
+        devio_egress_f32<<<noted(grid), kIoThreads, 0, s>>>(in, g, noted_dense(0, is_dense(dst, g, n_streams, 16)), static_cast<float*>(dst));
     } else {
         // a dense 16-bit destination takes one store of kEpt16 elements per lane: aligned for that, or element by element
         const dim3 grid((unsigned)ceil_div(ceil_div(count, kEpt16), kIoThreads));
-        const int dense = is_dense(dst, g, n_streams, 2 * kEpt16) ? 1 : 0;
+        const int dense = noted_dense(0, is_dense(dst, g, n_streams, 2 * kEpt16));
         switch (dtype) {
-            case REPET_I16: devio_egress_i16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<int16_t*>(dst)); break;
-            case REPET_F16: devio_egress_f16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<Half*>(dst)); break;
-            case REPET_BF16: devio_egress_bf16<<<grid, kIoThreads, 0, s>>>(in, g, dense, static_cast<BHalf*>(dst)); break;
+            case REPET_I16: devio_egress_i16<<<noted(grid), kIoThreads, 0, s>>>(in, g, dense, static_cast<int16_t*>(dst)); break;
+            case REPET_F16: devio_egress_f16<<<noted(grid), kIoThreads, 0, s>>>(in, g, dense, static_cast<Half*>(dst)); break;
+            case REPET_BF16: devio_egress_bf16<<<noted(grid), kIoThreads, 0, s>>>(in, g, dense, static_cast<BHalf*>(dst)); break;
             default: return hipErrorInvalidValue;
         }
     }
@@ -1365,7 +1389,7 @@ hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, i
 hipError_t launch_gain_fill(float* table, int32_t n, float a, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (!table) return hipErrorInvalidValue;
-    online_gain_fill<<<1, kIoThreads, 0, s>>>(table, n, a);
+    online_gain_fill<<<noted(dim3(1)), kIoThreads, 0, s>>>(table, n, a);
     return hipGetLastError();
 }
 
@@ -1378,7 +1402,7 @@ hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int
     for (int32_t first = 0; first < n_slots; first += kSlotResetIds) {
         g.n = std::min<int32_t>(kSlotResetIds, n_slots - first);
         for (int32_t k = 0; k < g.n; ++k) { g.slot[k] = (unsigned short)slots[first + k]; g.a[k] = a[first + k]; }
-        online_gain_set<<<1, kIoThreads, 0, s>>>(g);
+        online_gain_set<<<noted(dim3(1)), kIoThreads, 0, s>>>(g);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1388,7 +1412,7 @@ hipError_t launch_gain_set(float* tgt, const int32_t* slots, const float* a, int
 hipError_t launch_gain_commit(const float* tgt, const float* cur_old, float* cur_new, int32_t n_slots, int32_t slot, hipStream_t s) {
     if (n_slots <= 0) return hipSuccess;
     if (!tgt || !cur_old || !cur_new || cur_old == cur_new || slot >= n_slots) return hipErrorInvalidValue;
-    online_gain_commit<<<1, kIoThreads, 0, s>>>(tgt, cur_old, cur_new, n_slots, slot);
+    online_gain_commit<<<noted(dim3(1)), kIoThreads, 0, s>>>(tgt, cur_old, cur_new, n_slots, slot);
     return hipGetLastError();
 }
 
@@ -1399,14 +1423,14 @@ hipError_t launch_band_expand(float* tab, int32_t FS, int32_t F, const int32_t* 
     if (n <= 0) return hipSuccess;
     if (!tab || !job || FS < F || F < 1 || n > 65535 || n_bands < 1 || n_bands > F || rows < 1) return hipErrorInvalidValue;
     const BandExpandArgs a{tab, job, FS, F, n, n_bands, rows, init ? 1 : 0};
-    online_band_expand<<<dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)n), kIoThreads, 0, s>>>(a);
+    online_band_expand<<<noted(dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)n)), kIoThreads, 0, s>>>(a);
     return hipGetLastError();
 }
 
 hipError_t launch_band_commit(float* tab, int32_t FS, int32_t n_slots, int32_t slot, int mode, const int64_t* slot_start, hipStream_t s) {
     if (n_slots <= 0) return hipSuccess;
     if (!tab || FS < 1 || n_slots > 65535 || slot >= n_slots || mode < kBandCommit || mode > kBandCarry) return hipErrorInvalidValue;
-    online_band_commit<<<dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)(slot < 0 ? n_slots : 1)), kIoThreads, 0, s>>>(
+    online_band_commit<<<noted(dim3((unsigned)ceil_div(FS, kIoThreads), (unsigned)(slot < 0 ? n_slots : 1))), kIoThreads, 0, s>>>(
         tab, FS, slot, mode, slot_start);
     return hipGetLastError();
 }
@@ -1436,15 +1460,15 @@ hipError_t launch_stream_emit(const float* bg, const float* hi, const float* lo,
     const int vec_bytes = dtype == REPET_F64 || dtype == REPET_F32 ? 16 : 2 * kEpt16;
     for (int k = 0; k < n_dsts; ++k) {
         const IoGeo g{count, n, ch, dsts[k].strides[0], dsts[k].strides[1], dsts[k].strides[2]};
-        a.out[k] = EmitOut{dsts[k].p, g.s_clip, g.s_sample, g.s_channel, dsts[k].which, is_dense(dsts[k].p, g, n_streams, vec_bytes) ? 1 : 0};
+        a.out[k] = EmitOut{dsts[k].p, g.s_clip, g.s_sample, g.s_channel, dsts[k].which, noted_dense(k, is_dense(dsts[k].p, g, n_streams, vec_bytes))};
     }
     const dim3 grid16((unsigned)ceil_div(ceil_div(count, kEpt16), kIoThreads));
     switch (dtype) {
-        case REPET_F64: devio_emit_f64<<<dim3((unsigned)ceil_div(ceil_div(count, 2), kIoThreads)), kIoThreads, 0, s>>>(a); break;
-        case REPET_F32: devio_emit_f32<<<dim3((unsigned)ceil_div(ceil_div(count, 4), kIoThreads)), kIoThreads, 0, s>>>(a); break;
-        case REPET_I16: devio_emit_i16<<<grid16, kIoThreads, 0, s>>>(a); break;
-        case REPET_F16: devio_emit_f16<<<grid16, kIoThreads, 0, s>>>(a); break;
-        case REPET_BF16: devio_emit_bf16<<<grid16, kIoThreads, 0, s>>>(a); break;
+        case REPET_F64: devio_emit_f64<<<noted(dim3((unsigned)ceil_div(ceil_div(count, 2), kIoThreads))), kIoThreads, 0, s>>>(a); break;
+        case REPET_F32: devio_emit_f32<<<noted(dim3((unsigned)ceil_div(ceil_div(count, 4), kIoThreads))), kIoThreads, 0, s>>>(a); break;
+        case REPET_I16: devio_emit_i16<<<noted(grid16), kIoThreads, 0, s>>>(a); break;
+        case REPET_F16: devio_emit_f16<<<noted(grid16), kIoThreads, 0, s>>>(a); break;
+        case REPET_BF16: devio_emit_bf16<<<noted(grid16), kIoThreads, 0, s>>>(a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1478,10 +1502,10 @@ hipError_t launch_stream_levels(const float* bg, const float* hi, const float* l
     a.bg = bg; a.bg_fg = bg_fg; a.hi = hi; a.lo = lo; a.in_stream = in_stream; a.per = n * ch;
     a.slot_start = slot_start; a.pos0 = pos0; a.hop = hop; a.n_channels = ch; a.n_chunks = (int32_t)chunks;
     a.dst = dst; a.partial = partials; a.live_len = live_len;
-    devio_levels<<<dim3((unsigned)chunks, (unsigned)n_streams), kIoThreads, 0, s>>>(a);
+    devio_levels<<<noted(dim3((unsigned)chunks, (unsigned)n_streams)), kIoThreads, 0, s>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || chunks == 1) return e;
-    devio_levels_fold<<<dim3((unsigned)(n_streams * ch)), 64, 0, s>>>(partials, (int32_t)chunks, dst, live_len, ch);
+    devio_levels_fold<<<noted(dim3((unsigned)(n_streams * ch))), 64, 0, s>>>(partials, (int32_t)chunks, dst, live_len, ch);
     return hipGetLastError();
 }
 
@@ -1563,12 +1587,41 @@ hipError_t launch_tail_clear(float2* X, float* Mk, int64_t spec_stride, int64_t 
     if (!X || !lengths_dev || n_clips > 65535 || ch < 1 || ch > 65535 || (FS & 3)) return hipErrorInvalidValue;
     const int64_t groups = ceil_div(longest_tail * FS, (int64_t)kIoThreads * 4);
     const int64_t x_cap = std::max<int64_t>(1, kMaxIoGroups / ((int64_t)n_clips * ch));
-    devio_tail_clear<<<dim3((unsigned)std::min(groups, x_cap), (unsigned)n_clips, (unsigned)ch), kIoThreads, 0, s>>>(
+    devio_tail_clear<<<noted(dim3((unsigned)std::min(groups, x_cap), (unsigned)n_clips, (unsigned)ch)), kIoThreads, 0, s>>>(
         X, Mk, spec_stride, chan_stride, T, FS, W, H, lengths_dev);
     return hipGetLastError();
 }
 
-// the strided ingest, equal clips (lengths null) or ragged ones (lengths[b] in [0, n], checked by the caller, not all equal to n)
+// the strided ingest, equal clips (len_dev null) or ragged ones
+hipError_t launch_ingest(const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t strides[3], float* hi,
+                         float* lo, unsigned int* flag, const int64_t* len_dev, hipStream_t s) {
+    const int64_t count = n * ch * n_clips;
+    if (count <= 0) return hipSuccess;
+    if (!src || !hi || (dtype == REPET_F64 && !lo) || (reinterpret_cast<uintptr_t>(hi) & 15) ||
+        (dtype == REPET_F64 && (reinterpret_cast<uintptr_t>(lo) & 15)) || dtype < REPET_F32 || dtype > REPET_BF16)
+        return hipErrorInvalidValue;
+    IoGeo g{count, n, ch, strides[0], strides[1], strides[2]};
+    const int vec_bytes = dtype == REPET_F64 ? 16 : 4 * element_size(dtype);
+    const int dense = noted_dense(0, is_dense(src, g, n_clips, vec_bytes));
+    const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
+    if (len_dev) switch (dtype) {
+        case REPET_F64: devio_ingest_ragged_f64<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const double*>(src), g, dense, hi, lo, flag, len_dev); break;
+        case REPET_F32: devio_ingest_ragged_f32<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+        case REPET_I16: devio_ingest_ragged_i16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+        case REPET_F16: devio_ingest_ragged_f16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+        default: devio_ingest_ragged_bf16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag, len_dev); break;
+    }
+    else switch (dtype) {
+        case REPET_F64: devio_ingest_f64<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const double*>(src), g, dense, hi, lo, flag); break;
+        case REPET_F32: devio_ingest_f32<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag); break;
+        case REPET_I16: devio_ingest_i16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag); break;
+        case REPET_F16: devio_ingest_f16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag); break;
+        default: devio_ingest_bf16<<<noted(grid), kIoThreads, 0, s>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag); break;
+    }
+    return hipGetLastError();
+}
+
+// the upload through it: equal clips (lengths null) or ragged ones (lengths[b] in [0, n], checked by the caller, not all equal to n)
 static int upload_strided(repet_ctx* c, const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t strides[3],
                           const int64_t* lengths, void* wait_stream) {
     if (!c) return fail(REPET_ERR_BAD_ARG, "ctx is null");
@@ -1603,29 +1656,8 @@ static int upload_strided(repet_ctx* c, const void* src, int dtype, int32_t n_cl
         flag = c->nonfinite_word.as<unsigned int>();
         HIP_TRY(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
     }
-    if (count > 0) {
-        IoGeo g{count, n, ch, strides[0], strides[1], strides[2]};
-        const int vec_bytes = dtype == REPET_F64 ? 16 : 4 * element_size(dtype);
-        const int dense = is_dense(src, g, n_clips, vec_bytes) ? 1 : 0;
-        const dim3 grid((unsigned)ceil_div(ceil_div(count, 4), kIoThreads));
-        float* hi = c->audio.as<float>();
-        float* lo = c->audio_lo.as<float>();
-        if (len_dev) switch (dtype) {
-            case REPET_F64: devio_ingest_ragged_f64<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const double*>(src), g, dense, hi, lo, flag, len_dev); break;
-            case REPET_F32: devio_ingest_ragged_f32<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag, len_dev); break;
-            case REPET_I16: devio_ingest_ragged_i16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag, len_dev); break;
-            case REPET_F16: devio_ingest_ragged_f16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag, len_dev); break;
-            default: devio_ingest_ragged_bf16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag, len_dev); break;
-        }
-        else switch (dtype) {
-            case REPET_F64: devio_ingest_f64<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const double*>(src), g, dense, hi, lo, flag); break;
-            case REPET_F32: devio_ingest_f32<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const float*>(src), g, dense, hi, nullptr, flag); break;
-            case REPET_I16: devio_ingest_i16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const int16_t*>(src), g, dense, hi, nullptr, flag); break;
-            case REPET_F16: devio_ingest_f16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const Half*>(src), g, dense, hi, nullptr, flag); break;
-            default: devio_ingest_bf16<<<grid, kIoThreads, 0, c->stream>>>(static_cast<const BHalf*>(src), g, dense, hi, nullptr, flag); break;
-        }
-        HIP_TRY(hipGetLastError());
-    }
+    if (count > 0)
+        HIP_TRY(launch_ingest(src, dtype, n_clips, n, ch, strides, c->audio.as<float>(), c->audio_lo.as<float>(), flag, len_dev, c->stream));
     if (refuse) {
         // the refusal mode's one host wait: the flag word decides whether the clip is accepted
         unsigned int seen = 0;

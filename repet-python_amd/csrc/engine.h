@@ -352,6 +352,16 @@ int signal_caller(repet_ctx* c, void* signal_stream);
 // a background gain g in [0, 1] (BAD_ARG otherwise, NaN included) and what the egress multiplies the background by: (float)(1 - g)
 int check_background_gain(float gain);
 float background_gain_factor(float gain);
+// What the launchers of devio.hip (below) decided, for the stage entry of this family (repet_debug_devio_stage, engine_stages.hip): while
+// devio_report points at a record, every launch of devio.hip notes its grid there and counts, and the launchers note their own
+// dense / src_vec / dst_vec / held_vec decisions as they pass them to the kernels (-1: not decided by this call). Null otherwise.
+struct DevioReport {
+    int64_t launches = 0;
+    int64_t grid[3] = {0, 0, 0};                                  // of the last launch
+    int64_t dense[2] = {-1, -1};
+    int64_t src_vec[5] = {-1, -1, -1, -1, -1}, dst_vec[5] = {-1, -1, -1, -1, -1}, held_vec[5] = {-1, -1, -1, -1, -1};
+};
+extern thread_local DevioReport* devio_report;
 // the streaming handle's per-push data movement (devio.hip), n_streams streams at per-stream element strides:
 //   append   chunk [S][n][C] (strided, any device dtype) -> hi / lo at s * dst_stream + dst_off (fp32 + fp32 remainder)
 //   copies   up to kRowCopyParts parts of `blocks` runs of `len` floats per stream (src null: zeros), one launch
@@ -362,6 +372,7 @@ float background_gain_factor(float gain);
 //            kRowCopyParts runs of zeros per slot (ZeroPart, strides as RowCopy's), one launch per kSlotResetIds slots
 struct RowCopy { const float* src; float* dst; int64_t len, blocks, src_block, dst_block, src_stream, dst_stream; int64_t row_len = 0, frame0 = 0; };
 constexpr int kRowCopyParts = 5;
+static_assert(sizeof(DevioReport::src_vec) / sizeof(int64_t) == kRowCopyParts, "DevioReport holds one entry per part");
 struct ZeroPart { float* dst; int64_t len, blocks, dst_block, dst_stream; };
 constexpr int kSlotResetIds = 256;
 constexpr int64_t kSlotIdle = (int64_t)1 << 60;
@@ -400,6 +411,11 @@ hipError_t launch_slot_import(const SlotMove* parts, int n_parts, int64_t* slot_
 hipError_t launch_stream_append(const void* src, int dtype, int32_t n_streams, int64_t n, int32_t ch, const int64_t src_strides[3],
                                 float* hi, float* lo, int64_t dst_stream, int64_t dst_off, hipStream_t s);
 hipError_t launch_row_copies(const RowCopy* parts, int n_parts, int32_t n_streams, hipStream_t s, const int64_t* slot_start = nullptr);
+//   ingest   source [n_clips][n][ch] (strided, any ingest dtype) -> hi fp32 interleaved and, for float64, the remainders lo;
+//            flag (nullable): set to 1 where a live float sample is not finite; len_dev (nullable): the ragged form, clip b live
+//            below sample len_dev[b]. hi / lo 16-byte aligned. One launch
+hipError_t launch_ingest(const void* src, int dtype, int32_t n_clips, int64_t n, int32_t ch, const int64_t strides[3], float* hi,
+                         float* lo, unsigned int* flag, const int64_t* len_dev, hipStream_t s);
 hipError_t launch_stream_egress(const float* in, int32_t n_streams, int64_t n, int32_t ch, void* dst, int dtype,
                                 const int64_t strides[3], hipStream_t s);
 //   emit     background / foreground / mixture of an emission (or of an offline result) into one or two strided destinations

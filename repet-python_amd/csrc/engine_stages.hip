@@ -1196,3 +1196,374 @@ int repet_debug_peaks_stage(repet_ctx* c, const float* M, int32_t n_batch, int64
 }
 
 }  // extern "C"
+
+// ---- the stage entry of devio.hip (tests/test_gpu_devio_stages.py) ------------------------------------------------------
+// repet_debug_devio_stage runs ONE production launcher of devio.hip, unchanged, on device buffers the caller describes ("arenas").
+// Arena k is arena_bytes[k] bytes of the caller's; it is uploaded into an allocation of its own whose every other byte holds
+// `prefill`, its first byte arena_shift[k] (0, 4, 8 or 12; 2 for an arena of 16-bit elements) bytes behind a 256-byte boundary, and it comes back whole with
+// kArenaGuard bytes of that prefill in front of and behind it (arena_out[k]: arena_bytes[k] + 2 * kArenaGuard bytes). Every pointer
+// argument of a launcher is a pair of words (arena, offset in elements of the pointer's type; arena < 0: null). The words `iv`
+// are read in the order the op's branch below reads them; `fv` holds the float arguments. Before anything is enqueued the entry
+// walks what the launch may read and write: a cell outside the caller's bytes of an arena is REPET_ERR_BAD_ARG, never an access.
+// report_out[24] is the launcher's DevioReport: launches, grid[3], dense[2], src_vec[5], dst_vec[5], held_vec[5], 0 ..
+namespace {
+constexpr int64_t kArenaGuard = 512;
+constexpr int64_t kStageMax = (int64_t)1 << 28;
+
+struct Ref { int64_t arena = -1, off = 0; };
+
+struct Words {
+    const int64_t* v; int32_t n; int32_t at = 0; bool bad = false;
+    int64_t any() { if (at >= n) { bad = true; return 0; } return v[at++]; }
+    int64_t size() { const int64_t x = any(); if (x < 0 || x > kStageMax) bad = true; return bad ? 0 : x; }        // a count or a stride
+    int64_t off() { const int64_t x = any(); if (x < -kStageMax || x > kStageMax) bad = true; return bad ? 0 : x; }
+    // the length of a list that follows in the words: never more than the words that are left (it sizes a host vector)
+    int64_t count() { const int64_t x = size(); if (x > n - at) bad = true; return bad ? 0 : x; }
+    Ref ref() { Ref r; r.arena = off(); r.off = size(); return r; }
+};
+
+struct Arenas {
+    std::vector<Scratch> dev; std::vector<char*> first; std::vector<int64_t> bytes; std::vector<const char*> host; std::vector<int32_t> shift;
+    explicit Arenas(int n) : dev((size_t)n), first((size_t)n), bytes((size_t)n), host((size_t)n), shift((size_t)n) {}
+    // elements [lo, hi) of `es` bytes, counted from the element r names, lie in the caller's bytes (nothing to hold: true).
+    // An arena 2 bytes off the boundary holds 16-bit elements only: nothing wider is ever read at half its own alignment.
+    bool holds(Ref r, int64_t lo, int64_t hi, int es) const {
+        if (r.arena >= 0 && r.arena < (int64_t)bytes.size() && shift[(size_t)r.arena] == 2 && es != 2) return false;
+        if (hi <= lo) return r.arena < (int64_t)bytes.size();
+        if (r.arena < 0 || r.arena >= (int64_t)bytes.size()) return false;
+        return r.off + lo >= 0 && (r.off + hi) * es <= bytes[(size_t)r.arena];
+    }
+    bool null_or_holds(Ref r, int64_t lo, int64_t hi, int es) const { return r.arena < 0 || holds(r, lo, hi, es); }
+    template <typename T> T* at(Ref r) const { return r.arena < 0 ? nullptr : reinterpret_cast<T*>(first[(size_t)r.arena] + r.off * (int64_t)sizeof(T)); }
+    void* at_bytes(Ref r, int es) const { return r.arena < 0 ? nullptr : first[(size_t)r.arena] + r.off * es; }
+    template <typename T> const T* on_host(Ref r) const { return reinterpret_cast<const T*>(host[(size_t)r.arena] + r.off * (int64_t)sizeof(T)); }
+    bool aligned(Ref r, int es, int to) const { return r.arena < 0 || !(reinterpret_cast<uintptr_t>(at_bytes(r, es)) % (uintptr_t)to); }
+};
+
+// the elements of a [B][n][C] are few enough that no extent below overflows: at most kStageMax of them
+bool plane_ok(int64_t B, int64_t n, int64_t C) {
+    return B >= 1 && n >= 1 && C >= 1 && n * C <= kStageMax && B * (n * C) <= kStageMax;       // (each factor is at most kStageMax = 2^28)
+}
+// one past the largest element offset of a strided [B][n][C]
+int64_t span3(const int64_t st[3], int64_t B, int64_t n, int64_t C) {
+    return B < 1 || n < 1 || C < 1 ? 0 : st[0] * (B - 1) + st[1] * (n - 1) + st[2] * (C - 1) + 1;
+}
+// one past the last float of a part's runs over S streams (or slots)
+int64_t run_span(int64_t len, int64_t blocks, int64_t block, int64_t S, int64_t stream) {
+    return len < 1 || blocks < 1 || S < 1 ? 0 : (S - 1) * stream + (blocks - 1) * block + len;
+}
+
+enum DevioOp {
+    kOpIngest = 0, kOpEgress, kOpEmit, kOpLevels, kOpTailClear, kOpAppend, kOpRowCopies, kOpSlideHeld, kOpSlotSet, kOpFeed, kOpTake,
+    kOpSlotReset, kOpSlotExport, kOpSlotImport, kOpGainFill, kOpGainSet, kOpGainCommit, kOpBandExpand, kOpBandCommit
+};
+
+// the gain words of emit and levels: mode (0 none, 1 scalar fv[0], 2 tables), a_cur, a_tgt, ramp
+bool read_gain(Words& w, const Arenas& A, int64_t S, const double* fv, int32_t n_fv, EmitGain& g, bool& present) {
+    const int64_t mode = w.size();
+    const Ref cur = w.ref(), tgt = w.ref();
+    g.ramp = w.off();
+    if (w.bad || mode > 2) return false;
+    present = mode != 0;
+    if (mode == 1) { if (n_fv < 1) return false; g.scalar = true; g.a = (float)fv[0]; }
+    if (mode == 2) {
+        if (!A.holds(tgt, 0, S, 4) || !A.null_or_holds(cur, 0, S, 4)) return false;
+        g.a_cur = A.at<float>(cur); g.a_tgt = A.at<float>(tgt);
+    }
+    return true;
+}
+
+hipError_t run_devio_op(int32_t op, const Arenas& A, Words& w, const double* fv, int32_t n_fv, hipStream_t s, bool& refused) {
+    refused = true;                                               // (every early return below is a refusal)
+    switch (op) {
+    case kOpIngest: case kOpAppend: case kOpFeed: {
+        const int dtype = (int)w.size();
+        const int64_t B = w.size(), n = w.size(), C = w.size();
+        const int64_t st[3] = {w.size(), w.size(), w.size()};
+        const Ref src = w.ref(), hi = w.ref(), lo = w.ref();
+        const int es = dtype_bytes(dtype);
+        if (w.bad || !es || !plane_ok(B, n, C) || B > 65535 || !A.holds(src, 0, span3(st, B, n, C), es)) return hipErrorInvalidValue;
+        if (op == kOpIngest) {
+            const Ref flag = w.ref(), len = w.ref();
+            if (w.bad || !A.holds(hi, 0, B * n * C, 4) || (dtype == REPET_F64 && !A.holds(lo, 0, B * n * C, 4)) ||
+                !A.null_or_holds(flag, 0, 1, 4) || !A.null_or_holds(len, 0, B, 8))
+                return hipErrorInvalidValue;
+            refused = false;
+            return launch_ingest(A.at_bytes(src, es), dtype, (int32_t)B, n, (int32_t)C, st, A.at<float>(hi), A.at<float>(lo),
+                                 A.at<unsigned int>(flag), A.at<int64_t>(len), s);
+        }
+        if (op == kOpAppend) {
+            const int64_t d_stream = w.size(), d_off = w.size();
+            const int64_t end = (B - 1) * d_stream + d_off + n * C;
+            if (w.bad || !A.holds(hi, 0, end, 4) || !A.holds(lo, 0, end, 4)) return hipErrorInvalidValue;
+            refused = false;
+            return launch_stream_append(A.at_bytes(src, es), dtype, (int32_t)B, n, (int32_t)C, st, A.at<float>(hi), A.at<float>(lo), d_stream, d_off, s);
+        }
+        const int64_t ring_stride = w.size(), ring_len = w.size();
+        if (w.bad || 3 * B > w.n - w.at) return hipErrorInvalidValue;                     // (three lists of B words follow)
+        std::vector<int32_t> slots((size_t)B);
+        std::vector<int64_t> counts((size_t)B), wpos((size_t)B);
+        int64_t top = 0;
+        for (auto& v : slots) { v = (int32_t)w.size(); top = std::max<int64_t>(top, v); }
+        for (auto& v : counts) v = w.off();
+        for (auto& v : wpos) v = w.off();
+        if (w.bad || top > 65535 || !A.holds(hi, 0, (top + 1) * ring_stride, 4) || !A.holds(lo, 0, (top + 1) * ring_stride, 4))
+            return hipErrorInvalidValue;
+        refused = false;
+        return launch_feed(A.at_bytes(src, es), dtype, n, (int32_t)C, st, slots.data(), counts.data(), wpos.data(), (int32_t)B, A.at<float>(hi),
+                           A.at<float>(lo), ring_stride, ring_len, s);
+    }
+    case kOpEgress: {
+        const int dtype = (int)w.size();
+        const int64_t S = w.size(), n = w.size(), C = w.size();
+        const int64_t st[3] = {w.size(), w.size(), w.size()};
+        const Ref in = w.ref(), dst = w.ref();
+        const int es = dtype_bytes(dtype);
+        if (w.bad || !es || !plane_ok(S, n, C) || !A.holds(in, 0, S * n * C, 4) || !A.aligned(in, 4, 16) ||
+            !A.holds(dst, 0, span3(st, S, n, C), es))
+            return hipErrorInvalidValue;
+        refused = false;
+        return launch_stream_egress(A.at<float>(in), (int32_t)S, n, (int32_t)C, A.at_bytes(dst, es), dtype, st, s);
+    }
+    case kOpEmit: case kOpLevels: {
+        const int dtype = op == kOpEmit ? (int)w.size() : REPET_F64;
+        const int64_t S = w.size(), n = w.size(), C = w.size(), in_stream = w.size(), pos0 = w.any(), hop = w.any();
+        const Ref bg = w.ref(), hi = w.ref(), lo = w.ref(), table = w.ref(), bg_fg = w.ref(), live_len = w.ref();
+        EmitGain gain;
+        bool with_gain = false;
+        const int es = dtype_bytes(dtype);
+        if (w.bad || !es || !plane_ok(S, n, C) || S > 65535 || !read_gain(w, A, S, fv, n_fv, gain, with_gain)) return hipErrorInvalidValue;
+        const int64_t per = n * C;
+        if (!A.holds(bg, 0, S * per, 4) || !A.null_or_holds(bg_fg, 0, S * per, 4) || !A.holds(hi, 0, (S - 1) * in_stream + per, 4) ||
+            !A.null_or_holds(lo, 0, (S - 1) * in_stream + per, 4) || !A.null_or_holds(table, 0, S, 8) || !A.null_or_holds(live_len, 0, S, 8))
+            return hipErrorInvalidValue;
+        if (op == kOpLevels) {
+            const Ref dst = w.ref(), partial = w.ref();
+            if (w.bad || !A.holds(dst, 0, S * C * REPET_LEVEL_FIELDS, 8) ||
+                !A.null_or_holds(partial, 0, stream_levels_partials((int32_t)S, n, (int32_t)C), 8))
+                return hipErrorInvalidValue;
+            refused = false;
+            return launch_stream_levels(A.at<float>(bg), A.at<float>(hi), A.at<float>(lo), in_stream, A.at<int64_t>(table), pos0, hop, (int32_t)S, n,
+                                        (int32_t)C, A.at<double>(dst), A.at<double>(partial), s, with_gain ? &gain : nullptr, A.at<float>(bg_fg),
+                                        A.at<int64_t>(live_len));
+        }
+        // (emit_body reads bg and bg_fg in whole vectors of a thread's run: 16 bytes, 8 for float64)
+        if (!A.aligned(bg, 4, 16) || !A.aligned(bg_fg, 4, 16)) return hipErrorInvalidValue;
+        const int64_t n_dsts = w.size();
+        if (w.bad || n_dsts < 1 || n_dsts > 2) return hipErrorInvalidValue;
+        EmitDst d[2];
+        for (int k = 0; k < n_dsts; ++k) {
+            d[k].which = (int)w.size();
+            for (int q = 0; q < 3; ++q) d[k].strides[q] = w.size();
+            const Ref p = w.ref();
+            if (w.bad || d[k].which < REPET_OUT_BACKGROUND || d[k].which > REPET_OUT_MIXTURE || !A.holds(p, 0, span3(d[k].strides, S, n, C), es))
+                return hipErrorInvalidValue;
+            d[k].p = A.at_bytes(p, es);
+        }
+        refused = false;
+        return launch_stream_emit(A.at<float>(bg), A.at<float>(hi), A.at<float>(lo), in_stream, A.at<int64_t>(table), pos0, hop, (int32_t)S, n, (int32_t)C,
+                                  dtype, d, (int)n_dsts, s, with_gain ? &gain : nullptr, A.at<float>(bg_fg), A.at<int64_t>(live_len));
+    }
+    case kOpTailClear: {
+        const int64_t B = w.size(), C = w.size(), T = w.size(), FS = w.size(), W = w.size(), H = w.size(), spec = w.size(), chan = w.size(),
+                      longest = w.size();
+        const Ref X = w.ref(), Mk = w.ref(), len = w.ref();
+        const int64_t cells = B < 1 || C < 1 ? 0 : (B - 1) * spec + (C - 1) * chan + T * FS;
+        if (w.bad || B < 1 || C < 1 || H < 1 || FS < 4 || (spec & 3) || (chan & 3) || !A.holds(X, 0, cells, 8) || !A.aligned(X, 8, 16) ||
+            !A.null_or_holds(Mk, 0, cells, 4) || !A.aligned(Mk, 4, 16) || !A.holds(len, 0, B, 8))
+            return hipErrorInvalidValue;
+        refused = false;
+        return launch_tail_clear(A.at<float2>(X), A.at<float>(Mk), spec, chan, (int32_t)B, (int32_t)C, T, (int32_t)FS, (int32_t)W, (int32_t)H,
+                                 A.at<int64_t>(len), longest, s);
+    }
+    case kOpRowCopies: case kOpSlideHeld: {
+        const int64_t n_parts = w.size(), S = w.size();
+        const Ref table = w.ref();
+        if (w.bad || n_parts > kRowCopyParts || S < 1 || !A.null_or_holds(table, 0, S, 8)) return hipErrorInvalidValue;
+        RowCopy parts[kRowCopyParts];
+        HeldShift shifts[kRowCopyParts];
+        for (int k = 0; k < n_parts; ++k) {
+            const Ref src = w.ref(), dst = w.ref();
+            RowCopy& p = parts[k];
+            p.len = w.size(); p.blocks = w.size(); p.src_block = w.size(); p.dst_block = w.size(); p.src_stream = w.size(); p.dst_stream = w.size();
+            p.row_len = w.size(); p.frame0 = w.any();
+            shifts[k] = HeldShift{0, 0};
+            if (op == kOpSlideHeld) { shifts[k].delta = w.off(); shifts[k].zero_below = w.size(); }
+            // (a held stream reads from `delta` floats further on, from element zero_below of a run)
+            const int64_t low = std::min<int64_t>(0, shifts[k].delta + std::min(shifts[k].zero_below, p.len));
+            if (w.bad || !A.holds(dst, 0, run_span(p.len, p.blocks, p.dst_block, S, p.dst_stream), 4) ||
+                !A.null_or_holds(src, low, run_span(p.len, p.blocks, p.src_block, S, p.src_stream), 4))
+                return hipErrorInvalidValue;
+            p.src = A.at<float>(src); p.dst = A.at<float>(dst);
+        }
+        refused = false;
+        if (op == kOpRowCopies) return launch_row_copies(parts, (int)n_parts, (int32_t)S, s, A.at<int64_t>(table));
+        return launch_slide_held(parts, shifts, (int)n_parts, (int32_t)S, s, A.at<int64_t>(table));
+    }
+    case kOpSlotSet: {
+        const Ref table = w.ref();
+        const int64_t n_table = w.size(), n = w.count();
+        std::vector<int32_t> slots((size_t)n);
+        std::vector<int64_t> values((size_t)n);
+        for (auto& v : slots) { v = (int32_t)w.size(); if (v >= n_table) w.bad = true; }
+        for (auto& v : values) v = w.any();
+        if (w.bad || n_table > 65535 || !A.holds(table, 0, n_table, 8)) return hipErrorInvalidValue;
+        refused = false;
+        return launch_slot_set(A.at<int64_t>(table), slots.data(), values.data(), (int32_t)n, s);
+    }
+    case kOpTake: {
+        const int64_t n_slots = w.size(), len = w.size(), ring_stride = w.size(), ring_len = w.size(), d_stream = w.size(), d_off = w.size();
+        const Ref hi = w.ref(), lo = w.ref(), dhi = w.ref(), dlo = w.ref(), table = w.ref();
+        if (w.bad || n_slots > w.n - w.at) return hipErrorInvalidValue;                    // (the list of n_slots words follows)
+        std::vector<int64_t> rpos((size_t)n_slots);
+        for (auto& v : rpos) v = w.off();
+        if (w.bad || n_slots < 1 || !A.holds(hi, 0, n_slots * ring_stride, 4) || !A.holds(lo, 0, n_slots * ring_stride, 4) ||
+            !A.holds(dhi, 0, n_slots * d_stream, 4) || !A.holds(dlo, 0, n_slots * d_stream, 4) || !A.holds(table, 0, n_slots, 8))
+            return hipErrorInvalidValue;
+        refused = false;
+        return launch_take(A.at<float>(hi), A.at<float>(lo), ring_stride, ring_len, rpos.data(), (int32_t)n_slots, len, A.at<float>(dhi),
+                           A.at<float>(dlo), d_stream, d_off, A.at<int64_t>(table), s);
+    }
+    case kOpSlotReset: {
+        const Ref table = w.ref();
+        const int64_t n_table = w.size(), value = w.any(), n_slots = w.size(), n_parts = w.size();
+        if (w.bad || n_slots > w.n - w.at) return hipErrorInvalidValue;                    // (the list of n_slots words follows)
+        std::vector<int32_t> slots((size_t)n_slots);
+        int64_t top = 0;
+        for (auto& v : slots) { v = (int32_t)w.size(); top = std::max<int64_t>(top, v); }
+        if (w.bad || n_parts > kRowCopyParts || n_table > 65535 || top >= n_table || !A.holds(table, 0, n_table, 8)) return hipErrorInvalidValue;
+        ZeroPart parts[kRowCopyParts];
+        for (int k = 0; k < n_parts; ++k) {
+            const Ref dst = w.ref();
+            ZeroPart& p = parts[k];
+            p.len = w.size(); p.blocks = w.size(); p.dst_block = w.size(); p.dst_stream = w.size();
+            if (w.bad || !A.holds(dst, 0, run_span(p.len, p.blocks, p.dst_block, top + 1, p.dst_stream), 4)) return hipErrorInvalidValue;
+            p.dst = A.at<float>(dst);
+        }
+        refused = false;
+        return launch_slot_reset(A.at<int64_t>(table), value, slots.data(), (int32_t)n_slots, parts, (int)n_parts, s);
+    }
+    case kOpSlotExport: case kOpSlotImport: {
+        const int64_t n_parts = w.size();
+        const Ref table = w.ref();
+        const int64_t n_slots = w.size(), slot = w.size(), value = w.any(), shift = w.any();
+        if (w.bad || n_parts > kRowCopyParts || (op == kOpSlotImport && !A.holds(table, 0, n_slots, 8))) return hipErrorInvalidValue;
+        SlotMove parts[kRowCopyParts];
+        for (int k = 0; k < n_parts; ++k) {
+            const Ref src = w.ref(), dst = w.ref();
+            SlotMove& p = parts[k];
+            p.src_off = w.off(); p.len = w.size(); p.blocks = w.size(); p.src_block = w.size(); p.dst_block = w.size(); p.zero_below = w.size();
+            const bool reads = src.arena >= 0 && p.zero_below < p.len;
+            if (w.bad || !A.holds(dst, 0, run_span(p.len, p.blocks, p.dst_block, 1, 0), 4) ||
+                (reads && !A.holds(src, p.src_off + p.zero_below, p.src_off + run_span(p.len, p.blocks, p.src_block, 1, 0), 4)))
+                return hipErrorInvalidValue;
+            p.src = A.at<float>(src); p.dst = A.at<float>(dst);
+        }
+        refused = false;
+        if (op == kOpSlotExport) return launch_slot_export(parts, (int)n_parts, s);
+        return launch_slot_import(parts, (int)n_parts, A.at<int64_t>(table), (int32_t)n_slots, (int32_t)slot, value, shift, s);
+    }
+    case kOpGainFill: {
+        const Ref table = w.ref();
+        const int64_t n = w.size();
+        if (w.bad || n_fv < 1 || !A.holds(table, 0, n, 4)) return hipErrorInvalidValue;
+        refused = false;
+        return launch_gain_fill(A.at<float>(table), (int32_t)n, (float)fv[0], s);
+    }
+    case kOpGainSet: {
+        const Ref tgt = w.ref();
+        const int64_t n_table = w.size(), n = w.count();
+        std::vector<int32_t> slots((size_t)n);
+        std::vector<float> a((size_t)n);
+        for (auto& v : slots) { v = (int32_t)w.size(); if (v >= n_table) w.bad = true; }
+        if (w.bad || n_fv < n || n_table > 65535 || !A.holds(tgt, 0, n_table, 4)) return hipErrorInvalidValue;
+        for (int64_t k = 0; k < n; ++k) a[(size_t)k] = (float)fv[k];
+        refused = false;
+        return launch_gain_set(A.at<float>(tgt), slots.data(), a.data(), (int32_t)n, s);
+    }
+    case kOpGainCommit: {
+        const Ref tgt = w.ref(), cur_old = w.ref(), cur_new = w.ref();
+        const int64_t n = w.size(), slot = w.off();
+        if (w.bad || !A.holds(tgt, 0, n, 4) || !A.holds(cur_old, 0, n, 4) || !A.holds(cur_new, 0, n, 4)) return hipErrorInvalidValue;
+        refused = false;
+        return launch_gain_commit(A.at<float>(tgt), A.at<float>(cur_old), A.at<float>(cur_new), (int32_t)n, (int32_t)slot, s);
+    }
+    case kOpBandExpand: {
+        const Ref tab = w.ref(), job = w.ref();
+        const int64_t n_table = w.size(), FS = w.size(), F = w.size(), n = w.size(), n_bands = w.size(), rows = w.size(), init = w.size();
+        if (w.bad || n < 1 || n_bands < 1 || rows < 1 || !A.holds(tab, 0, n_table * kBandRows * FS, 4) ||
+            !A.holds(job, 0, band_job_words((int32_t)n, (int32_t)n_bands, (int32_t)rows), 4))
+            return hipErrorInvalidValue;
+        const int32_t* words = A.on_host<int32_t>(job);
+        for (int64_t k = 0; k < n; ++k) if (words[k] < 0 || words[k] >= n_table) return hipErrorInvalidValue;
+        refused = false;
+        return launch_band_expand(A.at<float>(tab), (int32_t)FS, (int32_t)F, A.at<int32_t>(job), (int32_t)n, (int32_t)n_bands, (int32_t)rows, init != 0, s);
+    }
+    case kOpBandCommit: {
+        const Ref tab = w.ref(), table = w.ref();
+        const int64_t FS = w.size(), n_slots = w.size(), slot = w.off(), mode = w.size();
+        if (w.bad || slot >= n_slots || !A.holds(tab, 0, n_slots * kBandRows * FS, 4) || !A.null_or_holds(table, 0, n_slots, 8))
+            return hipErrorInvalidValue;
+        refused = false;
+        return launch_band_commit(A.at<float>(tab), (int32_t)FS, (int32_t)n_slots, (int32_t)slot, (int)mode, A.at<int64_t>(table), s);
+    }
+    default: return hipErrorInvalidValue;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int repet_debug_devio_stage(repet_ctx* c, int32_t op, int32_t n_arenas, const void* const* arena_in, const int64_t* arena_bytes,
+                            const int32_t* arena_shift, void* const* arena_out, int32_t prefill, const int64_t* iv, int32_t n_iv,
+                            const double* fv, int32_t n_fv, int64_t* report_out) {
+    if (!c || !arena_in || !arena_bytes || !arena_shift || !arena_out || !iv || !report_out || (n_fv > 0 && !fv))
+        return fail(REPET_ERR_BAD_ARG, "null argument");
+    if (n_arenas < 1 || n_arenas > 16 || n_iv < 0 || n_fv < 0) return fail(REPET_ERR_BAD_ARG, "1 .. 16 arenas");
+    for (int k = 0; k < n_arenas; ++k) {
+        const int32_t sh = arena_shift[k];
+        if (arena_bytes[k] < 0 || arena_bytes[k] > ((int64_t)1 << 30) || !arena_in[k] || !arena_out[k] ||
+            !(sh == 0 || sh == 2 || sh == 4 || sh == 8 || sh == 12))
+            return fail(REPET_ERR_BAD_ARG, "an arena: up to 2^30 bytes, its first byte 0, 2, 4, 8 or 12 bytes behind a 256-byte boundary");
+    }
+    DeviceGuard guard(c->device);
+    const int fill = prefill & 255;
+    Arenas A(n_arenas);
+    for (int k = 0; k < n_arenas; ++k) {
+        const size_t k_ = (size_t)k;
+        const size_t total = (size_t)round_up(kArenaGuard + arena_shift[k] + arena_bytes[k] + kArenaGuard, 256);
+        HIP_TRY(A.dev[k_].b.ensure(total));
+        if (reinterpret_cast<uintptr_t>(A.dev[k_].b.p) & 255) return fail(REPET_ERR_HIP, "an allocation off a 256-byte boundary");
+        A.first[k_] = A.dev[k_].b.as<char>() + kArenaGuard + arena_shift[k];
+        A.bytes[k_] = arena_bytes[k];
+        A.shift[k_] = arena_shift[k];
+        A.host[k_] = static_cast<const char*>(arena_in[k]);
+        HIP_TRY(hipMemsetAsync(A.dev[k_].b.p, fill, total, c->stream));
+        if (arena_bytes[k] > 0) HIP_TRY(hipMemcpyAsync(A.first[k_], arena_in[k], (size_t)arena_bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    Words w{iv, n_iv};
+    DevioReport report;
+    bool refused = false;
+    devio_report = &report;
+    const hipError_t e = run_devio_op(op, A, w, fv, n_fv, c->stream, refused);
+    devio_report = nullptr;
+    if (refused || e == hipErrorInvalidValue) {
+        (void)hipStreamSynchronize(c->stream);
+        return fail(REPET_ERR_BAD_ARG, refused ? "the launch would index outside an arena (or the words do not describe the op)"
+                                               : "the launcher refused its arguments");
+    }
+    HIP_TRY(e);
+    for (int k = 0; k < n_arenas; ++k)
+        HIP_TRY(hipMemcpyAsync(arena_out[k], A.first[(size_t)k] - kArenaGuard, (size_t)(arena_bytes[k] + 2 * kArenaGuard), hipMemcpyDeviceToHost,
+                               c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t v[24] = {};
+    v[0] = report.launches;
+    for (int k = 0; k < 3; ++k) v[1 + k] = report.grid[k];
+    for (int k = 0; k < 2; ++k) v[4 + k] = report.dense[k];
+    for (int k = 0; k < kRowCopyParts; ++k) { v[6 + k] = report.src_vec[k]; v[11 + k] = report.dst_vec[k]; v[16 + k] = report.held_vec[k]; }
+    std::memcpy(report_out, v, sizeof(v));
+    return REPET_OK;
+}
+
+}  // extern "C"

@@ -726,6 +726,7 @@ def _stage_entry(name):
                                        i32, p, i64, i32, i32, p, p, p, p, p, p, i32, p, i32, p],
             "repet_debug_peaks_stage": [p, p, i32, i64, i32, i64, p, i64, i32, p, p, i64, i32, i32, i64, i32, i64, i64, C.c_double, i32, i32,
                                         i64, p, i32, i32, i32, i32, p, p, p, p, p, p, p, i32, p],
+            "repet_debug_devio_stage": [p, i32, i32, p, p, p, p, i32, p, i32, p, i32, p],
         }[name]
         _stage_entries[name] = fn
     return _stage_entries[name]
@@ -1078,6 +1079,44 @@ def _peaks_stage(M, n_cols=None, pitch=None, mode=0, row0=0, n_rows=None, min_va
     if refine == 2:
         out["u64"], out["stamped"] = u64, stamped.astype(bool)
     return out
+
+
+DEVIO_OPS = {name: k for k, name in enumerate((
+    "ingest", "egress", "emit", "levels", "tail_clear", "append", "row_copies", "slide_held", "slot_set", "feed", "take", "slot_reset",
+    "slot_export", "slot_import", "gain_fill", "gain_set", "gain_commit", "band_expand", "band_commit"))}
+DEVIO_GUARD = 512            # bytes of prefill returned in front of and behind every arena
+
+
+def _devio_stage(op, arenas, words, floats=(), shifts=None, prefill=0xA5):
+    """One production launcher of csrc/devio.hip on device buffers the caller describes (``repet_debug_devio_stage``; the words of
+    every ``op`` are listed where engine_stages.hip reads them). ``arenas``: NumPy arrays, each uploaded into an allocation of its
+    own with its first byte ``shifts[k]`` (0, 4, 8 or 12; 2 for 16-bit elements) bytes behind a 256-byte boundary and the byte ``prefill`` everywhere
+    else; a pointer argument is the pair of words (arena, element offset), arena -1 for null. Returns ``(outs, report)``:
+    ``outs[k]`` the bytes of arena k as the launch left them with ``DEVIO_GUARD`` bytes of guard on either side (uint8), and what the
+    launcher decided -- ``launches``, the last ``grid``, ``dense`` per destination, ``src_vec`` / ``dst_vec`` / ``held_vec`` per
+    part, -1 where the launcher decides no such thing. ValueError where the launch would index outside an arena, or the launcher
+    refuses its arguments; nothing is launched then."""
+    import ctypes as C
+    held = [np.ascontiguousarray(a) for a in arenas]
+    n = len(held)
+    shifts = [0] * n if shifts is None else [int(v) for v in shifts]
+    assert len(shifts) == n
+    outs = [np.empty(a.nbytes + 2 * DEVIO_GUARD, dtype=np.uint8) for a in held]
+    # (an empty array has no address NumPy would vouch for: a byte of its own stands in)
+    pad = np.zeros(16, dtype=np.uint8)
+    ins = (C.c_void_p * n)(*[(a if a.nbytes else pad).ctypes.data for a in held])
+    out_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    sizes = (C.c_int64 * n)(*[a.nbytes for a in held])
+    sh = (C.c_int32 * n)(*shifts)
+    iv = [int(v) for v in words]
+    fv = [float(v) for v in floats]
+    ivs, fvs = (C.c_int64 * max(1, len(iv)))(*iv), (C.c_double * max(1, len(fv)))(*fv)
+    rep = (C.c_int64 * 24)()
+    _native.check(_stage_entry("repet_debug_devio_stage")(_native.default_context(_device).handle, DEVIO_OPS[op], n, ins, sizes, sh, out_p,
+                                                          int(prefill), ivs, len(iv), fvs, len(fv), rep))
+    r = [int(v) for v in rep]
+    return outs, {"launches": r[0], "grid": tuple(r[1:4]), "dense": tuple(r[4:6]), "src_vec": tuple(r[6:11]), "dst_vec": tuple(r[11:16]),
+                  "held_vec": tuple(r[16:21])}
 
 
 def _selfsimilaritymatrix(data_matrix):
